@@ -3,6 +3,7 @@
 bodies (BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
     python bench.py --gpus 1 --steps 200 --warmup 100
+    python bench.py --gpus 1 --steps 200 --warmup 100 --full   # and everything else it measures (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --host native          # one process, no torchrun: nb_runner_create_multi
@@ -20,11 +21,16 @@ Inputs are synthetic (the seeded uniform_init the reference's own criterion benc
 benches/benchmark.rs:24) and are resident in HBM before the timed region starts.
 
 Rank 0 prints ONE JSON line, the same schema for every N and host.  `value` = N*(N-1)*K / wall seconds
-over all GPUs.  Extra keys ride along (none of them inside the timed region):
+over all GPUs.  A plain run measures the headline only.  With --full, extra keys ride along (none of
+them inside the timed region):
+  cpu_baseline               the CPU oracle on a sample of the same workload (N = 1)
   criterion                  the reference's own benchmark, benches/benchmark.rs:12-49 (N = 1)
   tree_1m_theta05, tree_4m_theta075_headless      Barnes-Hut legs (N = 1)
   native_host, config3_262144_allpairs, config4_4m_let_theta05   (N > 1) the one-process runner on the same
                              N devices, BASELINE configs[3] and configs[4], per-rank kernel / wait times
+  ranks, roofline kernel figures   (--host native, or N > 1) kernel times from a separate batch of steps
+
+--dump-outputs DIR writes the state after the last timed step, one float32 .npy per Particle field.
 """
 from __future__ import annotations
 
@@ -241,6 +247,20 @@ def run_extras_child(gpus, steps, warmup, limit_s=300):
     return json.loads(lines[-1])
 
 
+def dump_outputs(np, directory, particles, limit_bytes=64 << 20):
+    """What a caller of the timed path receives after its last step: DIR/<field>.npy (float32) for every
+    Particle field.  Above `limit_bytes` a fixed, seeded sample of 2^20 bodies is written instead, with
+    their body indices in DIR/sample_index.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    n = particles.shape[0]
+    if n * particles.itemsize > limit_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(n, 1 << 20, replace=False))
+        particles = particles[keep]
+        np.save(os.path.join(directory, "sample_index.npy"), keep.astype(np.float64))
+    for name in particles.dtype.names:
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(particles[name], dtype=np.float32))
+
+
 def hbm_traffic_from_profile(n):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC summary
     (profiles/*_pmc_summary.json, collected as MI355X_MICROARCH.md prescribes); null if the
@@ -266,14 +286,22 @@ def main():
     ap.add_argument("--bodies", type=int, default=65536)
     ap.add_argument("--host", choices=("rccl", "native"), default="rccl",
                     help="rccl: one process per GPU (torchrun when --gpus > 1); native: one process, nb_runner_create_multi")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tree", action="store_true", help="skip the Barnes-Hut legs (extra keys of the JSON line)")
-    ap.add_argument("--no-criterion", action="store_true", help="skip the reference's criterion rows")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1: skip native_host / config3 / config4")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, criterion rows and "
+                         "Barnes-Hut legs (N = 1), the other configurations (N > 1), and kernel times that take "
+                         "a batch of their own (--host native, N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-tree", action="store_true", help="with --full: skip the Barnes-Hut legs")
+    ap.add_argument("--no-criterion", action="store_true", help="with --full: skip the reference's criterion rows")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N > 1: skip native_host / config3 / config4")
     ap.add_argument("--extras-only", action="store_true",
                     help="(internal) print only the one-process runner's extra keys for --gpus N, as JSON")
     ap.add_argument("--variant", type=int, default=None, help="all-pairs kernel variant override")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step as DIR/<field>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch  # first: libnbody_hip.so then binds to the HIP runtime torch already loaded
@@ -299,6 +327,9 @@ def main():
     if not native and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run "
                          f"(or --host native for one process)")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: a rank of the one-process-per-GPU host holds only its own bodies' "
+                         "velocities and accelerations; use --host native for N > 1")
     if not torch.cuda.is_available() or nb.device_count() == 0:
         raise SystemExit("bench.py needs a HIP device: the product has no CPU fallback")
     # Rehearsal knobs (tests only): NB_DIST_BACKEND=gloo and NB_BENCH_SAME_DEVICE=1 let several
@@ -354,13 +385,14 @@ def main():
         t0 = time.perf_counter()
         runner.step_n(K)
         wall = time.perf_counter() - t0
-        state = nb.as_floats(runner.read_particles())
-        runner.set_profiling(True)                     # after the timed region: the same batch with timing marks
-        runner.step_n(K)
-        kms, wms = runner.rank_times(n_gpus)
+        particles = runner.read_particles()
+        if args.full:
+            runner.set_profiling(True)                 # after the timed region: the same batch with timing marks
+            runner.step_n(K)
+            kms, wms = runner.rank_times(n_gpus)
+            ranks_info = {"rank_kernel_ms": [x / K for x in kms], "rank_wait_ms": [x / K for x in wms]}
+            ms_kernel = max(kms) / K
         runner.destroy()
-        ranks_info = {"rank_kernel_ms": [x / K for x in kms], "rank_wait_ms": [x / K for x in wms]}
-        ms_kernel = max(kms) / K
     elif world == 1:
         sim = nb.NaiveSim.from_particles(sp, None, init, nb.Placement(device_id=local_rank))
         if args.variant is not None:
@@ -383,7 +415,7 @@ def main():
         _ms_total, ms_kernel = sim.encode_n_timed(K)
         sync_all()
         wall = time.perf_counter() - t0
-        state = nb.as_floats(sim.dest_particle_slice())
+        particles = sim.dest_particle_slice()
     else:
         sim = ShardedNaiveSim(sp, init, rank, world, local_rank, variant=args.variant)
         for _ in range(prewarm + W):
@@ -395,7 +427,8 @@ def main():
         sync_all()
         wall = time.perf_counter() - t0
         sim.wait()
-        state = nb.as_floats(sim.read_particles())
+        particles = sim.read_particles()
+    state = nb.as_floats(particles)
 
     wall_t = torch.tensor([wall], dtype=torch.float64, device="cuda")
     if world > 1:
@@ -404,8 +437,10 @@ def main():
 
     # sanity: the state is finite after the run (a diverged run is not a benchmark)
     assert np.isfinite(state).all(), "non-finite state after the timed steps"
+    if args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, particles)
 
-    if world > 1:
+    if world > 1 and args.full:
         # kernel-only duration of one rank's share (both halves + integrator), measured after
         # the timed region and the sanity check, without the exchange: the state is not used
         # again, only the launch durations are
@@ -420,7 +455,7 @@ def main():
 
     # BASELINE configs[3] through the RCCL host (every rank takes part; not in the timed region above)
     config3_rccl = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         try:
             n3 = 262144
             sp3 = nb.SimParams(particle_num=n3, g=G, e=E, dt=DT)
@@ -450,7 +485,8 @@ def main():
         value = pairs_per_step * K / wall
         per_rank = nb.shard_bodies_per_rank(n, n_gpus)
         local_pairs = min(per_rank, n) * (n - 1)              # pairs one launch evaluates
-        achieved = FLOP_PER_PAIR * local_pairs / (ms_kernel * 1e-3) / 1e12
+        # ms_kernel is None where the kernel time takes a batch of its own and --full is not given
+        achieved = FLOP_PER_PAIR * local_pairs / (ms_kernel * 1e-3) / 1e12 if ms_kernel else None
         traffic = hbm_traffic_from_profile(n) if n_gpus == 1 else None
         exchange = ("" if n_gpus == 1 else
                     " + peer stores of the float4 slices from the finish kernel, one event per rank and step" if native
@@ -472,34 +508,34 @@ def main():
                                           if args.variant is not None else "auto")},
             "roofline": {"bound": "mfma", "bound_detail": "fp32_valu_issue (the kernel issues no MFMA; the "
                          "schema's compute side)", "achieved": achieved, "peak": PEAK_FP32_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS,
+                         "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_TFLOPS if achieved else None,
                          "traffic": traffic,
-                         "hbm_gbps": (traffic / (ms_kernel * 1e-3) / 1e9) if traffic else None,
+                         "hbm_gbps": (traffic / (ms_kernel * 1e-3) / 1e9) if traffic and ms_kernel else None,
                          "hbm_peak_gbps": 8000.0,
                          "kernel": "nb::naive_step_kernel", "kernel_ms": ms_kernel,
                          "flop_per_pair": FLOP_PER_PAIR,
                          # the instruction-issue ceiling of this force law on this chip (DESIGN.md
                          # section 4: 12 packed + 4 transcendental issues per 2 pairs at the measured
                          # 1.85 / 3.41 ns per wave-instruction and SIMD): 3.59e12 pairs/s
-                         "issue_ceiling_frac": (achieved * 1e12 / FLOP_PER_PAIR) / 3.59e12,
+                         "issue_ceiling_frac": (achieved * 1e12 / FLOP_PER_PAIR) / 3.59e12 if achieved else None,
                          "note": "compute-bound on FP32 VALU issue; 157.3 TFLOP/s is both the "
                                  "vector and the f32-MFMA dense peak"},
         }
         if ranks_info:
             out["ranks"] = ranks_info
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nb, nb.as_floats(init), n)
-        if n_gpus == 1 and not args.no_criterion:
+        if args.full and n_gpus == 1 and not args.no_criterion:
             out["criterion"] = {"source": "benches/benchmark.rs:12-49: runner.step() per call, uniform_init, "
                                           "SimParams::default, theta 0.75", "rows": criterion_rows(nb, np, local_rank)}
-        if n_gpus == 1 and not args.no_tree:
+        if args.full and n_gpus == 1 and not args.no_tree:
             # Barnes-Hut beside the headline, measured in the same run: BASELINE configs[2]
             # (1,048,576 bodies, theta 0.5) and the reference's own headless configuration
             # (src/bin/headless.rs:15-27: 4,000,000 bodies, theta 0.75, uniform_init)
             out["tree_1m_theta05"] = tree_leg(nb, np, 1 << 20, 0.5, 3, 40, local_rank, 60,
                                               with_cpu=not args.no_cpu_baseline)
             out["tree_4m_theta075_headless"] = tree_leg(nb, np, 4000000, 0.75, 0, 20, local_rank, 20)
-        if n_gpus > 1 and not args.no_extras:
+        if args.full and n_gpus > 1 and not args.no_extras:
             if native:
                 ex = {"config3": native_extra(nb, np, "config3", device_ids, 20, 5),
                       "config4": native_extra(nb, np, "config4", device_ids, 20, 5)}

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.helpers import ROOT
@@ -39,14 +40,14 @@ def check_line(d, n_gpus, steps, warmup, shared=False):
 
 
 def test_one_gpu_both_hosts_same_schema():
-    a = run_bench(["--steps", "20", "--warmup", "3"])                                   # the driver's default shape
-    b = run_bench(["--steps", "20", "--warmup", "3", "--host", "native", "--no-cpu-baseline", "--no-tree",
+    a = run_bench(["--steps", "20", "--warmup", "3", "--full"])                         # the driver's --full shape
+    b = run_bench(["--steps", "20", "--warmup", "3", "--host", "native", "--full", "--no-cpu-baseline", "--no-tree",
                    "--no-criterion"])
     check_line(a, 1, 20, 3)
     check_line(b, 1, 20, 3)
     assert 0.9 < a["value"] / b["value"] < 1.1                       # the same kernel behind both boundaries
     assert set(b) - {"ranks"} <= set(a)
-    # the extras of the default N = 1 line
+    # the extras of the --full N = 1 line
     assert a["cpu_baseline"]["kind"] == "port" and a["cpu_baseline"]["cores"] >= 1
     rows = a["criterion"]["rows"]
     assert [(r["group"], r["n"]) for r in rows] == [(g, n) for g in ("naive", "tree")
@@ -59,7 +60,7 @@ def test_one_gpu_both_hosts_same_schema():
 
 def test_two_ranks_both_hosts_same_schema():
     env = {"NB_BENCH_SAME_DEVICE": "1"}
-    nat = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--host", "native"], env=env)
+    nat = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--host", "native", "--full"], env=env)
     check_line(nat, 2, 10, 3, shared=True)
     assert len(nat["ranks"]["rank_kernel_ms"]) == 2 and all(x > 0 for x in nat["ranks"]["rank_kernel_ms"])
     for key in ("config3_262144_allpairs", "config4_4m_let_theta05"):
@@ -68,9 +69,27 @@ def test_two_ranks_both_hosts_same_schema():
         assert len(got["rank_kernel_ms"]) == 2 and got["ms_per_step"] > 0
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29631"]
-    rccl = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3"], env=dict(env, NB_DIST_BACKEND="gloo"),
+    rccl = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--full"], env=dict(env, NB_DIST_BACKEND="gloo"),
                      launcher=launcher)
     check_line(rccl, 2, 10, 3, shared=True)
     assert "error" not in rccl["native_host"], rccl["native_host"]
     assert "error" not in rccl["config3_262144_allpairs"]["rccl_host"]
     assert set(nat) - {"ranks"} <= set(rccl) | {"ranks"}
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline and none of the extras; --dump-outputs writes the state after
+    the last timed step, and two runs with the same arguments write the same bytes."""
+    runs = [run_bench(["--steps", "20", "--warmup", "3", "--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for d in runs:
+        check_line(d, 1, 20, 3)
+        assert not {"cpu_baseline", "criterion", "tree_1m_theta05", "tree_4m_theta075_headless", "ranks"} & set(d)
+    import wgpu_n_body_amd as nb
+    init = nb.inits.uniform_init(nb.SimParams(particle_num=65536), seed=2)
+    for name, shape in (("position", (65536, 3)), ("velocity", (65536, 3)), ("acceleration", (65536, 3)),
+                        ("mass", (65536,))):
+        a, b = (np.load(tmp_path / d / f"{name}.npy") for d in ("a", "b"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all()
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
+    assert np.array_equal(np.load(tmp_path / "a" / "mass.npy"), init["mass"])      # the step does not touch masses
+    assert not np.array_equal(np.load(tmp_path / "a" / "position.npy"), init["position"])

@@ -10,7 +10,7 @@ cd $ROOT
 O=gpurun_out/${TAG}final
 rm -rf $O; mkdir -p $O
 need() { for f in "$@"; do [ -s "$f" ] || { echo "collect_profiles: $f is missing or empty"; exit 1; }; done; }
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
 need $O/bench_n1.json
 echo "bench done"
 bash tools/profile_bench.sh $TAG > $O/profile_bench.log 2>&1 || { tail $O/profile_bench.log; exit 1; }
