@@ -308,6 +308,66 @@ const char *nb_naive_variant_name(int variant);
  * counts, u64 x 4; "status": u32 x 4).  *bytes receives the buffer's length. */
 int nb_sim_debug_buffer(nb_sim *sim, const char *name, void *dst, size_t cap, size_t *bytes);
 
+/* ------------------------------------------------------------------------- */
+/* Diagnostics -- conserved-quantity monitor (no reference counterpart: the   */
+/* reference has no way to measure a run's energy or momentum)                */
+/* ------------------------------------------------------------------------- */
+/* Computed on the device for the state nb_sim_read_particles would return
+ * (the post-step state; step 0 = the initial state), in fp64 from the fp32
+ * state.  Sums over bodies, about the origin:
+ *   mass              M = sum m
+ *   com[3]            sum m x / M (NaN when M is 0)
+ *   momentum[3]       P = sum m v
+ *   angular_momentum  L = sum m (x cross v)
+ *   kinetic           K = sum m |v|^2 / 2
+ *   max_speed         max |v|
+ *   nonfinite         bodies with any non-finite position, velocity or mass
+ *                     component; they are left out of every sum (and of W)
+ * With NB_DIAG_POTENTIAL, over all pairs i < j (O(N^2), exact, no theta):
+ *   pair_sum          W = sum m_i m_j psi(r_ij), with the potential of the
+ *                     reference's pair force m_j g / (r^3 + e) (naive.wgsl:23-48):
+ *                       psi(r) = integral_r^inf ds / (s^3 + e)
+ *                              = atan2(sqrt3 a, 2r - a) / (sqrt3 a^2)
+ *                                - log1p(3ar / (r^2 - ar + a^2)) / (6a^2),  a = e^(1/3)
+ *                     (psi(0) = 2 pi / (3 sqrt3 a^2) is finite; psi(r) -> 1/(2r^2))
+ *   potential         U = -g dt W (the stored acceleration is sum(f) dt: the
+ *                     coupling is g dt, naive.wgsl:41)
+ *   total             E = K + U
+ * Without the flag these three are NaN.  E is a MONITOR, not an invariant:
+ * the reference evaluates body i's drifted position against body j's old one
+ * (SURVEY A6), so neither E nor P is conserved exactly by the integrator.
+ * Coincident distinct bodies each add psi(0); with e = 0 they make W = +inf.
+ * The sums run in a fixed order without float atomics: two calls on one state
+ * return bit-identical structs.  The call is ordered after the enqueued steps
+ * on the simulator's stream, ends with one synchronisation, reports a TreeSim's
+ * status words as nb_sim_read_particles does, and does not change the
+ * trajectory.  The pair pass is split into launches of bounded length. */
+#define NB_DIAG_MOMENTS 1u   /* always computed */
+#define NB_DIAG_POTENTIAL 2u /* add the O(N^2) pair potential */
+
+typedef struct nb_diagnostics {
+    uint64_t step_num;  /* the step the measured state is the result of */
+    uint64_t n;         /* bodies measured */
+    uint64_t nonfinite;
+    double mass;
+    double com[3];
+    double momentum[3];
+    double angular_momentum[3];
+    double kinetic;
+    double max_speed;
+    double pair_sum;  /* W (NaN without NB_DIAG_POTENTIAL) */
+    double potential; /* U = -g dt W */
+    double total;     /* E = kinetic + potential */
+    uint32_t flags;   /* what was computed (NB_DIAG_MOMENTS | requested bits) */
+    uint32_t reserved;
+} nb_diagnostics;
+
+/* Diagnostics of a simulator (no reference counterpart).  flags: any
+ * combination of NB_DIAG_* (0 = moments only).  NB_ERR_INVALID for a null
+ * argument, unknown flag bits or NB_DIAG_POTENTIAL with e < 0;
+ * NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out);
+
 int nb_sim_destroy(nb_sim *sim);
 
 /* ------------------------------------------------------------------------- */
@@ -378,6 +438,9 @@ int nb_runner_rank_times(nb_runner *runner, float *kernel_ms, float *wait_ms, in
 int nb_runner_read_particles(nb_runner *runner, nb_particle *dst, size_t n);
 int nb_runner_sim_params(const nb_runner *runner, nb_sim_params *out);
 int nb_runner_step_num(const nb_runner *runner, uint64_t *out);
+/* nb_sim_diagnostics of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out);
 /* Borrow the runner's simulator (owned by the runner); NULL for a several-GPU runner. */
 nb_sim *nb_runner_sim(nb_runner *runner);
 int nb_runner_destroy(nb_runner *runner);

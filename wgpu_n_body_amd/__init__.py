@@ -34,7 +34,7 @@ from ._lib import (NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS, OCTANT_DTYPE, PARTIC
 __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "TreeSim",
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
-           "shard_padded_bodies", "naive_variants"]
+           "shard_padded_bodies", "naive_variants", "Diagnostics"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
 
@@ -90,6 +90,39 @@ class Placement:
 
 
 InitFn = Callable[[SimParams], np.ndarray]
+
+
+@dataclass(frozen=True)
+class Diagnostics:
+    """nb_diagnostics (include/nbody.h "Diagnostics"; no reference counterpart): conserved-quantity
+    monitor of the state read_particles would return, computed on the device in fp64.  Vectors are
+    float64 arrays of 3.  pair_sum W = sum_{i<j} m_i m_j psi(r_ij), potential U = -g dt W and
+    total E = kinetic + U are NaN unless the potential was requested.  E is a monitor, not an
+    invariant of the integrator."""
+    step_num: int
+    n: int
+    nonfinite: int
+    mass: float
+    com: np.ndarray
+    momentum: np.ndarray
+    angular_momentum: np.ndarray
+    kinetic: float
+    max_speed: float
+    pair_sum: float
+    potential: float
+    total: float
+    flags: int
+
+    @staticmethod
+    def _from_c(d: "_lib.nb_diagnostics") -> "Diagnostics":
+        vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+        return Diagnostics(int(d.step_num), int(d.n), int(d.nonfinite), float(d.mass), vec(d.com),
+                           vec(d.momentum), vec(d.angular_momentum), float(d.kinetic), float(d.max_speed),
+                           float(d.pair_sum), float(d.potential), float(d.total), int(d.flags))
+
+
+def _diag_flags(potential: bool) -> int:
+    return _lib.NB_DIAG_MOMENTS | (_lib.NB_DIAG_POTENTIAL if potential else 0)
 
 
 def version() -> str:
@@ -271,6 +304,13 @@ class Simulator:
 
     read_particles = dest_particle_slice
 
+    def diagnostics(self, potential: bool = False) -> Diagnostics:
+        """Energy, momentum and angular momentum of the current state (nb_sim_diagnostics); with
+        potential=True also the exact O(N^2) pair potential."""
+        d = _lib.nb_diagnostics()
+        check(_lib.lib().nb_sim_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
+        return Diagnostics._from_c(d)
+
     def write_particles(self, particles) -> None:
         arr = as_particles(particles)
         check(_lib.lib().nb_sim_write_particles(self._h, arr.ctypes.data, arr.shape[0]))
@@ -418,6 +458,12 @@ class OfflineHeadless:
         out = np.zeros(n, dtype=PARTICLE_DTYPE)
         check(_lib.lib().nb_runner_read_particles(self._h, out.ctypes.data, n))
         return out
+
+    def diagnostics(self, potential: bool = False) -> Diagnostics:
+        """nb_runner_diagnostics: Simulator.diagnostics of the runner's simulator (one device only)."""
+        d = _lib.nb_diagnostics()
+        check(_lib.lib().nb_runner_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
+        return Diagnostics._from_c(d)
 
     def sim_params(self) -> SimParams:
         sp = _lib.nb_sim_params()

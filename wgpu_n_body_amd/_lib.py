@@ -38,12 +38,22 @@ class nb_placement(C.Structure):
                 ("stream", C.c_void_p), ("posm", C.c_void_p * 2)]
 
 
+class nb_diagnostics(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("mass", C.c_double), ("com", C.c_double * 3), ("momentum", C.c_double * 3),
+                ("angular_momentum", C.c_double * 3), ("kinetic", C.c_double), ("max_speed", C.c_double),
+                ("pair_sum", C.c_double), ("potential", C.c_double), ("total", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(nb_sim_params) == 16 and C.sizeof(nb_add_params) == 8
+assert C.sizeof(nb_diagnostics) == 152
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
 
 NB_OK, NB_ERR_INVALID, NB_ERR_NO_DEVICE, NB_ERR_HIP, NB_ERR_ALLOC, NB_ERR_UNSUPPORTED = range(6)
 NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS = 0, 1
+NB_DIAG_MOMENTS, NB_DIAG_POTENTIAL = 1, 2
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -55,10 +65,10 @@ ABI_SYMBOLS = [
     "nb_sim_wait", "nb_sim_sim_params", "nb_sim_read_particles", "nb_sim_write_particles",
     "nb_sim_read_tree", "nb_sim_exchange_region", "nb_sim_exchange_count",
     "nb_sim_exchange_region_i", "nb_sim_step_num", "nb_sim_encode_n_timed",
-    "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
+    "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
-    "nb_runner_sim_params", "nb_runner_sim", "nb_runner_destroy",
+    "nb_runner_sim_params", "nb_runner_diagnostics", "nb_runner_sim", "nb_runner_destroy",
 ]
 
 
@@ -115,6 +125,7 @@ def lib() -> C.CDLL:
     L.nb_sim_encode_n_timed.argtypes = [vp, C.c_int, P(C.c_float), P(C.c_float)]
     L.nb_sim_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]
     L.nb_sim_debug_buffer.argtypes = [vp, C.c_char_p, vp, sz, P(sz)]
+    L.nb_sim_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
     L.nb_naive_variant_count.restype = C.c_int
     L.nb_naive_variant_name.argtypes = [C.c_int]
     L.nb_naive_variant_name.restype = C.c_char_p
@@ -129,6 +140,7 @@ def lib() -> C.CDLL:
     L.nb_runner_set_profiling.argtypes = [vp, C.c_int]
     L.nb_runner_rank_times.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int]
     L.nb_runner_sim_params.argtypes = [vp, P(nb_sim_params)]
+    L.nb_runner_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
     L.nb_runner_sim.argtypes = [vp]
     L.nb_runner_sim.restype = vp
     L.nb_runner_destroy.argtypes = [vp]

@@ -23,6 +23,7 @@ ARCH = "gfx950"
 SOURCES = [
     ("nb_naive.hip", []),
     ("nb_tree.hip", []),
+    ("nb_diag.hip", []),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

@@ -3,10 +3,16 @@
 //
 //   headless [--sim naive|tree] [--n N] [--steps S] [--theta T] [--init uniform|disc|spherical]
 //            [--seed K] [--device D | --devices D0,D1,...] [--g G] [--dt DT] [--dump FILE]
+//            [--diag K [--diag-potential 1]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
 // a device id may repeat.
+//
+// --diag K prints the diagnostics (nb_runner_diagnostics) of step 0 and of every K-th step, one line
+// "Diagnostics: step S kinetic K potential U total E momentum px py pz angular_momentum lx ly lz"
+// (%.9e; potential and total are nan unless --diag-potential 1 adds the O(N^2) pair potential).  The
+// time they take is not part of any "Step Duration"; without --diag the output is unchanged.
 //
 // --dump FILE writes the final state as a snapshot (the layout of
 // wgpu_n_body_amd/snapshot.py: "NBSNAP01", u64 step, SimParams, Particle[n]).
@@ -35,18 +41,30 @@ static bool write_snapshot(const std::string &path, const nbody::SimParams &sp,
 }
 
 template <class Sim>
+static void print_diag(nbody::OfflineHeadless<Sim> &runner, bool potential) {
+    const nbody::Diagnostics d = runner.diagnostics(potential);
+    std::printf("Diagnostics: step %llu kinetic %.9e potential %.9e total %.9e momentum %.9e %.9e %.9e "
+                "angular_momentum %.9e %.9e %.9e\n",
+                (unsigned long long)d.step_num, d.kinetic, d.potential, d.total, d.momentum[0], d.momentum[1],
+                d.momentum[2], d.angular_momentum[0], d.angular_momentum[1], d.angular_momentum[2]);
+}
+
+template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
-               int steps, int device, const std::vector<int> &devices, const std::string &dump, int let) {
+               int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
+               int diag, bool diag_potential) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
     std::puts("Running Simulation");
+    if (diag > 0) print_diag(runner, diag_potential);
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
         runner.step();
         const auto us = std::chrono::duration_cast<std::chrono::microseconds>(
                             std::chrono::steady_clock::now() - t0).count();
         std::printf("Step Duration: %lld \xC2\xB5s\n", (long long)us);
+        if (diag > 0 && (i + 1) % diag == 0) print_diag(runner, diag_potential);
     }
     std::puts("Finished Running");
     if (!dump.empty()) {
@@ -64,7 +82,8 @@ int main(int argc, char **argv) {
     std::vector<int> devices;
     nbody::SimParams sp{4000000u, 0.000001f, 0.0001f, 0.016f};  // headless.rs:15-20
     float theta = 0.75f;
-    int steps = 10, device = -1, let = -1;
+    int steps = 10, device = -1, let = -1, diag = 0;
+    bool diag_potential = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -79,6 +98,8 @@ int main(int argc, char **argv) {
         else if (k == "--dt") sp.dt = (float)std::atof(v.c_str());
         else if (k == "--dump") dump = v;
         else if (k == "--let") let = std::atoi(v.c_str());  // with --devices and --sim tree: LET scheme, migrate every k-th step
+        else if (k == "--diag") diag = std::atoi(v.c_str());
+        else if (k == "--diag-potential") diag_potential = std::atoi(v.c_str()) != 0;
         else if (k == "--devices") {
             for (size_t a = 0; a <= v.size();) {
                 const size_t b = std::min(v.find(',', a), v.size());
@@ -93,8 +114,10 @@ int main(int argc, char **argv) {
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
-            return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1);
-        return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let);
+            return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
+                                        diag_potential);
+        return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
+                                       diag, diag_potential);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -33,6 +33,7 @@ static size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 // SimBase
 // ------------------------------------------------------------------------------------------
 SimBase::~SimBase() {
+    diag_release(diag);  // (the derived destructor has bound the device)
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -574,6 +575,24 @@ int nb_sim_debug_buffer(nb_sim *sim, const char *name, void *dst, size_t cap, si
     NB_SIM_CALL(sim, debug_buffer(name, dst, cap, bytes))
 }
 
+int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out) {
+    if (!out) {
+        set_error("diagnostics: out is null");
+        return NB_ERR_INVALID;
+    }
+    if (flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL)) {
+        set_error("diagnostics: unknown flag bits 0x%x", flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL));
+        return NB_ERR_INVALID;
+    }
+    NB_GUARD({
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        return sim_diagnostics(*sim->impl, flags, out);
+    })
+}
+
 int nb_naive_variant_count(void) { return naive_variant_count(); }
 const char *nb_naive_variant_name(int v) { return naive_variant_name(v); }
 
@@ -756,6 +775,18 @@ int nb_runner_step_num(const nb_runner *runner, uint64_t *out) {
         return NB_OK;
     }
     return nb_sim_step_num(runner->sim, out);
+}
+
+int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out) {
+    if (!runner || (!runner->sim && !runner->group)) {
+        set_error("null runner");
+        return NB_ERR_INVALID;
+    }
+    if (runner->group && out && !(flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL))) {
+        set_error("diagnostics: not available on a several-GPU runner (nb_runner_create_multi*)");
+        return NB_ERR_UNSUPPORTED;
+    }
+    return nb_sim_diagnostics(runner->sim, flags, out);
 }
 
 nb_sim *nb_runner_sim(nb_runner *runner) { return runner ? runner->sim : nullptr; }

@@ -8,6 +8,8 @@
 
 namespace nb {
 
+struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
+
 // What `trait Simulator` (src/sims/mod.rs:73-90) requires of an implementor, in HIP terms.
 class SimBase {
    public:
@@ -80,6 +82,10 @@ class SimBase {
         set_error("unknown tuning key '%s'", key);
         return NB_ERR_INVALID;
     }
+    // nb_sim_diagnostics: the buffers nb_sim_read_particles converts (x,y,z,m and vx,vy,vz,- per body,
+    // bodies [0, n)), and the status of the steps that produced them, read after the stream has drained
+    virtual void diag_state(const float4 **posm_out, const float4 **vel_out) const = 0;
+    virtual int diag_status() { return NB_OK; }
 
     nb_sim_params params{};
     nb_add_params add{};
@@ -88,7 +94,12 @@ class SimBase {
     bool own_stream = false;
     uint64_t step_num = 0;
     uint32_t n = 0, n_pad = 0, per_rank = 0, lo = 0, hi = 0;
+    DiagWork *diag = nullptr;  // allocated by the first nb_sim_diagnostics
 };
+
+// nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
+int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out);
+void diag_release(DiagWork *w);
 
 class NaiveSim final : public SimBase {
    public:
@@ -102,6 +113,10 @@ class NaiveSim final : public SimBase {
     int exchange_count() override { return 1; }
     int exchange_region(int index, void **dev_ptr, size_t *off, size_t *len, size_t *total) override;
     int set_tuning(const char *key, int value) override;
+    void diag_state(const float4 **posm_out, const float4 **vel_out) const override {
+        *posm_out = posm[cur];
+        *vel_out = vel;
+    }
     // one-process multi-GPU (nb_group.cpp): this simulator's two position buffers, and the peers'
     void position_buffers(float4 *out[2]) const {
         out[0] = posm[0];

@@ -3421,6 +3421,13 @@ class TreeSim final : public SimBase {
         return check_status();
     }
 
+    // the state read_particles converts: buffer set `cur` (which flips when the walk gathers)
+    void diag_state(const float4 **posm_out, const float4 **vel_out) const override {
+        *posm_out = posm[cur];
+        *vel_out = vel[cur];
+    }
+    int diag_status() override { return check_status(); }
+
     // device.poll(Wait) (offline_headless.rs:43) + the device status words: a step that overflowed
     // the 4N node buffer, cut a LET export short, met inseparable bodies or tripped the walk's
     // stack guard must not look like a good step to a caller that never reads particles back

@@ -28,6 +28,7 @@ namespace nbody {
 using Particle = nb_particle;    // 40 B
 using SimParams = nb_sim_params;  // 16 B
 using Octant = nb_octant;        // 52 B
+using Diagnostics = nb_diagnostics;  // conserved-quantity monitor (no reference counterpart)
 
 inline SimParams default_sim_params() {  // SimParams::default(), sims/mod.rs:62-71
     return SimParams{NB_DEFAULT_PARTICLE_NUM, NB_DEFAULT_G, NB_DEFAULT_E, NB_DEFAULT_DT};
@@ -127,6 +128,12 @@ class Simulator {
         check(nb_sim_step_num(h_, &v));
         return v;
     }
+    // energy, momentum, angular momentum of the current state; potential: the O(N^2) pair potential too
+    Diagnostics diagnostics(bool potential = false) {
+        Diagnostics d{};
+        check(nb_sim_diagnostics(h_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
+        return d;
+    }
     nb_sim *handle() { return h_; }
 
    protected:
@@ -225,6 +232,11 @@ class OfflineHeadless {
         uint64_t v = 0;
         check(nb_runner_step_num(r_, &v));
         return v;
+    }
+    Diagnostics diagnostics(bool potential = false) {  // one device only
+        Diagnostics d{};
+        check(nb_runner_diagnostics(r_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
+        return d;
     }
     std::vector<Particle> read_particles() {
         SimParams p{};
