@@ -368,6 +368,80 @@ typedef struct nb_diagnostics {
  * NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
 int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out);
 
+/* ------------------------------------------------------------------------- */
+/* Renderer -- frames of the particle state, drawn off screen on the device   */
+/* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
+/* and src/draw.wgsl; no window is opened)                                    */
+/* ------------------------------------------------------------------------- */
+/* The reference draws one small triangle per particle, without depth test or
+ * culling, every fragment the constant (1,1,1,0.25) alpha-blended over a constant
+ * clear colour (draw.wgsl:19-22, online_renderer.rs:340-352).  The blended pixel
+ * then depends only on how many triangles cover it, so the frame is defined by an
+ * integer coverage count per pixel and a closed-form colour.  The rule, which
+ * DESIGN.md 6c states in full (binary32, one rounding per operation, in this
+ * order), per body of the state nb_sim_read_particles would return:
+ *   clip      c_r = ((M[r,0] x + M[r,1] y) + M[r,2] z) + M[r,3], M[r,c] = view_proj[4c + r]
+ *             (draw.wgsl:17); drawn only if c_w > 0 and 0 <= c_z <= c_w (wgpu's
+ *             depth clip; all three vertices share c_z and c_w), else `clipped`
+ *   vertices  offsets (-s,-s), (s,-s), (0,s), s = half_size (online_renderer.rs:224,
+ *             draw.wgsl:13-16): ndc = (c_xy + off) / c_w, sx = (ndc_x 0.5 + 0.5) W,
+ *             sy = (0.5 - ndc_y 0.5) H; any |sx| or |sy| not below 2^22: `oversize`
+ *   snap      X = rint(256 sx), Y = rint(256 sy) (ties to even): 8 sub-pixel bits
+ *   coverage  pixel (i, j), centre (256 i + 128, 256 j + 128), by integer edge
+ *             functions, either winding, top-left rule, zero area covers nothing,
+ *             scissored to the image; counts[j W + i] = triangles covering it
+ *   colour    lin = 1 - (1 - clear)(1 - alpha)^k per channel, byte =
+ *             round(255 enc(lin)), enc = sRGB transfer with NB_RENDER_SRGB, A = 255
+ * A body with a non-finite coordinate is `nonfinite` and not drawn.
+ * drawn + clipped + oversize + nonfinite == n.  The order of the bodies does not
+ * matter (a TreeSim's state is in tree order).  The call is ordered after the
+ * enqueued steps on the simulator's stream, ends with one synchronisation, copies
+ * only the images asked for, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory. */
+#define NB_RENDER_SRGB 1u /* encode the bytes with the sRGB transfer function */
+
+typedef struct nb_camera { /* `Camera`, online_renderer.rs:12-20 */
+    float eye[3], target[3], up[3];
+    float aspect, fovy_deg, znear, zfar;
+} nb_camera;
+
+typedef struct nb_render_params {
+    uint32_t width, height; /* 1..16384 each */
+    float view_proj[16];    /* column-major (CameraUniform, online_renderer.rs:22-26) */
+    float half_size;        /* 0.006f (online_renderer.rs:224) */
+    float clear[3];         /* 0.01, 0, 0.05 (online_renderer.rs:345-349); each in [0,1] */
+    float alpha;            /* 0.25 (draw.wgsl:21); in [0,1] */
+    uint32_t flags, reserved;
+} nb_render_params;
+
+typedef struct nb_render_stats {
+    uint64_t step_num; /* the step the drawn state is the result of */
+    uint64_t n, drawn, clipped, oversize, nonfinite;
+    uint64_t fragments; /* sum of counts */
+    uint32_t max_count, reserved;
+} nb_render_stats;
+
+/* The camera OnlineRenderer::new sets up (online_renderer.rs:231-239): eye (0,1,2),
+ * target 0, up +y, aspect width/height, fovy 45 degrees, znear 1e-5, zfar 100. */
+int nb_camera_default(nb_camera *cam, uint32_t width, uint32_t height);
+/* Camera::build_view_projection_matrix (online_renderer.rs:41-54):
+ * OPENGL_TO_WGPU_MATRIX * perspective * look_at_rh with cgmath's formulas, evaluated
+ * in double from the float fields and rounded to float once; out is column-major.
+ * NB_ERR_INVALID for a camera that has no finite matrix. */
+int nb_camera_view_proj(const nb_camera *cam, float out[16]);
+/* The reference's frame: default camera, half_size, clear colour and alpha, sRGB. */
+int nb_render_params_default(nb_render_params *params, uint32_t width, uint32_t height);
+/* Draw the simulator's current state (the render pass of OnlineRenderer::render,
+ * online_renderer.rs:331-367).  rgba: width*height*4 bytes, rows top to bottom, or
+ * NULL; counts: width*height, or NULL; stats: or NULL.  NB_ERR_INVALID for null
+ * params, a size outside 1..16384, unknown flags, alpha or clear outside [0,1], a
+ * non-finite half_size or matrix (all checked before any device call);
+ * NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1).  Tuning key
+ * "render_design" (nb_sim_set_tuning; speed only, identical counts): 0 automatic,
+ * 1 direct (global atomics), 2 tiled (screen tiles in LDS). */
+int nb_sim_render(nb_sim *sim, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
+                  nb_render_stats *stats);
+
 int nb_sim_destroy(nb_sim *sim);
 
 /* ------------------------------------------------------------------------- */
@@ -441,6 +515,10 @@ int nb_runner_step_num(const nb_runner *runner, uint64_t *out);
 /* nb_sim_diagnostics of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out);
+/* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
+                     nb_render_stats *stats);
 /* Borrow the runner's simulator (owned by the runner); NULL for a several-GPU runner. */
 nb_sim *nb_runner_sim(nb_runner *runner);
 int nb_runner_destroy(nb_runner *runner);

@@ -34,7 +34,8 @@ from ._lib import (NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS, OCTANT_DTYPE, PARTIC
 __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "TreeSim",
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
-           "shard_padded_bodies", "naive_variants", "Diagnostics"]
+           "shard_padded_bodies", "naive_variants", "Diagnostics",
+           "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
 
@@ -123,6 +124,132 @@ class Diagnostics:
 
 def _diag_flags(potential: bool) -> int:
     return _lib.NB_DIAG_MOMENTS | (_lib.NB_DIAG_POTENTIAL if potential else 0)
+
+
+@dataclass(frozen=True)
+class Camera:
+    """nb_camera (`Camera`, online_renderer.rs:12-20)."""
+    eye: Sequence[float] = (0.0, 1.0, 2.0)
+    target: Sequence[float] = (0.0, 0.0, 0.0)
+    up: Sequence[float] = (0.0, 1.0, 0.0)
+    aspect: float = 1.0
+    fovy_deg: float = 45.0
+    znear: float = 0.00001
+    zfar: float = 100.0
+
+    @staticmethod
+    def default(width: int, height: int) -> "Camera":
+        """nb_camera_default: the camera OnlineRenderer::new sets up (online_renderer.rs:231-239)."""
+        c = _lib.nb_camera()
+        check(_lib.lib().nb_camera_default(C.byref(c), int(width), int(height)))
+        return Camera(tuple(c.eye), tuple(c.target), tuple(c.up), float(c.aspect), float(c.fovy_deg),
+                      float(c.znear), float(c.zfar))
+
+    def to_c(self) -> "_lib.nb_camera":
+        c = _lib.nb_camera()
+        for k in range(3):
+            c.eye[k], c.target[k], c.up[k] = float(self.eye[k]), float(self.target[k]), float(self.up[k])
+        c.aspect, c.fovy_deg, c.znear, c.zfar = self.aspect, self.fovy_deg, self.znear, self.zfar
+        return c
+
+    def view_proj(self) -> np.ndarray:
+        """nb_camera_view_proj: the 16 floats of OPENGL_TO_WGPU_MATRIX * perspective * look_at_rh,
+        column-major (online_renderer.rs:41-54)."""
+        out = (C.c_float * 16)()
+        c = self.to_c()
+        check(_lib.lib().nb_camera_view_proj(C.byref(c), out))
+        return np.array(list(out), dtype=np.float32)
+
+
+@dataclass(frozen=True)
+class RenderParams:
+    """nb_render_params: the frame's size, the column-major view-projection matrix and the constants of
+    the reference's draw pass (online_renderer.rs:224, 345-349; draw.wgsl:21)."""
+    width: int
+    height: int
+    view_proj: Sequence[float]
+    half_size: float = 0.006
+    clear: Sequence[float] = (0.01, 0.0, 0.05)
+    alpha: float = 0.25
+    srgb: bool = True
+
+    @staticmethod
+    def default(width: int, height: int) -> "RenderParams":
+        """nb_render_params_default: the reference's frame at this size."""
+        p = _lib.nb_render_params()
+        check(_lib.lib().nb_render_params_default(C.byref(p), int(width), int(height)))
+        return RenderParams(int(p.width), int(p.height), np.array(list(p.view_proj), dtype=np.float32),
+                            float(p.half_size), tuple(p.clear), float(p.alpha), bool(p.flags & _lib.NB_RENDER_SRGB))
+
+    def to_c(self) -> "_lib.nb_render_params":
+        p = _lib.nb_render_params()
+        p.width, p.height = int(self.width), int(self.height)
+        vp = np.asarray(self.view_proj, dtype=np.float32).reshape(-1)
+        if vp.size != 16:
+            raise ValueError("view_proj must hold 16 floats (column-major)")
+        for k in range(16):
+            p.view_proj[k] = float(vp[k])
+        p.half_size, p.alpha = float(self.half_size), float(self.alpha)
+        for k in range(3):
+            p.clear[k] = float(self.clear[k])
+        p.flags = _lib.NB_RENDER_SRGB if self.srgb else 0
+        return p
+
+
+@dataclass(frozen=True)
+class RenderStats:
+    """nb_render_stats: drawn + clipped + oversize + nonfinite == n; fragments = sum of the counts."""
+    step_num: int
+    n: int
+    drawn: int
+    clipped: int
+    oversize: int
+    nonfinite: int
+    fragments: int
+    max_count: int
+
+    @staticmethod
+    def _from_c(s: "_lib.nb_render_stats") -> "RenderStats":
+        return RenderStats(int(s.step_num), int(s.n), int(s.drawn), int(s.clipped), int(s.oversize),
+                           int(s.nonfinite), int(s.fragments), int(s.max_count))
+
+
+class Frame(np.ndarray):
+    """What render() returns: the (H, W, 4) uint8 RGBA image, rows top to bottom, with the frame's
+    RenderStats as .stats."""
+    stats: Optional[RenderStats] = None
+
+    def __array_finalize__(self, obj):
+        self.stats = getattr(obj, "stats", None)
+
+
+def _render_params(width, height, camera, view_proj, params) -> RenderParams:
+    if camera is not None and view_proj is not None:
+        raise ValueError("give a camera or a view_proj matrix, not both")
+    if view_proj is None:
+        view_proj = (camera if camera is not None else Camera.default(width, height)).view_proj()
+    return RenderParams(int(width), int(height), view_proj, **params)
+
+
+def _render(call, handle, rp: RenderParams, want_counts: bool):
+    p = rp.to_c()
+    rgba = np.empty((rp.height, rp.width, 4), dtype=np.uint8)
+    counts = np.empty((rp.height, rp.width), dtype=np.uint32) if want_counts else None
+    st = _lib.nb_render_stats()
+    check(call(handle, C.byref(p), rgba.ctypes.data, counts.ctypes.data if want_counts else None, C.byref(st)))
+    frame = rgba.view(Frame)
+    frame.stats = RenderStats._from_c(st)
+    return (frame, counts) if want_counts else frame
+
+
+def write_ppm(path, rgba) -> None:
+    """Write an (H, W, 3 or 4) uint8 image as a binary P6 file (the alpha channel is dropped)."""
+    a = np.asarray(rgba)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError("write_ppm takes an (H, W, 3 or 4) uint8 array")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
+        f.write(np.ascontiguousarray(a[:, :, :3]).tobytes())
 
 
 def version() -> str:
@@ -311,6 +438,16 @@ class Simulator:
         check(_lib.lib().nb_sim_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
         return Diagnostics._from_c(d)
 
+    def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
+               counts: bool = False, **params):
+        """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
+        online_renderer.rs:331-367): a Frame, the (H, W, 4) uint8 image with .stats; with counts=True
+        (frame, counts), counts the (H, W) uint32 coverage image.  camera: a Camera (default: the
+        reference's); view_proj: 16 floats, column-major, instead; params: half_size, clear, alpha,
+        srgb of RenderParams."""
+        return _render(_lib.lib().nb_sim_render, self._h, _render_params(width, height, camera, view_proj, params),
+                       counts)
+
     def write_particles(self, particles) -> None:
         arr = as_particles(particles)
         check(_lib.lib().nb_sim_write_particles(self._h, arr.ctypes.data, arr.shape[0]))
@@ -464,6 +601,12 @@ class OfflineHeadless:
         d = _lib.nb_diagnostics()
         check(_lib.lib().nb_runner_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
         return Diagnostics._from_c(d)
+
+    def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
+               counts: bool = False, **params):
+        """nb_runner_render: Simulator.render of the runner's simulator (one device only)."""
+        return _render(_lib.lib().nb_runner_render, self._h, _render_params(width, height, camera, view_proj, params),
+                       counts)
 
     def sim_params(self) -> SimParams:
         sp = _lib.nb_sim_params()

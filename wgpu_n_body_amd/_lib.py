@@ -46,14 +46,33 @@ class nb_diagnostics(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_camera(C.Structure):
+    _fields_ = [("eye", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3),
+                ("aspect", C.c_float), ("fovy_deg", C.c_float), ("znear", C.c_float), ("zfar", C.c_float)]
+
+
+class nb_render_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("view_proj", C.c_float * 16),
+                ("half_size", C.c_float), ("clear", C.c_float * 3), ("alpha", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class nb_render_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("drawn", C.c_uint64), ("clipped", C.c_uint64),
+                ("oversize", C.c_uint64), ("nonfinite", C.c_uint64), ("fragments", C.c_uint64),
+                ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(nb_sim_params) == 16 and C.sizeof(nb_add_params) == 8
 assert C.sizeof(nb_diagnostics) == 152
+assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
 
 NB_OK, NB_ERR_INVALID, NB_ERR_NO_DEVICE, NB_ERR_HIP, NB_ERR_ALLOC, NB_ERR_UNSUPPORTED = range(6)
 NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS = 0, 1
 NB_DIAG_MOMENTS, NB_DIAG_POTENTIAL = 1, 2
+NB_RENDER_SRGB = 1
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -65,10 +84,11 @@ ABI_SYMBOLS = [
     "nb_sim_wait", "nb_sim_sim_params", "nb_sim_read_particles", "nb_sim_write_particles",
     "nb_sim_read_tree", "nb_sim_exchange_region", "nb_sim_exchange_count",
     "nb_sim_exchange_region_i", "nb_sim_step_num", "nb_sim_encode_n_timed",
-    "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
+    "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics",
+    "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
-    "nb_runner_sim_params", "nb_runner_diagnostics", "nb_runner_sim", "nb_runner_destroy",
+    "nb_runner_sim_params", "nb_runner_diagnostics", "nb_runner_render", "nb_runner_sim", "nb_runner_destroy",
 ]
 
 
@@ -126,6 +146,10 @@ def lib() -> C.CDLL:
     L.nb_sim_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]
     L.nb_sim_debug_buffer.argtypes = [vp, C.c_char_p, vp, sz, P(sz)]
     L.nb_sim_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
+    L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]
+    L.nb_camera_view_proj.argtypes = [P(nb_camera), P(C.c_float)]
+    L.nb_render_params_default.argtypes = [P(nb_render_params), C.c_uint32, C.c_uint32]
+    L.nb_sim_render.argtypes = [vp, P(nb_render_params), vp, vp, P(nb_render_stats)]
     L.nb_naive_variant_count.restype = C.c_int
     L.nb_naive_variant_name.argtypes = [C.c_int]
     L.nb_naive_variant_name.restype = C.c_char_p
@@ -141,6 +165,7 @@ def lib() -> C.CDLL:
     L.nb_runner_rank_times.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int]
     L.nb_runner_sim_params.argtypes = [vp, P(nb_sim_params)]
     L.nb_runner_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
+    L.nb_runner_render.argtypes = [vp, P(nb_render_params), vp, vp, P(nb_render_stats)]
     L.nb_runner_sim.argtypes = [vp]
     L.nb_runner_sim.restype = vp
     L.nb_runner_destroy.argtypes = [vp]

@@ -24,6 +24,9 @@ SOURCES = [
     ("nb_naive.hip", []),
     ("nb_tree.hip", []),
     ("nb_diag.hip", []),
+    # the drawing rule and the camera are specified bit-exactly: no FMA contraction
+    ("nb_render.hip", ["-ffp-contract=off"]),
+    ("nb_camera.cpp", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

@@ -34,6 +34,7 @@ static size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 // ------------------------------------------------------------------------------------------
 SimBase::~SimBase() {
     diag_release(diag);  // (the derived destructor has bound the device)
+    render_release(render);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -564,6 +565,15 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         set_error("null key");
         return NB_ERR_INVALID;
     }
+    if (!std::strcmp(key, "render_design")) {  // the renderer's, whichever simulator holds the state
+        NB_GUARD({
+            if (!sim || !sim->impl) {
+                set_error("null simulator");
+                return NB_ERR_INVALID;
+            }
+            return sim_render_set_design(*sim->impl, value);
+        })
+    }
     NB_SIM_CALL(sim, set_tuning(key, value))
 }
 
@@ -590,6 +600,18 @@ int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out) {
             return NB_ERR_INVALID;
         }
         return sim_diagnostics(*sim->impl, flags, out);
+    })
+}
+
+int nb_sim_render(nb_sim *sim, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
+                  nb_render_stats *stats) {
+    if (int rc = render_check_params(params)) return rc;
+    NB_GUARD({
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        return sim_render(*sim->impl, *params, rgba, counts, stats);
     })
 }
 
@@ -787,6 +809,20 @@ int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out
         return NB_ERR_UNSUPPORTED;
     }
     return nb_sim_diagnostics(runner->sim, flags, out);
+}
+
+int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
+                     nb_render_stats *stats) {
+    if (int rc = render_check_params(params)) return rc;
+    if (!runner || (!runner->sim && !runner->group)) {
+        set_error("null runner");
+        return NB_ERR_INVALID;
+    }
+    if (runner->group) {
+        set_error("render: not available on a several-GPU runner (nb_runner_create_multi*)");
+        return NB_ERR_UNSUPPORTED;
+    }
+    return nb_sim_render(runner->sim, params, rgba, counts, stats);
 }
 
 nb_sim *nb_runner_sim(nb_runner *runner) { return runner ? runner->sim : nullptr; }

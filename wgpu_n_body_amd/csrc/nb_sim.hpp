@@ -9,6 +9,7 @@
 namespace nb {
 
 struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
+struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
 
 // What `trait Simulator` (src/sims/mod.rs:73-90) requires of an implementor, in HIP terms.
 class SimBase {
@@ -95,11 +96,19 @@ class SimBase {
     uint64_t step_num = 0;
     uint32_t n = 0, n_pad = 0, per_rank = 0, lo = 0, hi = 0;
     DiagWork *diag = nullptr;  // allocated by the first nb_sim_diagnostics
+    RenderWork *render = nullptr;  // allocated by the first nb_sim_render
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
 int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out);
 void diag_release(DiagWork *w);
+
+// nb_render.hip: nb_sim_render behind the handle (arguments already checked by render_check_params,
+// nb_camera.cpp), the "render_design" tuning key, and the release of the workspace
+int render_check_params(const nb_render_params *params);
+int sim_render(SimBase &sim, const nb_render_params &params, uint8_t *rgba, uint32_t *counts, nb_render_stats *stats);
+int sim_render_set_design(SimBase &sim, int design);
+void render_release(RenderWork *w);
 
 class NaiveSim final : public SimBase {
    public:

@@ -29,6 +29,9 @@ using Particle = nb_particle;    // 40 B
 using SimParams = nb_sim_params;  // 16 B
 using Octant = nb_octant;        // 52 B
 using Diagnostics = nb_diagnostics;  // conserved-quantity monitor (no reference counterpart)
+using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
+using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
+using RenderStats = nb_render_stats;
 
 inline SimParams default_sim_params() {  // SimParams::default(), sims/mod.rs:62-71
     return SimParams{NB_DEFAULT_PARTICLE_NUM, NB_DEFAULT_G, NB_DEFAULT_E, NB_DEFAULT_DT};
@@ -56,6 +59,30 @@ class Error : public std::runtime_error {
 inline void check(int rc) {
     if (rc != NB_OK) throw Error(rc, std::string("nbody_hip: ") + nb_last_error());
 }
+
+inline Camera default_camera(uint32_t width, uint32_t height) {  // online_renderer.rs:231-239
+    Camera c{};
+    check(nb_camera_default(&c, width, height));
+    return c;
+}
+inline RenderParams default_render_params(uint32_t width, uint32_t height) {
+    RenderParams p{};
+    check(nb_render_params_default(&p, width, height));
+    return p;
+}
+inline RenderParams render_params(const Camera &cam, uint32_t width, uint32_t height) {
+    RenderParams p = default_render_params(width, height);
+    check(nb_camera_view_proj(&cam, p.view_proj));  // Camera::build_view_projection_matrix
+    return p;
+}
+
+// A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
+struct Frame {
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> rgba;
+    std::vector<uint32_t> counts;  // filled on request
+    RenderStats stats{};
+};
 
 // init_fn: fn(&SimParams) -> Vec<Particle>, sims/mod.rs:79
 using InitFn = std::function<std::vector<Particle>(const SimParams &)>;
@@ -133,6 +160,16 @@ class Simulator {
         Diagnostics d{};
         check(nb_sim_diagnostics(h_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
         return d;
+    }
+    // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
+    Frame render(const RenderParams &p, bool counts = false) {
+        Frame f;
+        f.width = p.width;
+        f.height = p.height;
+        f.rgba.resize((size_t)p.width * p.height * 4);
+        if (counts) f.counts.resize((size_t)p.width * p.height);
+        check(nb_sim_render(h_, &p, f.rgba.data(), counts ? f.counts.data() : nullptr, &f.stats));
+        return f;
     }
     nb_sim *handle() { return h_; }
 
@@ -237,6 +274,15 @@ class OfflineHeadless {
         Diagnostics d{};
         check(nb_runner_diagnostics(r_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
         return d;
+    }
+    Frame render(const RenderParams &p, bool counts = false) {  // one device only
+        Frame f;
+        f.width = p.width;
+        f.height = p.height;
+        f.rgba.resize((size_t)p.width * p.height * 4);
+        if (counts) f.counts.resize((size_t)p.width * p.height);
+        check(nb_runner_render(r_, &p, f.rgba.data(), counts ? f.counts.data() : nullptr, &f.stats));
+        return f;
     }
     std::vector<Particle> read_particles() {
         SimParams p{};
