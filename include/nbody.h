@@ -297,7 +297,8 @@ int nb_sim_encode_n_timed(nb_sim *sim, int n, float *ms_total, float *ms_kernel)
  * computes the same step).  Also settable through the NB_NAIVE_VARIANT environment
  * variable at create time.  A TreeSim's keys ("tree_*": bodies per wave of the walk, sort
  * passes and fix-up, who gathers the velocities, where the tile scan runs, ...) are listed
- * with their defaults in TreeSim::set_tuning (nb_tree.hip): speed only -- every setting
+ * in the table of TreeSim::set_tuning (nb_tree.hip), one row per key with the values it accepts;
+ * the defaults are the initialisers of the members the rows point to: speed only -- every setting
  * computes the same step, bit for bit where the tests say so. */
 int nb_sim_set_tuning(nb_sim *sim, const char *key, int value);
 int nb_naive_variant_count(void);

@@ -1,6 +1,6 @@
 """Barnes-Hut parity on a real MI355X, through the C ABI -- `-m gpu`.
 
-Hot path under test: nb_sim_encode on a TreeSim (nb_tree.hip): bound, Morton keys, radix sort,
+Hot path under test: nb_sim_encode on a TreeSim (nb_tree.hip + nb_tree_*.hpp): bound, Morton keys, radix sort,
 reorder, octree build, mass/cog, tree walk + integrator -- the device replacement for
 TreeSim::encode (src/sims/tree.rs:262-353) + build_tree/sort_particles (tree.rs:417-602) +
 shaders/tree.wgsl:41-111.

@@ -9,5 +9,7 @@ P=wgpu_n_body_amd
 mkdir -p $P/_variants /tmp/nbv_$name
 python -m wgpu_n_body_amd.build > /dev/null 2>&1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -I$P/csrc "$@" -c $P/csrc/nb_tree.hip -o /tmp/nbv_$name/nb_tree.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $P/_variants/$name.so $P/_build/nb_naive.o /tmp/nbv_$name/nb_tree.o $P/_build/nb_abi.o $P/_build/nb_group.o $P/_build/nb_inits.o
+# every object of the in-tree build but nb_tree.o, so the list cannot go stale
+objs=$(ls $P/_build/*.o | grep -v '/nb_tree\.o$')
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $P/_variants/$name.so /tmp/nbv_$name/nb_tree.o $objs
 echo $P/_variants/$name.so

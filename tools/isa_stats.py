@@ -3,6 +3,9 @@ and the instruction mix of the hottest loop (the innermost loop with the most in
 Builder tool; runs in the CPU container (hipcc cross-compiles).
 
     python tools/isa_stats.py nb_tree.hip walk_cells_kernelILi8ELb0ELi0 [--dump]
+
+nb_tree.hip is the one translation unit of the Barnes-Hut path: its kernels are in the nb_tree_*.hpp headers
+it includes (the walk: nb_tree_walk.hpp), so it is still the file to compile.
 """
 import collections
 import os

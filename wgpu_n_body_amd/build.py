@@ -32,7 +32,6 @@ SOURCES = [
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction
     ("nb_inits.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["nb_common.hpp", "nb_sim.hpp", "nb_group.hpp", os.path.join(INCLUDE, "nbody.h")]
 
 
 def _hipcc() -> str:
@@ -66,8 +65,9 @@ def _newer(target: str, deps) -> bool:
 def build_native(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
-    hdrs.append(os.path.abspath(__file__))
+    # every header of the directory (as source_hash() lists it): an edited header recompiles all objects
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
+    hdrs += [os.path.join(INCLUDE, "nbody.h"), os.path.abspath(__file__)]
     common = ["-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}", "-Wall",
               "-Wno-unused-function"]
     objs = []

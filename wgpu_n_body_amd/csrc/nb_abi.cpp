@@ -1,7 +1,7 @@
 // nb_abi.cpp -- the C ABI of include/nbody.h: simulator objects (the reference's
 // `trait Simulator` implementors NaiveSim / TreeSim) and the OfflineHeadless-shaped runner.
 //
-// Host side only; the kernels live in nb_naive.hip / nb_tree.hip.  Everything the
+// Host side only; the kernels live in nb_naive.hip / nb_tree.hip (nb_tree_*.hpp).  Everything the
 // reference does through wgpu (buffers, bind groups, command encoders, queue.submit,
 // device.poll) maps to hipMalloc'd SoA buffers, a ping-pong index and one hipStream_t.
 #include <cstdlib>

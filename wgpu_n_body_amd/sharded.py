@@ -280,7 +280,7 @@ def _now() -> float:
 def _morton_keys(particles: np.ndarray) -> np.ndarray:
     """63-bit Morton keys of the positions quantised to 21 bits per axis in the cube
     [-bound, bound]^3, bound = max |coordinate| (as a float32, the value the device is given):
-    the same arithmetic as let_ref_key in nb_tree.hip."""
+    the same arithmetic as let_ref_key in csrc/nb_tree_let.hpp."""
     f = as_floats(particles)
     pos = f[:, 0:3].astype(np.float64)
     bound = float(np.float32(max(float(np.abs(f[:, 0:3]).max()), 1e-30)))
