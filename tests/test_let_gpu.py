@@ -589,7 +589,9 @@ def test_native_let_runner_reports_a_migration_that_overflows_its_segments(gpu):
     """A thin disc centred on the root's z = 0 border: a third of a rank's bodies change their top-level
     octant -- and with it their Morton domain -- within two steps, more than a migration segment
     (capacity / 8 bodies per destination) holds.  The step must fail with a message, not move a cut-off
-    list (LetTreeSim raises the same way; the remedy is a rebalance)."""
+    list (LetTreeSim raises the same way; the remedy is a rebalance).  The failure is one rank's host-side
+    error return: the other rank threads must still meet every barrier of the batch, so the runner stays
+    answerable afterwards -- a further step reports the failed state and destroy() returns."""
     nb = gpu
     sp, p = tagged(nb, 9000, 34, "disc")
     r = nb.OfflineHeadless(nb.TreeSim, nb.SimParams(particle_num=9000, g=0.00001, dt=0.0016),
@@ -598,6 +600,9 @@ def test_native_let_runner_reports_a_migration_that_overflows_its_segments(gpu):
     with pytest.raises(nb.NBodyError) as ei:
         r.step()
     assert "leavers" in str(ei.value)
+    with pytest.raises(nb.NBodyError) as again:
+        r.step()
+    assert "failed state" in str(again.value)
     r.destroy()
 
 

@@ -6,7 +6,10 @@ time per step is then the Python + ctypes + torch.distributed enqueue cost, whic
 below the per-rank kernel time (164 us at 8 ranks x 8192 bodies) for the
 pipelined loop to keep the GPU busy.
 
-    python tools/host_overhead.py [--bodies 2048] [--steps 3000]
+    python tools/host_overhead.py [--bodies 2048] [--steps 3000] [--runners-only]
+
+--runners-only prints just the rows of the one-process runners of the C ABI (no torch.distributed); with NB_LIB it
+measures another build of the library, which is how two builds are compared.
 """
 import argparse
 import os
@@ -16,12 +19,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main() -> None:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--bodies", type=int, default=2048)
-    ap.add_argument("--steps", type=int, default=3000)
-    args = ap.parse_args()
-
+def python_hosts(args) -> None:
     import torch
     import torch.distributed as dist
     import wgpu_n_body_amd as nb
@@ -79,6 +77,10 @@ def main() -> None:
         let.destroy()
     dist.destroy_process_group()
 
+
+def native_runners() -> None:
+    import wgpu_n_body_amd as nb
+
     # The one-process runner of the C ABI (nb_runner_create_multi): 8 ranks on this one GPU, 2,048
     # bodies -- kernels far shorter than the host work, so this is the library's own cost per step
     # (8 host threads: two launches, 7 event waits, one record each, one host barrier)
@@ -118,6 +120,17 @@ def main() -> None:
         t = time.perf_counter() - t0
         print(f"{'nb_runner_create_multi_let, n=%d, %d ranks' % (n, world):52s} {t / 64 * 1e6:8.1f} us/step", flush=True)
         runner.destroy()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bodies", type=int, default=2048)
+    ap.add_argument("--steps", type=int, default=3000)
+    ap.add_argument("--runners-only", action="store_true")
+    args = ap.parse_args()
+    if not args.runners_only:
+        python_hosts(args)
+    native_runners()
 
 
 if __name__ == "__main__":

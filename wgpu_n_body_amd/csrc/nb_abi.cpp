@@ -350,10 +350,14 @@ int NaiveSim::set_tuning(const char *key, int value) {
     return NB_ERR_INVALID;
 }
 
+// add_params == NULL: the all-pairs simulator
+static nb_add_params add_params_or_default(const nb_add_params *ap) {
+    return ap ? *ap : nb_add_params{NB_NAIVE_SIM_PARAMS, 0.f};
+}
+
 int make_sim_impl(std::unique_ptr<SimBase> &out, const nb_sim_params *sp, const nb_add_params *ap,
                   const nb_placement *pl, const nb_particle *particles, size_t count) {
-    nb_add_params add{NB_NAIVE_SIM_PARAMS, 0.f};
-    if (ap) add = *ap;
+    nb_add_params add = add_params_or_default(ap);
     std::unique_ptr<SimBase> impl;
     if (add.kind == NB_NAIVE_SIM_PARAMS) {
         impl.reset(new (std::nothrow) NaiveSim());
@@ -657,6 +661,14 @@ int nb_runner_create(nb_runner **out, const nb_sim_params *sim_params,
 static int runner_create_group(nb_runner **out, const nb_sim_params *sim_params, const nb_add_params *add_params,
                                nb_init_fn init, void *user, const int *device_ids, int n_devices, int let_migrate_every);
 
+static int check_runner(const nb_runner *runner) {  // a runner that owns a simulator or a group
+    if (!runner || (!runner->sim && !runner->group)) {
+        set_error("null runner");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 int nb_runner_create_multi(nb_runner **out, const nb_sim_params *sim_params, const nb_add_params *add_params,
                            nb_init_fn init, void *user, const int *device_ids, int n_devices) {
     return runner_create_group(out, sim_params, add_params, init, user, device_ids, n_devices, -1);
@@ -681,10 +693,7 @@ static int runner_create_group(nb_runner **out, const nb_sim_params *sim_params,
         *out = nullptr;
         if (n_devices == 1 && let_migrate_every < 0)
             return nb_runner_create(out, sim_params, add_params, init, user, device_ids[0]);
-        nb_add_params add;
-        add.kind = NB_NAIVE_SIM_PARAMS;
-        add.theta = 0.f;
-        if (add_params) add = *add_params;
+        const nb_add_params add = add_params_or_default(add_params);
         if (add.kind != NB_NAIVE_SIM_PARAMS && add.kind != NB_TREE_SIM_PARAMS) {
             set_error("unknown add_params.kind %d", add.kind);
             return NB_ERR_INVALID;
@@ -703,10 +712,7 @@ static int runner_create_group(nb_runner **out, const nb_sim_params *sim_params,
 
 // offline_headless.rs:38-44: encode -> submit -> cleanup -> poll(Wait)
 int nb_runner_step(nb_runner *runner) {
-    if (!runner || (!runner->sim && !runner->group)) {
-        set_error("null runner");
-        return NB_ERR_INVALID;
-    }
+    if (int rc = check_runner(runner)) return rc;
     if (runner->group) NB_GUARD({ return runner->group->step_n(1); })
     if (int rc = nb_sim_encode(runner->sim)) return rc;
     if (int rc = nb_sim_cleanup(runner->sim)) return rc;
@@ -714,10 +720,7 @@ int nb_runner_step(nb_runner *runner) {
 }
 
 int nb_runner_step_n(nb_runner *runner, int n) {
-    if (!runner || (!runner->sim && !runner->group)) {
-        set_error("null runner");
-        return NB_ERR_INVALID;
-    }
+    if (int rc = check_runner(runner)) return rc;
     if (runner->group) NB_GUARD({ return runner->group->step_n(n); })
     hipEvent_t ev[2] = {nullptr, nullptr};
     const bool prof = runner->profiling && runner->sim->impl && runner->sim->impl->bind_device() == NB_OK &&
@@ -737,17 +740,14 @@ int nb_runner_step_n(nb_runner *runner, int n) {
 }
 
 int nb_runner_set_profiling(nb_runner *runner, int on) {
-    if (!runner || (!runner->sim && !runner->group)) {
-        set_error("null runner");
-        return NB_ERR_INVALID;
-    }
+    if (int rc = check_runner(runner)) return rc;
     runner->profiling = on != 0;
     if (runner->group) return runner->group->set_profiling(on != 0);
     return NB_OK;
 }
 
 int nb_runner_rank_times(nb_runner *runner, float *kernel_ms, float *wait_ms, int n) {
-    if (!runner || (!runner->sim && !runner->group) || n < 1) {
+    if (check_runner(runner) || n < 1) {
         set_error("null runner");
         return NB_ERR_INVALID;
     }
@@ -800,10 +800,7 @@ int nb_runner_step_num(const nb_runner *runner, uint64_t *out) {
 }
 
 int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out) {
-    if (!runner || (!runner->sim && !runner->group)) {
-        set_error("null runner");
-        return NB_ERR_INVALID;
-    }
+    if (int rc = check_runner(runner)) return rc;
     if (runner->group && out && !(flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL))) {
         set_error("diagnostics: not available on a several-GPU runner (nb_runner_create_multi*)");
         return NB_ERR_UNSUPPORTED;
@@ -814,10 +811,7 @@ int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
                      nb_render_stats *stats) {
     if (int rc = render_check_params(params)) return rc;
-    if (!runner || (!runner->sim && !runner->group)) {
-        set_error("null runner");
-        return NB_ERR_INVALID;
-    }
+    if (int rc = check_runner(runner)) return rc;
     if (runner->group) {
         set_error("render: not available on a several-GPU runner (nb_runner_create_multi*)");
         return NB_ERR_UNSUPPORTED;

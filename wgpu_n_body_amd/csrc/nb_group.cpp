@@ -32,6 +32,12 @@
 // reads them: two events per rank and step ("step finished", "slices pushed").  Bit for bit the
 // single TreeSim.  The scheme that also shards the build -- Morton domains + LET exchange,
 // nb_runner_create_multi_let -- is hosted here too: see create_let / let_step below.
+//
+// The barrier contract.  The host barrier counts threads, not work: a batch of steps finishes (and the destructor
+// returns) only if every rank thread arrives at every barrier.  Per step that is 1 barrier in the all-pairs
+// scheme, 2 with the replicated tree, 2 with LET plus 1 on a migration step; per batch 1 more, after the streams
+// have drained.  A rank passes every one of them whether or not it, or a peer, has failed: an error (RankCtx::fail)
+// only stops the enqueuing between the barriers, on every rank, and no step function returns ahead of a barrier.
 #include <atomic>
 #include <algorithm>
 #include <cmath>
@@ -106,18 +112,49 @@ struct RankProf {
     }
 };
 
+// What a rank tells its peers with an event, one pair of events (steps t and t + 1) per kind
+enum EventKind {
+    kDone,    // "my step t has finished"
+    kPushed,  // Barnes-Hut: "my slices / my LET records are in every peer's arrays"
+    kMeta,    // LET: "my bounds are in every peer's table"
+    kEventKinds
+};
+
 struct DeviceGroup::Rank {
     std::unique_ptr<SimBase> sim;
     RankProf prof;
     NaiveSim *naive = nullptr;
     int device = 0;
-    hipEvent_t done[2] = {nullptr, nullptr};
-    hipEvent_t pushed[2] = {nullptr, nullptr};  // Barnes-Hut: "my slices / my LET records are in every peer's arrays"
-    hipEvent_t meta[2] = {nullptr, nullptr};    // LET: "my bounds are in every peer's table"
-    uint32_t active = 0;                        // LET: bodies this rank holds (changes with migration)
+    hipEvent_t ev[kEventKinds][2] = {};
+    uint32_t active = 0;  // LET: bodies this rank holds (changes with migration)
     std::thread th;
     int rc = NB_OK;
     std::string err;
+
+    // a rank on `device`: its simulator over `bodies` with placement rank / world, and its events
+    static int make(std::unique_ptr<Rank> &out, int device, int rank, int world, const nb_sim_params &sp,
+                    const nb_add_params &add, const nb_particle *bodies, size_t count) {
+        std::unique_ptr<Rank> rk(new Rank());
+        rk->device = device;
+        nb_placement pl{};
+        pl.device_id = device;
+        pl.rank = rank;
+        pl.world = world;
+        if (int rc = make_sim_impl(rk->sim, &sp, &add, &pl, bodies, count)) return rc;
+        NB_HIP_TRY(hipSetDevice(device));
+        for (auto &pair : rk->ev)
+            for (hipEvent_t &e : pair) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        out = std::move(rk);
+        return NB_OK;
+    }
+    ~Rank() {  // (the thread has been joined)
+        (void)hipSetDevice(device);
+        if (sim) (void)sim->wait();
+        for (auto &pair : ev)
+            for (hipEvent_t e : pair)
+                if (e) (void)hipEventDestroy(e);
+        prof.destroy();
+    }
 };
 
 struct DeviceGroup::Shared {
@@ -144,18 +181,7 @@ DeviceGroup::~DeviceGroup() {
     sh_->cv_cmd.notify_all();
     for (auto &r : ranks_)
         if (r->th.joinable()) r->th.join();
-    for (auto &r : ranks_) {
-        (void)hipSetDevice(r->device);
-        if (r->sim) (void)r->sim->wait();
-        for (hipEvent_t e : r->done)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : r->pushed)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : r->meta)
-            if (e) (void)hipEventDestroy(e);
-        r->prof.destroy();
-        r->sim.reset();
-    }
+    ranks_.clear();  // in rank order: each waits for its stream, then releases its events and its simulator
 }
 
 // ---- Barnes-Hut with a sharded build: Morton domains + LET exchange --------------
@@ -278,18 +304,13 @@ int DeviceGroup::create_let(const nb_sim_params &sp, const nb_add_params &add, c
     mig_cap_ = (uint32_t)std::max<size_t>(1024, capacity / 8);  // leavers per destination per migration
     std::vector<nb_particle> padded(capacity);
     for (int r = 0; r < world; ++r) {
-        std::unique_ptr<Rank> rk(new Rank());
-        rk->device = device_ids[r];
         const size_t lo = cuts[(size_t)r], cnt = cuts[(size_t)r + 1] - lo;
         std::fill(padded.begin(), padded.end(), nb_particle{});
         for (size_t i = 0; i < cnt; ++i) padded[i] = particles[order[lo + i]];
         nb_sim_params spl = sp;
         spl.particle_num = (uint32_t)capacity;
-        nb_placement pl{};
-        pl.device_id = device_ids[r];
-        pl.rank = 0;
-        pl.world = 1;
-        if (int rc = make_sim_impl(rk->sim, &spl, &add, &pl, padded.data(), capacity)) return rc;
+        std::unique_ptr<Rank> rk;  // a TreeSim of its own over the rank's bodies (placement rank 0 of 1)
+        if (int rc = Rank::make(rk, device_ids[r], 0, 1, spl, add, padded.data(), capacity)) return rc;
         SimBase &sim = *rk->sim;
         if (int rc = sim.set_tuning("tree_let_world", world)) return rc;
         if (int rc = sim.set_tuning("tree_let_rank", r)) return rc;
@@ -298,10 +319,6 @@ int DeviceGroup::create_let(const nb_sim_params &sp, const nb_add_params &add, c
         const unsigned long long none = 0;  // (one rank: no border, but not a null pointer)
         if (int rc = sim.let_set_owners(splits.empty() ? &none : splits.data(), world, ref_bound, mig_cap_)) return rc;
         rk->active = (uint32_t)cnt;
-        NB_HIP_TRY(hipSetDevice(rk->device));
-        for (hipEvent_t &e : rk->done) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : rk->pushed) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : rk->meta) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ranks_.push_back(std::move(rk));
     }
     sh_->mig.assign((size_t)world * (size_t)world, 0u);
@@ -325,8 +342,7 @@ int DeviceGroup::create(std::unique_ptr<DeviceGroup> &out, const nb_sim_params &
         return NB_ERR_ALLOC;
     }
     g->params_ = sp;
-    g->tree_ = add.kind == NB_TREE_SIM_PARAMS;
-    g->let_ = g->tree_ && let_migrate_every >= 0;
+    g->scheme_ = add.kind != NB_TREE_SIM_PARAMS ? kAllPairs : let_migrate_every >= 0 ? kLet : kReplicatedTree;
     g->migrate_every_ = let_migrate_every > 0 ? let_migrate_every : 0;
     const int world = n_devices;
     for (int r = 0; r < world; ++r) {
@@ -335,27 +351,15 @@ int DeviceGroup::create(std::unique_ptr<DeviceGroup> &out, const nb_sim_params &
             return NB_ERR_INVALID;
         }
     }
-    if (g->let_) {
+    if (g->scheme_ == kLet) {
         if (int rc = g->create_let(sp, add, particles, device_ids, world)) return rc;
-    }
-    for (int r = 0; r < world && !g->let_; ++r) {
-        if (device_ids[r] < 0 || device_ids[r] >= visible) {
-            set_error("device_ids[%d] = %d out of range (%d devices)", r, device_ids[r], visible);
-            return NB_ERR_INVALID;
+    } else {
+        for (int r = 0; r < world; ++r) {  // every rank over all bodies, as rank r of world
+            std::unique_ptr<Rank> rk;
+            if (int rc = Rank::make(rk, device_ids[r], r, world, sp, add, particles, sp.particle_num)) return rc;
+            if (g->scheme_ == kAllPairs) rk->naive = static_cast<NaiveSim *>(rk->sim.get());
+            g->ranks_.push_back(std::move(rk));
         }
-        std::unique_ptr<Rank> rk(new Rank());
-        rk->device = device_ids[r];
-        nb_placement pl{};
-        pl.device_id = device_ids[r];
-        pl.rank = r;
-        pl.world = world;
-        if (int rc = make_sim_impl(rk->sim, &sp, &add, &pl, particles, sp.particle_num)) return rc;
-        rk->naive = g->tree_ ? nullptr : static_cast<NaiveSim *>(rk->sim.get());
-        NB_HIP_TRY(hipSetDevice(rk->device));
-        for (hipEvent_t &e : rk->done) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : rk->pushed) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t &e : rk->meta) NB_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        g->ranks_.push_back(std::move(rk));
     }
     // peer access between every pair of distinct devices, then hand every rank its peers' buffers
     for (int r = 0; r < world; ++r) {
@@ -376,7 +380,7 @@ int DeviceGroup::create(std::unique_ptr<DeviceGroup> &out, const nb_sim_params &
     }
     if (world > 1)
         if (int rc = g->check_peer_stores()) return rc;
-    for (int r = 0; r < world && !g->tree_; ++r) {
+    for (int r = 0; r < world && g->scheme_ == kAllPairs; ++r) {
         float4 *b0[kMaxPeers], *b1[kMaxPeers];
         int k = 0;
         for (int q = 0; q < world; ++q) {
@@ -457,144 +461,194 @@ int DeviceGroup::check_peer_stores() {
     return rc;
 }
 
-// One LET step of rank r (see create_let).  Every rank thread passes the same barriers whatever fails.
-template <typename Fail, typename Failed>
-void DeviceGroup::let_step(int r, uint64_t t, Fail &fail, Failed &failed) {
-    Rank &me = *ranks_[r];
-    SimBase &sim = *me.sim;
-    const int world = (int)ranks_.size();
-    const bool prof = sh_->profiling.load(std::memory_order_relaxed);
-    auto mark_k = [&] { me.prof.mark(prof, RankProf::kKernel, sim.stream); };
-    auto mark_w = [&] { me.prof.mark(prof, RankProf::kWait, sim.stream); };
-    auto hip_ok = [&](hipError_t e, const char *what) {
+// What one rank's thread steps with, made by worker() for every batch: the rank, the group it belongs to, and
+// the error handling every step function shares.  An error is recorded once per rank, with its text, and raises
+// the group's flag; from then on every rank stops enqueuing and only keeps meeting the others (the barrier contract
+// at the top of this file).
+struct DeviceGroup::RankCtx {
+    DeviceGroup &g;
+    Rank &me;
+    SimBase &sim;
+    const int r, world;
+    const bool prof;
+
+    void fail(int rc) {
+        if (me.rc == NB_OK) {
+            me.rc = rc;
+            me.err = nb_last_error();
+        }
+        g.sh_->failed.store(true, std::memory_order_release);
+    }
+    // (asked several times per step and rank: a relaxed load, not the group's mutex -- a rank that sees the
+    // flag a step late only enqueues one more step of work that nobody reads)
+    bool failed() const { return g.sh_->failed.load(std::memory_order_relaxed); }
+    bool ok(int rc) {  // of a simulator call, which has set its own error text
+        if (rc != NB_OK) fail(rc);
+        return rc == NB_OK;
+    }
+    bool hip_ok(hipError_t e, const char *what) {
         if (e == hipSuccess) return true;
         set_error("%s failed: %s", what, hipGetErrorString(e));
         fail(NB_ERR_HIP);
         return false;
-    };
-    auto region = [&](int q, int k, void **base, size_t *seg) {  // base (and per-rank length) of region k on rank q
+    }
+    void barrier() { g.sh_->bar->wait(); }
+    void mark_kernel() { me.prof.mark(prof, RankProf::kKernel, sim.stream); }
+    void mark_wait() { me.prof.mark(prof, RankProf::kWait, sim.stream); }
+    bool record(EventKind kind, uint64_t t) { return hip_ok(hipEventRecord(me.ev[kind][t & 1], sim.stream), "hipEventRecord"); }
+
+    // this rank's stream waits for every peer's event of step t (none of them when `nothing_yet`: the first step),
+    // between a wait mark and a kernel mark; the first error ends it
+    hipError_t wait_events(EventKind kind, uint64_t t, bool nothing_yet = false) {
+        mark_wait();
+        hipError_t e = hipSuccess;
+        for (int q = 0; q < world && e == hipSuccess && !nothing_yet; ++q)
+            if (q != r) e = hipStreamWaitEvent(sim.stream, g.ranks_[q]->ev[kind][t & 1], 0);
+        mark_kernel();
+        return e;
+    }
+    bool wait_peers(EventKind kind, uint64_t t, bool nothing_yet = false) {
+        return hip_ok(wait_events(kind, t, nothing_yet), "hipStreamWaitEvent");
+    }
+
+    // base (and the length per rank) of exchange region k on rank q
+    bool region(int q, int k, void **base, size_t *seg = nullptr) {
         size_t off = 0, len = 0, total = 0;
-        if (int rc = ranks_[q]->sim->exchange_region(k, base, &off, &len, &total)) {
-            fail(rc);
-            return false;
-        }
+        if (!ok(g.ranks_[q]->sim->exchange_region(k, base, &off, &len, &total))) return false;
         if (seg) *seg = len;
         return true;
-    };
-    auto wait_peers = [&](int which, uint64_t idx) {  // 0 meta, 1 pushed, 2 done
-        mark_w();
-        for (int q = 0; q < world; ++q) {
-            if (q == r) continue;
-            Rank &p = *ranks_[q];
-            hipEvent_t ev = which == 0 ? p.meta[idx & 1] : which == 1 ? p.pushed[idx & 1] : p.done[idx & 1];
-            if (!hip_ok(hipStreamWaitEvent(sim.stream, ev, 0), "hipStreamWaitEvent")) return;
-        }
-        mark_k();
-    };
-    auto peers_of = [&](int k, void **bases) {  // bases of region k on every peer, in rank order
+    }
+    // bases of region k on every peer, in rank order: their number, or -1
+    int peer_bases(int k, void **bases) {
         int np = 0;
         for (int q = 0; q < world; ++q) {
             if (q == r) continue;
-            if (!region(q, k, &bases[np], nullptr)) return -1;
+            if (!region(q, k, &bases[np])) return -1;
             ++np;
         }
         return np;
-    };
+    }
 
-    const bool migrate = migrate_every_ > 0 && t > 0 && t % (uint64_t)migrate_every_ == 0;
-    mark_k();
-    if (migrate) {
-        // the bodies that left this rank's key range go to their new owners: leaver counts read on the
-        // host (they size the next launches), leavers pulled from the peers' send areas
-        std::vector<uint32_t> &mig = sh_->mig;
-        if (!failed()) {
-            void *base = nullptr;
-            if (int rc = sim.encode_phase(NB_PHASE_LET_MIGRATE)) fail(rc);
-            else if (hip_ok(hipStreamSynchronize(sim.stream), "hipStreamSynchronize") && region(r, 4, &base, nullptr))
-                (void)hip_ok(hipMemcpy(&mig[(size_t)r * world], static_cast<uint32_t *>(base) + (size_t)r * world,
-                                       sizeof(uint32_t) * (size_t)world, hipMemcpyDeviceToHost), "hipMemcpy");
-        }
-        sh_->bar->wait();  // every row of the table is in
-        if (!failed()) {
-            std::vector<uint32_t> recv((size_t)world, 0u);
-            void *mine = nullptr;
-            bool ok = region(r, 6, &mine, nullptr);
-            size_t at = 0;
-            for (int q = 0; q < world && ok; ++q) {
-                if (q == r) continue;
-                const uint32_t c = mig[(size_t)q * world + r];
-                recv[(size_t)q] = c;
-                if (c > mig_cap_) {
-                    set_error("LET migration: %u leavers from rank %d for rank %d, the segment holds %u", c, q, r, mig_cap_);
-                    fail(NB_ERR_INVALID);
-                    ok = false;
-                    break;
-                }
-                void *theirs = nullptr;
-                size_t seg = 0;
-                if (!region(q, 5, &theirs, &seg)) { ok = false; break; }
-                if (c)
-                    ok = hip_ok(hipMemcpyPeerAsync(static_cast<char *>(mine) + at * 48u, me.device,
-                                                   static_cast<char *>(theirs) + (size_t)r * seg, ranks_[q]->device,
-                                                   (size_t)c * 48u, sim.stream), "hipMemcpyPeerAsync");
-                at += c;
-            }
-            if (ok) {
-                const uint32_t stay = mig[(size_t)r * world + r];
-                if (int rc = sim.let_set_arrivals(stay, recv.data(), world)) fail(rc);
-                else me.active = stay + (uint32_t)at;
-            }
-        }
+    // one step (absolute index t, the same on every rank) of this rank in each scheme
+    void all_pairs_step(uint64_t t);
+    void replicated_tree_step(uint64_t t);
+    void let_step(uint64_t t);
+    void let_migrate();
+};
+
+// All-pairs: own j tiles, [the peers' slices of step t-1 are in] the other tiles + finish.  1 barrier.
+void DeviceGroup::RankCtx::all_pairs_step(uint64_t t) {
+    if (!failed()) {
+        mark_kernel();
+        (void)ok(sim.encode_phase(0));  // own j tiles: nothing to wait for
     }
+    barrier();  // every rank has recorded its "step t-1 finished"
+    if (!failed())
+        if (wait_peers(kDone, t - 1, t == 0) && ok(sim.encode_phase(1)))  // other tiles, finish: stores to self + peers
+            (void)record(kDone, t);
+}
+
+// Barnes-Hut, replicated tree: [peers' slices of step t-1 are in] build + walk my range
+// [every rank has finished step t] copy my slices into every peer's arrays.  2 barriers.
+void DeviceGroup::RankCtx::replicated_tree_step(uint64_t t) {
+    barrier();  // every rank has recorded its "slices of step t-1 pushed"
+    if (!failed())
+        if (wait_peers(kPushed, t - 1, t == 0) && ok(sim.encode())) (void)record(kDone, t);
+    barrier();  // every rank has recorded its "step t finished"
+    if (!failed()) {
+        hipError_t e = wait_events(kDone, t);
+        // positions/masses, velocities, accelerations: one launch stores the slices into every peer
+        void *bases[kReplicatedRegions * kMaxPeers];
+        int np = 0;
+        for (int q = 0; q < world && !failed(); ++q) {
+            if (q == r) continue;
+            for (int k = 0; k < kReplicatedRegions; ++k) (void)region(q, k, &bases[kReplicatedRegions * np + k]);
+            ++np;
+        }
+        if (!failed()) (void)ok(sim.push_exchange(bases, np));
+        if (e == hipSuccess) e = hipEventRecord(me.ev[kPushed][t & 1], sim.stream);
+        (void)hip_ok(e, "slice push");
+    }
+}
+
+// The migration ahead of a LET step: the bodies that left this rank's key range go to their new owners --
+// leaver counts read on the host (they size the next launches), leavers pulled from the peers' send areas.
+// 1 barrier, and nothing but returns behind it.
+void DeviceGroup::RankCtx::let_migrate() {
+    std::vector<uint32_t> &mig = g.sh_->mig;
+    if (!failed()) {
+        void *base = nullptr;
+        if (ok(sim.encode_phase(NB_PHASE_LET_MIGRATE)) && hip_ok(hipStreamSynchronize(sim.stream), "hipStreamSynchronize") &&
+            region(r, kLetMigrationCounts, &base))
+            (void)hip_ok(hipMemcpy(&mig[(size_t)r * world], static_cast<uint32_t *>(base) + (size_t)r * world,
+                                   sizeof(uint32_t) * (size_t)world, hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+    barrier();  // every row of the table is in
+    if (failed()) return;
+    std::vector<uint32_t> recv((size_t)world, 0u);
+    void *mine = nullptr;
+    if (!region(r, kLetArrivals, &mine)) return;
+    size_t at = 0;
+    for (int q = 0; q < world; ++q) {
+        if (q == r) continue;
+        const uint32_t c = mig[(size_t)q * world + r];
+        recv[(size_t)q] = c;
+        if (c > g.mig_cap_) {
+            set_error("LET migration: %u leavers from rank %d for rank %d, the segment holds %u", c, q, r, g.mig_cap_);
+            fail(NB_ERR_INVALID);
+            return;
+        }
+        void *theirs = nullptr;
+        size_t seg = 0;
+        if (!region(q, kLetLeavers, &theirs, &seg)) return;
+        if (c && !hip_ok(hipMemcpyPeerAsync(static_cast<char *>(mine) + at * kMigratedBodyBytes, me.device,
+                                            static_cast<char *>(theirs) + (size_t)r * seg, g.ranks_[q]->device,
+                                            (size_t)c * kMigratedBodyBytes, sim.stream), "hipMemcpyPeerAsync"))
+            return;
+        at += c;
+    }
+    const uint32_t stay = mig[(size_t)r * world + r];
+    if (ok(sim.let_set_arrivals(stay, recv.data(), world))) me.active = stay + (uint32_t)at;
+}
+
+// One LET step (see create_let).  2 barriers, and the migration's on a migration step.
+void DeviceGroup::RankCtx::let_step(uint64_t t) {
+    mark_kernel();
+    if (g.migrate_every_ > 0 && t > 0 && t % (uint64_t)g.migrate_every_ == 0) let_migrate();
     void *bases[kMaxPeers + 1];
-    if (!failed()) {
-        if (int rc = sim.encode_phase(NB_PHASE_LET_META)) fail(rc);
-        else {
-            const int np = peers_of(0, bases);
-            if (np >= 0) {
-                if (int rc = sim.push_region(0, bases, np)) fail(rc);
-                else (void)hip_ok(hipEventRecord(me.meta[t & 1], sim.stream), "hipEventRecord");
-            }
-        }
+    if (!failed() && ok(sim.encode_phase(NB_PHASE_LET_META))) {
+        const int np = peer_bases(kLetMeta, bases);
+        if (np >= 0 && ok(sim.push_region(kLetMeta, bases, np))) (void)record(kMeta, t);
     }
-    sh_->bar->wait();  // every rank has recorded "my bounds are pushed"
+    barrier();  // every rank has recorded "my bounds are pushed"
     if (!failed()) {
-        wait_peers(0, t);
-        if (!failed())
-            if (int rc = sim.encode_phase(NB_PHASE_LET_BUILD)) fail(rc);
+        (void)wait_peers(kMeta, t);
+        if (!failed()) (void)ok(sim.encode_phase(NB_PHASE_LET_BUILD));
         // the peers' tables and import areas are free once they have finished the previous walk
-        if (!failed() && t > 0) wait_peers(2, t - 1);
+        if (!failed() && t > 0) (void)wait_peers(kDone, t - 1);
         if (!failed()) {
-            const int np = peers_of(1, bases);
-            if (np >= 0)
-                if (int rc = sim.push_region(1, bases, np)) fail(rc);
+            const int np = peer_bases(kLetExportCounts, bases);
+            if (np >= 0) (void)ok(sim.push_region(kLetExportCounts, bases, np));
         }
         if (!failed()) {
             void *imports[kMaxPeers + 1] = {};
-            bool ok = true;
-            for (int q = 0; q < world && ok; ++q)
-                if (q != r) ok = region(q, 3, &imports[q], nullptr);
-            if (ok) {
-                if (int rc = sim.let_push_segments(imports, world, let_cap_)) fail(rc);
-                else (void)hip_ok(hipEventRecord(me.pushed[t & 1], sim.stream), "hipEventRecord");
-            }
+            bool all = true;
+            for (int q = 0; q < world && all; ++q)
+                if (q != r) all = region(q, kLetImportArea, &imports[q]);
+            if (all && ok(sim.let_push_segments(imports, world, g.let_cap_))) (void)record(kPushed, t);
         }
     }
-    sh_->bar->wait();  // every rank has recorded "my records are pushed"
+    barrier();  // every rank has recorded "my records are pushed"
     if (!failed()) {
-        wait_peers(1, t);
-        if (!failed()) {
-            if (int rc = sim.let_set_import_stride(let_cap_)) fail(rc);
-            else if (int rc2 = sim.encode_phase(NB_PHASE_LET_WALK)) fail(rc2);
-            else (void)hip_ok(hipEventRecord(me.done[t & 1], sim.stream), "hipEventRecord");
-        }
+        (void)wait_peers(kPushed, t);
+        if (!failed() && ok(sim.let_set_import_stride(g.let_cap_)) && ok(sim.encode_phase(NB_PHASE_LET_WALK)))
+            (void)record(kDone, t);
     }
 }
 
 // One rank's host thread: waits for a batch of steps, enqueues them, waits for its stream.
 void DeviceGroup::worker(int r) {
     Rank &me = *ranks_[r];
-    const int world = (int)ranks_.size();
     (void)hipSetDevice(me.device);
     uint64_t seen = 0;
     for (;;) {
@@ -606,97 +660,18 @@ void DeviceGroup::worker(int r) {
             seen = sh_->cmd_seq;
             steps = sh_->cmd_steps;
         }
-        auto fail = [&](int rc) {
-            if (me.rc == NB_OK) {
-                me.rc = rc;
-                me.err = nb_last_error();
-            }
-            sh_->failed.store(true, std::memory_order_release);
-        };
-        // (asked several times per step and rank: a relaxed load, not the group's mutex -- a rank that sees the
-        // flag a step late only enqueues one more step of work that nobody reads)
-        auto failed = [&] { return sh_->failed.load(std::memory_order_relaxed); };
-        const bool prof = sh_->profiling.load(std::memory_order_relaxed);
-        auto mark_k = [&] { me.prof.mark(prof, RankProf::kKernel, me.sim->stream); };
-        auto mark_w = [&] { me.prof.mark(prof, RankProf::kWait, me.sim->stream); };
-        // this rank's stream waits for every peer's event of step idx ("slices pushed" or "step finished")
-        auto wait_all = [&](bool pushed_ev, uint64_t idx) -> hipError_t {
-            hipError_t e = hipSuccess;
-            for (int q = 0; q < world && e == hipSuccess; ++q)
-                if (q != r)
-                    e = hipStreamWaitEvent(me.sim->stream, pushed_ev ? ranks_[q]->pushed[idx & 1] : ranks_[q]->done[idx & 1], 0);
-            return e;
-        };
-        for (int s = 0; s < steps && let_; ++s) let_step(r, step_ + (uint64_t)s, fail, failed);
-        for (int s = 0; s < steps && tree_ && !let_; ++s) {
-            // Barnes-Hut, replicated tree: [peers' slices of step t-1 are in] build + walk my range
-            // [every rank has finished step t] copy my slices into every peer's arrays
+        RankCtx c{*this, me, *me.sim, r, (int)ranks_.size(), sh_->profiling.load(std::memory_order_relaxed)};
+        for (int s = 0; s < steps; ++s) {
             const uint64_t t = step_ + (uint64_t)s;
-            sh_->bar->wait();  // every rank has recorded its "slices of step t-1 pushed"
-            if (!failed()) {
-                mark_w();
-                hipError_t e = t > 0 ? wait_all(true, t - 1) : hipSuccess;
-                mark_k();
-                if (e != hipSuccess) {
-                    set_error("hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-                    fail(NB_ERR_HIP);
-                } else if (int rc = me.sim->encode()) {
-                    fail(rc);
-                } else if ((e = hipEventRecord(me.done[t & 1], me.sim->stream)) != hipSuccess) {
-                    set_error("hipEventRecord failed: %s", hipGetErrorString(e));
-                    fail(NB_ERR_HIP);
-                }
-            }
-            sh_->bar->wait();  // every rank has recorded its "step t finished"
-            if (!failed()) {
-                mark_w();
-                hipError_t e = wait_all(false, t);
-                mark_k();
-                // positions/masses, velocities, accelerations: one launch stores the slices into every peer
-                void *bases[3 * kMaxPeers];
-                int np = 0;
-                for (int q = 0; q < world && !failed(); ++q) {
-                    if (q == r) continue;
-                    for (int k = 0; k < 3; ++k) {
-                        size_t o2 = 0, l2 = 0, t2 = 0;
-                        if (int rc = ranks_[q]->sim->exchange_region(k, &bases[3 * np + k], &o2, &l2, &t2)) fail(rc);
-                    }
-                    ++np;
-                }
-                if (!failed())
-                    if (int rc = me.sim->push_exchange(bases, np)) fail(rc);
-                if (e == hipSuccess) e = hipEventRecord(me.pushed[t & 1], me.sim->stream);
-                if (e != hipSuccess) {
-                    set_error("slice push failed: %s", hipGetErrorString(e));
-                    fail(NB_ERR_HIP);
-                }
+            switch (scheme_) {
+            case kAllPairs: c.all_pairs_step(t); break;
+            case kReplicatedTree: c.replicated_tree_step(t); break;
+            case kLet: c.let_step(t); break;
             }
         }
-        for (int s = 0; s < steps && !tree_; ++s) {
-            const uint64_t t = step_ + (uint64_t)s;  // absolute step index (same on every rank)
-            if (!failed()) {
-                mark_k();
-                if (int rc = me.sim->encode_phase(0)) fail(rc);  // own j tiles: nothing to wait for
-            }
-            sh_->bar->wait();  // every rank has recorded its "step t-1 finished"
-            if (!failed()) {
-                mark_w();
-                hipError_t e = t > 0 ? wait_all(false, t - 1) : hipSuccess;
-                mark_k();
-                if (e != hipSuccess) {
-                    set_error("hipStreamWaitEvent failed: %s", hipGetErrorString(e));
-                    fail(NB_ERR_HIP);
-                } else if (int rc = me.sim->encode_phase(1)) {  // other tiles, finish: stores to self + peers
-                    fail(rc);
-                } else if ((e = hipEventRecord(me.done[t & 1], me.sim->stream)) != hipSuccess) {
-                    set_error("hipEventRecord failed: %s", hipGetErrorString(e));
-                    fail(NB_ERR_HIP);
-                }
-            }
-        }
-        me.prof.mark(prof, RankProf::kEnd, me.sim->stream);
-        if (int rc = me.sim->wait()) fail(rc);
-        if (prof) me.prof.collect();
+        me.prof.mark(c.prof, RankProf::kEnd, me.sim->stream);
+        (void)c.ok(me.sim->wait());
+        if (c.prof) me.prof.collect();
         sh_->bar->wait();  // every stream has drained: all slices have landed everywhere
         {
             std::lock_guard<std::mutex> lk(sh_->mu);
@@ -760,7 +735,7 @@ int DeviceGroup::read_particles(nb_particle *dst, size_t count) {
         set_error("read_particles: asked for %zu of %zu particles", count, n);
         return NB_ERR_INVALID;
     }
-    if (let_) {  // rank by rank, every rank's bodies in its current tree order (as LetTreeSim.read_particles)
+    if (scheme_ == kLet) {  // rank by rank, every rank's bodies in its current tree order (as LetTreeSim.read_particles)
         size_t at = 0;
         std::vector<nb_particle> tmp;
         for (auto &rk : ranks_) {
@@ -775,7 +750,7 @@ int DeviceGroup::read_particles(nb_particle *dst, size_t count) {
         }
         return NB_OK;
     }
-    if (tree_) return ranks_[0]->sim->read_particles(dst, count);  // replicated: every rank holds every body
+    if (scheme_ == kReplicatedTree) return ranks_[0]->sim->read_particles(dst, count);  // replicated: every rank holds every body
     std::vector<nb_particle> tmp(n), all(n);
     for (size_t r = 0; r < ranks_.size(); ++r) {
         SimBase &s = *ranks_[r]->sim;

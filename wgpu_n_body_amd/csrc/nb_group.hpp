@@ -30,21 +30,22 @@ class DeviceGroup {
 
    private:
     DeviceGroup();
+    // Barnes-Hut as kReplicatedTree: full state and tree on every rank, partitioned walk, slices stored into the
+    // peers; as kLet: Morton domains, local trees, LET records stored into the peers
+    enum Scheme { kAllPairs, kReplicatedTree, kLet };
     struct Rank;
     struct Shared;
+    struct RankCtx;  // what a rank's thread steps with (nb_group.cpp)
     void worker(int r);
     int create_let(const nb_sim_params &sp, const nb_add_params &add, const nb_particle *particles,
                    const int *device_ids, int world);
-    template <typename Fail, typename Failed>
-    void let_step(int r, uint64_t t, Fail &fail, Failed &failed);
     std::string first_error() const;
     int check_peer_stores();  // create time: peer stores arrive behind their events (or NB_ERR_UNSUPPORTED)
     std::vector<std::unique_ptr<Rank>> ranks_;
     std::unique_ptr<Shared> sh_;
     nb_sim_params params_{};
     uint64_t step_ = 0;
-    bool tree_ = false;  // Barnes-Hut: replicated tree, partitioned walk, slices copied to the peers
-    bool let_ = false;   // Barnes-Hut: Morton domains, local trees, LET records pushed to the peers
+    Scheme scheme_ = kAllPairs;  // chosen once, in create()
     int migrate_every_ = 0;
     uint32_t let_cap_ = 0, mig_cap_ = 0;
 };

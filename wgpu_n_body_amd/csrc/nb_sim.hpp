@@ -11,6 +11,28 @@ namespace nb {
 struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
 struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
 
+// The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
+enum ExchangeRegion : int {
+    // replicated tree (placement world > 1): the rank's slice of each state array
+    kRegionPositions = 0,
+    kRegionVelocities = 1,
+    kRegionAccelerations = 2,
+    kReplicatedRegions = 3,
+    // LET (tree_let_world set): the protocol's four buffers ...
+    kLetMeta = 0,            // bounds, one row of kLetMetaWords words per rank (all-gathered)
+    kLetExportCounts = 1,    // one row of `world` counts per rank (all-gathered)
+    kLetExportSegments = 2,  // segment q = the records for peer q, segment stride = slice_bytes
+    kLetImportArea = 3,      // the peers' records, in rank order with this rank skipped
+    kLetRegions = 4,
+    // ... and the migration's three, after nb_sim_let_set_owners
+    kLetMigrationCounts = 4,  // one row of `world` counts per rank (all-gathered), stayers at [rank]
+    kLetLeavers = 5,          // segment q = the bodies whose new owner is q, segment stride = slice_bytes
+    kLetArrivals = 6,         // the bodies that arrived, packed in rank order
+    kLetRegionsWithMigration = 7,
+};
+// a migrated body in regions kLetLeavers / kLetArrivals: position + mass, velocity, acceleration
+constexpr size_t kMigratedBodyBytes = 3 * sizeof(float4);
+
 // What `trait Simulator` (src/sims/mod.rs:73-90) requires of an implementor, in HIP terms.
 class SimBase {
    public:

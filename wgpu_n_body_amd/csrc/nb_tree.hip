@@ -431,8 +431,8 @@ class TreeSim final : public SimBase {
             const size_t w = (size_t)world;
             let_mig_cap = seg_cap;
             if (int rc = alloc(&let_mig_counts, sizeof(uint32_t) * w * w)) return rc;
-            if (int rc = alloc(&let_mig_send, sizeof(float4) * 3 * w * (size_t)seg_cap)) return rc;
-            if (int rc = alloc(&let_mig_recv, sizeof(float4) * 3 * w * (size_t)seg_cap)) return rc;
+            if (int rc = alloc(&let_mig_send, kMigratedBodyBytes * w * (size_t)seg_cap)) return rc;
+            if (int rc = alloc(&let_mig_recv, kMigratedBodyBytes * w * (size_t)seg_cap)) return rc;
             NB_HIP_TRY(hipMemsetAsync(let_mig_counts, 0, sizeof(uint32_t) * w * w, stream));
             NB_HIP_TRY(hipStreamSynchronize(stream));
         }
@@ -1024,10 +1024,12 @@ class TreeSim final : public SimBase {
     // rank), 1 export counts (all-gather, one row of `world` u32 per rank), 2 the export segments
     // (segment q = records for peer q, stride = slice_bytes), 3 the import area (packed by the
     // caller in rank order, skipping itself).
-    int exchange_count() override { return let_world ? (let_mig_send ? 7 : 4) : 3; }
+    int exchange_count() override {
+        return let_world ? (let_mig_send ? kLetRegionsWithMigration : kLetRegions) : kReplicatedRegions;
+    }
     int exchange_region(int index, void **dev_ptr, size_t *off, size_t *len, size_t *total) override {
         if (let_world) {
-            if (index < 0 || index > (let_mig_send ? 6 : 3) || !let_send) {
+            if (index < 0 || index >= exchange_count() || !let_send) {
                 set_error("LET exchange region %d out of range (4 regions after tree_let_cap is set, 7 with "
                           "nb_sim_let_set_owners)", index);
                 return NB_ERR_INVALID;
@@ -1036,15 +1038,15 @@ class TreeSim final : public SimBase {
             void *base = nullptr;
             size_t o = 0, l = 0, t = 0;
             switch (index) {
-            case 0: base = let_metas; l = sizeof(uint32_t) * kLetMetaWords; o = l * let_rank; t = l * w; break;
-            case 1: base = let_counts; l = sizeof(uint32_t) * w; o = l * let_rank; t = l * w; break;
-            case 2: base = let_send; l = sizeof(NodeRec) * (size_t)let_cap; t = l * w; break;
-            case 3: base = rec + node_cap; l = sizeof(NodeRec) * (size_t)let_cap; t = l * w; break;
+            case kLetMeta: base = let_metas; l = sizeof(uint32_t) * kLetMetaWords; o = l * let_rank; t = l * w; break;
+            case kLetExportCounts: base = let_counts; l = sizeof(uint32_t) * w; o = l * let_rank; t = l * w; break;
+            case kLetExportSegments: base = let_send; l = sizeof(NodeRec) * (size_t)let_cap; t = l * w; break;
+            case kLetImportArea: base = rec + node_cap; l = sizeof(NodeRec) * (size_t)let_cap; t = l * w; break;
             // migration: 4 counts (all-gather, `world` u32 per rank, stayers at [rank]), 5 leavers per
             // owner (48 B per body, segment stride = slice_bytes), 6 arrivals (packed in rank order)
-            case 4: base = let_mig_counts; l = sizeof(uint32_t) * w; o = l * let_rank; t = l * w; break;
-            case 5: base = let_mig_send; l = sizeof(float4) * 3 * (size_t)let_mig_cap; t = l * w; break;
-            default: base = let_mig_recv; l = sizeof(float4) * 3 * (size_t)let_mig_cap; t = l * w; break;
+            case kLetMigrationCounts: base = let_mig_counts; l = sizeof(uint32_t) * w; o = l * let_rank; t = l * w; break;
+            case kLetLeavers: base = let_mig_send; l = kMigratedBodyBytes * (size_t)let_mig_cap; t = l * w; break;
+            default: base = let_mig_recv; l = kMigratedBodyBytes * (size_t)let_mig_cap; t = l * w; break;  // kLetArrivals
             }
             if (dev_ptr) *dev_ptr = base;
             if (off) *off = o;
@@ -1052,11 +1054,11 @@ class TreeSim final : public SimBase {
             if (total) *total = t;
             return NB_OK;
         }
-        if (index < 0 || index > 2) {
+        if (index < 0 || index >= kReplicatedRegions) {
             set_error("exchange region %d out of range (TreeSim has 3)", index);
             return NB_ERR_INVALID;
         }
-        float4 *base = index == 0 ? posm[cur] : index == 1 ? vel[cur] : acc[cur];
+        float4 *base = index == kRegionPositions ? posm[cur] : index == kRegionVelocities ? vel[cur] : acc[cur];
         if (dev_ptr) *dev_ptr = base;
         if (off) *off = sizeof(float4) * (size_t)per_rank * (size_t)place.rank;
         if (len) *len = sizeof(float4) * (size_t)per_rank;

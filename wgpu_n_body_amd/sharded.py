@@ -409,6 +409,12 @@ class LetTreeSim:
     host-side) re-cuts the domains from the current positions when the load has drifted."""
 
     META, BUILD, WALK, MIGRATE, WALK_OWN = 2, 3, 4, 5, 6
+    # the simulator's exchange regions in LET mode (nb_sim_exchange_region_i; csrc/nb_sim.hpp ExchangeRegion): bounds,
+    # export counts, export segments, import area; leaver counts, leavers per owner, arrivals
+    R_META, R_EXPORT_COUNTS, R_EXPORT_SEGMENTS, R_IMPORT_AREA = 0, 1, 2, 3
+    R_MIGRATION_COUNTS, R_LEAVERS, R_ARRIVALS = 4, 5, 6
+    RECORD_FLOATS = 8    # a tree record of the export segments / the import area: 32 bytes
+    BODY_FLOATS = 12     # a migrated body: position + mass, velocity, acceleration as three float4
     HEADROOM = 1.25     # body capacity of a rank relative to its start-up share
     STRIDE_MARGIN = 1.5  # fixed-stride exchange: records per peer = margin x the largest count seen + 1024
     force_exchange = False   # issue the collectives even at world == 1 (one-GPU rehearsal of the RCCL path)
@@ -494,6 +500,10 @@ class LetTreeSim:
                                  sync=lambda: self._torch.cuda.current_stream(self._dev).synchronize(),
                                  force=self.force_exchange)
 
+    def _exchange_records(self, counts: np.ndarray) -> list:
+        """counts[r, q] tree records from every rank r's export segment q into rank q's import area."""
+        return self._exchange_segments(counts, self.R_EXPORT_SEGMENTS, self.R_IMPORT_AREA, self.RECORD_FLOATS)
+
     def _counts_matrix(self, k: int) -> np.ndarray:
         t = self._torch
         self._all_gather(k)
@@ -530,7 +540,7 @@ class LetTreeSim:
     def _queue_counts_readback(self) -> None:
         """Copy this step's all-gathered counts matrix to pinned host memory without waiting."""
         t = self._torch
-        src = self._views[1][0].view(t.int32)
+        src = self._views[self.R_EXPORT_COUNTS][0].view(t.int32)
         pinned = t.empty(src.shape, dtype=t.int32, pin_memory=True)
         pinned.copy_(src, non_blocking=True)
         ev = t.cuda.Event()
@@ -542,11 +552,11 @@ class LetTreeSim:
         t = self._torch
         with t.cuda.stream(self.stream):
             self.sim.encode_phase(self.MIGRATE)
-            counts = self._counts_matrix(4)
+            counts = self._counts_matrix(self.R_MIGRATION_COUNTS)
             if (counts - np.diag(np.diag(counts))).max(initial=0) > self.mig_cap:
                 raise NBodyError("LET migration: more leavers for one rank than the segment holds "
                                  f"({int(counts.max())} > {self.mig_cap}); rebalance() first")
-            recv = self._exchange_segments(counts, 5, 6, 12)
+            recv = self._exchange_segments(counts, self.R_LEAVERS, self.R_ARRIVALS, self.BODY_FLOATS)
             self.sim.let_set_arrivals(int(counts[self.rank, self.rank]), recv)
         self.counts = [int(counts[:, r].sum()) for r in range(self.world)]
         self.last_migration = counts
@@ -558,7 +568,7 @@ class LetTreeSim:
             self.migrate()
         with t.cuda.stream(self.stream):
             self.sim.encode_phase(self.META)
-            self._all_gather(0)
+            self._all_gather(self.R_META)
             self.sim.encode_phase(self.BUILD)
             if self.overlap and self.world > 1:
                 built = t.cuda.Event()
@@ -567,9 +577,9 @@ class LetTreeSim:
                 with t.cuda.stream(self.side):               # side stream: counts -> host -> all-to-all
                     self.side.wait_event(built)
                     _t0 = _now()
-                    counts = self._counts_matrix(1)
+                    counts = self._counts_matrix(self.R_EXPORT_COUNTS)
                     _t1 = _now()
-                    recv_counts = self._exchange_segments(counts, 2, 3, 8)
+                    recv_counts = self._exchange_records(counts)
                     _t2 = _now()
                     arrived = t.cuda.Event()
                     arrived.record(self.side)
@@ -579,10 +589,10 @@ class LetTreeSim:
                 if stride is not None:
                     # no host round trip: counts all-gathered and consumed on the device, a fixed
                     # number of records per peer on the wire
-                    self._all_gather(1)
+                    self._all_gather(self.R_EXPORT_COUNTS)
                     fixed = np.full((self.world, self.world), stride, dtype=np.int64)
                     np.fill_diagonal(fixed, 0)
-                    self._exchange_segments(fixed, 2, 3, 8)
+                    self._exchange_records(fixed)
                     self._queue_counts_readback()
                     self.sim.let_set_import_stride(stride)
                     self.sim.encode_phase(self.WALK)
@@ -590,9 +600,9 @@ class LetTreeSim:
                     self.step_num += 1
                     return
                 _t0 = _now()
-                counts = self._counts_matrix(1)
+                counts = self._counts_matrix(self.R_EXPORT_COUNTS)
                 _t1 = _now()
-                recv_counts = self._exchange_segments(counts, 2, 3, 8)
+                recv_counts = self._exchange_records(counts)
                 _t2 = _now()
             if _TRACE:
                 print(f"[let rank {self.rank} step {self.step_num}] counts {(_t1 - _t0) * 1e3:.2f} ms, "
