@@ -295,7 +295,11 @@ int nb_sim_encode_n_timed(nb_sim *sim, int n, float *ms_total, float *ms_kernel)
 /* Tuning knobs with no reference counterpart.  key "naive_variant": index into the
  * all-pairs kernel variant table (tiling / packing choices of nb_naive.hip; every variant
  * computes the same step).  Also settable through the NB_NAIVE_VARIANT environment
- * variable at create time.  A TreeSim's keys ("tree_*": bodies per wave of the walk, sort
+ * variable at create time.  "naive_jsplit": j-splits across workgroups (0 = automatic).
+ * "naive_mass_runs": 1 (default) sums runs of equal masses without the per-pair mass
+ * multiply and applies the mass once per run; 0 multiplies every pair (bitwise the same
+ * step when the masses are one power of two, a different rounding of the sum otherwise).
+ * A TreeSim's keys ("tree_*": bodies per wave of the walk, sort
  * passes and fix-up, who gathers the velocities, where the tile scan runs, ...) are listed
  * in the table of TreeSim::set_tuning (nb_tree.hip), one row per key with the values it accepts;
  * the defaults are the initialisers of the members the rows point to: speed only -- every setting

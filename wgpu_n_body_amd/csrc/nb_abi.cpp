@@ -194,6 +194,7 @@ int NaiveSim::launch(int phase) {
     a.dt = params.dt;
     a.variant = variant;
     a.jsplit = jsplit;
+    a.mass_runs = mass_runs;
     a.partial = partial;
     a.partial_stride = per_rank;
     a.partial_slices = partial_slices;
@@ -345,6 +346,14 @@ int NaiveSim::set_tuning(const char *key, int value) {
         }
         jsplit = value;
         return ensure_workspace();
+    }
+    if (strcmp(key, "naive_mass_runs") == 0) {
+        if (value != 0 && value != 1) {
+            set_error("naive_mass_runs %d is neither 0 nor 1", value);
+            return NB_ERR_INVALID;
+        }
+        mass_runs = value;
+        return NB_OK;
     }
     set_error("unknown tuning key '%s'", key);
     return NB_ERR_INVALID;

@@ -65,6 +65,7 @@ struct NaiveLaunch {
     float g, e, dt;
     int variant;             // kernel variant (see nb_naive.hip); <0 = default
     int jsplit;              // j-splits across workgroups; <=0 = automatic
+    int mass_runs;           // 1: no per-pair mass multiply inside runs of equal masses; 0: always
     float4 *partial;         // [partial_slices][partial_stride] partial sums (j-split only)
     uint32_t partial_stride; // bodies per slice (>= hi-lo)
     uint32_t partial_slices; // slices allocated

@@ -18,9 +18,11 @@
 //     1 mul (m_j *), 3 fma = 12 full-rate + 2 quarter-rate VALU ops.  The reference's
 //     m g /(r^3+e) * (d/r) * dt  is evaluated as  (g dt) * m d / (r^4 + e r):  g*dt is
 //     applied once per body after the sum;
+//   * inside a run of equal masses the m_j multiply is taken out of the sum as well (11
+//     full-rate ops per pair): see naive_step_kernel;
 //   * self-exclusion is by INDEX as in naive.wgsl:30-32 (the body's new position differs
 //     from its own old one, so r != 0), but only the j tiles that overlap the
-//     workgroup's own i range (and the zero-padded tail tile) run the masked loop body.
+//     workgroup's own i range (and the tail tile, when it has padding) run the masked loop body.
 //
 // Summation order differs from the reference's sequential j loop (j is split over waves
 // and unrolled), so parity with the oracle is tolerance-based; see DESIGN.md.
@@ -32,6 +34,7 @@ namespace nb {
 namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 enum JSource { kLds = 0, kSmem = 1 };
 
@@ -58,8 +61,9 @@ __device__ __forceinline__ float drift(float x, float v, float dt) {
     return x + v * dt;  // aPos + aVel * params.dt
 }
 
-// One pair: accumulate m_j * d / (r^4 + e r) into (ax,ay,az).
-template <bool MASKED>
+// One pair: accumulate m_j * d / (r^4 + e r) into (ax,ay,az).  UNIFORM: the caller is inside a run
+// of equal masses and multiplies the sum by the run's mass later, so the weight is 1 / (r^4 + e r).
+template <bool MASKED, bool UNIFORM>
 __device__ __forceinline__ void pair(float xj, float yj, float zj, float mj, float xi, float yi,
                                      float zi, float e, bool valid, float &ax, float &ay,
                                      float &az) {
@@ -67,7 +71,8 @@ __device__ __forceinline__ void pair(float xj, float yj, float zj, float mj, flo
     const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
     const float r = __builtin_amdgcn_sqrtf(r2);           // v_sqrt_f32
     const float den = __builtin_fmaf(e, r, r2 * r2);      // r^4 + e r = r (r^3 + e)
-    float w = mj * __builtin_amdgcn_rcpf(den);            // v_rcp_f32
+    float w = __builtin_amdgcn_rcpf(den);                 // v_rcp_f32
+    if (!UNIFORM) w *= mj;
     if (MASKED) w = valid ? w : 0.0f;                     // self / padding: contributes exactly 0
     ax = __builtin_fmaf(w, dx, ax);
     ay = __builtin_fmaf(w, dy, ay);
@@ -75,7 +80,7 @@ __device__ __forceinline__ void pair(float xj, float yj, float zj, float mj, flo
 }
 
 // Two i bodies against one j body with packed fp32 (v_pk_*), lane-pairs in v2f registers.
-template <bool MASKED>
+template <bool MASKED, bool UNIFORM>
 __device__ __forceinline__ void pair2(float xj, float yj, float zj, float mj, v2f xi, v2f yi,
                                       v2f zi, float e, bool valid0, bool valid1, v2f &ax,
                                       v2f &ay, v2f &az) {
@@ -88,7 +93,7 @@ __device__ __forceinline__ void pair2(float xj, float yj, float zj, float mj, v2
     v2f rc;
     rc.x = __builtin_amdgcn_rcpf(den.x);
     rc.y = __builtin_amdgcn_rcpf(den.y);
-    v2f w = v2f{mj, mj} * rc;
+    v2f w = UNIFORM ? rc : v2f{mj, mj} * rc;
     if (MASKED) {
         w.x = valid0 ? w.x : 0.0f;
         w.y = valid1 ? w.y : 0.0f;
@@ -101,25 +106,35 @@ __device__ __forceinline__ void pair2(float xj, float yj, float zj, float mj, v2
 // The body of one 64-body j tile held in `tile` (LDS, wave-private) or read from global
 // memory through the scalar cache (SMEM).  j0 = global index of the tile's first body.
 // State is IB scalars per lane, or IB/2 packed pairs (v2f) when PACKED.
-template <int IB, bool PACKED, bool MASKED, int UNROLL, typename Ptr, typename T>
+template <int IB, int SRC, bool PACKED, bool MASKED, bool UNIFORM, int UNROLL, typename Ptr,
+          typename T>
 __device__ __forceinline__ void tile_body(Ptr tile, uint32_t j0, uint32_t n, const uint32_t *ii,
                                           const T *xi, const T *yi, const T *zi, float e, T *ax,
                                           T *ay, T *az) {
 #pragma unroll UNROLL
     for (uint32_t jj = 0; jj < kJTile; ++jj) {
-        const float4 pj = tile[jj];  // wave-uniform address: LDS broadcast / s_load
+        float4 pj = tile[jj];  // wave-uniform address: LDS broadcast / s_load
         const uint32_t j = j0 + jj;
+        // Unweighted packed body: keep the read 16 bytes wide although m_j is not used.  A 12-byte
+        // read leaves z_j in the last register of a triple, and the compiler then copies it into
+        // an aligned pair before every use as a packed operand (one v_mov per j).  The empty asm
+        // emits nothing; it only makes all four registers of the read live.
+        if constexpr (PACKED && UNIFORM && SRC == kLds) {
+            v4f q{pj.x, pj.y, pj.z, pj.w};
+            asm("" : "+v"(q));
+            pj = float4{q.x, q.y, q.z, q.w};
+        }
         if constexpr (PACKED) {
 #pragma unroll
             for (int k = 0; k < IB / 2; ++k)
-                pair2<MASKED>(pj.x, pj.y, pj.z, pj.w, xi[k], yi[k], zi[k], e,
-                              (j != ii[2 * k]) & (j < n), (j != ii[2 * k + 1]) & (j < n), ax[k],
-                              ay[k], az[k]);
+                pair2<MASKED, UNIFORM>(pj.x, pj.y, pj.z, pj.w, xi[k], yi[k], zi[k], e,
+                                       (j != ii[2 * k]) & (j < n), (j != ii[2 * k + 1]) & (j < n),
+                                       ax[k], ay[k], az[k]);
         } else {
 #pragma unroll
             for (int k = 0; k < IB; ++k)
-                pair<MASKED>(pj.x, pj.y, pj.z, pj.w, xi[k], yi[k], zi[k], e,
-                             (j != ii[k]) & (j < n), ax[k], ay[k], az[k]);
+                pair<MASKED, UNIFORM>(pj.x, pj.y, pj.z, pj.w, xi[k], yi[k], zi[k], e,
+                                      (j != ii[k]) & (j < n), ax[k], ay[k], az[k]);
         }
     }
 }
@@ -135,17 +150,62 @@ __device__ __forceinline__ float &elem<v2f>(v2f *a, int k) {
     return reinterpret_cast<float *>(a)[k];  // fully unrolled callers: stays in registers
 }
 
+// One j tile in the mode the wave is in.  `uniform` and `special` are wave-uniform.
+template <int IB, int SRC, bool PACKED, int UNROLL, typename Ptr, typename T>
+__device__ __forceinline__ void tile_any(bool uniform, bool special, Ptr tile, uint32_t j0,
+                                         uint32_t n, const uint32_t *ii, const T *xi, const T *yi,
+                                         const T *zi, float e, T *ax, T *ay, T *az) {
+    if (uniform) {
+        if (special)
+            tile_body<IB, SRC, PACKED, true, true, 2>(tile, j0, n, ii, xi, yi, zi, e, ax, ay, az);
+        else
+            tile_body<IB, SRC, PACKED, false, true, UNROLL>(tile, j0, n, ii, xi, yi, zi, e, ax, ay, az);
+    } else {
+        if (special)
+            tile_body<IB, SRC, PACKED, true, false, 2>(tile, j0, n, ii, xi, yi, zi, e, ax, ay, az);
+        else
+            tile_body<IB, SRC, PACKED, false, false, UNROLL>(tile, j0, n, ii, xi, yi, zi, e, ax, ay, az);
+    }
+}
+
+// Does lane `lane`'s body of the tile at j0 continue the run of mass bits `m_run`?  Padding
+// (index >= n) is masked out of the sum anyway and never ends a run.
+__device__ __forceinline__ bool tile_in_run(float m, uint32_t m_run, uint32_t j0, uint32_t lane,
+                                            uint32_t n) {
+    const bool differs = (__float_as_uint(m) != m_run) & (j0 + lane < n);
+    return __builtin_amdgcn_ballot_w64(differs) == 0;
+}
+
+// A wave leaves its run of equal masses: the sums of d / (r^4 + e r) become sums of m d / (...).
+template <int NV, typename T>
+__device__ __forceinline__ void scale_sums(uint32_t m_run, T *ax, T *ay, T *az) {
+    const float m = __uint_as_float(m_run);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        ax[k] *= m;
+        ay[k] *= m;
+        az[k] *= m;
+    }
+}
+
 // grid.x = ceil((hi-lo) / (64*IB)) i-tiles; grid.y = JS j-splits; block = 64*W threads.
 // JS == 1: the workgroup sees every j and finishes the step itself.  JS > 1 (few bodies per
 // launch: small N, or one rank's share of a multi-GPU run): workgroup (b, s) sums the j tiles
 // t with (t mod JS*W) in [s*W, (s+1)*W) and writes its partial sums to `partial[s][i-lo]`;
 // naive_finish_kernel then adds the JS partials in order s = 0..JS-1 and integrates.  Either
 // way a body's sum is built in one fixed order: results are deterministic.
+//
+// Runs of equal masses (mass_runs != 0): a wave starts its j loop summing d / (r^4 + e r) without
+// the per-pair m_j multiply, for as long as every real body of its tiles has the mass (bit for
+// bit) of its first j body; it multiplies its sums by that mass once, at the first tile that
+// breaks the run or after the loop, and sums any later tile with the weighted body.  The decision
+// is taken from the masses the wave reads this step, so it holds whoever wrote posm_src.
 template <int IB, int W, int SRC, bool PACKED, int UNROLL>
 __global__ __launch_bounds__(64 * W) void naive_step_kernel(
     const float4 *__restrict__ posm_src, float4 *__restrict__ posm_dst, float4 *__restrict__ vel,
     float4 *__restrict__ acc, float4 *__restrict__ partial, uint32_t partial_stride, uint32_t n,
-    uint32_t n_pad, uint32_t lo, uint32_t hi, float g, float e, float dt, TileWindow win) {
+    uint32_t n_pad, uint32_t lo, uint32_t hi, float g, float e, float dt, TileWindow win,
+    uint32_t mass_runs) {
     static_assert(!PACKED || IB % 2 == 0, "packed fp32 needs an even number of bodies per lane");
     using T = typename std::conditional<PACKED, v2f, float>::type;
     constexpr int NV = PACKED ? IB / 2 : IB;
@@ -186,39 +246,53 @@ __global__ __launch_bounds__(64 * W) void naive_step_kernel(
     // ---- all-pairs over this wave's share of the j tiles (naive.wgsl:26-46) --------------
     const uint32_t n_tiles = (n + kJTile - 1u) / kJTile;  // tail tile reads zero padding
     const uint32_t t_self_lo = i0 / kJTile, t_self_hi = (i0 + 64u * IB - 1u) / kJTile;
+    const uint32_t t_ragged = (n % kJTile) ? n_tiles - 1u : ~0u;  // the tile with padding to mask
+    bool in_run = mass_runs != 0u;  // wave-uniform: the sums so far lack the factor m_run
+    uint32_t m_run;                 // mass bits of this wave's first j body
     if constexpr (SRC == kLds) {
         float4 *my = s_tile + wave * 2 * kJTile;
         uint32_t vt = slot;
         float4 nxt = vt < win.count ? posm_src[win.tile(vt) * kJTile + lane] : float4{0, 0, 0, 0};
         uint32_t buf = 0;
+        m_run = __builtin_amdgcn_readfirstlane(__float_as_uint(nxt.w));
         for (; vt < win.count; vt += n_slots) {
             const uint32_t t = win.tile(vt);
             my[buf * kJTile + lane] = nxt;  // ds_write_b128; wave-private, no s_barrier needed
+            if (in_run && !tile_in_run(nxt.w, m_run, t * kJTile, lane, n)) {
+                scale_sums<NV>(m_run, ax, ay, az);
+                in_run = false;
+            }
             __builtin_amdgcn_wave_barrier();
             const uint32_t vn = vt + n_slots;
             if (vn < win.count) nxt = posm_src[win.tile(vn) * kJTile + lane];  // prefetch next tile
             const float4 *tile = my + buf * kJTile;
-            const bool special = (t >= t_self_lo && t <= t_self_hi) || (t + 1u == n_tiles);
-            if (special)
-                tile_body<IB, PACKED, true, 2>(tile, t * kJTile, n, ii, xi, yi, zi, e, ax, ay, az);
-            else
-                tile_body<IB, PACKED, false, UNROLL>(tile, t * kJTile, n, ii, xi, yi, zi, e, ax, ay,
-                                                     az);
+            const bool special = (t >= t_self_lo && t <= t_self_hi) || t == t_ragged;
+            tile_any<IB, SRC, PACKED, UNROLL>(in_run, special, tile, t * kJTile, n, ii, xi, yi, zi, e,
+                                              ax, ay, az);
             __builtin_amdgcn_wave_barrier();
             buf ^= 1u;
         }
     } else {
-        for (uint32_t vt = slot; vt < win.count; vt += n_slots) {
+        // the tile's masses, one per lane, for the run check only (a vector load a tile ahead; the
+        // j stream itself stays in SGPRs)
+        uint32_t vt = slot;
+        float m_nxt = vt < win.count ? posm_src[win.tile(vt) * kJTile + lane].w : 0.0f;
+        m_run = __builtin_amdgcn_readfirstlane(__float_as_uint(m_nxt));
+        for (; vt < win.count; vt += n_slots) {
             const uint32_t t = win.tile(vt);
             const float4 *tile = posm_src + t * kJTile;  // wave-uniform -> s_load_dwordx4+
-            const bool special = (t >= t_self_lo && t <= t_self_hi) || (t + 1u == n_tiles);
-            if (special)
-                tile_body<IB, PACKED, true, 2>(tile, t * kJTile, n, ii, xi, yi, zi, e, ax, ay, az);
-            else
-                tile_body<IB, PACKED, false, UNROLL>(tile, t * kJTile, n, ii, xi, yi, zi, e, ax, ay,
-                                                     az);
+            if (in_run && !tile_in_run(m_nxt, m_run, t * kJTile, lane, n)) {
+                scale_sums<NV>(m_run, ax, ay, az);
+                in_run = false;
+            }
+            const uint32_t vn = vt + n_slots;
+            if (in_run && vn < win.count) m_nxt = posm_src[win.tile(vn) * kJTile + lane].w;
+            const bool special = (t >= t_self_lo && t <= t_self_hi) || t == t_ragged;
+            tile_any<IB, SRC, PACKED, UNROLL>(in_run, special, tile, t * kJTile, n, ii, xi, yi, zi, e,
+                                              ax, ay, az);
         }
     }
+    if (in_run) scale_sums<NV>(m_run, ax, ay, az);  // the run lasted to the wave's last tile
 
     // ---- deterministic cross-wave reduction: wave 0 adds waves 1..W-1 in order -----------
     float sx[IB], sy[IB], sz[IB];
@@ -339,7 +413,8 @@ __global__ void soa_to_aos_kernel(const float4 *__restrict__ posm, const float4 
 
 // ---- variant table ----------------------------------------------------------------------------
 using KernelFn = void (*)(const float4 *, float4 *, float4 *, float4 *, float4 *, uint32_t,
-                          uint32_t, uint32_t, uint32_t, uint32_t, float, float, float, TileWindow);
+                          uint32_t, uint32_t, uint32_t, uint32_t, float, float, float, TileWindow,
+                          uint32_t);
 struct Variant {
     const char *name;
     KernelFn fn;
@@ -428,12 +503,13 @@ hipError_t launch_naive_step(const NaiveLaunch &a, hipStream_t stream) {
     const Variant &v = kVariants[p.variant];
     const dim3 block(64u * (uint32_t)v.w);
     const uint32_t nl = a.hi - a.lo;
+    const uint32_t mr = a.mass_runs ? 1u : 0u;
     if (a.phase == kPhaseAll) {
         if (p.jsplit > 1 && (!a.partial || a.partial_slices < p.jsplit)) return hipErrorInvalidValue;
         const TileWindow all{0u, p.n_tiles, ~0u, 0u};
         hipLaunchKernelGGL(v.fn, dim3(p.blocks, p.jsplit), block, 0, stream, a.posm_src, a.posm_dst,
                            a.vel, a.acc, p.jsplit > 1 ? a.partial : (float4 *)nullptr, a.partial_stride,
-                           a.n, a.n_pad, a.lo, a.hi, a.g, a.e, a.dt, all);
+                           a.n, a.n_pad, a.lo, a.hi, a.g, a.e, a.dt, all, mr);
         if (p.jsplit > 1)
             hipLaunchKernelGGL(naive_finish_kernel, dim3((nl + 255u) / 256u), dim3(256), 0, stream,
                                a.posm_src, a.posm_dst, a.vel, a.acc, a.partial, a.partial_stride,
@@ -445,12 +521,12 @@ hipError_t launch_naive_step(const NaiveLaunch &a, hipStream_t stream) {
         const TileWindow own{p.lo_tile, p.local_tiles, ~0u, 0u};
         hipLaunchKernelGGL(v.fn, dim3(p.blocks, p.js_local), block, 0, stream, a.posm_src, a.posm_dst,
                            a.vel, a.acc, a.partial, a.partial_stride, a.n, a.n_pad, a.lo, a.hi, a.g,
-                           a.e, a.dt, own);
+                           a.e, a.dt, own, mr);
     } else {
         const TileWindow rest{0u, p.n_tiles - p.local_tiles, p.lo_tile, p.local_tiles};
         hipLaunchKernelGGL(v.fn, dim3(p.blocks, p.js_remote), block, 0, stream, a.posm_src, a.posm_dst,
                            a.vel, a.acc, a.partial + (size_t)p.js_local * a.partial_stride,
-                           a.partial_stride, a.n, a.n_pad, a.lo, a.hi, a.g, a.e, a.dt, rest);
+                           a.partial_stride, a.n, a.n_pad, a.lo, a.hi, a.g, a.e, a.dt, rest, mr);
         hipLaunchKernelGGL(naive_finish_kernel, dim3((nl + 255u) / 256u), dim3(256), 0, stream,
                            a.posm_src, a.posm_dst, a.vel, a.acc, a.partial, a.partial_stride, p.jsplit,
                            a.lo, a.hi, a.g, a.dt, a.peers);

@@ -163,6 +163,7 @@ class NaiveSim final : public SimBase {
     nb_particle *d_aos = nullptr;           // AoS staging for the 40-byte boundary layout
     int cur = 0;                            // posm[cur] holds the current state
     int variant = -1, jsplit = 0;           // tuning overrides (<0 / 0 = automatic)
+    int mass_runs = 1;                      // sum runs of equal masses unweighted (nb_naive.hip)
     float4 *partial = nullptr;              // j-split partial sums [slices][per_rank]
     uint32_t partial_slices = 0;
     int ensure_workspace();
