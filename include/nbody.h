@@ -374,6 +374,93 @@ typedef struct nb_diagnostics {
 int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out);
 
 /* ------------------------------------------------------------------------- */
+/* Radial profiles -- per-shell mass and velocity moments (no reference       */
+/* counterpart: the reference has no way to measure a run's structure)        */
+/* ------------------------------------------------------------------------- */
+/* Bins the state nb_sim_read_particles would return by distance from a centre
+ * (spherical shells) or from an axis through it (NB_RADIAL_CYLINDRICAL: annuli
+ * of a disc), on the device, in one streaming pass over 32 B per body.  The
+ * rule, which DESIGN.md 6d states in full: everything in binary64 from the
+ * binary32 state, one rounding per operation, no contraction, in this order,
+ * per body with position x, velocity v, mass m:
+ *   d = (double)x - c, u = (double)v - v_c       (c, v_c: centre and its velocity)
+ *   spherical    r2 = (dx dx + dy dy) + dz dz
+ *   cylindrical  h = (dx nx + dy ny) + dz nz, p = d - h n, r2 = (px px + py py) + pz pz
+ *                (n = axis / sqrt((ax ax + ay ay) + az az), formed on the host)
+ *   bin          the k with edges[k]^2 <= r2 < edges[k+1]^2, the squares formed
+ *                once in fp64 on the host; the comparison is on r2 -- no sqrt, log
+ *                or division decides a bin, so the counts are exact integers.
+ *                r2 < edges[0]^2: `inside`; r2 >= edges[nbins]^2: `outside`
+ *   r = sqrt(r2); with q = d (spherical) or p (cylindrical):
+ *                u_r = ((qx ux + qy uy) + qz uz) / r
+ *                u_phi = ((nx wx + ny wy) + nz wz) / r, w = p cross u (cylindrical; 0 in
+ *                spherical mode); u_r = u_phi = 0 when r = 0
+ *   ang          m (d cross u), the full d in both modes; shape: m d_i d_j
+ * A body with any non-finite position, velocity or mass component is `nonfinite`
+ * and left out of everything (the predicate of nb_sim_diagnostics).
+ * inside_count + sum of count + outside_count + nonfinite == n.
+ * NB_RADIAL_CENTER_COM: c and v_c are the fp64 `com` and `momentum / mass` that
+ * nb_sim_diagnostics returns for the same state, bit for bit (the same moments
+ * pass runs ahead of the binning on the stream; no host round trip between them).
+ * The sums run in a fixed order without float atomics and the grid shapes depend
+ * on n and nbins alone: two calls on one state return bit-identical structs.  The
+ * call is ordered after the enqueued steps on the simulator's stream, ends with
+ * one synchronisation, reports a TreeSim's status words as nb_sim_read_particles
+ * does, and does not change the trajectory. */
+#define NB_RADIAL_MAX_BINS 256u
+#define NB_RADIAL_CYLINDRICAL 1u /* radius = distance from the axis through the centre; default: from the centre */
+#define NB_RADIAL_CENTER_COM 2u  /* centre = centre of mass, centre velocity = P/M of the measured state */
+
+typedef struct nb_radial_params {
+    uint32_t nbins, flags; /* 1..NB_RADIAL_MAX_BINS */
+    double center[3];      /* ignored with NB_RADIAL_CENTER_COM */
+    double velocity[3];    /* ignored with NB_RADIAL_CENTER_COM */
+    double axis[3];        /* cylindrical only; any non-zero finite vector, normalised in fp64 */
+    const double *edges;   /* nbins + 1 finite radii, edges[0] >= 0, strictly ascending */
+} nb_radial_params;
+
+typedef struct nb_radial_bin { /* 88 bytes */
+    uint64_t count;
+    double mass;    /* sum m */
+    double m_r;     /* sum m r            (mass-weighted mean radius = m_r / mass) */
+    double m_ur;    /* sum m u_r */
+    double m_ur2;   /* sum m u_r^2 */
+    double m_uphi;  /* sum m u_phi        (cylindrical; 0 in spherical mode) */
+    double m_uphi2; /* sum m u_phi^2      (cylindrical; 0 in spherical mode) */
+    double m_u2;    /* sum m |u|^2 */
+    double ang[3];  /* sum m (d x u) */
+} nb_radial_bin;
+
+typedef struct nb_radial_profile {
+    uint64_t step_num, n, nonfinite;
+    uint64_t inside_count, outside_count;   /* r < edges[0];  r >= edges[nbins] */
+    double inside_mass, outside_mass;
+    double mass;                            /* all finite bodies */
+    double center[3], velocity[3], axis[3]; /* the values used (axis normalised; 0 in spherical mode) */
+    double shape[6];                        /* sum m d_i d_j (xx,yy,zz,xy,xz,yz) over bodies with r < edges[nbins] */
+    uint32_t nbins, flags;
+} nb_radial_profile;
+
+/* The profile of a simulator's current state: out and bins[0 .. nbins).  NB_ERR_INVALID for a null
+ * pointer, nbins outside 1..NB_RADIAL_MAX_BINS, unknown flag bits, non-finite, negative or
+ * non-ascending edges, a non-finite centre, velocity or axis, or (cylindrical) a zero axis -- all
+ * checked before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_radial_profile(nb_sim *sim, const nb_radial_params *params, nb_radial_profile *out,
+                          nb_radial_bin *bins);
+/* Host only, no device.  nbins + 1 edges from rmin to rmax with a constant ratio (log; rmin > 0) or a
+ * constant step (linear; rmin >= 0): edges[0] == rmin and edges[nbins] == rmax exactly.
+ * NB_ERR_INVALID for a null pointer, nbins outside 1..NB_RADIAL_MAX_BINS, non-finite bounds,
+ * rmax <= rmin, or edges that do not come out strictly ascending. */
+int nb_radial_edges_log(double rmin, double rmax, uint32_t nbins, double *edges);
+int nb_radial_edges_linear(double rmin, double rmax, uint32_t nbins, double *edges);
+/* Host only, a pure function of its arguments: for each fraction f in (0, 1), radii[i] = the radius
+ * where the cumulative mass (inside_mass, then the bins in order) reaches f * p->mass, linear in r
+ * inside the bin that crosses; NaN where the crossing lies in `inside` or `outside` (or f is not in
+ * (0, 1)).  Binned, so limited by the bins' resolution.  edges: the p->nbins + 1 radii of the call. */
+int nb_radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, const double *edges,
+                         const double *fractions, uint32_t k, double *radii);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -520,6 +607,10 @@ int nb_runner_step_num(const nb_runner *runner, uint64_t *out);
 /* nb_sim_diagnostics of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out);
+/* nb_sim_radial_profile of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, nb_radial_profile *out,
+                             nb_radial_bin *bins);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -34,7 +34,7 @@ from ._lib import (NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS, OCTANT_DTYPE, PARTIC
 __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "TreeSim",
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
-           "shard_padded_bodies", "naive_variants", "Diagnostics",
+           "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -124,6 +124,131 @@ class Diagnostics:
 
 def _diag_flags(potential: bool) -> int:
     return _lib.NB_DIAG_MOMENTS | (_lib.NB_DIAG_POTENTIAL if potential else 0)
+
+
+def radial_edges(rmin: float, rmax: float, nbins: int = 64, log: bool = True) -> np.ndarray:
+    """nb_radial_edges_log / nb_radial_edges_linear: nbins + 1 radii from rmin to rmax (both exact) with
+    a constant ratio (log, rmin > 0) or a constant step."""
+    out = np.empty(int(nbins) + 1 if 1 <= int(nbins) <= _lib.NB_RADIAL_MAX_BINS else 1, dtype=np.float64)
+    fn = _lib.lib().nb_radial_edges_log if log else _lib.lib().nb_radial_edges_linear
+    check(fn(float(rmin), float(rmax), int(nbins), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+@dataclass(frozen=True)
+class RadialProfile:
+    """nb_radial_profile + nb_radial_bin[nbins] (include/nbody.h "Radial profiles"; no reference
+    counterpart): the state read_particles would return, binned on the device by distance from a centre
+    (or, cylindrical, from an axis through it).  Per-bin fields are float64 arrays of nbins (count:
+    uint64, ang: (nbins, 3)); `mass` is the mass of all finite bodies, `bin_mass` the per-bin sums.
+    inside_* / outside_* hold what fell below edges[0] / at or beyond edges[-1]."""
+    step_num: int
+    n: int
+    nonfinite: int
+    inside_count: int
+    outside_count: int
+    inside_mass: float
+    outside_mass: float
+    mass: float
+    center: np.ndarray
+    velocity: np.ndarray
+    axis: np.ndarray
+    shape: np.ndarray      # sum m d_i d_j: xx, yy, zz, xy, xz, yz over the bodies inside edges[-1]
+    flags: int
+    edges: np.ndarray      # nbins + 1
+    count: np.ndarray
+    bin_mass: np.ndarray   # sum m
+    m_r: np.ndarray        # sum m r
+    m_ur: np.ndarray       # sum m u_r
+    m_ur2: np.ndarray      # sum m u_r^2
+    m_uphi: np.ndarray     # sum m u_phi (cylindrical)
+    m_uphi2: np.ndarray    # sum m u_phi^2 (cylindrical)
+    m_u2: np.ndarray       # sum m |u|^2
+    ang: np.ndarray        # sum m (d x u)
+
+    @staticmethod
+    def _from_c(p: "_lib.nb_radial_profile", bins: np.ndarray, edges: np.ndarray) -> "RadialProfile":
+        vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+        return RadialProfile(int(p.step_num), int(p.n), int(p.nonfinite), int(p.inside_count), int(p.outside_count),
+                             float(p.inside_mass), float(p.outside_mass), float(p.mass), vec(p.center),
+                             vec(p.velocity), vec(p.axis), vec(p.shape), int(p.flags), edges.copy(),
+                             bins["count"].copy(), bins["mass"].copy(), bins["m_r"].copy(), bins["m_ur"].copy(),
+                             bins["m_ur2"].copy(), bins["m_uphi"].copy(), bins["m_uphi2"].copy(),
+                             bins["m_u2"].copy(), bins["ang"].copy())
+
+    @property
+    def nbins(self) -> int:
+        return self.edges.shape[0] - 1
+
+    @property
+    def cylindrical(self) -> bool:
+        return bool(self.flags & _lib.NB_RADIAL_CYLINDRICAL)
+
+    @property
+    def density(self) -> np.ndarray:
+        """bin_mass over the shell's volume 4 pi (b^3 - a^3) / 3, or (cylindrical) the annulus' area
+        pi (b^2 - a^2): a surface density."""
+        a, b = self.edges[:-1], self.edges[1:]
+        size = np.pi * (b * b - a * a) if self.cylindrical else 4.0 * np.pi / 3.0 * (b ** 3 - a ** 3)
+        return self.bin_mass / size
+
+    @property
+    def sigma_r(self) -> np.ndarray:
+        """Mass-weighted radial velocity dispersion per bin (NaN in a bin without mass)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = self.m_ur / self.bin_mass
+            return np.sqrt(np.maximum(self.m_ur2 / self.bin_mass - mean * mean, 0.0))
+
+    @property
+    def mean_uphi(self) -> np.ndarray:
+        """Mass-weighted mean tangential velocity per bin: a disc's rotation curve (cylindrical)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.m_uphi / self.bin_mass
+
+    @property
+    def cumulative_mass(self) -> np.ndarray:
+        """Mass within edges[k + 1]: inside_mass plus the bins up to and including k."""
+        return self.inside_mass + np.cumsum(self.bin_mass)
+
+    def lagrangian(self, fractions) -> np.ndarray:
+        """nb_radial_lagrangian: the radii enclosing the given fractions of `mass`, linear inside the bin
+        that crosses (so limited by the bins' resolution); NaN where the crossing is not in a bin."""
+        f = np.ascontiguousarray(np.atleast_1d(fractions), dtype=np.float64)
+        p = _lib.nb_radial_profile()
+        p.mass, p.inside_mass, p.outside_mass, p.nbins = self.mass, self.inside_mass, self.outside_mass, self.nbins
+        bins = np.zeros(self.nbins, dtype=_lib.RADIAL_BIN_DTYPE)
+        bins["mass"] = self.bin_mass
+        edges = np.ascontiguousarray(self.edges, dtype=np.float64)
+        out = np.empty(f.shape[0], dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(_lib.lib().nb_radial_lagrangian(C.byref(p), bins.ctypes.data, edges.ctypes.data_as(dp),
+                                              f.ctypes.data_as(dp), f.shape[0], out.ctypes.data_as(dp)))
+        return out
+
+
+def _radial_profile(call, handle, edges, nbins, rmin, rmax, log, cylindrical, axis, center, velocity):
+    if edges is None:
+        if rmin is None or rmax is None:
+            raise ValueError("radial_profile needs edges, or rmin and rmax")
+        edges = radial_edges(rmin, rmax, nbins, log)
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    p = _lib.nb_radial_params()
+    p.nbins = max(edges.shape[0] - 1, 0)
+    p.flags = _lib.NB_RADIAL_CYLINDRICAL if cylindrical else 0
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com" or three coordinates')
+        p.flags |= _lib.NB_RADIAL_CENTER_COM
+    else:
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    p.edges = edges.ctypes.data_as(C.POINTER(C.c_double))
+    out = _lib.nb_radial_profile()
+    bins = np.zeros(max(int(p.nbins), 1), dtype=_lib.RADIAL_BIN_DTYPE)
+    check(call(handle, C.byref(p), C.byref(out), bins.ctypes.data))
+    return RadialProfile._from_c(out, bins, edges)
 
 
 @dataclass(frozen=True)
@@ -438,6 +563,17 @@ class Simulator:
         check(_lib.lib().nb_sim_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
         return Diagnostics._from_c(d)
 
+    def radial_profile(self, edges=None, *, nbins: int = 64, rmin=None, rmax=None, log: bool = True,
+                       cylindrical: bool = False, axis=(0.0, 1.0, 0.0), center="com",
+                       velocity=(0.0, 0.0, 0.0)) -> RadialProfile:
+        """Per-shell mass and velocity moments of the current state (nb_sim_radial_profile).  edges: the
+        nbins + 1 radii, or rmin, rmax, nbins and log for radial_edges().  cylindrical: bin by distance
+        from `axis` through the centre (a disc's annuli) instead of from the centre.  center: "com" (the
+        centre of mass and its velocity P/M, as diagnostics() returns them) or three coordinates, then
+        with `velocity` as the centre's velocity."""
+        return _radial_profile(_lib.lib().nb_sim_radial_profile, self._h, edges, nbins, rmin, rmax, log,
+                               cylindrical, axis, center, velocity)
+
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
         """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
@@ -601,6 +737,13 @@ class OfflineHeadless:
         d = _lib.nb_diagnostics()
         check(_lib.lib().nb_runner_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
         return Diagnostics._from_c(d)
+
+    def radial_profile(self, edges=None, *, nbins: int = 64, rmin=None, rmax=None, log: bool = True,
+                       cylindrical: bool = False, axis=(0.0, 1.0, 0.0), center="com",
+                       velocity=(0.0, 0.0, 0.0)) -> RadialProfile:
+        """nb_runner_radial_profile: Simulator.radial_profile of the runner's simulator (one device only)."""
+        return _radial_profile(_lib.lib().nb_runner_radial_profile, self._h, edges, nbins, rmin, rmax, log,
+                               cylindrical, axis, center, velocity)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

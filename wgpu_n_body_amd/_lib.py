@@ -63,8 +63,33 @@ class nb_render_stats(C.Structure):
                 ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_radial_params(C.Structure):
+    _fields_ = [("nbins", C.c_uint32), ("flags", C.c_uint32), ("center", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("axis", C.c_double * 3), ("edges", C.POINTER(C.c_double))]
+
+
+class nb_radial_bin(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("mass", C.c_double), ("m_r", C.c_double), ("m_ur", C.c_double),
+                ("m_ur2", C.c_double), ("m_uphi", C.c_double), ("m_uphi2", C.c_double), ("m_u2", C.c_double),
+                ("ang", C.c_double * 3)]
+
+
+class nb_radial_profile(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("inside_count", C.c_uint64), ("outside_count", C.c_uint64),
+                ("inside_mass", C.c_double), ("outside_mass", C.c_double), ("mass", C.c_double),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("shape", C.c_double * 6), ("nbins", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# nb_radial_bin[] as a numpy record array
+RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
+                             ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
+
 assert C.sizeof(nb_sim_params) == 16 and C.sizeof(nb_add_params) == 8
 assert C.sizeof(nb_diagnostics) == 152
+assert C.sizeof(nb_radial_bin) == 88 == RADIAL_BIN_DTYPE.itemsize
+assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -73,6 +98,8 @@ NB_OK, NB_ERR_INVALID, NB_ERR_NO_DEVICE, NB_ERR_HIP, NB_ERR_ALLOC, NB_ERR_UNSUPP
 NB_NAIVE_SIM_PARAMS, NB_TREE_SIM_PARAMS = 0, 1
 NB_DIAG_MOMENTS, NB_DIAG_POTENTIAL = 1, 2
 NB_RENDER_SRGB = 1
+NB_RADIAL_MAX_BINS = 256
+NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM = 1, 2
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -85,10 +112,11 @@ ABI_SYMBOLS = [
     "nb_sim_read_tree", "nb_sim_exchange_region", "nb_sim_exchange_count",
     "nb_sim_exchange_region_i", "nb_sim_step_num", "nb_sim_encode_n_timed",
     "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics",
+    "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
-    "nb_runner_sim_params", "nb_runner_diagnostics", "nb_runner_render", "nb_runner_sim", "nb_runner_destroy",
+    "nb_runner_sim_params", "nb_runner_diagnostics", "nb_runner_radial_profile", "nb_runner_render", "nb_runner_sim", "nb_runner_destroy",
 ]
 
 
@@ -146,6 +174,11 @@ def lib() -> C.CDLL:
     L.nb_sim_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]
     L.nb_sim_debug_buffer.argtypes = [vp, C.c_char_p, vp, sz, P(sz)]
     L.nb_sim_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
+    L.nb_sim_radial_profile.argtypes = [vp, P(nb_radial_params), P(nb_radial_profile), vp]
+    for name in ("nb_radial_edges_log", "nb_radial_edges_linear"):
+        getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
+    L.nb_radial_lagrangian.argtypes = [P(nb_radial_profile), vp, P(C.c_double), P(C.c_double), C.c_uint32,
+                                       P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]
     L.nb_camera_view_proj.argtypes = [P(nb_camera), P(C.c_float)]
     L.nb_render_params_default.argtypes = [P(nb_render_params), C.c_uint32, C.c_uint32]
@@ -165,6 +198,7 @@ def lib() -> C.CDLL:
     L.nb_runner_rank_times.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int]
     L.nb_runner_sim_params.argtypes = [vp, P(nb_sim_params)]
     L.nb_runner_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
+    L.nb_runner_radial_profile.argtypes = [vp, P(nb_radial_params), P(nb_radial_profile), vp]
     L.nb_runner_render.argtypes = [vp, P(nb_render_params), vp, vp, P(nb_render_stats)]
     L.nb_runner_sim.argtypes = [vp]
     L.nb_runner_sim.restype = vp

@@ -27,6 +27,8 @@ SOURCES = [
     # the drawing rule and the camera are specified bit-exactly: no FMA contraction
     ("nb_render.hip", ["-ffp-contract=off"]),
     ("nb_camera.cpp", ["-ffp-contract=off"]),
+    # the binning rule is specified operation by operation: no FMA contraction
+    ("nb_radial.hip", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

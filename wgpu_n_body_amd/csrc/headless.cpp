@@ -4,6 +4,8 @@
 //   headless [--sim naive|tree] [--n N] [--steps S] [--theta T] [--init uniform|disc|spherical]
 //            [--seed K] [--device D | --devices D0,D1,...] [--g G] [--dt DT] [--dump FILE]
 //            [--e E] [--diag K [--diag-potential 1]] [--frames DIR [--frame-every K] [--frame-size WxH]]
+//            [--radial K --radial-range RMIN,RMAX [--radial-bins B] [--radial-log 0|1] [--radial-axis X,Y,Z]
+//             [--radial-center com|X,Y,Z]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -13,6 +15,16 @@
 // "Diagnostics: step S kinetic K potential U total E momentum px py pz angular_momentum lx ly lz"
 // (%.9e; potential and total are nan unless --diag-potential 1 adds the O(N^2) pair potential).  The
 // time they take is not part of any "Step Duration"; without --diag the output is unchanged.
+//
+// --radial K prints the radial profile (nb_runner_radial_profile) of step 0 and of every K-th step: B
+// bins (--radial-bins, default 64) between RMIN and RMAX, logarithmic unless --radial-log 0, about the
+// centre of mass unless --radial-center gives a point (at rest); --radial-axis bins by distance from
+// that axis through the centre (a disc's annuli) instead of from the centre.  One header line
+// "Radial: step S n N nonfinite B nbins NB flags F inside_count IC inside_mass IM outside_count OC
+// outside_mass OM mass M center x y z velocity x y z axis x y z shape xx yy zz xy xz yz" and one line
+// per bin "RadialBin: step S bin k lo E0 hi E1 count C mass M m_r . m_ur . m_ur2 . m_uphi . m_uphi2 .
+// m_u2 . ang x y z" (the fields of nb_radial_profile and nb_radial_bin; every real %.17g).  The time they
+// take is not part of any "Step Duration"; without --radial the output is unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
 // default camera, src/runners/online_renderer.rs:224-367) at step 0 and after every K-th step
@@ -57,6 +69,35 @@ static void print_diag(nbody::OfflineHeadless<Sim> &runner, bool potential) {
                 d.momentum[2], d.angular_momentum[0], d.angular_momentum[1], d.angular_momentum[2]);
 }
 
+struct RadialOptions {
+    int every = 0;
+    uint32_t bins = 64;
+    bool log = true, have_range = false;
+    double rmin = 0.0, rmax = 0.0;
+    nbody::RadialParams params{0, NB_RADIAL_CENTER_COM};  // flags, centre, axis
+};
+
+template <class Sim>
+static void print_radial(nbody::OfflineHeadless<Sim> &runner, const RadialOptions &ro) {
+    const nbody::RadialProfile r = runner.radial_profile(nbody::radial_edges(ro.rmin, ro.rmax, ro.bins, ro.log), ro.params);
+    const nb_radial_profile &p = r.profile;
+    const unsigned long long step = p.step_num;
+    std::printf("Radial: step %llu n %llu nonfinite %llu nbins %u flags %u inside_count %llu inside_mass %.17g "
+                "outside_count %llu outside_mass %.17g mass %.17g center %.17g %.17g %.17g velocity %.17g %.17g %.17g "
+                "axis %.17g %.17g %.17g shape %.17g %.17g %.17g %.17g %.17g %.17g\n",
+                step, (unsigned long long)p.n, (unsigned long long)p.nonfinite, p.nbins, p.flags,
+                (unsigned long long)p.inside_count, p.inside_mass, (unsigned long long)p.outside_count, p.outside_mass,
+                p.mass, p.center[0], p.center[1], p.center[2], p.velocity[0], p.velocity[1], p.velocity[2], p.axis[0],
+                p.axis[1], p.axis[2], p.shape[0], p.shape[1], p.shape[2], p.shape[3], p.shape[4], p.shape[5]);
+    for (uint32_t k = 0; k < p.nbins; ++k) {
+        const nbody::RadialBin &b = r.bins[k];
+        std::printf("RadialBin: step %llu bin %u lo %.17g hi %.17g count %llu mass %.17g m_r %.17g m_ur %.17g m_ur2 %.17g "
+                    "m_uphi %.17g m_uphi2 %.17g m_u2 %.17g ang %.17g %.17g %.17g\n",
+                    step, k, r.edges[k], r.edges[k + 1], (unsigned long long)b.count, b.mass, b.m_r, b.m_ur, b.m_ur2,
+                    b.m_uphi, b.m_uphi2, b.m_u2, b.ang[0], b.ang[1], b.ang[2]);
+    }
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -93,12 +134,13 @@ static bool write_frame(nbody::OfflineHeadless<Sim> &runner, const FrameOptions 
 template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
-               int diag, bool diag_potential, const FrameOptions &frames) {
+               int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
     std::puts("Running Simulation");
     if (diag > 0) print_diag(runner, diag_potential);
+    if (radial.every > 0) print_radial(runner, radial);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -107,6 +149,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                             std::chrono::steady_clock::now() - t0).count();
         std::printf("Step Duration: %lld \xC2\xB5s\n", (long long)us);
         if (diag > 0 && (i + 1) % diag == 0) print_diag(runner, diag_potential);
+        if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -128,6 +171,7 @@ int main(int argc, char **argv) {
     int steps = 10, device = -1, let = -1, diag = 0;
     bool diag_potential = false;
     FrameOptions frames;
+    RadialOptions radial;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -145,6 +189,34 @@ int main(int argc, char **argv) {
         else if (k == "--let") let = std::atoi(v.c_str());  // with --devices and --sim tree: LET scheme, migrate every k-th step
         else if (k == "--diag") diag = std::atoi(v.c_str());
         else if (k == "--diag-potential") diag_potential = std::atoi(v.c_str()) != 0;
+        else if (k == "--radial") radial.every = std::atoi(v.c_str());
+        else if (k == "--radial-bins") radial.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--radial-log") radial.log = std::atoi(v.c_str()) != 0;
+        else if (k == "--radial-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &radial.rmin, &radial.rmax) != 2) {
+                std::fprintf(stderr, "--radial-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            radial.have_range = true;
+        }
+        else if (k == "--radial-axis") {
+            double *a = radial.params.axis;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
+                std::fprintf(stderr, "--radial-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+            radial.params.flags |= NB_RADIAL_CYLINDRICAL;
+        }
+        else if (k == "--radial-center") {
+            double *c = radial.params.center;
+            if (v == "com") radial.params.flags |= NB_RADIAL_CENTER_COM;
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) == 3)
+                radial.params.flags &= ~NB_RADIAL_CENTER_COM;
+            else {
+                std::fprintf(stderr, "--radial-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--frames") frames.dir = v;
         else if (k == "--frame-every") frames.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--frame-size") {
@@ -165,15 +237,19 @@ int main(int argc, char **argv) {
         }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
+    if (radial.every > 0 && !radial.have_range) {
+        std::fprintf(stderr, "--radial needs --radial-range RMIN,RMAX\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames);
+                                        diag_potential, frames, radial);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames);
+                                       diag, diag_potential, frames, radial);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

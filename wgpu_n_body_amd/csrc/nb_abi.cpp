@@ -4,6 +4,7 @@
 // Host side only; the kernels live in nb_naive.hip / nb_tree.hip (nb_tree_*.hpp).  Everything the
 // reference does through wgpu (buffers, bind groups, command encoders, queue.submit,
 // device.poll) maps to hipMalloc'd SoA buffers, a ping-pong index and one hipStream_t.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -35,6 +36,7 @@ static size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 SimBase::~SimBase() {
     diag_release(diag);  // (the derived destructor has bound the device)
     render_release(render);
+    radial_release(radial);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -421,6 +423,81 @@ static int make_sim(nb_sim **out, const nb_sim_params *sp, const nb_add_params *
 // ==========================================================================================
 using namespace nb;
 
+// nb_sim_radial_profile: everything that can be refused without a device
+static int radial_check_params(const nb_radial_params *p, const nb_radial_profile *out, const nb_radial_bin *bins) {
+    if (!p || !out || !bins || !p->edges) {
+        set_error("radial_profile: null %s", !p ? "params" : !out ? "out" : !bins ? "bins" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_RADIAL_MAX_BINS) {
+        set_error("radial_profile: nbins must be 1..%u (got %u)", NB_RADIAL_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & ~(NB_RADIAL_CYLINDRICAL | NB_RADIAL_CENTER_COM)) {
+        set_error("radial_profile: unknown flag bits 0x%x", p->flags & ~(NB_RADIAL_CYLINDRICAL | NB_RADIAL_CENTER_COM));
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("radial_profile: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (!(p->flags & NB_RADIAL_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("radial_profile: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    const double *a = p->axis;
+    if (!std::isfinite(a[0]) || !std::isfinite(a[1]) || !std::isfinite(a[2])) {
+        set_error("radial_profile: axis must be finite");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & NB_RADIAL_CYLINDRICAL) {
+        // (an axis whose length over- or underflows has no finite unit vector either)
+        const double len = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+        if (!(len > 0.0) || !std::isfinite(len)) {
+            set_error("radial_profile: a cylindrical profile needs a non-zero axis");
+            return NB_ERR_INVALID;
+        }
+    }
+    return NB_OK;
+}
+
+static int radial_edges(const char *what, bool log, double rmin, double rmax, uint32_t nbins, double *edges) {
+    if (!edges) {
+        set_error("%s: edges is null", what);
+        return NB_ERR_INVALID;
+    }
+    if (nbins < 1 || nbins > NB_RADIAL_MAX_BINS) {
+        set_error("%s: nbins must be 1..%u (got %u)", what, NB_RADIAL_MAX_BINS, nbins);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(rmin) || !std::isfinite(rmax) || !(rmax > rmin) || !(log ? rmin > 0.0 : rmin >= 0.0)) {
+        set_error("%s: needs finite %s rmin < rmax (got %g, %g)", what, log ? "0 <" : "0 <=", rmin, rmax);
+        return NB_ERR_INVALID;
+    }
+    double prev = rmin;
+    for (uint32_t k = 1; k < nbins; ++k) {  // checked before anything is written
+        const double t = (double)k / (double)nbins;
+        const double e = log ? rmin * std::pow(rmax / rmin, t) : rmin + (rmax - rmin) * t;
+        if (!(e > prev) || !(e < rmax)) {
+            set_error("%s: %u bins between %g and %g are not strictly ascending in fp64", what, nbins, rmin, rmax);
+            return NB_ERR_INVALID;
+        }
+        prev = e;
+    }
+    edges[0] = rmin;
+    for (uint32_t k = 1; k < nbins; ++k) {
+        const double t = (double)k / (double)nbins;
+        edges[k] = log ? rmin * std::pow(rmax / rmin, t) : rmin + (rmax - rmin) * t;
+    }
+    edges[nbins] = rmax;
+    return NB_OK;
+}
+
 #define NB_GUARD(body)                                            \
     try {                                                         \
         body                                                      \
@@ -614,6 +691,52 @@ int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out) {
         }
         return sim_diagnostics(*sim->impl, flags, out);
     })
+}
+
+int nb_sim_radial_profile(nb_sim *sim, const nb_radial_params *params, nb_radial_profile *out,
+                          nb_radial_bin *bins) {
+    if (int rc = radial_check_params(params, out, bins)) return rc;
+    NB_GUARD({
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        return sim_radial_profile(*sim->impl, *params, out, bins);
+    })
+}
+
+int nb_radial_edges_log(double rmin, double rmax, uint32_t nbins, double *edges) {
+    return radial_edges("radial_edges_log", true, rmin, rmax, nbins, edges);
+}
+int nb_radial_edges_linear(double rmin, double rmax, uint32_t nbins, double *edges) {
+    return radial_edges("radial_edges_linear", false, rmin, rmax, nbins, edges);
+}
+
+int nb_radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, const double *edges,
+                         const double *fractions, uint32_t k, double *radii) {
+    if (!p || !bins || !edges || (k && (!fractions || !radii))) {
+        set_error("radial_lagrangian: null argument");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_RADIAL_MAX_BINS) {
+        set_error("radial_lagrangian: profile with %u bins", p->nbins);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        const double f = fractions[i], target = f * p->mass;
+        radii[i] = std::nan("");
+        if (!(f > 0.0 && f < 1.0) || !(target >= p->inside_mass)) continue;  // ... or the crossing lies in `inside`
+        double cum = p->inside_mass;
+        for (uint32_t b = 0; b < p->nbins; ++b) {
+            const double m = bins[b].mass, next = cum + m;
+            if (target <= next) {  // linear in r inside the bin that crosses
+                radii[i] = m > 0.0 ? edges[b] + (target - cum) / m * (edges[b + 1] - edges[b]) : edges[b];
+                break;
+            }
+            cum = next;
+        }
+    }
+    return NB_OK;
 }
 
 int nb_sim_render(nb_sim *sim, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
@@ -815,6 +938,17 @@ int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out
         return NB_ERR_UNSUPPORTED;
     }
     return nb_sim_diagnostics(runner->sim, flags, out);
+}
+
+int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, nb_radial_profile *out,
+                             nb_radial_bin *bins) {
+    if (int rc = radial_check_params(params, out, bins)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (runner->group) {
+        set_error("radial_profile: not available on a several-GPU runner (nb_runner_create_multi*)");
+        return NB_ERR_UNSUPPORTED;
+    }
+    return nb_sim_radial_profile(runner->sim, params, out, bins);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -35,7 +35,7 @@ constexpr uint32_t kPairChunks = 128;    // at most this many j-chunks per i-til
 // every launch near or under ~45 ms.  A 4 M-body potential is ~230 launches.
 constexpr uint64_t kPairsPerLaunch = 1ull << 35;
 
-enum MomField { kM = 0, kMX = 1, kMV = 4, kL = 7, kK = 10, kVmax = 11, kBad = 12, kW = 13 };
+enum MomField { kM = kDiagResMass, kMX = kDiagResMX, kMV = kDiagResMV, kL = 7, kK = 10, kVmax = 11, kBad = 12, kW = 13 };
 
 struct PsiConst {
     float e;      // softening
@@ -264,6 +264,38 @@ void diag_release(DiagWork *w) {
     delete w;
 }
 
+// the workspace of the moments pass, allocated by the first call that needs it
+static int diag_work(SimBase &sim) {
+    if (sim.diag) return NB_OK;  // kept only once complete
+    std::unique_ptr<DiagWork, void (*)(DiagWork *)> fresh(new DiagWork(), diag_release);
+    NB_HIP_TRY(hipMalloc(&fresh->mom, sizeof(double) * kMomMaxBlocks * kMomFields));
+    NB_HIP_TRY(hipMalloc(&fresh->res, sizeof(double) * kMomFields));
+    NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_res, sizeof(double) * kMomFields, hipHostMallocDefault));
+    sim.diag = fresh.release();
+    return NB_OK;
+}
+
+static int launch_moments(SimBase &sim, uint32_t *mom_blocks) {
+    const float4 *posm = nullptr, *vel = nullptr;
+    sim.diag_state(&posm, &vel);
+    *mom_blocks = std::min(kMomMaxBlocks, (sim.n + 4 * kDiagThreads - 1) / (4 * kDiagThreads));
+    hipLaunchKernelGGL(diag_moments_kernel, dim3(*mom_blocks), dim3(kDiagThreads), 0, sim.stream, posm, vel, sim.n,
+                       sim.diag->mom);
+    NB_HIP_TRY(hipGetLastError());
+    return NB_OK;
+}
+
+int diag_enqueue_moments(SimBase &sim, const double **res_dev) {
+    if (int rc = diag_work(sim)) return rc;
+    uint32_t mom_blocks = 0;
+    if (int rc = launch_moments(sim, &mom_blocks)) return rc;
+    hipLaunchKernelGGL(diag_finish_kernel, dim3(1), dim3(kDiagThreads), 0, sim.stream, sim.diag->mom, mom_blocks,
+                       sim.diag->pairs, 0u, sim.diag->res);
+    NB_HIP_TRY(hipGetLastError());
+    *res_dev = sim.diag->res;
+    return NB_OK;
+}
+
 int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out) {
     const bool potential = (flags & NB_DIAG_POTENTIAL) != 0;
     if (sim.place.world > 1) {
@@ -276,13 +308,7 @@ int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out) {
         return NB_ERR_INVALID;
     }
     if (int rc = sim.bind_device()) return rc;
-    if (!sim.diag) {  // kept only once complete
-        std::unique_ptr<DiagWork, void (*)(DiagWork *)> fresh(new DiagWork(), diag_release);
-        NB_HIP_TRY(hipMalloc(&fresh->mom, sizeof(double) * kMomMaxBlocks * kMomFields));
-        NB_HIP_TRY(hipMalloc(&fresh->res, sizeof(double) * kMomFields));
-        NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_res, sizeof(double) * kMomFields, hipHostMallocDefault));
-        sim.diag = fresh.release();
-    }
+    if (int rc = diag_work(sim)) return rc;
     DiagWork &w = *sim.diag;
     const uint32_t n = sim.n;
     const float4 *posm = nullptr, *vel = nullptr;
@@ -302,10 +328,8 @@ int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out) {
 
     double r[kMomFields] = {};
     if (n > 0) {
-        const uint32_t mom_blocks = std::min(kMomMaxBlocks, (n + 4 * kDiagThreads - 1) / (4 * kDiagThreads));
-        hipLaunchKernelGGL(diag_moments_kernel, dim3(mom_blocks), dim3(kDiagThreads), 0, sim.stream, posm, vel, n,
-                           w.mom);
-        NB_HIP_TRY(hipGetLastError());
+        uint32_t mom_blocks = 0;
+        if (int rc = launch_moments(sim, &mom_blocks)) return rc;
         if (potential) {
             PsiConst c{};
             const double a = std::cbrt((double)e);

@@ -10,6 +10,7 @@ namespace nb {
 
 struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
 struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
+struct RadialWork;  // nb_radial.hip: the radial profile's slabs, squared edges and pinned result
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -119,11 +120,17 @@ class SimBase {
     uint32_t n = 0, n_pad = 0, per_rank = 0, lo = 0, hi = 0;
     DiagWork *diag = nullptr;  // allocated by the first nb_sim_diagnostics
     RenderWork *render = nullptr;  // allocated by the first nb_sim_render
+    RadialWork *radial = nullptr;  // allocated by the first nb_sim_radial_profile
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
 int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out);
 void diag_release(DiagWork *w);
+// the moments pass and its finish alone, enqueued on the simulator's stream (n > 0; the device is bound):
+// *res_dev = the finished sums on the device, mass at [kDiagResMass], sum m x at [kDiagResMX + k], sum m v
+// at [kDiagResMV + k] -- what sim_diagnostics divides into `com` and reports as `momentum`
+constexpr int kDiagResMass = 0, kDiagResMX = 1, kDiagResMV = 4;
+int diag_enqueue_moments(SimBase &sim, const double **res_dev);
 
 // nb_render.hip: nb_sim_render behind the handle (arguments already checked by render_check_params,
 // nb_camera.cpp), the "render_design" tuning key, and the release of the workspace
@@ -131,6 +138,11 @@ int render_check_params(const nb_render_params *params);
 int sim_render(SimBase &sim, const nb_render_params &params, uint8_t *rgba, uint32_t *counts, nb_render_stats *stats);
 int sim_render_set_design(SimBase &sim, int design);
 void render_release(RenderWork *w);
+
+// nb_radial.hip: nb_sim_radial_profile behind the handle (arguments already checked, nb_abi.cpp) and
+// the release of its workspace
+int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_profile *out, nb_radial_bin *bins);
+void radial_release(RadialWork *w);
 
 class NaiveSim final : public SimBase {
    public:

@@ -29,6 +29,8 @@ using Particle = nb_particle;    // 40 B
 using SimParams = nb_sim_params;  // 16 B
 using Octant = nb_octant;        // 52 B
 using Diagnostics = nb_diagnostics;  // conserved-quantity monitor (no reference counterpart)
+using RadialParams = nb_radial_params;    // bins, flags, centre, axis and edges of a radial profile
+using RadialBin = nb_radial_bin;          // 88 B
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -75,6 +77,41 @@ inline RenderParams render_params(const Camera &cam, uint32_t width, uint32_t he
     check(nb_camera_view_proj(&cam, p.view_proj));  // Camera::build_view_projection_matrix
     return p;
 }
+
+// nbins + 1 radii from rmin to rmax, constant ratio (log) or constant step
+inline std::vector<double> radial_edges(double rmin, double rmax, uint32_t nbins, bool log = true) {
+    std::vector<double> e((size_t)nbins + 1);
+    check((log ? nb_radial_edges_log : nb_radial_edges_linear)(rmin, rmax, nbins, e.data()));
+    return e;
+}
+
+// A radial profile (no reference counterpart): the header, the bins and the edges they lie between
+struct RadialProfile {
+    nb_radial_profile profile{};
+    std::vector<RadialBin> bins;
+    std::vector<double> edges;
+    // radii enclosing the given fractions of profile.mass (binned: limited by the bins' resolution)
+    std::vector<double> lagrangian(const std::vector<double> &fractions) const {
+        std::vector<double> r(fractions.size());
+        check(nb_radial_lagrangian(&profile, bins.data(), edges.data(), fractions.data(), (uint32_t)fractions.size(),
+                                   r.data()));
+        return r;
+    }
+};
+
+namespace detail {
+template <class H>
+RadialProfile radial_profile(int (*call)(H *, const nb_radial_params *, nb_radial_profile *, nb_radial_bin *), H *h,
+                             const std::vector<double> &edges, RadialParams p) {
+    RadialProfile r;
+    r.edges = edges;
+    r.bins.resize(edges.size() > 1 ? edges.size() - 1 : 1);
+    p.nbins = edges.empty() ? 0u : (uint32_t)(edges.size() - 1);
+    p.edges = r.edges.data();
+    check(call(h, &p, &r.profile, r.bins.data()));
+    return r;
+}
+}  // namespace detail
 
 // A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
 struct Frame {
@@ -160,6 +197,11 @@ class Simulator {
         Diagnostics d{};
         check(nb_sim_diagnostics(h_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
         return d;
+    }
+    // per-shell mass and velocity moments of the current state between `edges`; p: flags
+    // (NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
+    RadialProfile radial_profile(const std::vector<double> &edges, const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
+        return detail::radial_profile(nb_sim_radial_profile, h_, edges, p);
     }
     // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
     Frame render(const RenderParams &p, bool counts = false) {
@@ -274,6 +316,10 @@ class OfflineHeadless {
         Diagnostics d{};
         check(nb_runner_diagnostics(r_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
         return d;
+    }
+    RadialProfile radial_profile(const std::vector<double> &edges,  // one device only
+                                 const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
+        return detail::radial_profile(nb_runner_radial_profile, r_, edges, p);
     }
     Frame render(const RenderParams &p, bool counts = false) {  // one device only
         Frame f;
