@@ -1,6 +1,7 @@
 """Random Barnes-Hut cases against the CPU oracle (test infrastructure, like tests/): sizes, distributions,
 theta, cube scale and walk shape drawn at random; the checks are tests/test_tree_gpu.py's (tree and order
-bit-exact, positions bit-exact after one step, accelerations within the fp32 tolerances, visit counts).
+bit-exact, positions bit-exact after one step, accelerations within the fp32 tolerances, visit counts), plus
+those of tests/test_tree_precision_gpu.py: node moments and the integrator on every case, the binary64 walk on a sample.
 usage: tree_fuzz.py [SECONDS [SEED]]"""
 import os
 import sys
@@ -13,7 +14,10 @@ sys.path.insert(0, ROOT)
 import wgpu_n_body_amd as nb  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from tests.helpers import DT, E, G, bits, make_state  # noqa: E402
+from tests import tree_ref as R  # noqa: E402
 from tests.test_tree_gpu import WALK_SHAPES, check_tree, rel_err, run_tree  # noqa: E402
+
+WALK_SAMPLE = 256    # bodies at either end of the sorted order held to tree_ref.K (the ragged tail is always in)
 
 
 def fuzz(budget=60.0, seed=1, max_cases=None, log=print):
@@ -54,6 +58,19 @@ def fuzz(budget=60.0, seed=1, max_cases=None, log=print):
             assert np.isfinite(r["dst"]).all()
             assert np.array_equal(bits(r["dst"][:, 0:3]), bits(ref["dst"][:, 0:3]))
             assert np.array_equal(r["dst"][:, 9], ref["dst"][:, 9])
+            # every internal node's moments against binary64, per node (tests/tree_ref.py)
+            R.check_moments(r["tree"], s)
+            # the integrator: new velocity from the GPU's own new acceleration, and the mass, bit for bit
+            src = s[r["order"]]
+            v_new = R.kick32(R.kick32(src[:, 3:6], src[:, 6:9], dt), r["dst"][:, 6:9], dt)
+            assert np.array_equal(bits(r["dst"][:, 3:6]), bits(v_new))
+            assert np.array_equal(bits(r["dst"][:, 9]), bits(src[:, 9]))
+            # the first and the last bodies of the sorted order against the binary64 walk of the GPU's own tree
+            pick = np.unique(np.concatenate([np.arange(min(n, WALK_SAMPLE)), np.arange(max(0, n - WALK_SAMPLE), n)]))
+            w = R.walk64(r["tree"], r["root_width"], r["order"], r["dst"][:, 0:3], theta, g, E, dt, bodies=pick)
+            units = R.force_units(r["dst"][pick, 6:9], w)
+            assert (units[~w["flagged"]] <= R.K).all(), (int(pick[np.argmax(np.where(w["flagged"], 0.0, units))]),
+                                                         float(units[~w["flagged"]].max()))
             err = rel_err(r["dst"][:, 6:9], ref["dst"][:, 6:9])
             assert np.median(err) < 1e-5, np.median(err)
             assert np.percentile(err, 99) < 1e-4, np.percentile(err, 99)

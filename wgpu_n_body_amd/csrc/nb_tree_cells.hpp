@@ -91,7 +91,7 @@ struct __attribute__((aligned(32))) NodeRec {
                             // (tree.wgsl:82; rounded once here, so that every test of the cell -- each body's own,
                             // the group's all-open shortcut, a LET export's box test -- compares the same number
                             // with its r^2: size/dist < theta (tree.wgsl:63-64) as mac2 < r^2);
-                            // leaf: -1, which makes the test always true
+                            // leaf: -1, which makes the test always true; a cell of mass 0: +inf, never true
 };
 
 // ---- 6a. mass moments by prefix sums ------------------------------------------------------------
@@ -616,6 +616,12 @@ __global__ void fill_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint3
             const float4 q = float4{(float)((b2.x - a.x) / m), (float)((b2.y - a.y) / m),
                                     (float)((b2.z - a.z) / m), (float)m};
             if (AOS) cogm[id] = q;
+            // A cell whose bodies are all massless (tracers): m = 0 and q = 0 / 0 = NaN, as the reference has it --
+            // there the comparison with NaN is false and the cell is merely opened.  The walk with the bodies across
+            // the lanes predicates the force by a zero weight, and 0 x NaN is NaN: the RECORD carries a finite centre
+            // and an infinite acceptance radius instead -- always opened, never taken, at no cost to the walk.
+            const bool massless = m == 0.0;
+            const float4 qr = massless ? float4{0.f, 0.f, 0.f, 0.f} : q;
             // children are allocated contiguously in octant order (tree.rs:517-519), so the walk
             // only needs the first child's id and how many there are
             // a tree that outgrew its 4N capacity (status[1]) keeps the walk in bounds: a cell whose
@@ -623,12 +629,12 @@ __global__ void fill_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint3
             // ... and children always carry larger ids than their parent (breadth-first numbering), which
             // is what lets the walk terminate without a visit budget: enforce it here
             if (cnt == 0u || first + cnt > n_nodes || first <= id) {
-                rec[id] = NodeRec{q, 0u, 0u, ~0u, -1.0f};
+                rec[id] = NodeRec{qr, 0u, 0u, ~0u, massless ? __builtin_inff() : -1.0f};
             } else {
                 const float root_width = __uint_as_float(*bound_bits) * 2.0f;
                 float size2 = root_width * root_width;
                 for (uint32_t l = 0; l < d; ++l) size2 *= 0.25f;  // exact: the width halves per level
-                rec[id] = NodeRec{q, first, cnt, ~0u, size2 * inv_theta2};
+                rec[id] = NodeRec{qr, first, cnt, ~0u, massless ? __builtin_inff() : size2 * inv_theta2};
             }
         }
         if (AOS) {
