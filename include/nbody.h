@@ -461,6 +461,95 @@ int nb_radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, 
                          const double *fractions, uint32_t k, double *radii);
 
 /* ------------------------------------------------------------------------- */
+/* Field probes -- exact acceleration and potential at arbitrary points (no   */
+/* reference counterpart: the reference evaluates its force law at bodies only)*/
+/* ------------------------------------------------------------------------- */
+/* The all-pairs force law of the step and its potential, summed on the device
+ * over the state nb_sim_read_particles would return, at m points that need not
+ * be bodies.  The rule, which DESIGN.md 6e states in full.  The sums run over
+ * exactly the bodies nb_sim_diagnostics counts as finite; a body with any
+ * non-finite position, velocity or mass component is left out and reported in
+ * stats.nonfinite.  For a point p (three fp32 coordinates) and body j, in fp32:
+ *   d = x_j - p,  r2 = dx dx + dy dy + dz dz,  r = sqrt(r2),  g = params.g, e = params.e
+ *   coincident   r2 == 0 (in practice: the same coordinates).  Such a body adds
+ *                nothing to either sum and is counted in the sample's `coincident`:
+ *                the field at a body's own position is the field of the others,
+ *                which is the step's self-exclusion by index whenever no two
+ *                distinct bodies coincide
+ *   acc          g sum_j m_j d / (r^4 + e r): the reference's pair force
+ *                m g / (r^3 + e) * d / r (naive.wgsl:38-39) without the dt that the
+ *                stored Particle.acceleration carries (stored = acc * dt)
+ *   potential    -g sum_j m_j psi(r), psi as in "Diagnostics" above; then
+ *                diagnostics.potential == (dt / 2) sum_i m_i potential(x_i) up to
+ *                rounding whenever no two distinct bodies coincide
+ * Arithmetic: the per-pair terms in fp32 with the step's 1-ulp sqrt and reciprocal;
+ * runs of at most 64 consecutive bodies summed in fp32; each run folded into an
+ * fp64 sum; the partial sums of the body chunks added in fp64 in a fixed order;
+ * the result multiplied once by (double)g.  Against the same sums in binary64 a
+ * component of acc is within 80 * 2^-24 * g sum_j m_j |d_k| / (r^4 + e r), and
+ * the potential within 5e-6 * g sum_j |m_j| psi(r).
+ * No float atomics, and the grid and the chunking are functions of (m, n, flags)
+ * alone: two calls return bit-identical samples, and a point's sample does not
+ * depend on its place in the array (permuting the points permutes the samples
+ * bit for bit).  The last bits may differ between calls with different m or
+ * different flags.
+ * A point with a non-finite coordinate gets NaN in every requested field
+ * (coincident 0) and is counted in stats.nonfinite_points; fields not requested
+ * are NaN; n = 0 gives zeros; m = 0 is valid, only synchronises, and measures
+ * nothing (stats.nonfinite is 0).  The call is ordered after the enqueued steps
+ * on the simulator's stream, ends with one synchronisation, reports a TreeSim's
+ * status words as nb_sim_read_particles does, and does not change the
+ * trajectory.  The points go in bands, one launch per band of at most 2^35 pairs
+ * ("field_launch_pairs_log2", nb_sim_set_tuning, 16..40: speed and testing only,
+ * identical samples). */
+#define NB_FIELD_ACCEL 1u
+#define NB_FIELD_POTENTIAL 2u
+#define NB_FIELD_MAX_POINTS (1u << 24)
+
+typedef struct nb_field_sample { /* 40 bytes */
+    double acc[3];
+    double potential;
+    uint32_t coincident; /* bodies at the point itself (left out of both sums) */
+    uint32_t reserved;
+} nb_field_sample;
+
+typedef struct nb_field_stats {
+    uint64_t step_num; /* the step the measured state is the result of */
+    uint64_t n;        /* bodies of the simulator */
+    uint64_t nonfinite;
+    uint64_t points, nonfinite_points;
+    uint32_t flags;    /* what was computed */
+    uint32_t launches; /* bands */
+} nb_field_stats;
+
+/* The field of a simulator's current state at `points` (3 floats per point) into out[0 .. m).
+ * flags: NB_FIELD_ACCEL, NB_FIELD_POTENTIAL or both.  stats may be null.  NB_ERR_INVALID for a null
+ * handle, null points or out with m > 0, flags zero or with unknown bits, m > NB_FIELD_MAX_POINTS, or
+ * NB_FIELD_POTENTIAL with e < 0 -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded
+ * simulator (placement world > 1). */
+int nb_sim_field(nb_sim *sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
+                 nb_field_stats *stats);
+/* Host only, no device: k * n_phi points on k rings about `axis` through `center`, for a rotation curve.
+ * Ring i, azimuth q is points[3 (i n_phi + q)] = c + R_i (cos(2 pi q / n_phi) e1 + sin(2 pi q / n_phi) e2),
+ * formed in fp64 and rounded once.  n = axis normalised in fp64; e1 = the coordinate axis of the smallest
+ * |n_k| (the lowest index on ties), made orthogonal to n and normalised; e2 = n cross e1.
+ * NB_ERR_INVALID for a null pointer, a zero or non-finite axis, a non-finite centre, negative or
+ * non-finite radii, or n_phi = 0. */
+int nb_field_rings(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                   float *points);
+typedef struct nb_field_ring { /* means over the n_phi samples of one ring */
+    double a_R;       /* acc . rhat, rhat the unit vector from the axis to the fp32 point actually used */
+    double a_n;       /* acc . n */
+    double potential;
+    double v_c;       /* sqrt(max(0, -R_i a_R)): the circular velocity */
+} nb_field_ring;
+/* Host only, a pure function of its arguments: the ring means of `samples` taken at the `points`
+ * nb_field_rings wrote for the same center, axis, radii, k and n_phi.  A point on the axis has no rhat
+ * and adds 0 to a_R.  Refusals as nb_field_rings, and null samples or out. */
+int nb_field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
+                        uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -611,6 +700,10 @@ int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, nb_radial_profile *out,
                              nb_radial_bin *bins);
+/* nb_sim_field of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
+                    nb_field_stats *stats);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -35,6 +35,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
+           "Field", "RingMeans", "field_rings",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -249,6 +250,72 @@ def _radial_profile(call, handle, edges, nbins, rmin, rmax, log, cylindrical, ax
     bins = np.zeros(max(int(p.nbins), 1), dtype=_lib.RADIAL_BIN_DTYPE)
     check(call(handle, C.byref(p), C.byref(out), bins.ctypes.data))
     return RadialProfile._from_c(out, bins, edges)
+
+
+@dataclass(frozen=True)
+class Field:
+    """nb_field_sample[M] + nb_field_stats (include/nbody.h "Field probes"; no reference counterpart): the
+    exact all-pairs acceleration (without the dt the stored Particle.acceleration carries) and potential
+    of the state read_particles would return, at M points.  A field that was not requested is NaN."""
+    acc: np.ndarray          # (M, 3) float64
+    potential: np.ndarray    # (M,) float64
+    coincident: np.ndarray   # (M,) uint32: bodies at the point itself, left out of both sums
+    step_num: int
+    n: int
+    nonfinite: int           # bodies left out, as diagnostics() counts them
+    points: int
+    nonfinite_points: int
+    flags: int
+    launches: int
+
+
+@dataclass(frozen=True)
+class RingMeans:
+    """nb_field_ring[k]: per ring the means over its azimuths of the radial and axial acceleration and the
+    potential, and the circular velocity sqrt(max(0, -R a_R))."""
+    radii: np.ndarray
+    a_R: np.ndarray
+    a_n: np.ndarray
+    potential: np.ndarray
+    v_c: np.ndarray
+    field: Field             # the samples behind the means, ring-major
+
+
+def _vec3(v):
+    return (C.c_double * 3)(*(float(x) for x in v))
+
+
+def field_rings(radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16) -> np.ndarray:
+    """nb_field_rings: (len(radii) * n_phi, 3) float32 points, n_phi evenly spaced on each ring of radius
+    radii[i] about `axis` through `center`, ring-major."""
+    r = np.ascontiguousarray(np.atleast_1d(radii), dtype=np.float64)
+    out = np.empty((r.shape[0] * max(int(n_phi), 0), 3), dtype=np.float32)
+    check(_lib.lib().nb_field_rings(_vec3(center), _vec3(axis), r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0],
+                                    int(n_phi), out.ctypes.data))
+    return out
+
+
+def _field(call, handle, points, accel, potential) -> Field:
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    flags = (_lib.NB_FIELD_ACCEL if accel else 0) | (_lib.NB_FIELD_POTENTIAL if potential else 0)
+    out = np.zeros(pts.shape[0], dtype=_lib.FIELD_SAMPLE_DTYPE)
+    st = _lib.nb_field_stats()
+    check(call(handle, pts.ctypes.data, pts.shape[0], flags, out.ctypes.data, C.byref(st)))
+    return Field(out["acc"].copy(), out["potential"].copy(), out["coincident"].copy(), int(st.step_num), int(st.n),
+                 int(st.nonfinite), int(st.points), int(st.nonfinite_points), int(st.flags), int(st.launches))
+
+
+def _circular_velocity(call, handle, radii, axis, center, n_phi, potential) -> RingMeans:
+    r = np.ascontiguousarray(np.atleast_1d(radii), dtype=np.float64)
+    pts = field_rings(r, axis=axis, center=center, n_phi=n_phi)
+    f = _field(call, handle, pts, True, potential)
+    samples = np.zeros(pts.shape[0], dtype=_lib.FIELD_SAMPLE_DTYPE)
+    samples["acc"], samples["potential"] = f.acc, f.potential
+    out = np.zeros(r.shape[0], dtype=_lib.FIELD_RING_DTYPE)
+    check(_lib.lib().nb_field_ring_means(_vec3(center), _vec3(axis), r.ctypes.data_as(C.POINTER(C.c_double)),
+                                         r.shape[0], int(n_phi), pts.ctypes.data, samples.ctypes.data,
+                                         out.ctypes.data))
+    return RingMeans(r, out["a_R"].copy(), out["a_n"].copy(), out["potential"].copy(), out["v_c"].copy(), f)
 
 
 @dataclass(frozen=True)
@@ -574,6 +641,18 @@ class Simulator:
         return _radial_profile(_lib.lib().nb_sim_radial_profile, self._h, edges, nbins, rmin, rmax, log,
                                cylindrical, axis, center, velocity)
 
+    def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
+        """The exact acceleration and potential of the current state at `points` ((M, 3), float32), summed
+        over all bodies on the device (nb_sim_field).  A body at a point itself adds nothing and is counted
+        in `.coincident`, so the field at a body's position is the field of the others."""
+        return _field(_lib.lib().nb_sim_field, self._h, points, accel, potential)
+
+    def circular_velocity(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16,
+                          potential: bool = False) -> RingMeans:
+        """The rotation curve from the force: field() on n_phi points of each ring of field_rings(), then
+        the ring means (nb_field_ring_means): v_c = sqrt(max(0, -R a_R))."""
+        return _circular_velocity(_lib.lib().nb_sim_field, self._h, radii, axis, center, n_phi, potential)
+
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
         """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
@@ -744,6 +823,15 @@ class OfflineHeadless:
         """nb_runner_radial_profile: Simulator.radial_profile of the runner's simulator (one device only)."""
         return _radial_profile(_lib.lib().nb_runner_radial_profile, self._h, edges, nbins, rmin, rmax, log,
                                cylindrical, axis, center, velocity)
+
+    def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
+        """nb_runner_field: Simulator.field of the runner's simulator (one device only)."""
+        return _field(_lib.lib().nb_runner_field, self._h, points, accel, potential)
+
+    def circular_velocity(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16,
+                          potential: bool = False) -> RingMeans:
+        """Simulator.circular_velocity of the runner's simulator (one device only)."""
+        return _circular_velocity(_lib.lib().nb_runner_field, self._h, radii, axis, center, n_phi, potential)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

@@ -82,6 +82,24 @@ class nb_radial_profile(C.Structure):
                 ("shape", C.c_double * 6), ("nbins", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class nb_field_sample(C.Structure):
+    _fields_ = [("acc", C.c_double * 3), ("potential", C.c_double), ("coincident", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class nb_field_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("points", C.c_uint64),
+                ("nonfinite_points", C.c_uint64), ("flags", C.c_uint32), ("launches", C.c_uint32)]
+
+
+class nb_field_ring(C.Structure):
+    _fields_ = [("a_R", C.c_double), ("a_n", C.c_double), ("potential", C.c_double), ("v_c", C.c_double)]
+
+
+# nb_field_sample[] and nb_field_ring[] as numpy record arrays
+FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
+FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -90,6 +108,8 @@ assert C.sizeof(nb_sim_params) == 16 and C.sizeof(nb_add_params) == 8
 assert C.sizeof(nb_diagnostics) == 152
 assert C.sizeof(nb_radial_bin) == 88 == RADIAL_BIN_DTYPE.itemsize
 assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
+assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.sizeof(nb_field_stats) == 48
+assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -100,6 +120,8 @@ NB_DIAG_MOMENTS, NB_DIAG_POTENTIAL = 1, 2
 NB_RENDER_SRGB = 1
 NB_RADIAL_MAX_BINS = 256
 NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM = 1, 2
+NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
+NB_FIELD_MAX_POINTS = 1 << 24
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -113,6 +135,7 @@ ABI_SYMBOLS = [
     "nb_sim_exchange_region_i", "nb_sim_step_num", "nb_sim_encode_n_timed",
     "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics",
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
+    "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
@@ -179,6 +202,11 @@ def lib() -> C.CDLL:
         getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_radial_lagrangian.argtypes = [P(nb_radial_profile), vp, P(C.c_double), P(C.c_double), C.c_uint32,
                                        P(C.c_double)]
+    L.nb_sim_field.argtypes = [vp, vp, sz, C.c_uint32, vp, P(nb_field_stats)]
+    L.nb_runner_field.argtypes = [vp, vp, sz, C.c_uint32, vp, P(nb_field_stats)]
+    L.nb_field_rings.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp]
+    L.nb_field_ring_means.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp, vp,
+                                      vp]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]
     L.nb_camera_view_proj.argtypes = [P(nb_camera), P(C.c_float)]
     L.nb_render_params_default.argtypes = [P(nb_render_params), C.c_uint32, C.c_uint32]

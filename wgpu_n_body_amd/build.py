@@ -29,6 +29,7 @@ SOURCES = [
     ("nb_camera.cpp", ["-ffp-contract=off"]),
     # the binning rule is specified operation by operation: no FMA contraction
     ("nb_radial.hip", ["-ffp-contract=off"]),
+    ("nb_field.hip", []),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

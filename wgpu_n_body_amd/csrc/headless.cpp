@@ -6,6 +6,8 @@
 //            [--e E] [--diag K [--diag-potential 1]] [--frames DIR [--frame-every K] [--frame-size WxH]]
 //            [--radial K --radial-range RMIN,RMAX [--radial-bins B] [--radial-log 0|1] [--radial-axis X,Y,Z]
 //             [--radial-center com|X,Y,Z]]
+//            [--rotcurve K --rotcurve-range RMIN,RMAX [--rotcurve-bins B] [--rotcurve-phi Q]
+//             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -25,6 +27,12 @@
 // per bin "RadialBin: step S bin k lo E0 hi E1 count C mass M m_r . m_ur . m_ur2 . m_uphi . m_uphi2 .
 // m_u2 . ang x y z" (the fields of nb_radial_profile and nb_radial_bin; every real %.17g).  The time they
 // take is not part of any "Step Duration"; without --radial the output is unchanged.
+//
+// --rotcurve K prints the rotation curve from the force (nb_runner_field on rings, nb_field_ring_means)
+// of step 0 and of every K-th step: B radii (--rotcurve-bins, default 32) linear from RMIN to RMAX, Q
+// points per ring (--rotcurve-phi, default 16) about --rotcurve-axis (default 0,1,0) through
+// --rotcurve-center (default 0,0,0).  One line per ring "rotcurve <step> <R> <a_R> <a_n> <v_c>" (%.9e).
+// The time they take is not part of any "Step Duration"; without --rotcurve the output is unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
 // default camera, src/runners/online_renderer.rs:224-367) at step 0 and after every K-th step
@@ -98,6 +106,25 @@ static void print_radial(nbody::OfflineHeadless<Sim> &runner, const RadialOption
     }
 }
 
+struct RotcurveOptions {
+    int every = 0;
+    uint32_t bins = 32, phi = 16;
+    bool have_range = false;
+    double rmin = 0.0, rmax = 0.0;
+    std::array<double, 3> axis{0.0, 1.0, 0.0}, center{0.0, 0.0, 0.0};
+};
+
+template <class Sim>
+static void print_rotcurve(nbody::OfflineHeadless<Sim> &runner, const RotcurveOptions &ro) {
+    std::vector<double> radii(ro.bins);
+    for (uint32_t i = 0; i < ro.bins; ++i)
+        radii[i] = ro.bins > 1 ? ro.rmin + (ro.rmax - ro.rmin) * (double)i / (double)(ro.bins - 1) : ro.rmin;
+    const nbody::RingMeans r = runner.circular_velocity(radii, ro.axis, ro.center, ro.phi);
+    for (uint32_t i = 0; i < ro.bins; ++i)
+        std::printf("rotcurve %llu %.9e %.9e %.9e %.9e\n", (unsigned long long)r.field.stats.step_num, radii[i],
+                    r.rings[i].a_R, r.rings[i].a_n, r.rings[i].v_c);
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -134,13 +161,15 @@ static bool write_frame(nbody::OfflineHeadless<Sim> &runner, const FrameOptions 
 template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
-               int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial) {
+               int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
+               const RotcurveOptions &rotcurve) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
     std::puts("Running Simulation");
     if (diag > 0) print_diag(runner, diag_potential);
     if (radial.every > 0) print_radial(runner, radial);
+    if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -150,6 +179,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         std::printf("Step Duration: %lld \xC2\xB5s\n", (long long)us);
         if (diag > 0 && (i + 1) % diag == 0) print_diag(runner, diag_potential);
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
+        if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -172,6 +202,7 @@ int main(int argc, char **argv) {
     bool diag_potential = false;
     FrameOptions frames;
     RadialOptions radial;
+    RotcurveOptions rotcurve;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -217,6 +248,23 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (k == "--rotcurve") rotcurve.every = std::atoi(v.c_str());
+        else if (k == "--rotcurve-bins") rotcurve.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--rotcurve-phi") rotcurve.phi = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--rotcurve-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &rotcurve.rmin, &rotcurve.rmax) != 2) {
+                std::fprintf(stderr, "--rotcurve-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            rotcurve.have_range = true;
+        }
+        else if (k == "--rotcurve-axis" || k == "--rotcurve-center") {
+            double *a = k == "--rotcurve-axis" ? rotcurve.axis.data() : rotcurve.center.data();
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
+                std::fprintf(stderr, "%s takes X,Y,Z, not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--frames") frames.dir = v;
         else if (k == "--frame-every") frames.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--frame-size") {
@@ -241,15 +289,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--radial needs --radial-range RMIN,RMAX\n");
         return 2;
     }
+    if (rotcurve.every > 0 && !rotcurve.have_range) {
+        std::fprintf(stderr, "--rotcurve needs --rotcurve-range RMIN,RMAX\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial);
+                                        diag_potential, frames, radial, rotcurve);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial);
+                                       diag, diag_potential, frames, radial, rotcurve);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -37,6 +37,7 @@ SimBase::~SimBase() {
     diag_release(diag);  // (the derived destructor has bound the device)
     render_release(render);
     radial_release(radial);
+    field_release(field);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -498,6 +499,67 @@ static int radial_edges(const char *what, bool log, double rmin, double rmax, ui
     return NB_OK;
 }
 
+// nb_sim_field: everything about the arguments that can be refused without a device
+static int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out) {
+    if (m > 0 && (!points || !out)) {
+        set_error("field: null %s", !points ? "points" : "out");
+        return NB_ERR_INVALID;
+    }
+    if (!flags || (flags & ~(NB_FIELD_ACCEL | NB_FIELD_POTENTIAL))) {
+        set_error("field: flags must be NB_FIELD_ACCEL, NB_FIELD_POTENTIAL or both (got 0x%x)", flags);
+        return NB_ERR_INVALID;
+    }
+    if (m > NB_FIELD_MAX_POINTS) {
+        set_error("field: at most %u points (got %zu)", NB_FIELD_MAX_POINTS, m);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_field_rings / nb_field_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
+static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
+                      uint32_t n_phi, double n[3], double e1[3], double e2[3]) {
+    if (!center || !axis || (k && !radii)) {
+        set_error("%s: null %s", what, !center ? "center" : !axis ? "axis" : "radii");
+        return NB_ERR_INVALID;
+    }
+    if (n_phi == 0) {
+        set_error("%s: n_phi must be at least 1", what);
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(center[a]) || !std::isfinite(axis[a])) {
+            set_error("%s: center and axis must be finite", what);
+            return NB_ERR_INVALID;
+        }
+    // (an axis whose length over- or underflows has no finite unit vector either)
+    const double len = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) {
+        set_error("%s: needs a non-zero axis", what);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i)
+        if (!std::isfinite(radii[i]) || radii[i] < 0.0) {
+            set_error("%s: radii must be finite and >= 0 (radii[%u] = %g)", what, i, radii[i]);
+            return NB_ERR_INVALID;
+        }
+    for (int a = 0; a < 3; ++a) n[a] = axis[a] / len;
+    int s = 0;  // the coordinate axis of the smallest |n_k|, the lowest index on ties
+    for (int a = 1; a < 3; ++a)
+        if (std::fabs(n[a]) < std::fabs(n[s])) s = a;
+    double el = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        e1[a] = (a == s ? 1.0 : 0.0) - n[s] * n[a];
+        el += e1[a] * e1[a];
+    }
+    el = std::sqrt(el);  // >= sqrt(2/3): |n_s| <= 1/sqrt(3)
+    for (int a = 0; a < 3; ++a) e1[a] /= el;
+    e2[0] = n[1] * e1[2] - n[2] * e1[1];
+    e2[1] = n[2] * e1[0] - n[0] * e1[2];
+    e2[2] = n[0] * e1[1] - n[1] * e1[0];
+    return NB_OK;
+}
+
 #define NB_GUARD(body)                                            \
     try {                                                         \
         body                                                      \
@@ -664,6 +726,18 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
             return sim_render_set_design(*sim->impl, value);
         })
     }
+    if (!std::strcmp(key, "field_launch_pairs_log2")) {  // the field probes', whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 16 || value > 40) {
+            set_error("field_launch_pairs_log2: 16..40, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->field_pairs_log2 = value;
+        return NB_OK;
+    }
     NB_SIM_CALL(sim, set_tuning(key, value))
 }
 
@@ -735,6 +809,75 @@ int nb_radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, 
             }
             cum = next;
         }
+    }
+    return NB_OK;
+}
+
+int nb_sim_field(nb_sim *sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
+                 nb_field_stats *stats) {
+    if (int rc = field_check_args(points, m, flags, out)) return rc;
+    NB_GUARD({
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        return sim_field(*sim->impl, points, m, flags, out, stats);
+    })
+}
+
+int nb_field_rings(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                   float *points) {
+    double n[3], e1[3], e2[3];
+    if (int rc = ring_basis("field_rings", center, axis, radii, k, n_phi, n, e1, e2)) return rc;
+    if (k && !points) {
+        set_error("field_rings: null points");
+        return NB_ERR_INVALID;
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (uint32_t i = 0; i < k; ++i)
+        for (uint32_t q = 0; q < n_phi; ++q) {
+            const double phi = two_pi * (double)q / (double)n_phi, c = std::cos(phi), s = std::sin(phi);
+            float *p = points + 3 * ((size_t)i * n_phi + q);
+            for (int a = 0; a < 3; ++a) p[a] = (float)(center[a] + radii[i] * (c * e1[a] + s * e2[a]));
+        }
+    return NB_OK;
+}
+
+int nb_field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
+                        uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out) {
+    double n[3], e1[3], e2[3];
+    if (int rc = ring_basis("field_ring_means", center, axis, radii, k, n_phi, n, e1, e2)) return rc;
+    if (k && (!points || !samples || !out)) {
+        set_error("field_ring_means: null %s", !points ? "points" : !samples ? "samples" : "out");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        double a_r = 0.0, a_n = 0.0, pot = 0.0;
+        for (uint32_t q = 0; q < n_phi; ++q) {
+            const size_t j = (size_t)i * n_phi + q;
+            const nb_field_sample &f = samples[j];
+            double d[3], h = 0.0;  // the fp32 point actually used, from the centre; its height along n
+            for (int a = 0; a < 3; ++a) {
+                d[a] = (double)points[3 * j + a] - center[a];
+                h += d[a] * n[a];
+            }
+            double len = 0.0, dot = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                d[a] -= h * n[a];
+                len += d[a] * d[a];
+                dot += f.acc[a] * d[a];
+            }
+            len = std::sqrt(len);
+            if (len > 0.0) a_r += dot / len;
+            a_n += f.acc[0] * n[0] + f.acc[1] * n[1] + f.acc[2] * n[2];
+            pot += f.potential;
+        }
+        nb_field_ring r{};
+        r.a_R = a_r / (double)n_phi;
+        r.a_n = a_n / (double)n_phi;
+        r.potential = pot / (double)n_phi;
+        r.v_c = std::sqrt(std::fmax(0.0, -radii[i] * r.a_R));
+        out[i] = r;
     }
     return NB_OK;
 }
@@ -949,6 +1092,17 @@ int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, 
         return NB_ERR_UNSUPPORTED;
     }
     return nb_sim_radial_profile(runner->sim, params, out, bins);
+}
+
+int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
+                    nb_field_stats *stats) {
+    if (int rc = field_check_args(points, m, flags, out)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (runner->group) {
+        set_error("field: not available on a several-GPU runner (nb_runner_create_multi*)");
+        return NB_ERR_UNSUPPORTED;
+    }
+    return nb_sim_field(runner->sim, points, m, flags, out, stats);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

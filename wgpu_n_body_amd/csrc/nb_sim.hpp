@@ -11,6 +11,7 @@ namespace nb {
 struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
 struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
 struct RadialWork;  // nb_radial.hip: the radial profile's slabs, squared edges and pinned result
+struct FieldWork;  // nb_field.hip: the field probes' points, slabs and pinned samples
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -121,6 +122,8 @@ class SimBase {
     DiagWork *diag = nullptr;  // allocated by the first nb_sim_diagnostics
     RenderWork *render = nullptr;  // allocated by the first nb_sim_render
     RadialWork *radial = nullptr;  // allocated by the first nb_sim_radial_profile
+    FieldWork *field = nullptr;  // allocated by the first nb_sim_field
+    int field_pairs_log2 = 35;  // "field_launch_pairs_log2": pairs per launch of nb_sim_field, 2^16 .. 2^40
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
@@ -129,7 +132,8 @@ void diag_release(DiagWork *w);
 // the moments pass and its finish alone, enqueued on the simulator's stream (n > 0; the device is bound):
 // *res_dev = the finished sums on the device, mass at [kDiagResMass], sum m x at [kDiagResMX + k], sum m v
 // at [kDiagResMV + k] -- what sim_diagnostics divides into `com` and reports as `momentum`
-constexpr int kDiagResMass = 0, kDiagResMX = 1, kDiagResMV = 4;
+// (and the count of non-finite bodies at [kDiagResBad])
+constexpr int kDiagResMass = 0, kDiagResMX = 1, kDiagResMV = 4, kDiagResBad = 12;
 int diag_enqueue_moments(SimBase &sim, const double **res_dev);
 
 // nb_render.hip: nb_sim_render behind the handle (arguments already checked by render_check_params,
@@ -143,6 +147,11 @@ void render_release(RenderWork *w);
 // the release of its workspace
 int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_profile *out, nb_radial_bin *bins);
 void radial_release(RadialWork *w);
+
+// nb_field.hip: nb_sim_field behind the handle (arguments already checked, nb_abi.cpp) and the release of
+// its workspace
+int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out, nb_field_stats *stats);
+void field_release(FieldWork *w);
 
 class NaiveSim final : public SimBase {
    public:

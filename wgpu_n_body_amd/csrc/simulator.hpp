@@ -14,6 +14,7 @@
 // (src/sims/tree.rs:278-280); here it throws.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <stdexcept>
@@ -31,6 +32,8 @@ using Octant = nb_octant;        // 52 B
 using Diagnostics = nb_diagnostics;  // conserved-quantity monitor (no reference counterpart)
 using RadialParams = nb_radial_params;    // bins, flags, centre, axis and edges of a radial profile
 using RadialBin = nb_radial_bin;          // 88 B
+using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and coincident count at a point
+using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -109,6 +112,51 @@ RadialProfile radial_profile(int (*call)(H *, const nb_radial_params *, nb_radia
     p.nbins = edges.empty() ? 0u : (uint32_t)(edges.size() - 1);
     p.edges = r.edges.data();
     check(call(h, &p, &r.profile, r.bins.data()));
+    return r;
+}
+}  // namespace detail
+
+// The field at a set of points (no reference counterpart): the samples and what the call measured
+struct Field {
+    std::vector<FieldSample> samples;
+    nb_field_stats stats{};
+};
+
+// k * n_phi points (3 floats each, ring-major) on the rings of the given radii about `axis` through `center`
+inline std::vector<float> field_rings(const std::vector<double> &radii, const std::array<double, 3> &axis,
+                                      const std::array<double, 3> &center, uint32_t n_phi) {
+    std::vector<float> pts(3 * radii.size() * (size_t)n_phi);
+    check(nb_field_rings(center.data(), axis.data(), radii.data(), (uint32_t)radii.size(), n_phi, pts.data()));
+    return pts;
+}
+
+// A rotation curve from the force: per ring the means of nb_field_ring_means, and the samples behind them
+struct RingMeans {
+    std::vector<double> radii;
+    std::vector<FieldRing> rings;
+    Field field;
+};
+
+namespace detail {
+template <class H>
+Field field(int (*call)(H *, const float *, size_t, uint32_t, nb_field_sample *, nb_field_stats *), H *h,
+            const std::vector<float> &points, uint32_t flags) {
+    Field f;
+    f.samples.resize(points.size() / 3);
+    check(call(h, points.data(), points.size() / 3, flags, f.samples.data(), &f.stats));
+    return f;
+}
+template <class H>
+RingMeans circular_velocity(int (*call)(H *, const float *, size_t, uint32_t, nb_field_sample *, nb_field_stats *),
+                            H *h, const std::vector<double> &radii, const std::array<double, 3> &axis,
+                            const std::array<double, 3> &center, uint32_t n_phi, bool potential) {
+    RingMeans r;
+    r.radii = radii;
+    const std::vector<float> pts = field_rings(radii, axis, center, n_phi);
+    r.field = field(call, h, pts, NB_FIELD_ACCEL | (potential ? NB_FIELD_POTENTIAL : 0u));
+    r.rings.resize(radii.size());
+    check(nb_field_ring_means(center.data(), axis.data(), radii.data(), (uint32_t)radii.size(), n_phi, pts.data(),
+                              r.field.samples.data(), r.rings.data()));
     return r;
 }
 }  // namespace detail
@@ -202,6 +250,16 @@ class Simulator {
     // (NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
     RadialProfile radial_profile(const std::vector<double> &edges, const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
         return detail::radial_profile(nb_sim_radial_profile, h_, edges, p);
+    }
+    // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
+    Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
+        return detail::field(nb_sim_field, h_, points, flags);
+    }
+    // the rotation curve from the force on n_phi points of each ring: v_c = sqrt(max(0, -R a_R))
+    RingMeans circular_velocity(const std::vector<double> &radii, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
+                                const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
+                                bool potential = false) {
+        return detail::circular_velocity(nb_sim_field, h_, radii, axis, center, n_phi, potential);
     }
     // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
     Frame render(const RenderParams &p, bool counts = false) {
@@ -320,6 +378,15 @@ class OfflineHeadless {
     RadialProfile radial_profile(const std::vector<double> &edges,  // one device only
                                  const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
         return detail::radial_profile(nb_runner_radial_profile, r_, edges, p);
+    }
+    Field field(const std::vector<float> &points,  // one device only
+                uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
+        return detail::field(nb_runner_field, r_, points, flags);
+    }
+    RingMeans circular_velocity(const std::vector<double> &radii, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
+                                const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
+                                bool potential = false) {  // one device only
+        return detail::circular_velocity(nb_runner_field, r_, radii, axis, center, n_phi, potential);
     }
     Frame render(const RenderParams &p, bool counts = false) {  // one device only
         Frame f;
