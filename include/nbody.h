@@ -550,6 +550,86 @@ int nb_field_ring_means(const double center[3], const double axis[3], const doub
                         uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out);
 
 /* ------------------------------------------------------------------------- */
+/* Projected maps -- per-cell mass and velocity moments on a 2-D grid (no     */
+/* reference counterpart: structure in two dimensions, without symmetry)      */
+/* ------------------------------------------------------------------------- */
+/* Projects the state nb_sim_read_particles would return along a line of sight
+ * onto a metric, orthographic width x height grid and sums, per cell, the count,
+ * the mass and (NB_MAP_VELOCITY) five velocity terms: the surface-density map,
+ * the line-of-sight velocity map and the dispersion map, on the device.  The
+ * rule, which DESIGN.md 6f states in full: everything in binary64 from the
+ * binary32 state, one rounding per operation, no contraction, in this order:
+ *   frame     n = axis / sqrt((ax ax + ay ay) + az az); e1 = the coordinate axis of
+ *             the smallest |n_k| (the lowest index on ties), made orthogonal to n
+ *             and normalised; e2 = n cross e1 -- the vectors of nb_field_rings, so
+ *             ring points and map cells share coordinates (nb_map_frame)
+ *   per body  d = (double)x - c, u = (double)v - v_c   (c, v_c: centre and its velocity)
+ *             a = (dx e1x + dy e1y) + dz e1z; b, h the same with e2, n
+ *             ua, ub, w the same from u
+ *   edges     xe[i] = lo + (double)i ((hi - lo) / W) for i < W, xe[W] = hi exactly;
+ *             ye the same from y_range and H (nb_map_edges)
+ *   cell      the (i, j) with xe[i] <= a < xe[i+1] and ye[j] <= b < ye[j+1]: decided by
+ *             comparisons against those edges, so the counts are exact integers
+ *   outside   a or b outside its window, or h not in [depth lo, depth hi); every
+ *             comparison with a NaN is false, so a NaN a, b or h (a NaN centre of
+ *             mass: no mass) puts the body outside
+ *   terms     m, m ua, m ub, m w, (m w) w, m ((ux ux + uy uy) + uz uz)
+ * A body with any non-finite position, velocity or mass component is `nonfinite`
+ * and left out of everything (the predicate of nb_sim_diagnostics).
+ * binned_count + outside_count + nonfinite == n; sum of counts == binned_count.
+ * NB_MAP_CENTER_COM: c and v_c are the fp64 `com` and `momentum / mass` that
+ * nb_sim_diagnostics returns for the same state, bit for bit (the same moments
+ * pass runs ahead on the stream; no host round trip).
+ * No float atomics and no summation order that depends on timing: the result is
+ * a function of the stored state and the parameters alone, two calls on one state
+ * return bit-identical counts, planes and stats, and every double is within
+ * 1e-10 of its sum of |term| of the binary64 sum.  The call is ordered after the
+ * enqueued steps on the simulator's stream, ends with one synchronisation,
+ * reports a TreeSim's status words as nb_sim_read_particles does, and does not
+ * change the trajectory.
+ * "map_segment_len" (nb_sim_set_tuning, 256..65536, a multiple of 256; default
+ * 4096; speed and testing only): a cell's bodies are summed in runs of at most
+ * this many bodies of its 8 x 8-cell tile, the runs then in order. */
+#define NB_MAP_MAX_SIDE 4096u
+#define NB_MAP_MAX_CELLS (1u << 22)
+#define NB_MAP_CENTER_COM 1u /* centre = com, centre velocity = P/M of the measured state (as NB_RADIAL_CENTER_COM) */
+#define NB_MAP_VELOCITY 2u   /* add the five velocity planes */
+
+typedef struct nb_map_params {
+    uint32_t width, height, flags, reserved; /* sides 1..NB_MAP_MAX_SIDE, at most NB_MAP_MAX_CELLS cells; reserved 0 */
+    double center[3], velocity[3];           /* ignored with NB_MAP_CENTER_COM */
+    double axis[3];                          /* line of sight; any non-zero finite vector */
+    double x_range[2], y_range[2];           /* window in the plane coordinates a, b: [lo, hi) */
+    double depth_range[2];                   /* slab along the line of sight: lo <= h < hi; -inf, +inf = everything */
+} nb_map_params;
+
+typedef struct nb_map_stats {
+    uint64_t step_num, n, nonfinite, binned_count, outside_count;
+    double binned_mass, outside_mass, mass; /* mass: all finite bodies */
+    double center[3], velocity[3];          /* the values used */
+    double n_hat[3], e1[3], e2[3];          /* the frame used */
+    uint32_t width, height, flags, max_count;
+} nb_map_stats;
+
+/* The map of a simulator's current state.  counts: height * width values, row j the cells with b in
+ * [ye[j], ye[j+1]) (row 0 is the smallest b: mathematical orientation).  planes: P planes of height * width
+ * doubles, plane-major: P = 1 `mass`; with NB_MAP_VELOCITY P = 6: mass, m_ua, m_ub, m_w, m_w2, m_u2.
+ * counts, planes and stats may each be null: what is not asked for is not copied, and a call with none of
+ * them synchronises and measures nothing.  NB_ERR_INVALID for a null handle or params, a side outside
+ * 1..NB_MAP_MAX_SIDE, more than NB_MAP_MAX_CELLS cells, unknown flag bits or reserved != 0, a zero or
+ * non-finite axis, a non-finite centre or velocity without NB_MAP_CENTER_COM, a non-finite window bound,
+ * hi <= lo in any range, a NaN depth bound, or edges that do not come out strictly ascending -- all
+ * checked before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats);
+/* Host only, no device: the frame of a map about `axis` (see above).  NB_ERR_INVALID for a null pointer or
+ * a zero or non-finite axis. */
+int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]);
+/* Host only, no device: the cells + 1 edges of a window [lo, hi) (see above).  NB_ERR_INVALID for a null
+ * pointer, cells outside 1..NB_MAP_MAX_SIDE, non-finite bounds, hi <= lo, or edges that do not come out
+ * strictly ascending. */
+int nb_map_edges(double lo, double hi, uint32_t cells, double *edges);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -704,6 +784,10 @@ int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, 
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
                     nb_field_stats *stats);
+/* nb_sim_map of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *counts, double *planes,
+                  nb_map_stats *stats);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -35,7 +35,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
-           "Field", "RingMeans", "field_rings",
+           "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -316,6 +316,124 @@ def _circular_velocity(call, handle, radii, axis, center, n_phi, potential) -> R
                                          r.shape[0], int(n_phi), pts.ctypes.data, samples.ctypes.data,
                                          out.ctypes.data))
     return RingMeans(r, out["a_R"].copy(), out["a_n"].copy(), out["potential"].copy(), out["v_c"].copy(), f)
+
+
+def map_frame(axis):
+    """nb_map_frame: (n_hat, e1, e2) of a map about `axis`, float64 arrays of 3.  n_hat is the axis normalised,
+    e1 the coordinate axis of the smallest |n_k| made orthogonal to it, e2 = n_hat x e1: the vectors
+    field_rings() lays its points with."""
+    out = [(C.c_double * 3)() for _ in range(3)]
+    check(_lib.lib().nb_map_frame(_vec3(axis), *out))
+    return tuple(np.array(list(v), dtype=np.float64) for v in out)
+
+
+def map_edges(lo: float, hi: float, cells: int) -> np.ndarray:
+    """nb_map_edges: the cells + 1 edges of a map's window, lo + i (hi - lo) / cells with edges[cells] = hi."""
+    out = np.empty(int(cells) + 1 if 1 <= int(cells) <= _lib.NB_MAP_MAX_SIDE else 1, dtype=np.float64)
+    check(_lib.lib().nb_map_edges(float(lo), float(hi), int(cells), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+MAP_PLANES = ("mass", "m_ua", "m_ub", "m_w", "m_w2", "m_u2")
+
+
+@dataclass(frozen=True)
+class ProjectedMap:
+    """nb_sim_map's counts, planes and nb_map_stats (include/nbody.h "Projected maps"; no reference
+    counterpart): the state read_particles would return, projected along n_hat onto the plane coordinates
+    a (along e1, columns) and b (along e2, rows; row 0 is the smallest b) and summed per cell on the
+    device.  counts: (H, W) uint32; the planes (H, W) float64, the five velocity planes None unless
+    velocities were asked for.  w is the velocity along the line of sight, ua and ub in the plane."""
+    counts: np.ndarray
+    mass: np.ndarray
+    m_ua: Optional[np.ndarray]   # sum m ua
+    m_ub: Optional[np.ndarray]   # sum m ub
+    m_w: Optional[np.ndarray]    # sum m w
+    m_w2: Optional[np.ndarray]   # sum m w^2
+    m_u2: Optional[np.ndarray]   # sum m |u|^2
+    x_edges: np.ndarray          # W + 1
+    y_edges: np.ndarray          # H + 1
+    step_num: int
+    n: int
+    nonfinite: int
+    binned_count: int
+    outside_count: int
+    binned_mass: float
+    outside_mass: float
+    total_mass: float            # nb_map_stats.mass: all finite bodies
+    center: np.ndarray
+    velocity: np.ndarray
+    n_hat: np.ndarray
+    e1: np.ndarray
+    e2: np.ndarray
+    flags: int
+    max_count: int
+
+    def _per_mass(self, plane):
+        if plane is None:
+            raise ValueError("this map was taken without velocities")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.mass != 0.0, plane / self.mass, np.nan)
+
+    @property
+    def surface_density(self) -> np.ndarray:
+        """mass over the cell's area (NaN in a cell without mass)."""
+        area = np.outer(np.diff(self.y_edges), np.diff(self.x_edges))
+        return np.where(self.mass != 0.0, self.mass / area, np.nan)
+
+    @property
+    def mean_w(self) -> np.ndarray:
+        """Mass-weighted mean line-of-sight velocity per cell (NaN in a cell without mass)."""
+        return self._per_mass(self.m_w)
+
+    @property
+    def mean_ua(self) -> np.ndarray:
+        return self._per_mass(self.m_ua)
+
+    @property
+    def mean_ub(self) -> np.ndarray:
+        return self._per_mass(self.m_ub)
+
+    @property
+    def sigma_w(self) -> np.ndarray:
+        """Mass-weighted line-of-sight velocity dispersion per cell: sqrt(max(0, m_w2 / mass - mean_w^2))."""
+        mean = self.mean_w
+        return np.sqrt(np.maximum(self._per_mass(self.m_w2) - mean * mean, 0.0))
+
+
+def _projected_map(call, handle, width, height, extent, axis, center, velocity, depth, velocities) -> ProjectedMap:
+    p = _lib.nb_map_params()
+    p.width, p.height = int(width), int(height)
+    p.flags = _lib.NB_MAP_VELOCITY if velocities else 0
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com" or three coordinates')
+        if velocity is not None:
+            raise ValueError('center="com" brings its own velocity')
+        p.flags |= _lib.NB_MAP_CENTER_COM
+    else:
+        velocity = (0.0, 0.0, 0.0) if velocity is None else velocity
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    x0, x1, y0, y1 = (float(v) for v in extent)
+    p.x_range[0], p.x_range[1], p.y_range[0], p.y_range[1] = x0, x1, y0, y1
+    p.depth_range[0], p.depth_range[1] = (-np.inf, np.inf) if depth is None else (float(depth[0]), float(depth[1]))
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    ok = 1 <= p.width <= _lib.NB_MAP_MAX_SIDE and 1 <= p.height <= _lib.NB_MAP_MAX_SIDE and \
+        p.width * p.height <= _lib.NB_MAP_MAX_CELLS
+    h, w = (p.height, p.width) if ok else (1, 1)  # (the call refuses the sizes itself)
+    nplanes = len(MAP_PLANES) if velocities else 1
+    counts = np.empty((h, w), dtype=np.uint32)
+    planes = np.empty((nplanes, h, w), dtype=np.float64)
+    st = _lib.nb_map_stats()
+    check(call(handle, C.byref(p), counts.ctypes.data, planes.ctypes.data, C.byref(st)))
+    vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+    rest = [planes[k] for k in range(1, nplanes)] if velocities else [None] * 5
+    return ProjectedMap(counts, planes[0], *rest, map_edges(x0, x1, w), map_edges(y0, y1, h), int(st.step_num),
+                        int(st.n), int(st.nonfinite), int(st.binned_count), int(st.outside_count),
+                        float(st.binned_mass), float(st.outside_mass), float(st.mass), vec(st.center),
+                        vec(st.velocity), vec(st.n_hat), vec(st.e1), vec(st.e2), int(st.flags), int(st.max_count))
 
 
 @dataclass(frozen=True)
@@ -653,6 +771,17 @@ class Simulator:
         the ring means (nb_field_ring_means): v_c = sqrt(max(0, -R a_R))."""
         return _circular_velocity(_lib.lib().nb_sim_field, self._h, radii, axis, center, n_phi, potential)
 
+    def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                      depth=None, velocities: bool = True) -> ProjectedMap:
+        """Per-cell count, mass and velocity moments of the current state on a width x height grid seen
+        along `axis` (nb_sim_map).  extent: (x0, x1, y0, y1), the window [x0, x1) x [y0, y1) in the plane
+        coordinates of map_frame(axis) about the centre.  center: "com" (the centre of mass and its
+        velocity P/M, as diagnostics() returns them) or three coordinates, then with `velocity` (default:
+        at rest).  depth: (lo, hi) keeps the bodies with lo <= h < hi along the line of sight.
+        velocities=False returns the counts and the mass alone."""
+        return _projected_map(_lib.lib().nb_sim_map, self._h, width, height, extent, axis, center, velocity, depth,
+                              velocities)
+
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
         """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
@@ -832,6 +961,12 @@ class OfflineHeadless:
                           potential: bool = False) -> RingMeans:
         """Simulator.circular_velocity of the runner's simulator (one device only)."""
         return _circular_velocity(_lib.lib().nb_runner_field, self._h, radii, axis, center, n_phi, potential)
+
+    def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                      depth=None, velocities: bool = True) -> ProjectedMap:
+        """nb_runner_map: Simulator.projected_map of the runner's simulator (one device only)."""
+        return _projected_map(_lib.lib().nb_runner_map, self._h, width, height, extent, axis, center, velocity, depth,
+                              velocities)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

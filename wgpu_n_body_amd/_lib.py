@@ -96,6 +96,21 @@ class nb_field_ring(C.Structure):
     _fields_ = [("a_R", C.c_double), ("a_n", C.c_double), ("potential", C.c_double), ("v_c", C.c_double)]
 
 
+class nb_map_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("x_range", C.c_double * 2), ("y_range", C.c_double * 2), ("depth_range", C.c_double * 2)]
+
+
+class nb_map_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("binned_count", C.c_uint64), ("outside_count", C.c_uint64),
+                ("binned_mass", C.c_double), ("outside_mass", C.c_double), ("mass", C.c_double),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("n_hat", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_count", C.c_uint32)]
+
+
 # nb_field_sample[] and nb_field_ring[] as numpy record arrays
 FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
 FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
@@ -110,6 +125,7 @@ assert C.sizeof(nb_radial_bin) == 88 == RADIAL_BIN_DTYPE.itemsize
 assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
 assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.sizeof(nb_field_stats) == 48
 assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
+assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -122,6 +138,8 @@ NB_RADIAL_MAX_BINS = 256
 NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM = 1, 2
 NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
+NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
+NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -136,6 +154,7 @@ ABI_SYMBOLS = [
     "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics",
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
+    "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
@@ -207,6 +226,10 @@ def lib() -> C.CDLL:
     L.nb_field_rings.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp]
     L.nb_field_ring_means.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp, vp,
                                       vp]
+    L.nb_sim_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
+    L.nb_runner_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
+    L.nb_map_frame.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
+    L.nb_map_edges.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]
     L.nb_camera_view_proj.argtypes = [P(nb_camera), P(C.c_float)]
     L.nb_render_params_default.argtypes = [P(nb_render_params), C.c_uint32, C.c_uint32]

@@ -30,6 +30,8 @@ SOURCES = [
     # the binning rule is specified operation by operation: no FMA contraction
     ("nb_radial.hip", ["-ffp-contract=off"]),
     ("nb_field.hip", []),
+    # the cell rule is specified operation by operation: no FMA contraction
+    ("nb_map.hip", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

@@ -8,6 +8,8 @@
 //             [--radial-center com|X,Y,Z]]
 //            [--rotcurve K --rotcurve-range RMIN,RMAX [--rotcurve-bins B] [--rotcurve-phi Q]
 //             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
+//            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
+//             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -33,6 +35,14 @@
 // points per ring (--rotcurve-phi, default 16) about --rotcurve-axis (default 0,1,0) through
 // --rotcurve-center (default 0,0,0).  One line per ring "rotcurve <step> <R> <a_R> <a_n> <v_c>" (%.9e).
 // The time they take is not part of any "Step Duration"; without --rotcurve the output is unchanged.
+//
+// --maps DIR writes the projected map (nb_runner_map) of step 0 and of every K-th step (--map-every,
+// default 1) as DIR/map_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape (7, H, W) -- the counts as
+// doubles, then the planes mass, m_ua, m_ub, m_w, m_w2, m_u2 -- of the window [X0, X1) x [Y0, Y1) seen
+// along --map-axis (default 0,1,0) about the centre of mass unless --map-center gives a point (at rest),
+// row 0 the smallest b; --map-depth keeps LO <= h < HI along the line of sight.  One line per map
+// "map <step> <binned> <outside> <nonfinite> <max_count>".  DIR must exist.  The time they take is not
+// part of any "Step Duration"; without --maps the output is unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
 // default camera, src/runners/online_renderer.rs:224-367) at step 0 and after every K-th step
@@ -125,6 +135,52 @@ static void print_rotcurve(nbody::OfflineHeadless<Sim> &runner, const RotcurveOp
                     r.rings[i].a_R, r.rings[i].a_n, r.rings[i].v_c);
 }
 
+struct MapOptions {
+    std::string dir;
+    int every = 1;
+    bool have_size = false, have_extent = false;
+    nbody::MapParams params = nbody::map_params(0, 0, 0.0, 0.0, 0.0, 0.0);
+};
+
+template <class Sim>
+static bool write_map(nbody::OfflineHeadless<Sim> &runner, const MapOptions &mo) {
+    const nbody::ProjectedMap m = runner.projected_map(mo.params);
+    char name[64];
+    std::snprintf(name, sizeof name, "/map_%06llu.npy", (unsigned long long)m.stats.step_num);
+    const std::string path = mo.dir + name;
+    std::FILE *out = std::fopen(path.c_str(), "wb");
+    if (!out) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    // NumPy format 1.0: magic, version, a little-endian uint16 header length, the header padded with spaces
+    // to a multiple of 64 bytes in all and ended by a newline
+    char dict[128];
+    const int len = std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (7, %u, %u), }",
+                                  m.height, m.width);
+    const size_t total = (10 + (size_t)len + 1 + 63) / 64 * 64, hlen = total - 10;
+    std::string head("\x93NUMPY\x01\x00", 8);
+    head += (char)(hlen & 0xff);
+    head += (char)(hlen >> 8);
+    head += dict;
+    head.append(total - 1 - head.size(), ' ');
+    head += '\n';
+    const size_t cells = (size_t)m.width * m.height;
+    std::vector<double> cnt(cells);
+    for (size_t i = 0; i < cells; ++i) cnt[i] = (double)m.counts[i];
+    bool ok = std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
+              std::fwrite(cnt.data(), sizeof(double), cells, out) == cells &&
+              std::fwrite(m.planes.data(), sizeof(double), m.planes.size(), out) == m.planes.size();
+    if (std::fclose(out) != 0 || !ok) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("map %llu %llu %llu %llu %u\n", (unsigned long long)m.stats.step_num,
+                (unsigned long long)m.stats.binned_count, (unsigned long long)m.stats.outside_count,
+                (unsigned long long)m.stats.nonfinite, m.stats.max_count);
+    return true;
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -162,7 +218,7 @@ template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
-               const RotcurveOptions &rotcurve) {
+               const RotcurveOptions &rotcurve, const MapOptions &maps) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -170,6 +226,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (diag > 0) print_diag(runner, diag_potential);
     if (radial.every > 0) print_radial(runner, radial);
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
+    if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -180,6 +237,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (diag > 0 && (i + 1) % diag == 0) print_diag(runner, diag_potential);
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
+        if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -203,6 +261,7 @@ int main(int argc, char **argv) {
     FrameOptions frames;
     RadialOptions radial;
     RotcurveOptions rotcurve;
+    MapOptions maps;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -265,6 +324,47 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (k == "--maps") maps.dir = v;
+        else if (k == "--map-every") maps.every = std::max(1, std::atoi(v.c_str()));
+        else if (k == "--map-size") {
+            if (std::sscanf(v.c_str(), "%ux%u", &maps.params.width, &maps.params.height) != 2) {
+                std::fprintf(stderr, "--map-size takes WxH, not %s\n", v.c_str());
+                return 2;
+            }
+            maps.have_size = true;
+        }
+        else if (k == "--map-extent") {
+            nbody::MapParams &mp = maps.params;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf", &mp.x_range[0], &mp.x_range[1], &mp.y_range[0],
+                            &mp.y_range[1]) != 4) {
+                std::fprintf(stderr, "--map-extent takes X0,X1,Y0,Y1, not %s\n", v.c_str());
+                return 2;
+            }
+            maps.have_extent = true;
+        }
+        else if (k == "--map-axis") {
+            double *a = maps.params.axis;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
+                std::fprintf(stderr, "--map-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--map-center") {
+            double *c = maps.params.center;
+            if (v == "com") maps.params.flags |= NB_MAP_CENTER_COM;
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) == 3)
+                maps.params.flags &= ~NB_MAP_CENTER_COM;
+            else {
+                std::fprintf(stderr, "--map-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--map-depth") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &maps.params.depth_range[0], &maps.params.depth_range[1]) != 2) {
+                std::fprintf(stderr, "--map-depth takes LO,HI, not %s\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--frames") frames.dir = v;
         else if (k == "--frame-every") frames.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--frame-size") {
@@ -293,15 +393,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--rotcurve needs --rotcurve-range RMIN,RMAX\n");
         return 2;
     }
+    if (!maps.dir.empty() && !(maps.have_size && maps.have_extent)) {
+        std::fprintf(stderr, "--maps needs --map-size WxH and --map-extent X0,X1,Y0,Y1\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve);
+                                        diag_potential, frames, radial, rotcurve, maps);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve);
+                                       diag, diag_potential, frames, radial, rotcurve, maps);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

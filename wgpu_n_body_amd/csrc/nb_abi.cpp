@@ -30,6 +30,31 @@ void set_error(const char *fmt, ...) {
 
 static size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
+// The frame nb_field_rings and the maps share (include/nbody.h): n the unit axis, e1 the coordinate axis
+// of the smallest |n_k| made orthogonal to n, e2 = n x e1.
+bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(axis[a])) return false;
+    // (an axis whose length over- or underflows has no finite unit vector either)
+    const double len = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) return false;
+    for (int a = 0; a < 3; ++a) n[a] = axis[a] / len;
+    int s = 0;  // the coordinate axis of the smallest |n_k|, the lowest index on ties
+    for (int a = 1; a < 3; ++a)
+        if (std::fabs(n[a]) < std::fabs(n[s])) s = a;
+    double el = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        e1[a] = (a == s ? 1.0 : 0.0) - n[s] * n[a];
+        el += e1[a] * e1[a];
+    }
+    el = std::sqrt(el);  // >= sqrt(2/3): |n_s| <= 1/sqrt(3)
+    for (int a = 0; a < 3; ++a) e1[a] /= el;
+    e2[0] = n[1] * e1[2] - n[2] * e1[1];
+    e2[1] = n[2] * e1[0] - n[0] * e1[2];
+    e2[2] = n[0] * e1[1] - n[1] * e1[0];
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------
 // SimBase
 // ------------------------------------------------------------------------------------------
@@ -38,6 +63,7 @@ SimBase::~SimBase() {
     render_release(render);
     radial_release(radial);
     field_release(field);
+    map_release(map);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -532,9 +558,8 @@ static int ring_basis(const char *what, const double *center, const double *axis
             set_error("%s: center and axis must be finite", what);
             return NB_ERR_INVALID;
         }
-    // (an axis whose length over- or underflows has no finite unit vector either)
-    const double len = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
-    if (!(len > 0.0) || !std::isfinite(len)) {
+    double fn[3], f1[3], f2[3];  // (nothing is written on a refusal)
+    if (!axis_frame(axis, fn, f1, f2)) {
         set_error("%s: needs a non-zero axis", what);
         return NB_ERR_INVALID;
     }
@@ -543,20 +568,75 @@ static int ring_basis(const char *what, const double *center, const double *axis
             set_error("%s: radii must be finite and >= 0 (radii[%u] = %g)", what, i, radii[i]);
             return NB_ERR_INVALID;
         }
-    for (int a = 0; a < 3; ++a) n[a] = axis[a] / len;
-    int s = 0;  // the coordinate axis of the smallest |n_k|, the lowest index on ties
-    for (int a = 1; a < 3; ++a)
-        if (std::fabs(n[a]) < std::fabs(n[s])) s = a;
-    double el = 0.0;
     for (int a = 0; a < 3; ++a) {
-        e1[a] = (a == s ? 1.0 : 0.0) - n[s] * n[a];
-        el += e1[a] * e1[a];
+        n[a] = fn[a];
+        e1[a] = f1[a];
+        e2[a] = f2[a];
     }
-    el = std::sqrt(el);  // >= sqrt(2/3): |n_s| <= 1/sqrt(3)
-    for (int a = 0; a < 3; ++a) e1[a] /= el;
-    e2[0] = n[1] * e1[2] - n[2] * e1[1];
-    e2[1] = n[2] * e1[0] - n[0] * e1[2];
-    e2[2] = n[0] * e1[1] - n[1] * e1[0];
+    return NB_OK;
+}
+
+// nb_map_edges / nb_sim_map: the cell size of `cells` cells in [lo, hi), refused unless the edges
+// lo + i * size (i < cells), hi come out strictly ascending
+static int map_cell_size(const char *what, double lo, double hi, uint32_t cells, double *size) {
+    if (cells < 1 || cells > NB_MAP_MAX_SIDE) {
+        set_error("%s: a side must be 1..%u cells (got %u)", what, NB_MAP_MAX_SIDE, cells);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) {
+        set_error("%s: a window needs finite lo < hi (got %g, %g)", what, lo, hi);
+        return NB_ERR_INVALID;
+    }
+    const double d = (hi - lo) / (double)cells;
+    double prev = lo;
+    for (uint32_t i = 1; i <= cells; ++i) {
+        const double e = i < cells ? lo + (double)i * d : hi;
+        if (!(e > prev) || !std::isfinite(e)) {
+            set_error("%s: %u cells between %g and %g are not strictly ascending in fp64", what, cells, lo, hi);
+            return NB_ERR_INVALID;
+        }
+        prev = e;
+    }
+    *size = d;
+    return NB_OK;
+}
+
+// nb_sim_map: everything that can be refused without a device; the frame and the cell sizes on the way
+static int map_check_params(const nb_map_params *p, MapPlan *plan) {
+    if (!p) {
+        set_error("map: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->width < 1 || p->width > NB_MAP_MAX_SIDE || p->height < 1 || p->height > NB_MAP_MAX_SIDE) {
+        set_error("map: a side must be 1..%u cells (got %u x %u)", NB_MAP_MAX_SIDE, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)p->width * p->height > NB_MAP_MAX_CELLS) {
+        set_error("map: at most %u cells (got %u x %u)", NB_MAP_MAX_CELLS, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~(NB_MAP_CENTER_COM | NB_MAP_VELOCITY)) || p->reserved) {
+        set_error("map: unknown flag bits 0x%x or reserved %u != 0", p->flags & ~(NB_MAP_CENTER_COM | NB_MAP_VELOCITY),
+                  p->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (!axis_frame(p->axis, plan->n, plan->e1, plan->e2)) {
+        set_error("map: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    if (!(p->flags & NB_MAP_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("map: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    if (int rc = map_cell_size("map: x_range", p->x_range[0], p->x_range[1], p->width, &plan->dx)) return rc;
+    if (int rc = map_cell_size("map: y_range", p->y_range[0], p->y_range[1], p->height, &plan->dy)) return rc;
+    // (either bound may be infinite; a NaN fails the comparison)
+    if (!(p->depth_range[1] > p->depth_range[0])) {
+        set_error("map: depth_range needs lo < hi without NaN (got %g, %g)", p->depth_range[0], p->depth_range[1]);
+        return NB_ERR_INVALID;
+    }
     return NB_OK;
 }
 
@@ -738,6 +818,18 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->field_pairs_log2 = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "map_segment_len")) {  // the maps', whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 256 || value > 65536 || value % 256) {
+            set_error("map_segment_len: a multiple of 256 in 256..65536, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->map_segment_len = value;
+        return NB_OK;
+    }
     NB_SIM_CALL(sim, set_tuning(key, value))
 }
 
@@ -879,6 +971,48 @@ int nb_field_ring_means(const double center[3], const double axis[3], const doub
         r.v_c = std::sqrt(std::fmax(0.0, -radii[i] * r.a_R));
         out[i] = r;
     }
+    return NB_OK;
+}
+
+int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
+    MapPlan plan{};
+    if (int rc = map_check_params(params, &plan)) return rc;
+    NB_GUARD({
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        return sim_map(*sim->impl, *params, plan, counts, planes, stats);
+    })
+}
+
+int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
+    if (!axis || !n_hat || !e1 || !e2) {
+        set_error("map_frame: null argument");
+        return NB_ERR_INVALID;
+    }
+    double n[3], f1[3], f2[3];
+    if (!axis_frame(axis, n, f1, f2)) {
+        set_error("map_frame: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 3; ++a) {
+        n_hat[a] = n[a];
+        e1[a] = f1[a];
+        e2[a] = f2[a];
+    }
+    return NB_OK;
+}
+
+int nb_map_edges(double lo, double hi, uint32_t cells, double *edges) {
+    if (!edges) {
+        set_error("map_edges: edges is null");
+        return NB_ERR_INVALID;
+    }
+    double d = 0.0;
+    if (int rc = map_cell_size("map_edges", lo, hi, cells, &d)) return rc;
+    for (uint32_t i = 0; i < cells; ++i) edges[i] = lo + (double)i * d;
+    edges[cells] = hi;
     return NB_OK;
 }
 
@@ -1103,6 +1237,18 @@ int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t f
         return NB_ERR_UNSUPPORTED;
     }
     return nb_sim_field(runner->sim, points, m, flags, out, stats);
+}
+
+int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *counts, double *planes,
+                  nb_map_stats *stats) {
+    MapPlan plan{};
+    if (int rc = map_check_params(params, &plan)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (runner->group) {
+        set_error("map: not available on a several-GPU runner (nb_runner_create_multi*)");
+        return NB_ERR_UNSUPPORTED;
+    }
+    return nb_sim_map(runner->sim, params, counts, planes, stats);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -1,0 +1,784 @@
+// nb_map.hip -- nb_sim_map: per-cell mass and velocity moments of a simulator's current state on a 2-D
+// grid (include/nbody.h "Projected maps"; no reference counterpart).
+//
+// A map has up to 2^22 cells, so the per-block slab of nb_radial.hip (256 bins) does not carry over.
+// The bodies are grouped by 8 x 8-cell tile instead, stably, and every tile's list is summed in LDS:
+//   classify  -- one thread per body over the float4 SoA state (SimBase::diag_state): fp64, no
+//                contraction, the cell by comparisons against the edges lo + i * size.  Writes one key per
+//                body, (tile << 6) | cell in the tile, or the key of the tile past the last for a body
+//                that is outside or non-finite.  The global sums (class counts, masses) go through
+//                per-block slabs and a fixed-order finish;
+//   group     -- a stable LSD radix sort of (key, body index) on the tile bits, 8 bits a pass (one pass
+//                up to 255 tiles, two up to 65,535, else three): count / scan / scatter, one wave per
+//                chunk of bodies, the rank inside a chunk by wave ballots in body order, so the order
+//                of a tile's list is the order of the bodies.  No atomic reservation;
+//   lists     -- the first and last position of every tile in the sorted keys, the tiles' lists cut into
+//                segments of at most "map_segment_len" bodies, and the segments numbered by a scan
+//                (every block its 1,024 tiles, then the blocks before it added);
+//   sum       -- one block of 256 threads per segment stages 256 bodies of the list at a time in LDS (the
+//                cell within the tile, then the terms, field-major; the terms recomputed from the
+//                gathered body, 32 B).  Thread (q, c) = (tid / 64, tid % 64) adds the staged bodies of
+//                cell c in quarter q in list order; the four quarters are added in order at the end.  A
+//                tile of one segment is written once with plain stores; the segments of a longer list
+//                go to partials, added in segment order by the combine kernel;
+//   finish    -- the maximum count and the global sums, in a fixed order.
+// Cells that no body reaches are cleared beforehand.  Without NB_MAP_VELOCITY only the mass is formed,
+// staged and summed.  With NB_MAP_CENTER_COM the moments pass of nb_diag.hip runs first on the same
+// stream and the threads divide its sums into the centre themselves: no host round trip.
+// No float atomics; the grids and the cuts depend on n, the grid, the segment length and the lists'
+// lengths alone: the result is bitwise reproducible.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+#include "nb_common.hpp"
+#include "nb_sim.hpp"
+
+namespace nb {
+
+namespace {
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kTile = 8, kTileCells = kTile * kTile;  // cells per tile = the low 6 bits of a key
+constexpr uint32_t kCellBits = 6;
+constexpr uint32_t kRadix = 256;          // 8 bits of the tile per sort pass
+constexpr uint32_t kSortBlocks = 2048;    // at most this many chunks (one wave each) per sort pass
+constexpr uint32_t kScanThreads = 1024;   // the one-block scans
+constexpr uint32_t kGlobalFields = 8;     // see GlobalField
+constexpr uint32_t kMaxFields = 6;        // planes with NB_MAP_VELOCITY
+constexpr uint32_t kMaxBlocks = 1024;     // the maximum over the counts: grid-stride beyond
+constexpr uint32_t kNoCell = 0xff;
+// res: [0, 6) the centre and velocity used, then the global sums, then the maximum count
+constexpr uint32_t kUsed = 8, kResMax = kUsed + kGlobalFields, kResDoubles = kResMax + 1;
+
+enum GlobalField { kGBinned = 0, kGOutside, kGBad, kGBinnedMass, kGOutsideMass, kGMass };
+
+struct MapConst {
+    double c[3], vc[3], n[3], e1[3], e2[3];
+    double xlo, xhi, ylo, yhi, dlo, dhi, dx, dy;
+    uint32_t w, h, tiles_x, tiles;
+    uint32_t center_com;
+};
+
+__device__ inline bool body_ok(float4 p, float4 v) {  // the predicate of nb_diag.hip
+    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w) && isfinite(v.x) && isfinite(v.y) &&
+           isfinite(v.z);
+}
+
+// fixed-order wave reduction (xor butterfly: every lane ends with the same, order-fixed sum)
+__device__ inline double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// The cell of coordinate a among `cells` cells of size d from lo, hi the last edge: the i with
+// edge(i) <= a < edge(i + 1), edge(i) = lo + i * d below `cells` and hi at it.  lo <= a < hi is known.
+// A division guesses, the comparisons decide.
+__device__ inline uint32_t cell_of(double a, double lo, double d, uint32_t cells) {
+#pragma clang fp contract(off)
+    const double g = (a - lo) / d;
+    uint32_t i = g >= (double)(cells - 1) ? cells - 1 : (uint32_t)g;  // (g >= 0)
+    while (i > 0 && a < lo + (double)i * d) --i;
+    while (i + 1 < cells && a >= lo + (double)(i + 1) * d) ++i;
+    return i;
+}
+
+// One body by the rule of include/nbody.h: true when it is binned, then *key = (tile << 6) | cell in tile
+__device__ inline bool classify(float4 p, const MapConst &k, const double (&c)[3], uint32_t *key) {
+#pragma clang fp contract(off)
+    const double dx = (double)p.x - c[0], dy = (double)p.y - c[1], dz = (double)p.z - c[2];
+    const double a = (dx * k.e1[0] + dy * k.e1[1]) + dz * k.e1[2];
+    const double b = (dx * k.e2[0] + dy * k.e2[1]) + dz * k.e2[2];
+    const double h = (dx * k.n[0] + dy * k.n[1]) + dz * k.n[2];
+    if (!(a >= k.xlo && a < k.xhi && b >= k.ylo && b < k.yhi && h >= k.dlo && h < k.dhi)) return false;
+    const uint32_t i = cell_of(a, k.xlo, k.dx, k.w), j = cell_of(b, k.ylo, k.dy, k.h);
+    const uint32_t tile = (j / kTile) * k.tiles_x + i / kTile;
+    *key = (tile << kCellBits) | ((j % kTile) * kTile + i % kTile);
+    return true;
+}
+
+// The terms of a body: F = 1 the mass, F = 6 mass, m ua, m ub, m w, (m w) w, m |u|^2
+template <uint32_t F>
+__device__ inline void terms(float4 p, float4 v, const MapConst &k, const double *vc, double (&t)[F]) {
+#pragma clang fp contract(off)
+    const double m = p.w;
+    t[0] = m;
+    if constexpr (F > 1) {
+        const double ux = (double)v.x - vc[0], uy = (double)v.y - vc[1], uz = (double)v.z - vc[2];
+        const double ua = (ux * k.e1[0] + uy * k.e1[1]) + uz * k.e1[2];
+        const double ub = (ux * k.e2[0] + uy * k.e2[1]) + uz * k.e2[2];
+        const double w = (ux * k.n[0] + uy * k.n[1]) + uz * k.n[2];
+        t[1] = m * ua;
+        t[2] = m * ub;
+        t[3] = m * w;
+        t[4] = (m * w) * w;
+        t[5] = m * ((ux * ux + uy * uy) + uz * uz);
+    }
+}
+
+// ---- classify: keys[i] for every body, one slab of kGlobalFields doubles per block -----------------
+// mom: the finished moments of nb_diag.hip (NB_MAP_CENTER_COM) or null.  Block 0 also writes the centre
+// and velocity it used to used[0..6).
+__global__ __launch_bounds__(kThreads) void map_classify_kernel(const float4 *__restrict__ posm,
+                                                                const float4 *__restrict__ vel, uint32_t n,
+                                                                MapConst k, const double *__restrict__ mom,
+                                                                uint32_t *__restrict__ keys,
+                                                                double *__restrict__ slabs, double *__restrict__ used) {
+    __shared__ double part[kThreads / kWave][kGlobalFields];
+    const uint32_t tid = threadIdx.x;
+    double c[3], vc[3];
+    for (int a = 0; a < 3; ++a) {
+        c[a] = k.c[a];
+        vc[a] = k.vc[a];
+    }
+    if (k.center_com) {  // `com` and `momentum / mass` exactly as sim_diagnostics forms them
+        const double mass = mom[kDiagResMass];
+        for (int a = 0; a < 3; ++a) {
+            c[a] = mom[kDiagResMX + a] / mass;
+            vc[a] = mom[kDiagResMV + a] / mass;
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0)
+        for (int a = 0; a < 3; ++a) {
+            used[a] = c[a];
+            used[3 + a] = vc[a];
+        }
+    double glob[kGlobalFields];
+    for (uint32_t f = 0; f < kGlobalFields; ++f) glob[f] = 0.0;
+    const size_t i = (size_t)blockIdx.x * kThreads + tid;
+    if (i < n) {
+        const float4 p = posm[i], v = vel[i];
+        uint32_t key = k.tiles << kCellBits;  // the tile past the last: not binned
+        if (!body_ok(p, v)) {
+            glob[kGBad] = 1.0;
+        } else {
+            const double m = p.w;
+            glob[kGMass] = m;
+            if (classify(p, k, c, &key)) {
+                glob[kGBinned] = 1.0;
+                glob[kGBinnedMass] = m;
+            } else {
+                glob[kGOutside] = 1.0;
+                glob[kGOutsideMass] = m;
+            }
+        }
+        keys[i] = key;
+    }
+    const uint32_t lane = tid % kWave, wave = tid / kWave;
+    for (uint32_t f = 0; f <= kGMass; ++f) glob[f] = wave_sum(glob[f]);
+    if (lane == 0)
+        for (uint32_t f = 0; f < kGlobalFields; ++f) part[wave][f] = glob[f];
+    __syncthreads();
+    if (tid < kGlobalFields) {
+        double s = part[0][tid];
+        for (uint32_t w = 1; w < kThreads / kWave; ++w) s += part[w][tid];
+        slabs[(size_t)blockIdx.x * kGlobalFields + tid] = s;
+    }
+}
+
+// ---- group: one pass of the stable sort, digit = (key >> shift) & 255 ---------------------------
+// Chunk b = bodies [b * chunk, (b + 1) * chunk) of the pass's input, one wave each.
+// count: hist[d * blocks + b] = bodies of chunk b with digit d
+__global__ __launch_bounds__(kWave) void map_sort_count_kernel(const uint32_t *__restrict__ keys, uint32_t n,
+                                                               uint32_t chunk, uint32_t shift,
+                                                               uint32_t *__restrict__ hist) {
+    __shared__ uint32_t cnt[kRadix];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t d = lane; d < kRadix; d += kWave) cnt[d] = 0;
+    __syncthreads();
+    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
+    for (size_t i = lo + lane; i < hi; i += kWave) atomicAdd(&cnt[(keys[i] >> shift) & (kRadix - 1)], 1u);
+    __syncthreads();
+    for (uint32_t d = lane; d < kRadix; d += kWave) hist[(size_t)d * gridDim.x + blockIdx.x] = cnt[d];
+}
+
+// An exclusive scan of v[0 .. count) in place by one block, thread t owning a run of `per` elements; returns
+// the sum of all of them.
+__device__ inline uint32_t block_scan_runs(uint32_t *v, uint32_t count, uint32_t *lds /* [2][kScanThreads] */) {
+    const uint32_t tid = threadIdx.x, per = (count + kScanThreads - 1) / kScanThreads;
+    const size_t lo = std::min<size_t>(count, (size_t)tid * per), hi = std::min<size_t>(count, lo + per);
+    uint32_t s = 0;
+    for (size_t i = lo; i < hi; ++i) s += v[i];
+    uint32_t *a = lds, *b = lds + kScanThreads;
+    a[tid] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele
+        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
+        __syncthreads();
+        uint32_t *t = a;
+        a = b;
+        b = t;
+    }
+    uint32_t run = a[tid] - s;  // exclusive
+    const uint32_t total = a[kScanThreads - 1];
+    for (size_t i = lo; i < hi; ++i) {
+        const uint32_t x = v[i];
+        v[i] = run;
+        run += x;
+    }
+    __syncthreads();
+    return total;
+}
+
+// scan: block d scans the row of digit d over the chunks in place and writes the row's sum to totals[d]; the
+// scatter adds the digits below itself
+__global__ __launch_bounds__(kScanThreads) void map_sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t blocks,
+                                                                     uint32_t *__restrict__ totals) {
+    __shared__ uint32_t lds[2 * kScanThreads];
+    const uint32_t total = block_scan_runs(hist + (size_t)blockIdx.x * blocks, blocks, lds);
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// scatter: body i of chunk b goes to (bodies with a lower digit) + offs[d * blocks + b] + (bodies of the chunk
+// before i with digit d).  idx_in null: the identity (the first pass).
+__global__ __launch_bounds__(kWave) void map_sort_scatter_kernel(const uint32_t *__restrict__ key_in,
+                                                                 const uint32_t *__restrict__ idx_in,
+                                                                 uint32_t *__restrict__ key_out,
+                                                                 uint32_t *__restrict__ idx_out, uint32_t n,
+                                                                 uint32_t chunk, uint32_t shift,
+                                                                 const uint32_t *__restrict__ offs,
+                                                                 const uint32_t *__restrict__ totals) {
+    __shared__ uint32_t base[kRadix];
+    const uint32_t lane = threadIdx.x;
+    {  // lane l owns digits 4 l .. 4 l + 3: an exclusive scan of the 256 totals, four a lane, then over the wave
+        constexpr uint32_t kPer = kRadix / kWave;
+        uint32_t t[kPer], sum = 0;
+        for (uint32_t q = 0; q < kPer; ++q) {
+            t[q] = totals[lane * kPer + q];
+            sum += t[q];
+        }
+        uint32_t inc = sum;
+        for (uint32_t o = 1; o < kWave; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o);
+            if (lane >= o) inc += y;
+        }
+        uint32_t run = inc - sum;
+        for (uint32_t q = 0; q < kPer; ++q) {
+            const uint32_t d = lane * kPer + q;
+            base[d] = run + offs[(size_t)d * gridDim.x + blockIdx.x];
+            run += t[q];
+        }
+    }
+    __syncthreads();
+    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (size_t i0 = lo; i0 < hi; i0 += kWave) {
+        const size_t i = i0 + lane;
+        const bool valid = i < hi;
+        const uint32_t key = valid ? key_in[i] : 0u;
+        const uint32_t src = valid ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
+        const uint32_t d = (key >> shift) & (kRadix - 1);
+        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & below), group = (uint32_t)__popcll(same);
+        const uint32_t pos = base[d] + rank;
+        __syncthreads();
+        if (valid && rank + 1 == group) base[d] += group;  // one lane per digit present
+        __syncthreads();
+        if (valid && pos < n) {
+            key_out[pos] = key;
+            idx_out[pos] = src;
+        }
+    }
+}
+
+// ---- lists: tile t's bodies are positions [first[t], last[t]) of the sorted keys (0, 0: none) ------
+__global__ __launch_bounds__(kThreads) void map_bounds_kernel(const uint32_t *__restrict__ keys, uint32_t n,
+                                                              uint32_t tiles, uint32_t *__restrict__ first,
+                                                              uint32_t *__restrict__ last) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = keys[i] >> kCellBits;
+    const uint32_t tp = i > 0 ? keys[i - 1] >> kCellBits : 0xffffffffu;
+    if (t != tp) {
+        if (t < tiles) first[t] = (uint32_t)i;
+        if (i > 0 && tp < tiles) last[tp] = (uint32_t)i;
+    }
+    if (i + 1 == n && t < tiles) last[t] = n;
+}
+
+__device__ inline uint32_t segments_of(uint32_t len, uint32_t seg_len) { return (len + seg_len - 1) / seg_len; }
+
+// seg_off[t] = segments of the tiles before t, seg_off[tiles] = all; part_off likewise, counting only the
+// segments of tiles with more than one (they go through partials); seg_tile[g] = the tile of segment g.
+// In two launches of ceil((tiles + 1) / 1024) blocks: each block scans its 1,024 tiles and leaves its two
+// sums in block_tot; then every tile adds the sums of the blocks before its own and writes its segments' tile.
+__global__ __launch_bounds__(kScanThreads) void map_segments_local_kernel(const uint32_t *__restrict__ first,
+                                                                          const uint32_t *__restrict__ last,
+                                                                          uint32_t tiles, uint32_t seg_len,
+                                                                          uint32_t *__restrict__ seg_off,
+                                                                          uint32_t *__restrict__ part_off,
+                                                                          uint32_t *__restrict__ block_tot) {
+    __shared__ uint32_t lds[2][2 * kScanThreads];
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * kScanThreads + tid;
+    const uint32_t s = t < tiles ? segments_of(last[t] - first[t], seg_len) : 0u, p = s > 1 ? s : 0u;
+    uint32_t *a0 = lds[0], *b0 = lds[0] + kScanThreads, *a1 = lds[1], *b1 = lds[1] + kScanThreads;
+    a0[tid] = s;
+    a1[tid] = p;
+    __syncthreads();
+    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele, both sums at once
+        b0[tid] = tid >= o ? a0[tid] + a0[tid - o] : a0[tid];
+        b1[tid] = tid >= o ? a1[tid] + a1[tid - o] : a1[tid];
+        __syncthreads();
+        uint32_t *x = a0;
+        a0 = b0;
+        b0 = x;
+        x = a1;
+        a1 = b1;
+        b1 = x;
+    }
+    if (t <= tiles) {
+        seg_off[t] = a0[tid] - s;
+        part_off[t] = a1[tid] - p;
+    }
+    if (tid == kScanThreads - 1) {
+        block_tot[2 * blockIdx.x] = a0[tid];
+        block_tot[2 * blockIdx.x + 1] = a1[tid];
+    }
+}
+
+__global__ __launch_bounds__(kScanThreads) void map_segments_final_kernel(const uint32_t *__restrict__ first,
+                                                                          const uint32_t *__restrict__ last,
+                                                                          uint32_t tiles, uint32_t seg_len,
+                                                                          uint32_t *__restrict__ seg_off,
+                                                                          uint32_t *__restrict__ part_off,
+                                                                          const uint32_t *__restrict__ block_tot,
+                                                                          uint32_t *__restrict__ seg_tile,
+                                                                          uint32_t seg_cap) {
+    __shared__ uint32_t before[2];
+    const uint32_t tid = threadIdx.x, t = blockIdx.x * kScanThreads + tid;
+    if (tid < 2) {  // (at most 65 blocks)
+        uint32_t sum = 0;
+        for (uint32_t b = 0; b < blockIdx.x; ++b) sum += block_tot[2 * b + tid];
+        before[tid] = sum;
+    }
+    __syncthreads();
+    if (t > tiles) return;
+    const uint32_t g0 = seg_off[t] + before[0];
+    seg_off[t] = g0;
+    part_off[t] += before[1];
+    if (t == tiles) return;
+    const uint32_t g1 = g0 + segments_of(last[t] - first[t], seg_len);
+    for (uint32_t g = g0; g < g1 && g < seg_cap; ++g) seg_tile[g] = t;
+}
+
+// ---- sum: one block per segment ------------------------------------------------------------------
+// planes: [F][h * w]; parts: [slot][F + 1][64] doubles (the count last), slot = part_off[tile] + segment
+template <uint32_t F>
+__global__ __launch_bounds__(kThreads) void map_sum_kernel(const float4 *__restrict__ posm,
+                                                           const float4 *__restrict__ vel, MapConst k,
+                                                           const uint32_t *__restrict__ keys,
+                                                           const uint32_t *__restrict__ idx,
+                                                           const uint32_t *__restrict__ first,
+                                                           const uint32_t *__restrict__ last,
+                                                           const uint32_t *__restrict__ seg_off,
+                                                           const uint32_t *__restrict__ part_off,
+                                                           const uint32_t *__restrict__ seg_tile, uint32_t seg_len,
+                                                           uint32_t n, uint32_t part_cap,
+                                                           const double *__restrict__ used,
+                                                           uint32_t *__restrict__ counts, double *__restrict__ planes,
+                                                           double *__restrict__ parts) {
+    __shared__ double stage[F][kThreads];  // [field][staged body]; at the end [field][thread]
+    __shared__ uint32_t cell_in[kThreads];  // the staged body's cell in the tile; at the end the thread's count
+    const uint32_t g = blockIdx.x;
+    if (g >= seg_off[k.tiles]) return;  // (uniform over the block)
+    const uint32_t tid = threadIdx.x, tile = seg_tile[g];
+    if (tile >= k.tiles) return;
+    const uint32_t s = g - seg_off[tile];
+    const uint32_t t0 = first[tile], t1 = last[tile];
+    const uint32_t lo = t0 + s * seg_len, hi = t1 - lo > seg_len ? lo + seg_len : t1;
+    const uint32_t nseg = segments_of(t1 - t0, seg_len);
+    double vc[3];
+    for (int a = 0; a < 3; ++a) vc[a] = used[3 + a];
+    const uint32_t my_cell = tid % kTileCells, q0 = tid & ~(kTileCells - 1);
+    double acc[F];
+    for (uint32_t f = 0; f < F; ++f) acc[f] = 0.0;
+    uint32_t cnt = 0;
+    for (uint32_t j0 = lo; j0 < hi; j0 += kThreads) {
+        const uint32_t j = j0 + tid;
+        uint32_t cell = kNoCell;
+        if (j < hi) {
+            const uint32_t body = idx[j];
+            if (body < n) {
+                cell = keys[j] & (kTileCells - 1);
+                double t[F];
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (F > 1) v = vel[body];  // the mass alone needs no velocity
+                terms<F>(posm[body], v, k, vc, t);
+                for (uint32_t f = 0; f < F; ++f) stage[f][tid] = t[f];
+            }
+        }
+        cell_in[tid] = cell;
+        __syncthreads();
+        for (uint32_t i = q0; i < q0 + kTileCells; ++i) {
+            if (cell_in[i] == my_cell) {
+                for (uint32_t f = 0; f < F; ++f) acc[f] += stage[f][i];
+                ++cnt;
+            }
+        }
+        __syncthreads();  // the staged bodies have been read
+    }
+    // the four quarters of every cell, in order
+    for (uint32_t f = 0; f < F; ++f) stage[f][tid] = acc[f];
+    cell_in[tid] = cnt;
+    __syncthreads();
+    if (tid >= kTileCells) return;
+    double sum[F];
+    for (uint32_t f = 0; f < F; ++f) {
+        sum[f] = stage[f][tid];
+        for (uint32_t q = kTileCells; q < kThreads; q += kTileCells) sum[f] += stage[f][q + tid];
+    }
+    for (uint32_t q = kTileCells; q < kThreads; q += kTileCells) cnt += cell_in[q + tid];
+    if (nseg > 1) {
+        const size_t slot = (size_t)part_off[tile] + s;
+        if (slot >= part_cap) return;
+        double *p = parts + slot * (F + 1) * kTileCells;
+        for (uint32_t f = 0; f < F; ++f) p[f * kTileCells + tid] = sum[f];
+        p[F * kTileCells + tid] = (double)cnt;
+        return;
+    }
+    const uint32_t x = (tile % k.tiles_x) * kTile + tid % kTile, y = (tile / k.tiles_x) * kTile + tid / kTile;
+    if (x < k.w && y < k.h) {
+        const size_t cell = (size_t)y * k.w + x, cells = (size_t)k.w * k.h;
+        counts[cell] = cnt;
+        for (uint32_t f = 0; f < F; ++f) planes[f * cells + cell] = sum[f];
+    }
+}
+
+// combine: the block of a longer list's first segment adds the list's partials in segment order
+template <uint32_t F>
+__global__ __launch_bounds__(kTileCells) void map_combine_kernel(MapConst k, const uint32_t *__restrict__ first,
+                                                                 const uint32_t *__restrict__ last,
+                                                                 const uint32_t *__restrict__ seg_off,
+                                                                 const uint32_t *__restrict__ part_off,
+                                                                 const uint32_t *__restrict__ seg_tile,
+                                                                 uint32_t seg_len, uint32_t part_cap,
+                                                                 const double *__restrict__ parts,
+                                                                 uint32_t *__restrict__ counts,
+                                                                 double *__restrict__ planes) {
+    const uint32_t g = blockIdx.x;
+    if (g >= seg_off[k.tiles]) return;
+    const uint32_t tid = threadIdx.x, tile = seg_tile[g];
+    if (tile >= k.tiles || g != seg_off[tile]) return;
+    const uint32_t nseg = segments_of(last[tile] - first[tile], seg_len);
+    if (nseg < 2 || (size_t)part_off[tile] + nseg > part_cap) return;
+    const double *p = parts + (size_t)part_off[tile] * (F + 1) * kTileCells;
+    double sum[F + 1];
+    for (uint32_t f = 0; f <= F; ++f) sum[f] = p[f * kTileCells + tid];
+    for (uint32_t s = 1; s < nseg; ++s) {
+        p += (F + 1) * kTileCells;
+        for (uint32_t f = 0; f <= F; ++f) sum[f] += p[f * kTileCells + tid];
+    }
+    const uint32_t x = (tile % k.tiles_x) * kTile + tid % kTile, y = (tile / k.tiles_x) * kTile + tid / kTile;
+    if (x < k.w && y < k.h) {
+        const size_t cell = (size_t)y * k.w + x, cells = (size_t)k.w * k.h;
+        counts[cell] = (uint32_t)sum[F];  // (exact: below 2^32)
+        for (uint32_t f = 0; f < F; ++f) planes[f * cells + cell] = sum[f];
+    }
+}
+
+// ---- finish: the maximum count per block, then everything in a fixed order ---------------------------
+__global__ __launch_bounds__(kThreads) void map_max_kernel(const uint32_t *__restrict__ counts, size_t cells,
+                                                           uint32_t *__restrict__ block_max) {
+    __shared__ uint32_t m[kThreads];
+    uint32_t best = 0;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < cells; i += (size_t)gridDim.x * kThreads)
+        best = std::max(best, counts[i]);
+    m[threadIdx.x] = best;
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) m[threadIdx.x] = std::max(m[threadIdx.x], m[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) block_max[blockIdx.x] = m[0];
+}
+
+// res[f] = sum over the classify blocks of slab element f: thread (f, g) = (tid % 8, tid / 8) sums blocks g,
+// g + 32, ...; then the 32 partials in order.  res[kGlobalFields] = the maximum of block_max.
+__global__ __launch_bounds__(kThreads) void map_finish_kernel(const double *__restrict__ slabs, uint32_t blocks,
+                                                              const uint32_t *__restrict__ block_max,
+                                                              uint32_t max_blocks, double *__restrict__ res) {
+    constexpr uint32_t kGroups = kThreads / kGlobalFields;
+    __shared__ double pp[kGroups][kGlobalFields];
+    __shared__ uint32_t m[kThreads];
+    const uint32_t tid = threadIdx.x, f = tid % kGlobalFields, g = tid / kGlobalFields;
+    double s = 0.0;
+    for (uint32_t b = g; b < blocks; b += kGroups) s += slabs[(size_t)b * kGlobalFields + f];
+    pp[g][f] = s;
+    uint32_t best = 0;
+    for (uint32_t b = tid; b < max_blocks; b += kThreads) best = std::max(best, block_max[b]);
+    m[tid] = best;
+    __syncthreads();
+    if (tid < kGlobalFields) {
+        double r = pp[0][tid];
+        for (uint32_t q = 1; q < kGroups; ++q) r += pp[q][tid];
+        res[tid] = r;
+    }
+    if (tid == kThreads - 1) {
+        uint32_t r = 0;
+        for (uint32_t q = 0; q < kThreads; ++q) r = std::max(r, m[q]);
+        res[kGlobalFields] = (double)r;
+    }
+}
+
+uint32_t bits_of(uint32_t x) {
+    uint32_t b = 0;
+    while (x) {
+        ++b;
+        x >>= 1;
+    }
+    return b;
+}
+
+}  // namespace
+
+struct MapBuf {  // a device buffer that grows to the largest request so far
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+struct MapWork {
+    MapBuf keys[2], idx[2];       // [n] uint32 each: the sort's two sides
+    MapBuf hist;                  // [256][chunks] uint32, then the 256 digit totals
+    MapBuf first, last;           // [tiles] uint32
+    MapBuf seg_off, part_off;     // [tiles + 1] uint32
+    MapBuf seg_tile;              // [segments possible] uint32
+    MapBuf block_tot;             // [blocks of the segment scan][2] uint32
+    MapBuf parts;                 // [partial slots][fields + 1][64] doubles
+    MapBuf slabs;                 // [classify blocks][kGlobalFields] doubles
+    MapBuf counts, planes;        // [cells] uint32, [fields][cells] doubles
+    uint32_t *block_max = nullptr;  // [kMaxBlocks]
+    double *res = nullptr;          // [kResDoubles]
+    double *h_res = nullptr;        // pinned, as res
+};
+
+void map_release(MapWork *w) {
+    if (!w) return;
+    for (MapBuf *b : {&w->keys[0], &w->keys[1], &w->idx[0], &w->idx[1], &w->hist, &w->first, &w->last, &w->seg_off,
+                      &w->part_off, &w->seg_tile, &w->block_tot, &w->parts, &w->slabs, &w->counts, &w->planes})
+        if (b->p) (void)hipFree(b->p);
+    if (w->block_max) (void)hipFree(w->block_max);
+    if (w->res) (void)hipFree(w->res);
+    if (w->h_res) (void)hipHostFree(w->h_res);
+    delete w;
+}
+
+namespace {
+
+// At least `bytes` behind b; an equal or smaller request allocates nothing.  A failure leaves b empty.
+int map_reserve(MapBuf &b, size_t bytes) {
+    if (bytes <= b.cap) return NB_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        set_error("map: cannot allocate %zu bytes of device workspace", bytes);
+        return NB_ERR_ALLOC;
+    }
+    b.cap = bytes;
+    return NB_OK;
+}
+
+template <uint32_t F>
+int launch_sums(SimBase &sim, MapWork &w, const MapConst &k, const float4 *posm, const float4 *vel, const uint32_t *keys,
+                const uint32_t *idx, uint32_t seg_len, uint32_t seg_cap, uint32_t part_cap) {
+    const uint32_t *first = (const uint32_t *)w.first.p, *last = (const uint32_t *)w.last.p;
+    const uint32_t *seg_off = (const uint32_t *)w.seg_off.p, *part_off = (const uint32_t *)w.part_off.p;
+    const uint32_t *seg_tile = (const uint32_t *)w.seg_tile.p;
+    hipLaunchKernelGGL(map_sum_kernel<F>, dim3(seg_cap), dim3(kThreads), 0, sim.stream, posm, vel, k, keys, idx, first,
+                       last, seg_off, part_off, seg_tile, seg_len, sim.n, part_cap, (const double *)w.res,
+                       (uint32_t *)w.counts.p, (double *)w.planes.p, (double *)w.parts.p);
+    NB_HIP_TRY(hipGetLastError());
+    if (part_cap > 0) {
+        hipLaunchKernelGGL(map_combine_kernel<F>, dim3(seg_cap), dim3(kTileCells), 0, sim.stream, k, first, last,
+                           seg_off, part_off, seg_tile, seg_len, part_cap, (const double *)w.parts.p,
+                           (uint32_t *)w.counts.p, (double *)w.planes.p);
+        NB_HIP_TRY(hipGetLastError());
+    }
+    return NB_OK;
+}
+
+}  // namespace
+
+int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
+            nb_map_stats *stats) {
+    if (sim.place.world > 1) {
+        set_error("map: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
+        return NB_ERR_UNSUPPORTED;
+    }
+    if (int rc = sim.bind_device()) return rc;
+    if (!counts && !planes && !stats) {  // nothing to measure
+        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+        return sim.diag_status();
+    }
+    if (!sim.map) {  // kept only once complete
+        std::unique_ptr<MapWork, void (*)(MapWork *)> fresh(new MapWork(), map_release);
+        if (hipMalloc(&fresh->block_max, sizeof(uint32_t) * kMaxBlocks) != hipSuccess ||
+            hipMalloc(&fresh->res, sizeof(double) * kResDoubles) != hipSuccess ||
+            hipHostMalloc((void **)&fresh->h_res, sizeof(double) * kResDoubles, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("map: cannot allocate the result workspace");
+            return NB_ERR_ALLOC;
+        }
+        sim.map = fresh.release();
+    }
+    MapWork &w = *sim.map;
+    const uint32_t n = sim.n, width = params.width, height = params.height;
+    const bool com = (params.flags & NB_MAP_CENTER_COM) != 0, velocity = (params.flags & NB_MAP_VELOCITY) != 0;
+    const uint32_t fields = velocity ? kMaxFields : 1;
+    const size_t cells = (size_t)width * height;
+
+    MapConst k{};
+    for (int a = 0; a < 3; ++a) {
+        k.c[a] = com ? 0.0 : params.center[a];
+        k.vc[a] = com ? 0.0 : params.velocity[a];
+        k.n[a] = plan.n[a];
+        k.e1[a] = plan.e1[a];
+        k.e2[a] = plan.e2[a];
+    }
+    k.xlo = params.x_range[0];
+    k.xhi = params.x_range[1];
+    k.ylo = params.y_range[0];
+    k.yhi = params.y_range[1];
+    k.dlo = params.depth_range[0];
+    k.dhi = params.depth_range[1];
+    k.dx = plan.dx;
+    k.dy = plan.dy;
+    k.w = width;
+    k.h = height;
+    k.tiles_x = (width + kTile - 1) / kTile;
+    k.tiles = k.tiles_x * ((height + kTile - 1) / kTile);
+    k.center_com = com;
+
+    std::memset(w.h_res, 0, sizeof(double) * kResDoubles);
+    if (n > 0) {
+        const uint32_t seg_len = (uint32_t)sim.map_segment_len;
+        const uint32_t class_blocks = (n + kThreads - 1) / kThreads;
+        // the sort: chunks of a multiple of 64 bodies, at least 256, at most kSortBlocks of them
+        const uint32_t chunk = std::max(256u, ((n + kSortBlocks - 1) / kSortBlocks + kWave - 1) / kWave * kWave);
+        const uint32_t sort_blocks = (n + chunk - 1) / chunk;
+        const uint32_t passes = (bits_of(k.tiles) + 7) / 8;  // keys' tiles run 0 .. tiles
+        // segments: a tile with bodies has at most 1 + (len - 1) / seg_len; those of longer lists number
+        // at most 2 (len / seg_len)
+        const uint32_t seg_cap = std::min(k.tiles, n) + n / seg_len;
+        const uint32_t part_cap = 2 * (n / seg_len);
+        for (int s = 0; s < 2; ++s) {
+            if (int rc = map_reserve(w.keys[s], sizeof(uint32_t) * n)) return rc;
+            if (int rc = map_reserve(w.idx[s], sizeof(uint32_t) * n)) return rc;
+        }
+        if (int rc = map_reserve(w.hist, sizeof(uint32_t) * kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = map_reserve(w.first, sizeof(uint32_t) * k.tiles)) return rc;
+        if (int rc = map_reserve(w.last, sizeof(uint32_t) * k.tiles)) return rc;
+        if (int rc = map_reserve(w.seg_off, sizeof(uint32_t) * (k.tiles + 1))) return rc;
+        if (int rc = map_reserve(w.part_off, sizeof(uint32_t) * (k.tiles + 1))) return rc;
+        if (int rc = map_reserve(w.seg_tile, sizeof(uint32_t) * seg_cap)) return rc;
+        const uint32_t list_blocks = (k.tiles + 1 + kScanThreads - 1) / kScanThreads;
+        if (int rc = map_reserve(w.block_tot, sizeof(uint32_t) * 2 * list_blocks)) return rc;
+        if (int rc = map_reserve(w.parts, sizeof(double) * std::max<size_t>(1, part_cap) * (fields + 1) * kTileCells))
+            return rc;
+        if (int rc = map_reserve(w.slabs, sizeof(double) * kGlobalFields * class_blocks)) return rc;
+        if (int rc = map_reserve(w.counts, sizeof(uint32_t) * cells)) return rc;
+        if (int rc = map_reserve(w.planes, sizeof(double) * fields * cells)) return rc;
+
+        const float4 *posm = nullptr, *vel = nullptr;
+        sim.diag_state(&posm, &vel);
+        const double *mom = nullptr;
+        if (com)
+            if (int rc = diag_enqueue_moments(sim, &mom)) return rc;
+        hipLaunchKernelGGL(map_classify_kernel, dim3(class_blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, k, mom,
+                           (uint32_t *)w.keys[0].p, (double *)w.slabs.p, w.res);
+        NB_HIP_TRY(hipGetLastError());
+        int side = 0;
+        for (uint32_t pass = 0; pass < passes; ++pass, side ^= 1) {
+            const uint32_t shift = kCellBits + 8 * pass;
+            hipLaunchKernelGGL(map_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream,
+                               (const uint32_t *)w.keys[side].p, n, chunk, shift, (uint32_t *)w.hist.p);
+            NB_HIP_TRY(hipGetLastError());
+            uint32_t *totals = (uint32_t *)w.hist.p + (size_t)kRadix * sort_blocks;
+            hipLaunchKernelGGL(map_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream,
+                               (uint32_t *)w.hist.p, sort_blocks, totals);
+            NB_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(map_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream,
+                               (const uint32_t *)w.keys[side].p, pass ? (const uint32_t *)w.idx[side].p : nullptr,
+                               (uint32_t *)w.keys[side ^ 1].p, (uint32_t *)w.idx[side ^ 1].p, n, chunk, shift,
+                               (const uint32_t *)w.hist.p, (const uint32_t *)totals);
+            NB_HIP_TRY(hipGetLastError());
+        }
+        const uint32_t *keys = (const uint32_t *)w.keys[side].p, *idx = (const uint32_t *)w.idx[side].p;
+        NB_HIP_TRY(hipMemsetAsync(w.first.p, 0, sizeof(uint32_t) * k.tiles, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.last.p, 0, sizeof(uint32_t) * k.tiles, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.counts.p, 0, sizeof(uint32_t) * cells, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.planes.p, 0, sizeof(double) * fields * cells, sim.stream));
+        hipLaunchKernelGGL(map_bounds_kernel, dim3(class_blocks), dim3(kThreads), 0, sim.stream, keys, n, k.tiles,
+                           (uint32_t *)w.first.p, (uint32_t *)w.last.p);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(map_segments_local_kernel, dim3(list_blocks), dim3(kScanThreads), 0, sim.stream,
+                           (const uint32_t *)w.first.p, (const uint32_t *)w.last.p, k.tiles, seg_len,
+                           (uint32_t *)w.seg_off.p, (uint32_t *)w.part_off.p, (uint32_t *)w.block_tot.p);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(map_segments_final_kernel, dim3(list_blocks), dim3(kScanThreads), 0, sim.stream,
+                           (const uint32_t *)w.first.p, (const uint32_t *)w.last.p, k.tiles, seg_len,
+                           (uint32_t *)w.seg_off.p, (uint32_t *)w.part_off.p, (const uint32_t *)w.block_tot.p,
+                           (uint32_t *)w.seg_tile.p, seg_cap);
+        NB_HIP_TRY(hipGetLastError());
+        if (int rc = velocity ? launch_sums<kMaxFields>(sim, w, k, posm, vel, keys, idx, seg_len, seg_cap, part_cap)
+                              : launch_sums<1>(sim, w, k, posm, vel, keys, idx, seg_len, seg_cap, part_cap))
+            return rc;
+        const uint32_t max_blocks = (uint32_t)std::min<size_t>(kMaxBlocks, (cells + kThreads - 1) / kThreads);
+        hipLaunchKernelGGL(map_max_kernel, dim3(max_blocks), dim3(kThreads), 0, sim.stream,
+                           (const uint32_t *)w.counts.p, cells, w.block_max);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(map_finish_kernel, dim3(1), dim3(kThreads), 0, sim.stream, (const double *)w.slabs.p,
+                           class_blocks, (const uint32_t *)w.block_max, max_blocks, w.res + kUsed);
+        NB_HIP_TRY(hipGetLastError());
+        NB_HIP_TRY(hipMemcpyAsync(w.h_res, w.res, sizeof(double) * kResDoubles, hipMemcpyDeviceToHost, sim.stream));
+        if (counts)
+            NB_HIP_TRY(hipMemcpyAsync(counts, w.counts.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, sim.stream));
+        if (planes)
+            NB_HIP_TRY(hipMemcpyAsync(planes, w.planes.p, sizeof(double) * fields * cells, hipMemcpyDeviceToHost,
+                                      sim.stream));
+        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+    } else {
+        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+        for (int a = 0; a < 6; ++a) w.h_res[a] = com ? std::nan("") : (a < 3 ? k.c[a] : k.vc[a - 3]);  // com of no mass
+        if (counts) std::memset(counts, 0, sizeof(uint32_t) * cells);
+        if (planes) std::memset(planes, 0, sizeof(double) * fields * cells);
+    }
+    if (int rc = sim.diag_status()) return rc;
+
+    if (stats) {
+        const double *used = w.h_res, *g = w.h_res + kUsed;
+        nb_map_stats o{};
+        o.step_num = sim.step_num;
+        o.n = n;
+        o.nonfinite = (uint64_t)g[kGBad];
+        o.binned_count = (uint64_t)g[kGBinned];
+        o.outside_count = (uint64_t)g[kGOutside];
+        o.binned_mass = g[kGBinnedMass];
+        o.outside_mass = g[kGOutsideMass];
+        o.mass = g[kGMass];
+        for (int a = 0; a < 3; ++a) {
+            o.center[a] = used[a];
+            o.velocity[a] = used[3 + a];
+            o.n_hat[a] = plan.n[a];
+            o.e1[a] = plan.e1[a];
+            o.e2[a] = plan.e2[a];
+        }
+        o.width = width;
+        o.height = height;
+        o.flags = params.flags;
+        o.max_count = (uint32_t)w.h_res[kResMax];
+        *stats = o;
+    }
+    return NB_OK;
+}
+
+}  // namespace nb

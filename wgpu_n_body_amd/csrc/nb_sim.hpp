@@ -12,6 +12,7 @@ struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned resul
 struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
 struct RadialWork;  // nb_radial.hip: the radial profile's slabs, squared edges and pinned result
 struct FieldWork;  // nb_field.hip: the field probes' points, slabs and pinned samples
+struct MapWork;  // nb_map.hip: the projected map's keys, lists, partials and device images
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -124,6 +125,8 @@ class SimBase {
     RadialWork *radial = nullptr;  // allocated by the first nb_sim_radial_profile
     FieldWork *field = nullptr;  // allocated by the first nb_sim_field
     int field_pairs_log2 = 35;  // "field_launch_pairs_log2": pairs per launch of nb_sim_field, 2^16 .. 2^40
+    MapWork *map = nullptr;  // allocated by the first nb_sim_map, grown by the largest call so far
+    int map_segment_len = 4096;  // "map_segment_len": bodies of a tile summed by one block of nb_sim_map
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
@@ -152,6 +155,19 @@ void radial_release(RadialWork *w);
 // its workspace
 int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out, nb_field_stats *stats);
 void field_release(FieldWork *w);
+
+// nb_map.hip: nb_sim_map behind the handle (arguments already checked by map_check_params, nb_abi.cpp, which
+// also forms the frame and the cell sizes) and the release of its workspace
+struct MapPlan {
+    double n[3], e1[3], e2[3];  // axis_frame of the caller's axis
+    double dx, dy;              // (hi - lo) / W, (hi - lo) / H
+};
+int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
+            nb_map_stats *stats);
+void map_release(MapWork *w);
+// nb_abi.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
+// rule of include/nbody.h); false for an axis without a finite, non-zero length
+bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]);
 
 class NaiveSim final : public SimBase {
    public:

@@ -15,6 +15,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <stdexcept>
@@ -34,6 +35,8 @@ using RadialParams = nb_radial_params;    // bins, flags, centre, axis and edges
 using RadialBin = nb_radial_bin;          // 88 B
 using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and coincident count at a point
 using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
+using MapParams = nb_map_params;          // grid, window, line of sight and centre of a projected map
+using MapStats = nb_map_stats;
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -161,6 +164,51 @@ RingMeans circular_velocity(int (*call)(H *, const float *, size_t, uint32_t, nb
 }
 }  // namespace detail
 
+// A projected map (no reference counterpart): width * height counts, row 0 the smallest b, the planes
+// (1, or 6 with NB_MAP_VELOCITY: mass, m_ua, m_ub, m_w, m_w2, m_u2) plane-major, and what the call measured
+struct ProjectedMap {
+    uint32_t width = 0, height = 0, nplanes = 0;
+    std::vector<uint32_t> counts;
+    std::vector<double> planes;
+    MapStats stats{};
+    const double *plane(uint32_t k) const { return planes.data() + (size_t)k * width * height; }
+};
+
+// The parameters of a map of the window [x0, x1) x [y0, y1) about the centre of mass, seen along `axis`,
+// with the velocity planes and no depth cut
+inline MapParams map_params(uint32_t width, uint32_t height, double x0, double x1, double y0, double y1,
+                            const std::array<double, 3> &axis = {0.0, 1.0, 0.0}) {
+    MapParams p{};
+    p.width = width;
+    p.height = height;
+    p.flags = NB_MAP_CENTER_COM | NB_MAP_VELOCITY;
+    for (int k = 0; k < 3; ++k) p.axis[k] = axis[(size_t)k];
+    p.x_range[0] = x0;
+    p.x_range[1] = x1;
+    p.y_range[0] = y0;
+    p.y_range[1] = y1;
+    p.depth_range[0] = -HUGE_VAL;
+    p.depth_range[1] = HUGE_VAL;
+    return p;
+}
+
+namespace detail {
+template <class H>
+ProjectedMap projected_map(int (*call)(H *, const nb_map_params *, uint32_t *, double *, nb_map_stats *), H *h,
+                           const MapParams &p) {
+    ProjectedMap m;
+    const bool ok = p.width >= 1 && p.width <= NB_MAP_MAX_SIDE && p.height >= 1 && p.height <= NB_MAP_MAX_SIDE &&
+                    (uint64_t)p.width * p.height <= NB_MAP_MAX_CELLS;  // (the call refuses the sizes itself)
+    m.width = ok ? p.width : 1;
+    m.height = ok ? p.height : 1;
+    m.nplanes = (p.flags & NB_MAP_VELOCITY) ? 6 : 1;
+    m.counts.resize((size_t)m.width * m.height);
+    m.planes.resize((size_t)m.nplanes * m.width * m.height);
+    check(call(h, &p, m.counts.data(), m.planes.data(), &m.stats));
+    return m;
+}
+}  // namespace detail
+
 // A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
 struct Frame {
     uint32_t width = 0, height = 0;
@@ -252,6 +300,7 @@ class Simulator {
         return detail::radial_profile(nb_sim_radial_profile, h_, edges, p);
     }
     // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
+    ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(nb_sim_map, h_, p); }
     Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
         return detail::field(nb_sim_field, h_, points, flags);
     }
@@ -378,6 +427,9 @@ class OfflineHeadless {
     RadialProfile radial_profile(const std::vector<double> &edges,  // one device only
                                  const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
         return detail::radial_profile(nb_runner_radial_profile, r_, edges, p);
+    }
+    ProjectedMap projected_map(const MapParams &p) {  // one device only
+        return detail::projected_map(nb_runner_map, r_, p);
     }
     Field field(const std::vector<float> &points,  // one device only
                 uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
