@@ -59,11 +59,7 @@ bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]) {
 // SimBase
 // ------------------------------------------------------------------------------------------
 SimBase::~SimBase() {
-    diag_release(diag);  // (the derived destructor has bound the device)
-    render_release(render);
-    radial_release(radial);
-    field_release(field);
-    map_release(map);
+    for (auto &w : work) w.reset();  // in slot order, before the stream (the derived destructor has bound the device)
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -712,6 +708,15 @@ int nb_sim_create_from_particles(nb_sim **out, const nb_sim_params *sim_params,
         }                                     \
         return (sim)->impl->expr;             \
     })
+// ... and a free function over the object behind the handle: the analysis passes
+#define NB_SIM_PASS(sim, fn, ...)                 \
+    NB_GUARD({                                    \
+        if (!(sim) || !(sim)->impl) {             \
+            set_error("null simulator");          \
+            return NB_ERR_INVALID;                \
+        }                                         \
+        return fn(*(sim)->impl, __VA_ARGS__);     \
+    })
 
 int nb_sim_encode(nb_sim *sim) { NB_SIM_CALL(sim, encode()) }
 int nb_sim_encode_phase(nb_sim *sim, int phase) { NB_SIM_CALL(sim, encode_phase(phase)) }
@@ -798,13 +803,7 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         return NB_ERR_INVALID;
     }
     if (!std::strcmp(key, "render_design")) {  // the renderer's, whichever simulator holds the state
-        NB_GUARD({
-            if (!sim || !sim->impl) {
-                set_error("null simulator");
-                return NB_ERR_INVALID;
-            }
-            return sim_render_set_design(*sim->impl, value);
-        })
+        NB_SIM_PASS(sim, sim_render_set_design, value)
     }
     if (!std::strcmp(key, "field_launch_pairs_log2")) {  // the field probes', whichever simulator holds the state
         if (!sim || !sim->impl) {
@@ -850,25 +849,13 @@ int nb_sim_diagnostics(nb_sim *sim, uint32_t flags, nb_diagnostics *out) {
         set_error("diagnostics: unknown flag bits 0x%x", flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL));
         return NB_ERR_INVALID;
     }
-    NB_GUARD({
-        if (!sim || !sim->impl) {
-            set_error("null simulator");
-            return NB_ERR_INVALID;
-        }
-        return sim_diagnostics(*sim->impl, flags, out);
-    })
+    NB_SIM_PASS(sim, sim_diagnostics, flags, out)
 }
 
 int nb_sim_radial_profile(nb_sim *sim, const nb_radial_params *params, nb_radial_profile *out,
                           nb_radial_bin *bins) {
     if (int rc = radial_check_params(params, out, bins)) return rc;
-    NB_GUARD({
-        if (!sim || !sim->impl) {
-            set_error("null simulator");
-            return NB_ERR_INVALID;
-        }
-        return sim_radial_profile(*sim->impl, *params, out, bins);
-    })
+    NB_SIM_PASS(sim, sim_radial_profile, *params, out, bins)
 }
 
 int nb_radial_edges_log(double rmin, double rmax, uint32_t nbins, double *edges) {
@@ -908,13 +895,7 @@ int nb_radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, 
 int nb_sim_field(nb_sim *sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
                  nb_field_stats *stats) {
     if (int rc = field_check_args(points, m, flags, out)) return rc;
-    NB_GUARD({
-        if (!sim || !sim->impl) {
-            set_error("null simulator");
-            return NB_ERR_INVALID;
-        }
-        return sim_field(*sim->impl, points, m, flags, out, stats);
-    })
+    NB_SIM_PASS(sim, sim_field, points, m, flags, out, stats)
 }
 
 int nb_field_rings(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
@@ -977,13 +958,7 @@ int nb_field_ring_means(const double center[3], const double axis[3], const doub
 int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
-    NB_GUARD({
-        if (!sim || !sim->impl) {
-            set_error("null simulator");
-            return NB_ERR_INVALID;
-        }
-        return sim_map(*sim->impl, *params, plan, counts, planes, stats);
-    })
+    NB_SIM_PASS(sim, sim_map, *params, plan, counts, planes, stats)
 }
 
 int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
@@ -1019,13 +994,7 @@ int nb_map_edges(double lo, double hi, uint32_t cells, double *edges) {
 int nb_sim_render(nb_sim *sim, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,
                   nb_render_stats *stats) {
     if (int rc = render_check_params(params)) return rc;
-    NB_GUARD({
-        if (!sim || !sim->impl) {
-            set_error("null simulator");
-            return NB_ERR_INVALID;
-        }
-        return sim_render(*sim->impl, *params, rgba, counts, stats);
-    })
+    NB_SIM_PASS(sim, sim_render, *params, rgba, counts, stats)
 }
 
 int nb_naive_variant_count(void) { return naive_variant_count(); }
@@ -1208,12 +1177,17 @@ int nb_runner_step_num(const nb_runner *runner, uint64_t *out) {
     return nb_sim_step_num(runner->sim, out);
 }
 
+// the analysis passes read the whole state of one simulator
+static int refuse_group(const nb_runner *runner, const char *name) {
+    if (!runner->group) return NB_OK;
+    set_error("%s: not available on a several-GPU runner (nb_runner_create_multi*)", name);
+    return NB_ERR_UNSUPPORTED;
+}
+
 int nb_runner_diagnostics(nb_runner *runner, uint32_t flags, nb_diagnostics *out) {
     if (int rc = check_runner(runner)) return rc;
-    if (runner->group && out && !(flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL))) {
-        set_error("diagnostics: not available on a several-GPU runner (nb_runner_create_multi*)");
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (out && !(flags & ~(NB_DIAG_MOMENTS | NB_DIAG_POTENTIAL)))  // (a group is refused for valid arguments only)
+        if (int rc = refuse_group(runner, "diagnostics")) return rc;
     return nb_sim_diagnostics(runner->sim, flags, out);
 }
 
@@ -1221,10 +1195,7 @@ int nb_runner_radial_profile(nb_runner *runner, const nb_radial_params *params, 
                              nb_radial_bin *bins) {
     if (int rc = radial_check_params(params, out, bins)) return rc;
     if (int rc = check_runner(runner)) return rc;
-    if (runner->group) {
-        set_error("radial_profile: not available on a several-GPU runner (nb_runner_create_multi*)");
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_group(runner, "radial_profile")) return rc;
     return nb_sim_radial_profile(runner->sim, params, out, bins);
 }
 
@@ -1232,10 +1203,7 @@ int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t f
                     nb_field_stats *stats) {
     if (int rc = field_check_args(points, m, flags, out)) return rc;
     if (int rc = check_runner(runner)) return rc;
-    if (runner->group) {
-        set_error("field: not available on a several-GPU runner (nb_runner_create_multi*)");
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_group(runner, "field")) return rc;
     return nb_sim_field(runner->sim, points, m, flags, out, stats);
 }
 
@@ -1244,10 +1212,7 @@ int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *coun
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
     if (int rc = check_runner(runner)) return rc;
-    if (runner->group) {
-        set_error("map: not available on a several-GPU runner (nb_runner_create_multi*)");
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_group(runner, "map")) return rc;
     return nb_sim_map(runner->sim, params, counts, planes, stats);
 }
 
@@ -1255,10 +1220,7 @@ int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t 
                      nb_render_stats *stats) {
     if (int rc = render_check_params(params)) return rc;
     if (int rc = check_runner(runner)) return rc;
-    if (runner->group) {
-        set_error("render: not available on a several-GPU runner (nb_runner_create_multi*)");
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_group(runner, "render")) return rc;
     return nb_sim_render(runner->sim, params, rgba, counts, stats);
 }
 

@@ -4,19 +4,19 @@
 // Two passes over the float4 SoA state the simulator hands out (SimBase::diag_state), then one
 // fixed-order finish:
 //   moments  -- one streaming pass over posm and vel (32 B per body): each body's terms in fp64,
-//               reduced per wave (shuffles) and per block (LDS) into one 16-double slab per block;
+//               reduced per wave and per block (block_row, nb_analysis.hpp) into one 16-double slab per block;
 //   pairs    -- W = sum_{i<j} m_i m_j psi(r_ij) over the upper triangle of 256 x 256 tiles: a block
 //               owns one i-tile and a chunk of j-tiles at or right of the diagonal, stages every
 //               j-tile through LDS, evaluates psi in fp32, folds each row's fp32 run of 64 pairs into
 //               fp64, and writes one double per block.  The i-tiles go in row bands, one launch per
 //               band, each bounded in pairs so that no launch runs for long on a shared GPU;
-//   finish   -- one block sums the slabs in a fixed order and writes 16 doubles, copied once into
-//               pinned host memory ahead of the one synchronisation.
+//   finish   -- one block sums the slabs in a fixed order (the moments by sum_over_blocks in 16 groups)
+//               and writes 16 doubles, copied once into pinned host memory ahead of the one synchronisation.
 // No float atomics: the grid shapes depend on n alone, so the result is bitwise reproducible.
 #include <cmath>
 #include <cstring>
-#include <memory>
 
+#include "nb_analysis.hpp"
 #include "nb_common.hpp"
 #include "nb_psi.hpp"
 #include "nb_sim.hpp"
@@ -25,7 +25,7 @@ namespace nb {
 
 namespace {
 
-constexpr uint32_t kDiagThreads = 256;   // both passes: 4 waves per block
+constexpr uint32_t kDiagThreads = kBlock;  // both passes: 4 waves per block
 constexpr uint32_t kMomMaxBlocks = 1024; // moments grid cap (grid-stride beyond)
 constexpr uint32_t kMomFields = 16;      // per-block slab: see MomField
 constexpr uint32_t kPairTile = 256;      // bodies per i-tile and per j-tile
@@ -38,27 +38,18 @@ constexpr uint64_t kPairsPerLaunch = 1ull << 35;
 
 enum MomField { kM = kDiagResMass, kMX = kDiagResMX, kMV = kDiagResMV, kL = 7, kK = 10, kVmax = 11, kBad = kDiagResBad, kW = 13 };
 
-// fixed-order wave reduction (xor butterfly: every lane ends with the same, order-fixed sum)
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ inline double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
+constexpr uint32_t kMomMax = 1u << kVmax;  // the one field reduced by fmax
 
 // ---- moments: one slab of kMomFields doubles per block -------------------------------------
 __global__ __launch_bounds__(kDiagThreads) void diag_moments_kernel(const float4 *__restrict__ posm,
                                                                     const float4 *__restrict__ vel, uint32_t n,
                                                                     double *__restrict__ slabs) {
-    double acc[kK + 1];
-    for (int k = 0; k <= kK; ++k) acc[k] = 0.0;
-    double vmax = 0.0, bad = 0.0;
+    double acc[kBad + 1];
+    for (int k = 0; k <= kBad; ++k) acc[k] = 0.0;
     for (uint32_t i = blockIdx.x * kDiagThreads + threadIdx.x; i < n; i += gridDim.x * kDiagThreads) {
         const float4 p = posm[i], v = vel[i];
         if (!body_ok(p, v)) {
-            bad += 1.0;
+            acc[kBad] += 1.0;
             continue;
         }
         const double m = p.w, x = p.x, y = p.y, z = p.z, vx = v.x, vy = v.y, vz = v.z;
@@ -74,29 +65,10 @@ __global__ __launch_bounds__(kDiagThreads) void diag_moments_kernel(const float4
         acc[kL + 2] += m * (x * vy - y * vx);
         const double v2 = vx * vx + vy * vy + vz * vz;
         acc[kK] += 0.5 * m * v2;
-        vmax = fmax(vmax, sqrt(v2));
+        acc[kVmax] = fmax(acc[kVmax], sqrt(v2));
     }
     __shared__ double part[kDiagThreads / kWave][kMomFields];
-    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    for (int k = 0; k <= kK; ++k) acc[k] = wave_sum(acc[k]);
-    vmax = wave_max(vmax);
-    bad = wave_sum(bad);
-    if (lane == 0) {
-        for (int k = 0; k <= kK; ++k) part[wave][k] = acc[k];
-        part[wave][kVmax] = vmax;
-        part[wave][kBad] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < kMomFields) {
-        const uint32_t f = threadIdx.x;
-        double s = 0.0;
-        if (f <= kBad) {
-            s = part[0][f];
-            for (uint32_t w = 1; w < kDiagThreads / kWave; ++w)
-                s = f == kVmax ? fmax(s, part[w][f]) : s + part[w][f];
-        }
-        slabs[(size_t)blockIdx.x * kMomFields + f] = s;
-    }
+    block_row<kMomFields, kBad + 1, kMomMax>(acc, part, slabs + (size_t)blockIdx.x * kMomFields);
 }
 
 // one i body against the 256 staged j bodies: fp32 runs of kPairRun pairs, folded into fp64
@@ -171,29 +143,21 @@ __global__ __launch_bounds__(kDiagThreads) void diag_pairs_kernel(const float4 *
 }
 
 // ---- finish: fixed-order sums of every slab -> res[kMomFields] ------------------------------
-// thread (f, g) = (tid % 16, tid / 16) sums field f of blocks g, g + 16, ...; then 16 partials per
-// field in order.  The pair slabs: thread k sums k, k + 256, ...; then 256 partials in order.
+// the moments by sum_over_blocks in 16 groups.  The pair slabs: thread k sums k, k + 256, ...; then 256
+// partials in order.
 __global__ __launch_bounds__(kDiagThreads) void diag_finish_kernel(const double *__restrict__ mom, uint32_t mom_blocks,
                                                                    const double *__restrict__ pairs,
                                                                    uint32_t pair_slabs, double *__restrict__ res) {
     constexpr uint32_t kGroups = kDiagThreads / kMomFields;
     __shared__ double mp[kGroups][kMomFields];
     __shared__ double pp[kDiagThreads];
-    const uint32_t tid = threadIdx.x, f = tid % kMomFields, g = tid / kMomFields;
-    double s = 0.0;  // (every field is >= 0 or a sum)
-    for (uint32_t b = g; b < mom_blocks; b += kGroups) {
-        const double v = mom[(size_t)b * kMomFields + f];
-        s = f == kVmax ? fmax(s, v) : s + v;
-    }
-    mp[g][f] = s;
+    const uint32_t tid = threadIdx.x;
     double w = 0.0;
     for (uint32_t k = tid; k < pair_slabs; k += kDiagThreads) w += pairs[k];
     pp[tid] = w;
-    __syncthreads();
+    const double m = sum_over_blocks<kGroups, kMomMax>(mom, mom_blocks, kMomFields, tid % kMomFields, mp);
     if (tid < kMomFields) {
-        double r = mp[0][tid];
-        for (uint32_t q = 1; q < kGroups; ++q) r = tid == kVmax ? fmax(r, mp[q][tid]) : r + mp[q][tid];
-        if (tid != kW) res[tid] = r;
+        if (tid != kW) res[tid] = m;
     } else if (tid == kDiagThreads - 1) {
         double r = 0.0;
         for (uint32_t k = 0; k < kDiagThreads; ++k) r += pp[k];
@@ -203,69 +167,57 @@ __global__ __launch_bounds__(kDiagThreads) void diag_finish_kernel(const double 
 
 }  // namespace
 
-struct DiagWork {
-    double *mom = nullptr;    // [kMomMaxBlocks][kMomFields]
-    double *pairs = nullptr;  // [pair_cap]
-    size_t pair_cap = 0;
-    double *res = nullptr;    // [kMomFields]
-    double *h_res = nullptr;  // pinned
+struct DiagWork : Workspace {
+    DeviceBuf<double> mom;    // [kMomMaxBlocks][kMomFields]
+    DeviceBuf<double> pairs;  // the pair slabs of the largest call so far
+    DeviceBuf<double> res;    // [kMomFields]
+    PinnedBuf<double> h_res;  // as res
 };
 
-void diag_release(DiagWork *w) {
-    if (!w) return;
-    if (w->mom) (void)hipFree(w->mom);
-    if (w->pairs) (void)hipFree(w->pairs);
-    if (w->res) (void)hipFree(w->res);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    delete w;
-}
-
 // the workspace of the moments pass, allocated by the first call that needs it
-static int diag_work(SimBase &sim) {
-    if (sim.diag) return NB_OK;  // kept only once complete
-    std::unique_ptr<DiagWork, void (*)(DiagWork *)> fresh(new DiagWork(), diag_release);
-    NB_HIP_TRY(hipMalloc(&fresh->mom, sizeof(double) * kMomMaxBlocks * kMomFields));
-    NB_HIP_TRY(hipMalloc(&fresh->res, sizeof(double) * kMomFields));
-    NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_res, sizeof(double) * kMomFields, hipHostMallocDefault));
-    sim.diag = fresh.release();
-    return NB_OK;
+static int diag_work(SimBase &sim, DiagWork **w) {
+    return workspace(sim, kWorkDiag, w, [](DiagWork &f) {
+        NB_HIP_TRY(f.mom.reserve(kMomMaxBlocks * kMomFields));
+        NB_HIP_TRY(f.res.reserve(kMomFields));
+        NB_HIP_TRY(f.h_res.reserve(kMomFields));
+        return NB_OK;
+    });
 }
 
-static int launch_moments(SimBase &sim, uint32_t *mom_blocks) {
+static int launch_moments(SimBase &sim, DiagWork &w, uint32_t *mom_blocks) {
     const float4 *posm = nullptr, *vel = nullptr;
     sim.diag_state(&posm, &vel);
     *mom_blocks = std::min(kMomMaxBlocks, (sim.n + 4 * kDiagThreads - 1) / (4 * kDiagThreads));
     hipLaunchKernelGGL(diag_moments_kernel, dim3(*mom_blocks), dim3(kDiagThreads), 0, sim.stream, posm, vel, sim.n,
-                       sim.diag->mom);
+                       w.mom);
     NB_HIP_TRY(hipGetLastError());
     return NB_OK;
 }
 
 int diag_enqueue_moments(SimBase &sim, const double **res_dev) {
-    if (int rc = diag_work(sim)) return rc;
+    DiagWork *w = nullptr;
+    if (int rc = diag_work(sim, &w)) return rc;
     uint32_t mom_blocks = 0;
-    if (int rc = launch_moments(sim, &mom_blocks)) return rc;
-    hipLaunchKernelGGL(diag_finish_kernel, dim3(1), dim3(kDiagThreads), 0, sim.stream, sim.diag->mom, mom_blocks,
-                       sim.diag->pairs, 0u, sim.diag->res);
+    if (int rc = launch_moments(sim, *w, &mom_blocks)) return rc;
+    hipLaunchKernelGGL(diag_finish_kernel, dim3(1), dim3(kDiagThreads), 0, sim.stream, w->mom, mom_blocks,
+                       w->pairs, 0u, w->res);
     NB_HIP_TRY(hipGetLastError());
-    *res_dev = sim.diag->res;
+    *res_dev = w->res;
     return NB_OK;
 }
 
 int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out) {
     const bool potential = (flags & NB_DIAG_POTENTIAL) != 0;
-    if (sim.place.world > 1) {
-        set_error("diagnostics: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_sharded(sim, "diagnostics")) return rc;
     const float e = sim.params.e;
     if (potential && !(e >= 0.f)) {
         set_error("diagnostics: the pair potential needs e >= 0 (e = %g)", (double)e);
         return NB_ERR_INVALID;
     }
     if (int rc = sim.bind_device()) return rc;
-    if (int rc = diag_work(sim)) return rc;
-    DiagWork &w = *sim.diag;
+    DiagWork *work = nullptr;
+    if (int rc = diag_work(sim, &work)) return rc;
+    DiagWork &w = *work;
     const uint32_t n = sim.n;
     const float4 *posm = nullptr, *vel = nullptr;
     sim.diag_state(&posm, &vel);
@@ -274,18 +226,12 @@ int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out) {
     const uint32_t cj = std::max(1u, (n_tiles + kPairChunks - 1) / kPairChunks);  // j-tiles per block
     const uint32_t chunks = (n_tiles + cj - 1) / cj;
     const size_t pair_slabs = potential ? (size_t)n_tiles * chunks : 0;
-    if (pair_slabs > w.pair_cap) {
-        if (w.pairs) NB_HIP_TRY(hipFree(w.pairs));
-        w.pairs = nullptr;
-        w.pair_cap = 0;
-        NB_HIP_TRY(hipMalloc(&w.pairs, sizeof(double) * pair_slabs));
-        w.pair_cap = pair_slabs;
-    }
+    NB_HIP_TRY(w.pairs.reserve(pair_slabs));
 
     double r[kMomFields] = {};
     if (n > 0) {
         uint32_t mom_blocks = 0;
-        if (int rc = launch_moments(sim, &mom_blocks)) return rc;
+        if (int rc = launch_moments(sim, w, &mom_blocks)) return rc;
         if (potential) {
             const PsiConst c = psi_const(e);
             // row bands: i-tile t meets (n_tiles - t) j-tiles; a band ends before it exceeds the budget

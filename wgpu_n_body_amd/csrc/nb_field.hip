@@ -20,8 +20,8 @@
 // the array a point stands.
 #include <cmath>
 #include <cstring>
-#include <memory>
 
+#include "nb_analysis.hpp"
 #include "nb_common.hpp"
 #include "nb_psi.hpp"
 #include "nb_sim.hpp"
@@ -225,33 +225,14 @@ void launch_field(uint32_t flags, int ib, dim3 grid, hipStream_t stream, const f
 
 }  // namespace
 
-struct FieldWork {
-    float4 *pts = nullptr, *h_pts = nullptr;            // [pts_cap] points; h_pts pinned
-    nb_field_sample *out = nullptr, *h_out = nullptr;   // [pts_cap] samples; h_out pinned
-    size_t pts_cap = 0;
-    double *slab = nullptr;  // [chunks][kSlabFields][points of one band]
-    size_t slab_cap = 0;
-    double *h_bad = nullptr;  // pinned: the diagnostics' non-finite count
+struct FieldWork : Workspace {  // (all but the last grow to the largest call so far)
+    DeviceBuf<float4> pts;             // [padded points]
+    PinnedBuf<float4> h_pts;           // as pts
+    DeviceBuf<nb_field_sample> out;    // [padded points]
+    PinnedBuf<nb_field_sample> h_out;  // as out
+    DeviceBuf<double> slab;            // [chunks][kSlabFields][points of one band]
+    PinnedBuf<double> h_bad;           // [1] the diagnostics' non-finite count
 };
-
-void field_release(FieldWork *w) {
-    if (!w) return;
-    if (w->pts) (void)hipFree(w->pts);
-    if (w->out) (void)hipFree(w->out);
-    if (w->slab) (void)hipFree(w->slab);
-    if (w->h_pts) (void)hipHostFree(w->h_pts);
-    if (w->h_out) (void)hipHostFree(w->h_out);
-    if (w->h_bad) (void)hipHostFree(w->h_bad);
-    delete w;
-}
-
-static int field_work(SimBase &sim) {
-    if (sim.field) return NB_OK;  // kept only once complete
-    std::unique_ptr<FieldWork, void (*)(FieldWork *)> fresh(new FieldWork(), field_release);
-    NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_bad, sizeof(double), hipHostMallocDefault));
-    sim.field = fresh.release();
-    return NB_OK;
-}
 
 // Points per lane, by measurement: a function of m and the flags alone.  The acceleration
 // alone runs fastest with whole tiles of 256 points, four per lane, and with a handful of points on the
@@ -263,18 +244,20 @@ static int points_per_lane(size_t m, uint32_t flags) {
 
 int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out,
               nb_field_stats *stats) {
-    if (sim.place.world > 1) {
-        set_error("field: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
-        return NB_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_sharded(sim, "field")) return rc;
     const float e = sim.params.e;
     if ((flags & NB_FIELD_POTENTIAL) && !(e >= 0.f)) {
         set_error("field: the potential needs e >= 0 (e = %g)", (double)e);
         return NB_ERR_INVALID;
     }
     if (int rc = sim.bind_device()) return rc;
-    if (int rc = field_work(sim)) return rc;
-    FieldWork &w = *sim.field;
+    FieldWork *work = nullptr;
+    if (int rc = workspace(sim, kWorkField, &work, [](FieldWork &f) {
+            NB_HIP_TRY(f.h_bad.reserve(1));
+            return NB_OK;
+        }))
+        return rc;
+    FieldWork &w = *work;
     const uint32_t n = sim.n, mm = (uint32_t)m;
 
     // the plan: a function of (m, n, flags) alone
@@ -293,33 +276,16 @@ int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_fi
         chunks = (n_tiles + cj - 1) / cj;        // every chunk holds at least one tile
     }
 
-    if (m_pad > w.pts_cap) {
-        if (w.pts) NB_HIP_TRY(hipFree(w.pts));
-        if (w.out) NB_HIP_TRY(hipFree(w.out));
-        if (w.h_pts) NB_HIP_TRY(hipHostFree(w.h_pts));
-        if (w.h_out) NB_HIP_TRY(hipHostFree(w.h_out));
-        w.pts = w.h_pts = nullptr;
-        w.out = w.h_out = nullptr;
-        w.pts_cap = 0;
-        NB_HIP_TRY(hipMalloc(&w.pts, sizeof(float4) * m_pad));
-        NB_HIP_TRY(hipMalloc(&w.out, sizeof(nb_field_sample) * m_pad));
-        NB_HIP_TRY(hipHostMalloc((void **)&w.h_pts, sizeof(float4) * m_pad, hipHostMallocDefault));
-        NB_HIP_TRY(hipHostMalloc((void **)&w.h_out, sizeof(nb_field_sample) * m_pad, hipHostMallocDefault));
-        w.pts_cap = m_pad;
-    }
+    NB_HIP_TRY(w.pts.reserve(m_pad));
+    NB_HIP_TRY(w.out.reserve(m_pad));
+    NB_HIP_TRY(w.h_pts.reserve(m_pad));
+    NB_HIP_TRY(w.h_out.reserve(m_pad));
     // bands of point tiles: a tile meets tile_pts * n pairs; at least one tile per launch.  The slab holds one band.
     uint32_t band = p_tiles;
     if (mm > 0 && n > 0)
         band = (uint32_t)std::min<uint64_t>(p_tiles, std::max<uint64_t>(1, (1ull << sim.field_pairs_log2) / ((uint64_t)tile_pts * n)));
     const uint32_t stride = band * tile_pts;
-    const size_t slab_doubles = (size_t)chunks * kSlabFields * stride;
-    if (slab_doubles > w.slab_cap) {
-        if (w.slab) NB_HIP_TRY(hipFree(w.slab));
-        w.slab = nullptr;
-        w.slab_cap = 0;
-        NB_HIP_TRY(hipMalloc(&w.slab, sizeof(double) * slab_doubles));
-        w.slab_cap = slab_doubles;
-    }
+    NB_HIP_TRY(w.slab.reserve((size_t)chunks * kSlabFields * stride));
 
     uint64_t bad_points = 0;
     uint32_t launches = 0;

@@ -7,7 +7,7 @@
 //                contraction, the cell by comparisons against the edges lo + i * size.  Writes one key per
 //                body, (tile << 6) | cell in the tile, or the key of the tile past the last for a body
 //                that is outside or non-finite.  The global sums (class counts, masses) go through
-//                per-block slabs and a fixed-order finish;
+//                per-block slabs (block_row, nb_analysis.hpp) and a fixed-order finish;
 //   group     -- a stable LSD radix sort of (key, body index) on the tile bits, 8 bits a pass (one pass
 //                up to 255 tiles, two up to 65,535, else three): count / scan / scatter, one wave per
 //                chunk of bodies, the rank inside a chunk by wave ballots in body order, so the order
@@ -21,7 +21,7 @@
 //                cell c in quarter q in list order; the four quarters are added in order at the end.  A
 //                tile of one segment is written once with plain stores; the segments of a longer list
 //                go to partials, added in segment order by the combine kernel;
-//   finish    -- the maximum count and the global sums, in a fixed order.
+//   finish    -- the maximum count and the global sums, in a fixed order (sum_over_blocks in 32 groups).
 // Cells that no body reaches are cleared beforehand.  Without NB_MAP_VELOCITY only the mass is formed,
 // staged and summed.  With NB_MAP_CENTER_COM the moments pass of nb_diag.hip runs first on the same
 // stream and the threads divide its sums into the centre themselves: no host round trip.
@@ -30,8 +30,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 
+#include "nb_analysis.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -39,7 +39,7 @@ namespace nb {
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
+constexpr uint32_t kThreads = kBlock;
 constexpr uint32_t kTile = 8, kTileCells = kTile * kTile;  // cells per tile = the low 6 bits of a key
 constexpr uint32_t kCellBits = 6;
 constexpr uint32_t kRadix = 256;          // 8 bits of the tile per sort pass
@@ -52,7 +52,7 @@ constexpr uint32_t kNoCell = 0xff;
 // res: [0, 6) the centre and velocity used, then the global sums, then the maximum count
 constexpr uint32_t kUsed = 8, kResMax = kUsed + kGlobalFields, kResDoubles = kResMax + 1;
 
-enum GlobalField { kGBinned = 0, kGOutside, kGBad, kGBinnedMass, kGOutsideMass, kGMass };
+enum GlobalField { kGBinned = 0, kGOutside, kGBad, kGBinnedMass, kGOutsideMass, kGMass, kGLive };
 
 struct MapConst {
     double c[3], vc[3], n[3], e1[3], e2[3];
@@ -60,17 +60,6 @@ struct MapConst {
     uint32_t w, h, tiles_x, tiles;
     uint32_t center_com;
 };
-
-__device__ inline bool body_ok(float4 p, float4 v) {  // the predicate of nb_diag.hip
-    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w) && isfinite(v.x) && isfinite(v.y) &&
-           isfinite(v.z);
-}
-
-// fixed-order wave reduction (xor butterfly: every lane ends with the same, order-fixed sum)
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // The cell of coordinate a among `cells` cells of size d from lo, hi the last edge: the i with
 // edge(i) <= a < edge(i + 1), edge(i) = lo + i * d below `cells` and hi at it.  lo <= a < hi is known.
@@ -119,7 +108,7 @@ __device__ inline void terms(float4 p, float4 v, const MapConst &k, const double
 
 // ---- classify: keys[i] for every body, one slab of kGlobalFields doubles per block -----------------
 // mom: the finished moments of nb_diag.hip (NB_MAP_CENTER_COM) or null.  Block 0 also writes the centre
-// and velocity it used to used[0..6).
+// and velocity it used to used[0..6) (centre_used).
 __global__ __launch_bounds__(kThreads) void map_classify_kernel(const float4 *__restrict__ posm,
                                                                 const float4 *__restrict__ vel, uint32_t n,
                                                                 MapConst k, const double *__restrict__ mom,
@@ -128,24 +117,9 @@ __global__ __launch_bounds__(kThreads) void map_classify_kernel(const float4 *__
     __shared__ double part[kThreads / kWave][kGlobalFields];
     const uint32_t tid = threadIdx.x;
     double c[3], vc[3];
-    for (int a = 0; a < 3; ++a) {
-        c[a] = k.c[a];
-        vc[a] = k.vc[a];
-    }
-    if (k.center_com) {  // `com` and `momentum / mass` exactly as sim_diagnostics forms them
-        const double mass = mom[kDiagResMass];
-        for (int a = 0; a < 3; ++a) {
-            c[a] = mom[kDiagResMX + a] / mass;
-            vc[a] = mom[kDiagResMV + a] / mass;
-        }
-    }
-    if (blockIdx.x == 0 && tid == 0)
-        for (int a = 0; a < 3; ++a) {
-            used[a] = c[a];
-            used[3 + a] = vc[a];
-        }
-    double glob[kGlobalFields];
-    for (uint32_t f = 0; f < kGlobalFields; ++f) glob[f] = 0.0;
+    centre_used(k.c, k.vc, k.center_com, mom, used, c, vc);
+    double glob[kGLive];
+    for (uint32_t f = 0; f < kGLive; ++f) glob[f] = 0.0;
     const size_t i = (size_t)blockIdx.x * kThreads + tid;
     if (i < n) {
         const float4 p = posm[i], v = vel[i];
@@ -165,16 +139,7 @@ __global__ __launch_bounds__(kThreads) void map_classify_kernel(const float4 *__
         }
         keys[i] = key;
     }
-    const uint32_t lane = tid % kWave, wave = tid / kWave;
-    for (uint32_t f = 0; f <= kGMass; ++f) glob[f] = wave_sum(glob[f]);
-    if (lane == 0)
-        for (uint32_t f = 0; f < kGlobalFields; ++f) part[wave][f] = glob[f];
-    __syncthreads();
-    if (tid < kGlobalFields) {
-        double s = part[0][tid];
-        for (uint32_t w = 1; w < kThreads / kWave; ++w) s += part[w][tid];
-        slabs[(size_t)blockIdx.x * kGlobalFields + tid] = s;
-    }
+    block_row<kGlobalFields, kGLive>(glob, part, slabs + (size_t)blockIdx.x * kGlobalFields);
 }
 
 // ---- group: one pass of the stable sort, digit = (key >> shift) & 255 ---------------------------
@@ -499,27 +464,20 @@ __global__ __launch_bounds__(kThreads) void map_max_kernel(const uint32_t *__res
     if (threadIdx.x == 0) block_max[blockIdx.x] = m[0];
 }
 
-// res[f] = sum over the classify blocks of slab element f: thread (f, g) = (tid % 8, tid / 8) sums blocks g,
-// g + 32, ...; then the 32 partials in order.  res[kGlobalFields] = the maximum of block_max.
+// res[f] = sum over the classify blocks of slab element f, by sum_over_blocks in 32 groups.
+// res[kGlobalFields] = the maximum of block_max.
 __global__ __launch_bounds__(kThreads) void map_finish_kernel(const double *__restrict__ slabs, uint32_t blocks,
                                                               const uint32_t *__restrict__ block_max,
                                                               uint32_t max_blocks, double *__restrict__ res) {
     constexpr uint32_t kGroups = kThreads / kGlobalFields;
     __shared__ double pp[kGroups][kGlobalFields];
     __shared__ uint32_t m[kThreads];
-    const uint32_t tid = threadIdx.x, f = tid % kGlobalFields, g = tid / kGlobalFields;
-    double s = 0.0;
-    for (uint32_t b = g; b < blocks; b += kGroups) s += slabs[(size_t)b * kGlobalFields + f];
-    pp[g][f] = s;
+    const uint32_t tid = threadIdx.x;
     uint32_t best = 0;
     for (uint32_t b = tid; b < max_blocks; b += kThreads) best = std::max(best, block_max[b]);
     m[tid] = best;
-    __syncthreads();
-    if (tid < kGlobalFields) {
-        double r = pp[0][tid];
-        for (uint32_t q = 1; q < kGroups; ++q) r += pp[q][tid];
-        res[tid] = r;
-    }
+    const double sum = sum_over_blocks<kGroups>(slabs, blocks, kGlobalFields, tid % kGlobalFields, pp);
+    if (tid < kGlobalFields) res[tid] = sum;
     if (tid == kThreads - 1) {
         uint32_t r = 0;
         for (uint32_t q = 0; q < kThreads; ++q) r = std::max(r, m[q]);
@@ -538,69 +496,45 @@ uint32_t bits_of(uint32_t x) {
 
 }  // namespace
 
-struct MapBuf {  // a device buffer that grows to the largest request so far
-    void *p = nullptr;
-    size_t cap = 0;
+struct MapWork : Workspace {  // (all but the last three grow to the largest call so far)
+    DeviceBuf<uint32_t> keys[2], idx[2];    // [n] each: the sort's two sides
+    DeviceBuf<uint32_t> hist;               // [256][chunks], then the 256 digit totals
+    DeviceBuf<uint32_t> first, last;        // [tiles]
+    DeviceBuf<uint32_t> seg_off, part_off;  // [tiles + 1]
+    DeviceBuf<uint32_t> seg_tile;           // [segments possible]
+    DeviceBuf<uint32_t> block_tot;          // [blocks of the segment scan][2]
+    DeviceBuf<double> parts;                // [partial slots][fields + 1][64]
+    DeviceBuf<double> slabs;                // [classify blocks][kGlobalFields]
+    DeviceBuf<uint32_t> counts;             // [cells]
+    DeviceBuf<double> planes;               // [fields][cells]
+    DeviceBuf<uint32_t> block_max;          // [kMaxBlocks]
+    DeviceBuf<double> res;                  // [kResDoubles]
+    PinnedBuf<double> h_res;                // as res
 };
-
-struct MapWork {
-    MapBuf keys[2], idx[2];       // [n] uint32 each: the sort's two sides
-    MapBuf hist;                  // [256][chunks] uint32, then the 256 digit totals
-    MapBuf first, last;           // [tiles] uint32
-    MapBuf seg_off, part_off;     // [tiles + 1] uint32
-    MapBuf seg_tile;              // [segments possible] uint32
-    MapBuf block_tot;             // [blocks of the segment scan][2] uint32
-    MapBuf parts;                 // [partial slots][fields + 1][64] doubles
-    MapBuf slabs;                 // [classify blocks][kGlobalFields] doubles
-    MapBuf counts, planes;        // [cells] uint32, [fields][cells] doubles
-    uint32_t *block_max = nullptr;  // [kMaxBlocks]
-    double *res = nullptr;          // [kResDoubles]
-    double *h_res = nullptr;        // pinned, as res
-};
-
-void map_release(MapWork *w) {
-    if (!w) return;
-    for (MapBuf *b : {&w->keys[0], &w->keys[1], &w->idx[0], &w->idx[1], &w->hist, &w->first, &w->last, &w->seg_off,
-                      &w->part_off, &w->seg_tile, &w->block_tot, &w->parts, &w->slabs, &w->counts, &w->planes})
-        if (b->p) (void)hipFree(b->p);
-    if (w->block_max) (void)hipFree(w->block_max);
-    if (w->res) (void)hipFree(w->res);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    delete w;
-}
 
 namespace {
 
-// At least `bytes` behind b; an equal or smaller request allocates nothing.  A failure leaves b empty.
-int map_reserve(MapBuf &b, size_t bytes) {
-    if (bytes <= b.cap) return NB_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        set_error("map: cannot allocate %zu bytes of device workspace", bytes);
-        return NB_ERR_ALLOC;
-    }
-    b.cap = bytes;
-    return NB_OK;
+// At least `count` elements behind b.  A failure leaves b empty and the simulator usable: the sticky error
+// is cleared.
+template <class T>
+int map_reserve(DeviceBuf<T> &b, size_t count) {
+    if (b.reserve(count) == hipSuccess) return NB_OK;
+    (void)hipGetLastError();
+    set_error("map: cannot allocate %zu bytes of device workspace", sizeof(T) * count);
+    return NB_ERR_ALLOC;
 }
 
 template <uint32_t F>
 int launch_sums(SimBase &sim, MapWork &w, const MapConst &k, const float4 *posm, const float4 *vel, const uint32_t *keys,
                 const uint32_t *idx, uint32_t seg_len, uint32_t seg_cap, uint32_t part_cap) {
-    const uint32_t *first = (const uint32_t *)w.first.p, *last = (const uint32_t *)w.last.p;
-    const uint32_t *seg_off = (const uint32_t *)w.seg_off.p, *part_off = (const uint32_t *)w.part_off.p;
-    const uint32_t *seg_tile = (const uint32_t *)w.seg_tile.p;
+    const uint32_t *first = w.first, *last = w.last, *seg_off = w.seg_off, *part_off = w.part_off;
+    const uint32_t *seg_tile = w.seg_tile;
     hipLaunchKernelGGL(map_sum_kernel<F>, dim3(seg_cap), dim3(kThreads), 0, sim.stream, posm, vel, k, keys, idx, first,
-                       last, seg_off, part_off, seg_tile, seg_len, sim.n, part_cap, (const double *)w.res,
-                       (uint32_t *)w.counts.p, (double *)w.planes.p, (double *)w.parts.p);
+                       last, seg_off, part_off, seg_tile, seg_len, sim.n, part_cap, w.res, w.counts, w.planes, w.parts);
     NB_HIP_TRY(hipGetLastError());
     if (part_cap > 0) {
         hipLaunchKernelGGL(map_combine_kernel<F>, dim3(seg_cap), dim3(kTileCells), 0, sim.stream, k, first, last,
-                           seg_off, part_off, seg_tile, seg_len, part_cap, (const double *)w.parts.p,
-                           (uint32_t *)w.counts.p, (double *)w.planes.p);
+                           seg_off, part_off, seg_tile, seg_len, part_cap, w.parts, w.counts, w.planes);
         NB_HIP_TRY(hipGetLastError());
     }
     return NB_OK;
@@ -610,27 +544,23 @@ int launch_sums(SimBase &sim, MapWork &w, const MapConst &k, const float4 *posm,
 
 int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
             nb_map_stats *stats) {
-    if (sim.place.world > 1) {
-        set_error("map: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
-        return NB_ERR_UNSUPPORTED;
-    }
-    if (int rc = sim.bind_device()) return rc;
+    if (int rc = analysis_begin(sim, "map")) return rc;
     if (!counts && !planes && !stats) {  // nothing to measure
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
         return sim.diag_status();
     }
-    if (!sim.map) {  // kept only once complete
-        std::unique_ptr<MapWork, void (*)(MapWork *)> fresh(new MapWork(), map_release);
-        if (hipMalloc(&fresh->block_max, sizeof(uint32_t) * kMaxBlocks) != hipSuccess ||
-            hipMalloc(&fresh->res, sizeof(double) * kResDoubles) != hipSuccess ||
-            hipHostMalloc((void **)&fresh->h_res, sizeof(double) * kResDoubles, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("map: cannot allocate the result workspace");
-            return NB_ERR_ALLOC;
-        }
-        sim.map = fresh.release();
-    }
-    MapWork &w = *sim.map;
+    MapWork *work = nullptr;
+    if (int rc = workspace(sim, kWorkMap, &work, [](MapWork &f) {
+            if (f.block_max.reserve(kMaxBlocks) != hipSuccess || f.res.reserve(kResDoubles) != hipSuccess ||
+                f.h_res.reserve(kResDoubles) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("map: cannot allocate the result workspace");
+                return NB_ERR_ALLOC;
+            }
+            return NB_OK;
+        }))
+        return rc;
+    MapWork &w = *work;
     const uint32_t n = sim.n, width = params.width, height = params.height;
     const bool com = (params.flags & NB_MAP_CENTER_COM) != 0, velocity = (params.flags & NB_MAP_VELOCITY) != 0;
     const uint32_t fields = velocity ? kMaxFields : 1;
@@ -671,22 +601,22 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
         const uint32_t seg_cap = std::min(k.tiles, n) + n / seg_len;
         const uint32_t part_cap = 2 * (n / seg_len);
         for (int s = 0; s < 2; ++s) {
-            if (int rc = map_reserve(w.keys[s], sizeof(uint32_t) * n)) return rc;
-            if (int rc = map_reserve(w.idx[s], sizeof(uint32_t) * n)) return rc;
+            if (int rc = map_reserve(w.keys[s], n)) return rc;
+            if (int rc = map_reserve(w.idx[s], n)) return rc;
         }
-        if (int rc = map_reserve(w.hist, sizeof(uint32_t) * kRadix * (sort_blocks + 1))) return rc;
-        if (int rc = map_reserve(w.first, sizeof(uint32_t) * k.tiles)) return rc;
-        if (int rc = map_reserve(w.last, sizeof(uint32_t) * k.tiles)) return rc;
-        if (int rc = map_reserve(w.seg_off, sizeof(uint32_t) * (k.tiles + 1))) return rc;
-        if (int rc = map_reserve(w.part_off, sizeof(uint32_t) * (k.tiles + 1))) return rc;
-        if (int rc = map_reserve(w.seg_tile, sizeof(uint32_t) * seg_cap)) return rc;
+        if (int rc = map_reserve(w.hist, (size_t)kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = map_reserve(w.first, k.tiles)) return rc;
+        if (int rc = map_reserve(w.last, k.tiles)) return rc;
+        if (int rc = map_reserve(w.seg_off, (size_t)k.tiles + 1)) return rc;
+        if (int rc = map_reserve(w.part_off, (size_t)k.tiles + 1)) return rc;
+        if (int rc = map_reserve(w.seg_tile, seg_cap)) return rc;
         const uint32_t list_blocks = (k.tiles + 1 + kScanThreads - 1) / kScanThreads;
-        if (int rc = map_reserve(w.block_tot, sizeof(uint32_t) * 2 * list_blocks)) return rc;
-        if (int rc = map_reserve(w.parts, sizeof(double) * std::max<size_t>(1, part_cap) * (fields + 1) * kTileCells))
+        if (int rc = map_reserve(w.block_tot, (size_t)2 * list_blocks)) return rc;
+        if (int rc = map_reserve(w.parts, std::max<size_t>(1, part_cap) * (fields + 1) * kTileCells))
             return rc;
-        if (int rc = map_reserve(w.slabs, sizeof(double) * kGlobalFields * class_blocks)) return rc;
-        if (int rc = map_reserve(w.counts, sizeof(uint32_t) * cells)) return rc;
-        if (int rc = map_reserve(w.planes, sizeof(double) * fields * cells)) return rc;
+        if (int rc = map_reserve(w.slabs, (size_t)kGlobalFields * class_blocks)) return rc;
+        if (int rc = map_reserve(w.counts, cells)) return rc;
+        if (int rc = map_reserve(w.planes, fields * cells)) return rc;
 
         const float4 *posm = nullptr, *vel = nullptr;
         sim.diag_state(&posm, &vel);
@@ -694,61 +624,58 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
         if (com)
             if (int rc = diag_enqueue_moments(sim, &mom)) return rc;
         hipLaunchKernelGGL(map_classify_kernel, dim3(class_blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, k, mom,
-                           (uint32_t *)w.keys[0].p, (double *)w.slabs.p, w.res);
+                           w.keys[0], w.slabs, w.res);
         NB_HIP_TRY(hipGetLastError());
         int side = 0;
         for (uint32_t pass = 0; pass < passes; ++pass, side ^= 1) {
             const uint32_t shift = kCellBits + 8 * pass;
-            hipLaunchKernelGGL(map_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream,
-                               (const uint32_t *)w.keys[side].p, n, chunk, shift, (uint32_t *)w.hist.p);
+            hipLaunchKernelGGL(map_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.keys[side], n,
+                               chunk, shift, w.hist);
             NB_HIP_TRY(hipGetLastError());
-            uint32_t *totals = (uint32_t *)w.hist.p + (size_t)kRadix * sort_blocks;
-            hipLaunchKernelGGL(map_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream,
-                               (uint32_t *)w.hist.p, sort_blocks, totals);
+            uint32_t *totals = w.hist + (size_t)kRadix * sort_blocks;
+            hipLaunchKernelGGL(map_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream, w.hist,
+                               sort_blocks, totals);
             NB_HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(map_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream,
-                               (const uint32_t *)w.keys[side].p, pass ? (const uint32_t *)w.idx[side].p : nullptr,
-                               (uint32_t *)w.keys[side ^ 1].p, (uint32_t *)w.idx[side ^ 1].p, n, chunk, shift,
-                               (const uint32_t *)w.hist.p, (const uint32_t *)totals);
+                               w.keys[side], pass ? (const uint32_t *)w.idx[side] : nullptr, w.keys[side ^ 1],
+                               w.idx[side ^ 1], n, chunk, shift, w.hist, totals);
             NB_HIP_TRY(hipGetLastError());
         }
-        const uint32_t *keys = (const uint32_t *)w.keys[side].p, *idx = (const uint32_t *)w.idx[side].p;
-        NB_HIP_TRY(hipMemsetAsync(w.first.p, 0, sizeof(uint32_t) * k.tiles, sim.stream));
-        NB_HIP_TRY(hipMemsetAsync(w.last.p, 0, sizeof(uint32_t) * k.tiles, sim.stream));
-        NB_HIP_TRY(hipMemsetAsync(w.counts.p, 0, sizeof(uint32_t) * cells, sim.stream));
-        NB_HIP_TRY(hipMemsetAsync(w.planes.p, 0, sizeof(double) * fields * cells, sim.stream));
+        const uint32_t *keys = w.keys[side], *idx = w.idx[side];
+        NB_HIP_TRY(hipMemsetAsync(w.first, 0, sizeof(uint32_t) * k.tiles, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.last, 0, sizeof(uint32_t) * k.tiles, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * cells, sim.stream));
+        NB_HIP_TRY(hipMemsetAsync(w.planes, 0, sizeof(double) * fields * cells, sim.stream));
         hipLaunchKernelGGL(map_bounds_kernel, dim3(class_blocks), dim3(kThreads), 0, sim.stream, keys, n, k.tiles,
-                           (uint32_t *)w.first.p, (uint32_t *)w.last.p);
+                           w.first, w.last);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(map_segments_local_kernel, dim3(list_blocks), dim3(kScanThreads), 0, sim.stream,
-                           (const uint32_t *)w.first.p, (const uint32_t *)w.last.p, k.tiles, seg_len,
-                           (uint32_t *)w.seg_off.p, (uint32_t *)w.part_off.p, (uint32_t *)w.block_tot.p);
+                           w.first, w.last, k.tiles, seg_len, w.seg_off, w.part_off, w.block_tot);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(map_segments_final_kernel, dim3(list_blocks), dim3(kScanThreads), 0, sim.stream,
-                           (const uint32_t *)w.first.p, (const uint32_t *)w.last.p, k.tiles, seg_len,
-                           (uint32_t *)w.seg_off.p, (uint32_t *)w.part_off.p, (const uint32_t *)w.block_tot.p,
-                           (uint32_t *)w.seg_tile.p, seg_cap);
+                           w.first, w.last, k.tiles, seg_len, w.seg_off, w.part_off, w.block_tot, w.seg_tile,
+                           seg_cap);
         NB_HIP_TRY(hipGetLastError());
         if (int rc = velocity ? launch_sums<kMaxFields>(sim, w, k, posm, vel, keys, idx, seg_len, seg_cap, part_cap)
                               : launch_sums<1>(sim, w, k, posm, vel, keys, idx, seg_len, seg_cap, part_cap))
             return rc;
         const uint32_t max_blocks = (uint32_t)std::min<size_t>(kMaxBlocks, (cells + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(map_max_kernel, dim3(max_blocks), dim3(kThreads), 0, sim.stream,
-                           (const uint32_t *)w.counts.p, cells, w.block_max);
+        hipLaunchKernelGGL(map_max_kernel, dim3(max_blocks), dim3(kThreads), 0, sim.stream, w.counts, cells,
+                           w.block_max);
         NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(map_finish_kernel, dim3(1), dim3(kThreads), 0, sim.stream, (const double *)w.slabs.p,
-                           class_blocks, (const uint32_t *)w.block_max, max_blocks, w.res + kUsed);
+        hipLaunchKernelGGL(map_finish_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, class_blocks,
+                           w.block_max, max_blocks, w.res + kUsed);
         NB_HIP_TRY(hipGetLastError());
         NB_HIP_TRY(hipMemcpyAsync(w.h_res, w.res, sizeof(double) * kResDoubles, hipMemcpyDeviceToHost, sim.stream));
         if (counts)
-            NB_HIP_TRY(hipMemcpyAsync(counts, w.counts.p, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, sim.stream));
+            NB_HIP_TRY(hipMemcpyAsync(counts, w.counts, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost, sim.stream));
         if (planes)
-            NB_HIP_TRY(hipMemcpyAsync(planes, w.planes.p, sizeof(double) * fields * cells, hipMemcpyDeviceToHost,
+            NB_HIP_TRY(hipMemcpyAsync(planes, w.planes, sizeof(double) * fields * cells, hipMemcpyDeviceToHost,
                                       sim.stream));
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
     } else {
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
-        for (int a = 0; a < 6; ++a) w.h_res[a] = com ? std::nan("") : (a < 3 ? k.c[a] : k.vc[a - 3]);  // com of no mass
+        centre_used_empty(w.h_res, com, k.c, k.vc);
         if (counts) std::memset(counts, 0, sizeof(uint32_t) * cells);
         if (planes) std::memset(planes, 0, sizeof(double) * fields * cells);
     }

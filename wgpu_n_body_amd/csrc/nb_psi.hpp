@@ -1,6 +1,7 @@
 // nb_psi.hpp -- what the pair passes over the float4 SoA state share (nb_diag.hip: the pair potential of
-// the whole state; nb_field.hip: the field at arbitrary points): the predicate that decides which bodies
-// count, and psi, the potential of the reference's force law, with the constants its fp32 form needs.
+// the whole state; nb_field.hip: the field at arbitrary points): psi, the potential of the reference's
+// force law, with the constants its fp32 form needs.  (The predicate that decides which bodies count is
+// nb_analysis.hpp's.)
 #pragma once
 
 #include <cmath>
@@ -32,15 +33,6 @@ inline PsiConst psi_const(float e) {
 }
 
 #ifdef __HIPCC__
-
-__device__ inline bool finite4(float4 p) {
-    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w);
-}
-
-// a body counts when its position, mass and velocity are all finite
-__device__ inline bool body_ok(float4 p, float4 v) {
-    return finite4(p) && isfinite(v.x) && isfinite(v.y) && isfinite(v.z);
-}
 
 // psi(r) = integral_r^inf ds / (s^3 + e), fp32, from r^2.  Far branch (r^3 >= 8e, x = e/r^3 <= 1/8):
 // 1/(2r^2) sum_k (-x)^k 2/(3k+2), eight terms (truncation (1/8)^8 * 2/26 < 5e-9).  Near branch: the

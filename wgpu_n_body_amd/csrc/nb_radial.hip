@@ -11,15 +11,17 @@
 //              staged bodies of segment s in body order and adds those of bin b to its registers.  At
 //              nbins = 256 a thread scans the whole tile for its bin; at nbins = 1 every thread owns one
 //              body, so bodies that all fall into one bin still sum in parallel.  At the end the block
-//              adds its 256 / P segments per bin in order and writes one slab;
-//   finish  -- every element of the slab is summed over the blocks in a fixed order.
+//              adds its 256 / P segments per bin in order and writes one slab (what is not binned: block_row,
+//              nb_analysis.hpp);
+//   finish  -- every element of the slab is summed over the blocks in a fixed order (sum_over_blocks in
+//              16 groups).
 // With NB_RADIAL_CENTER_COM the moments pass of nb_diag.hip runs first on the same stream and the
 // threads divide its sums into the centre themselves: no host round trip.
 // No float atomics, and the grid depends on n and nbins alone: the result is bitwise reproducible.
 #include <cmath>
 #include <cstring>
-#include <memory>
 
+#include "nb_analysis.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -27,7 +29,7 @@ namespace nb {
 
 namespace {
 
-constexpr uint32_t kThreads = 256;       // = bodies per tile; 4 waves per block
+constexpr uint32_t kThreads = kBlock;    // = bodies per tile; 4 waves per block
 constexpr uint32_t kMaxBins = NB_RADIAL_MAX_BINS;
 constexpr uint32_t kEdgeSlots = 512;     // squared edges in LDS, padded with +inf for the search
 constexpr uint32_t kBinFields = 11;      // see BinField
@@ -39,24 +41,13 @@ constexpr uint32_t kUsed = 8;            // res[0..6): the centre and velocity u
 constexpr uint16_t kNoBin = 0xffff;
 
 enum BinField { kBMass = 0, kBR, kBUr, kBUr2, kBUphi, kBUphi2, kBU2, kBAng, kBCount = 10 };
-enum GlobalField { kGInCount = 0, kGOutCount, kGBad, kGInMass, kGOutMass, kGMass, kGShape /* 6..11 */ };
+enum GlobalField { kGInCount = 0, kGOutCount, kGBad, kGInMass, kGOutMass, kGMass, kGShape /* 6..11 */, kGLive = 12 };
 
 struct RadialConst {
     double c[3], vc[3], axis[3];  // axis: the unit vector (cylindrical)
     uint32_t nbins, p2;           // p2 = P
     uint32_t cylindrical, center_com;
 };
-
-__device__ inline bool body_ok(float4 p, float4 v) {  // the predicate of nb_diag.hip
-    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w) && isfinite(v.x) && isfinite(v.y) &&
-           isfinite(v.z);
-}
-
-// fixed-order wave reduction (xor butterfly: every lane ends with the same, order-fixed sum)
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One body by the rule of include/nbody.h: its class (cnt = edges at or below r2: 0 inside, nbins + 1
 // outside), its ten bin terms and its six shape terms.
@@ -108,7 +99,7 @@ __device__ inline uint32_t classify(float4 p, float4 v, const RadialConst &k, co
 
 // ---- bins: one slab of kGlobalFields + nbins * kBinFields doubles per block ----------------
 // mom: the finished moments of nb_diag.hip (NB_RADIAL_CENTER_COM) or null.  e2g: nbins + 1 squared edges.
-// Block 0 also writes the centre and velocity it used to used[0..6).
+// Block 0 also writes the centre and velocity it used to used[0..6) (centre_used).
 __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const float4 *__restrict__ posm,
                                                                const float4 *__restrict__ vel, uint32_t n,
                                                                RadialConst k, const double *__restrict__ mom,
@@ -121,29 +112,14 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const float4 *__r
     const uint32_t tid = threadIdx.x;
     for (uint32_t j = tid; j < kEdgeSlots; j += kThreads) e2[j] = j <= k.nbins ? e2g[j] : INFINITY;
     double c[3], vc[3];
-    for (int a = 0; a < 3; ++a) {
-        c[a] = k.c[a];
-        vc[a] = k.vc[a];
-    }
-    if (k.center_com) {  // `com` and `momentum / mass` exactly as sim_diagnostics forms them
-        const double mass = mom[kDiagResMass];
-        for (int a = 0; a < 3; ++a) {
-            c[a] = mom[kDiagResMX + a] / mass;
-            vc[a] = mom[kDiagResMV + a] / mass;
-        }
-    }
-    if (blockIdx.x == 0 && tid == 0)
-        for (int a = 0; a < 3; ++a) {
-            used[a] = c[a];
-            used[3 + a] = vc[a];
-        }
+    centre_used(k.c, k.vc, k.center_com, mom, used, c, vc);
     __syncthreads();
 
     const uint32_t my_bin = tid & (k.p2 - 1), seg0 = tid & ~(k.p2 - 1);  // this thread's bin and first staged body
     double acc[kBinFields];
     for (uint32_t f = 0; f < kBinFields; ++f) acc[f] = 0.0;
-    double glob[kGlobalFields];
-    for (uint32_t f = 0; f < kGlobalFields; ++f) glob[f] = 0.0;
+    double glob[kGLive];
+    for (uint32_t f = 0; f < kGLive; ++f) glob[f] = 0.0;
 
     const uint32_t n_tiles = (n + kThreads - 1) / kThreads;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p;
@@ -197,14 +173,11 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const float4 *__r
         __syncthreads();  // the tile has been read
     }
 
+    // what is not binned, by the last 16 threads (the last wave: busy with the bins only at nbins > 192); then
     // the segments of every bin, in order
     for (uint32_t f = 0; f < kBinFields; ++f) stage[f][tid] = acc[f];
-    const uint32_t lane = tid % kWave, wave = tid / kWave;
-    for (uint32_t f = 0; f < kGShape + 6; ++f) glob[f] = wave_sum(glob[f]);
-    if (lane == 0)
-        for (uint32_t f = 0; f < kGlobalFields; ++f) part[wave][f] = glob[f];
-    __syncthreads();
     double *slab = slabs + (size_t)blockIdx.x * (kGlobalFields + k.nbins * kBinFields);
+    block_row<kGlobalFields, kGLive>(glob, part, slab, kThreads - kGlobalFields);
     if (tid < k.nbins) {
         for (uint32_t f = 0; f < kBinFields; ++f) {
             double s = stage[f][tid];
@@ -212,32 +185,17 @@ __global__ __launch_bounds__(kThreads) void radial_bins_kernel(const float4 *__r
             slab[kGlobalFields + tid * kBinFields + f] = s;
         }
     }
-    if (tid >= kThreads - kGlobalFields) {  // (the last wave: busy with the bins only at nbins > 192)
-        const uint32_t f = tid - (kThreads - kGlobalFields);
-        double s = part[0][f];
-        for (uint32_t w = 1; w < kThreads / kWave; ++w) s += part[w][f];
-        slab[f] = s;
-    }
 }
 
 // ---- finish: res[e] = sum over the blocks of slab element e, in a fixed order -----------------
-// thread (e, g) = (tid % 16, tid / 16) of block x sums element 16 x + e of blocks g, g + 16, ...; then the
-// 16 partials in order.
+// block x owns elements 16 x .. 16 x + 15, summed by sum_over_blocks in 16 groups.
 __global__ __launch_bounds__(kThreads) void radial_finish_kernel(const double *__restrict__ slabs, uint32_t blocks,
                                                                  uint32_t elems, double *__restrict__ res) {
     constexpr uint32_t kPer = 16, kGroups = kThreads / kPer;
     __shared__ double pp[kGroups][kPer];
-    const uint32_t tid = threadIdx.x, e = blockIdx.x * kPer + tid % kPer, g = tid / kPer;
-    double s = 0.0;
-    if (e < elems)
-        for (uint32_t b = g; b < blocks; b += kGroups) s += slabs[(size_t)b * elems + e];
-    pp[g][tid % kPer] = s;
-    __syncthreads();
-    if (tid < kPer && e < elems) {
-        double r = pp[0][tid];
-        for (uint32_t q = 1; q < kGroups; ++q) r += pp[q][tid];
-        res[e] = r;
-    }
+    const uint32_t tid = threadIdx.x, e = blockIdx.x * kPer + tid % kPer;
+    const double r = sum_over_blocks<kGroups>(slabs, blocks, elems, e, pp);
+    if (tid < kPer && e < elems) res[e] = r;
 }
 
 uint32_t pow2_at_least(uint32_t x) {
@@ -248,42 +206,28 @@ uint32_t pow2_at_least(uint32_t x) {
 
 }  // namespace
 
-struct RadialWork {
-    double *slabs = nullptr;  // [blocks][kGlobalFields + nbins * kBinFields], blocks * P <= kBlockBins
-    double *res = nullptr;    // [kUsed + kMaxElems]
-    double *e2 = nullptr;     // [kMaxBins + 1] squared edges
-    double *h_res = nullptr;  // pinned, as res
-    double *h_e2 = nullptr;   // pinned, as e2
+struct RadialWork : Workspace {
+    DeviceBuf<double> slabs;  // [blocks][kGlobalFields + nbins * kBinFields], blocks * P <= kBlockBins
+    DeviceBuf<double> res;    // [kUsed + kMaxElems]
+    DeviceBuf<double> e2;     // [kMaxBins + 1] squared edges
+    PinnedBuf<double> h_res;  // as res
+    PinnedBuf<double> h_e2;   // as e2
 };
 
-void radial_release(RadialWork *w) {
-    if (!w) return;
-    if (w->slabs) (void)hipFree(w->slabs);
-    if (w->res) (void)hipFree(w->res);
-    if (w->e2) (void)hipFree(w->e2);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    if (w->h_e2) (void)hipHostFree(w->h_e2);
-    delete w;
-}
-
 int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_profile *out, nb_radial_bin *bins) {
-    if (sim.place.world > 1) {
-        set_error("radial_profile: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
-        return NB_ERR_UNSUPPORTED;
-    }
-    if (int rc = sim.bind_device()) return rc;
-    if (!sim.radial) {  // kept only once complete
-        std::unique_ptr<RadialWork, void (*)(RadialWork *)> fresh(new RadialWork(), radial_release);
-        // the largest slab set: P = 1 has kMaxBlocks blocks of 16 + 11 doubles, P = 256 has 256 of 16 + 2816
-        const size_t slab_doubles = (size_t)kBlockBins * kBinFields + (size_t)kMaxBlocks * kGlobalFields;
-        NB_HIP_TRY(hipMalloc(&fresh->slabs, sizeof(double) * slab_doubles));
-        NB_HIP_TRY(hipMalloc(&fresh->res, sizeof(double) * (kUsed + kMaxElems)));
-        NB_HIP_TRY(hipMalloc(&fresh->e2, sizeof(double) * (kMaxBins + 1)));
-        NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_res, sizeof(double) * (kUsed + kMaxElems), hipHostMallocDefault));
-        NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_e2, sizeof(double) * (kMaxBins + 1), hipHostMallocDefault));
-        sim.radial = fresh.release();
-    }
-    RadialWork &w = *sim.radial;
+    if (int rc = analysis_begin(sim, "radial_profile")) return rc;
+    RadialWork *work = nullptr;
+    if (int rc = workspace(sim, kWorkRadial, &work, [](RadialWork &f) {
+            // the largest slab set: P = 1 has kMaxBlocks blocks of 16 + 11 doubles, P = 256 has 256 of 16 + 2816
+            NB_HIP_TRY(f.slabs.reserve((size_t)kBlockBins * kBinFields + (size_t)kMaxBlocks * kGlobalFields));
+            NB_HIP_TRY(f.res.reserve(kUsed + kMaxElems));
+            NB_HIP_TRY(f.e2.reserve(kMaxBins + 1));
+            NB_HIP_TRY(f.h_res.reserve(kUsed + kMaxElems));
+            NB_HIP_TRY(f.h_e2.reserve(kMaxBins + 1));
+            return NB_OK;
+        }))
+        return rc;
+    RadialWork &w = *work;
     const uint32_t n = sim.n, nbins = params.nbins;
     const bool cyl = (params.flags & NB_RADIAL_CYLINDRICAL) != 0, com = (params.flags & NB_RADIAL_CENTER_COM) != 0;
 
@@ -325,7 +269,7 @@ int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_p
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
     } else {
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
-        for (int a = 0; a < 6; ++a) w.h_res[a] = com ? std::nan("") : (a < 3 ? k.c[a] : k.vc[a - 3]);  // com of no mass
+        centre_used_empty(w.h_res, com, k.c, k.vc);
     }
     if (int rc = sim.diag_status()) return rc;
 

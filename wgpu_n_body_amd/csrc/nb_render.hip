@@ -22,8 +22,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 
+#include "nb_analysis.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -425,56 +425,33 @@ __global__ __launch_bounds__(kThreads) void render_finish_kernel(const uint32_t 
     }
 }
 
-template <class T>
-int grow(T *&ptr, size_t &cap, size_t want) {
-    if (want <= cap) return NB_OK;
-    if (ptr) NB_HIP_TRY(hipFree(ptr));
-    ptr = nullptr;
-    cap = 0;
-    NB_HIP_TRY(hipMalloc((void **)&ptr, sizeof(T) * want));
-    cap = want;
-    return NB_OK;
-}
-
 }  // namespace
 
-struct RenderWork {
-    uint32_t *counts = nullptr, *rgba = nullptr;  // [pixels]
-    size_t counts_cap = 0, rgba_cap = 0;
-    uint32_t *large = nullptr;                    // [n] bodies whose box a lane does not walk
-    size_t large_cap = 0;
-    uint32_t *list = nullptr;                     // tiled: [4 n] body indices by tile
-    size_t list_cap = 0;
-    uint32_t *tiles = nullptr;                    // tiled: count, cursor [kMaxTiles], offsets [kMaxTiles + 1]
-    uint32_t *words = nullptr;                    // [8]
-    uint32_t *class_slab = nullptr;               // [kBodyBlocks][4]
-    unsigned long long *slab_sum = nullptr;       // [kPixelBlocks]
-    uint32_t *slab_max = nullptr;                 // [kPixelBlocks]
-    unsigned long long *res = nullptr, *h_res = nullptr;  // [kResWords], device and pinned
-    int design = 0;                               // "render_design": 0 automatic, 1 direct, 2 tiled
+struct RenderWork : Workspace {
+    DeviceBuf<uint32_t> counts, rgba;            // [pixels] of the largest frame so far
+    DeviceBuf<uint32_t> large;                   // [n] bodies whose box a lane does not walk
+    DeviceBuf<uint32_t> list;                    // tiled: [4 n] body indices by tile
+    DeviceBuf<uint32_t> tiles;                   // tiled: count, cursor [kMaxTiles], offsets [kMaxTiles + 1]
+    DeviceBuf<uint32_t> words;                   // [8]
+    DeviceBuf<uint32_t> class_slab;              // [kBodyBlocks][4]
+    DeviceBuf<unsigned long long> slab_sum;      // [kPixelBlocks]
+    DeviceBuf<uint32_t> slab_max;                // [kPixelBlocks]
+    DeviceBuf<unsigned long long> res;           // [kResWords]
+    PinnedBuf<unsigned long long> h_res;         // as res
+    int design = 0;                              // "render_design": 0 automatic, 1 direct, 2 tiled
 };
 
-void render_release(RenderWork *w) {
-    if (!w) return;
-    for (void *p : {(void *)w->counts, (void *)w->rgba, (void *)w->large, (void *)w->list, (void *)w->tiles,
-                    (void *)w->words, (void *)w->class_slab, (void *)w->slab_sum, (void *)w->slab_max, (void *)w->res})
-        if (p) (void)hipFree(p);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    delete w;
-}
-
-static int render_work(SimBase &sim) {
-    if (sim.render) return NB_OK;
-    std::unique_ptr<RenderWork, void (*)(RenderWork *)> fresh(new RenderWork(), render_release);  // kept once complete
-    NB_HIP_TRY(hipMalloc((void **)&fresh->tiles, sizeof(uint32_t) * (3 * kMaxTiles + 1)));
-    NB_HIP_TRY(hipMalloc((void **)&fresh->words, sizeof(uint32_t) * 8));
-    NB_HIP_TRY(hipMalloc((void **)&fresh->class_slab, sizeof(uint32_t) * 4 * kBodyBlocks));
-    NB_HIP_TRY(hipMalloc((void **)&fresh->slab_sum, sizeof(unsigned long long) * kPixelBlocks));
-    NB_HIP_TRY(hipMalloc((void **)&fresh->slab_max, sizeof(uint32_t) * kPixelBlocks));
-    NB_HIP_TRY(hipMalloc((void **)&fresh->res, sizeof(unsigned long long) * kResWords));
-    NB_HIP_TRY(hipHostMalloc((void **)&fresh->h_res, sizeof(unsigned long long) * kResWords, hipHostMallocDefault));
-    sim.render = fresh.release();
-    return NB_OK;
+static int render_work(SimBase &sim, RenderWork **w) {
+    return workspace(sim, kWorkRender, w, [](RenderWork &f) {
+        NB_HIP_TRY(f.tiles.reserve(3 * kMaxTiles + 1));
+        NB_HIP_TRY(f.words.reserve(8));
+        NB_HIP_TRY(f.class_slab.reserve(4 * kBodyBlocks));
+        NB_HIP_TRY(f.slab_sum.reserve(kPixelBlocks));
+        NB_HIP_TRY(f.slab_max.reserve(kPixelBlocks));
+        NB_HIP_TRY(f.res.reserve(kResWords));
+        NB_HIP_TRY(f.h_res.reserve(kResWords));
+        return NB_OK;
+    });
 }
 
 int sim_render_set_design(SimBase &sim, int design) {
@@ -483,20 +460,18 @@ int sim_render_set_design(SimBase &sim, int design) {
         return NB_ERR_INVALID;
     }
     if (int rc = sim.bind_device()) return rc;
-    if (int rc = render_work(sim)) return rc;
-    sim.render->design = design;
+    RenderWork *w = nullptr;
+    if (int rc = render_work(sim, &w)) return rc;
+    w->design = design;
     return NB_OK;
 }
 
 // (the arguments were checked by nb_sim_render)
 int sim_render(SimBase &sim, const nb_render_params &rp, uint8_t *rgba, uint32_t *counts, nb_render_stats *stats) {
-    if (sim.place.world > 1) {
-        set_error("render: not available on a sharded simulator (placement world %d > 1)", sim.place.world);
-        return NB_ERR_UNSUPPORTED;
-    }
-    if (int rc = sim.bind_device()) return rc;
-    if (int rc = render_work(sim)) return rc;
-    RenderWork &w = *sim.render;
+    if (int rc = analysis_begin(sim, "render")) return rc;
+    RenderWork *work = nullptr;
+    if (int rc = render_work(sim, &work)) return rc;
+    RenderWork &w = *work;
     const uint32_t n = sim.n;
     const size_t pixels = (size_t)rp.width * rp.height;
 
@@ -528,11 +503,10 @@ int sim_render(SimBase &sim, const nb_render_params &rp, uint8_t *rgba, uint32_t
                   kTileH, tiles);
         return NB_ERR_UNSUPPORTED;
     }
-    if (int rc = grow(w.counts, w.counts_cap, pixels)) return rc;
-    if (int rc = grow(w.rgba, w.rgba_cap, pixels)) return rc;
-    if (int rc = grow(w.large, w.large_cap, (size_t)n)) return rc;
-    if (tiled)
-        if (int rc = grow(w.list, w.list_cap, 4 * (size_t)n)) return rc;
+    NB_HIP_TRY(w.counts.reserve(pixels));
+    NB_HIP_TRY(w.rgba.reserve(pixels));
+    NB_HIP_TRY(w.large.reserve(n));
+    if (tiled) NB_HIP_TRY(w.list.reserve(4 * (size_t)n));
 
     const float4 *posm = nullptr, *vel = nullptr;
     sim.diag_state(&posm, &vel);

@@ -8,11 +8,12 @@
 
 namespace nb {
 
-struct DiagWork;  // nb_diag.hip: the diagnostics' device slabs and pinned result
-struct RenderWork;  // nb_render.hip: the renderer's images, lists and slabs
-struct RadialWork;  // nb_radial.hip: the radial profile's slabs, squared edges and pinned result
-struct FieldWork;  // nb_field.hip: the field probes' points, slabs and pinned samples
-struct MapWork;  // nb_map.hip: the projected map's keys, lists, partials and device images
+// The workspace of an analysis pass (nb_analysis.hpp): a struct of buffers that free themselves, made by the
+// pass's first call and kept in the pass's slot of SimBase::work until the simulator goes.
+struct Workspace {
+    virtual ~Workspace() = default;
+};
+enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -120,18 +121,13 @@ class SimBase {
     bool own_stream = false;
     uint64_t step_num = 0;
     uint32_t n = 0, n_pad = 0, per_rank = 0, lo = 0, hi = 0;
-    DiagWork *diag = nullptr;  // allocated by the first nb_sim_diagnostics
-    RenderWork *render = nullptr;  // allocated by the first nb_sim_render
-    RadialWork *radial = nullptr;  // allocated by the first nb_sim_radial_profile
-    FieldWork *field = nullptr;  // allocated by the first nb_sim_field
+    std::unique_ptr<Workspace> work[kWorkSlots];  // the analysis passes' workspaces (nb_analysis.hpp)
     int field_pairs_log2 = 35;  // "field_launch_pairs_log2": pairs per launch of nb_sim_field, 2^16 .. 2^40
-    MapWork *map = nullptr;  // allocated by the first nb_sim_map, grown by the largest call so far
     int map_segment_len = 4096;  // "map_segment_len": bodies of a tile summed by one block of nb_sim_map
 };
 
-// nb_diag.hip: nb_sim_diagnostics behind the handle, and the release of its workspace
+// nb_diag.hip: nb_sim_diagnostics behind the handle
 int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out);
-void diag_release(DiagWork *w);
 // the moments pass and its finish alone, enqueued on the simulator's stream (n > 0; the device is bound):
 // *res_dev = the finished sums on the device, mass at [kDiagResMass], sum m x at [kDiagResMX + k], sum m v
 // at [kDiagResMV + k] -- what sim_diagnostics divides into `com` and reports as `momentum`
@@ -140,31 +136,25 @@ constexpr int kDiagResMass = 0, kDiagResMX = 1, kDiagResMV = 4, kDiagResBad = 12
 int diag_enqueue_moments(SimBase &sim, const double **res_dev);
 
 // nb_render.hip: nb_sim_render behind the handle (arguments already checked by render_check_params,
-// nb_camera.cpp), the "render_design" tuning key, and the release of the workspace
+// nb_camera.cpp) and the "render_design" tuning key
 int render_check_params(const nb_render_params *params);
 int sim_render(SimBase &sim, const nb_render_params &params, uint8_t *rgba, uint32_t *counts, nb_render_stats *stats);
 int sim_render_set_design(SimBase &sim, int design);
-void render_release(RenderWork *w);
 
-// nb_radial.hip: nb_sim_radial_profile behind the handle (arguments already checked, nb_abi.cpp) and
-// the release of its workspace
+// nb_radial.hip: nb_sim_radial_profile behind the handle (arguments already checked, nb_abi.cpp)
 int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_profile *out, nb_radial_bin *bins);
-void radial_release(RadialWork *w);
 
-// nb_field.hip: nb_sim_field behind the handle (arguments already checked, nb_abi.cpp) and the release of
-// its workspace
+// nb_field.hip: nb_sim_field behind the handle (arguments already checked, nb_abi.cpp)
 int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out, nb_field_stats *stats);
-void field_release(FieldWork *w);
 
 // nb_map.hip: nb_sim_map behind the handle (arguments already checked by map_check_params, nb_abi.cpp, which
-// also forms the frame and the cell sizes) and the release of its workspace
+// also forms the frame and the cell sizes)
 struct MapPlan {
     double n[3], e1[3], e2[3];  // axis_frame of the caller's axis
     double dx, dy;              // (hi - lo) / W, (hi - lo) / H
 };
 int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
             nb_map_stats *stats);
-void map_release(MapWork *w);
 // nb_abi.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
 // rule of include/nbody.h); false for an axis without a finite, non-zero length
 bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]);
