@@ -630,6 +630,89 @@ int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[
 int nb_map_edges(double lo, double hi, uint32_t cells, double *edges);
 
 /* ------------------------------------------------------------------------- */
+/* Friends-of-friends groups -- which bodies belong together (no reference    */
+/* counterpart: the clumps of the current state, on the device)               */
+/* ------------------------------------------------------------------------- */
+/* Partitions the state nb_sim_read_particles would return into the connected
+ * components of the "friends" graph and sums a catalogue of the larger ones.
+ * The rule, which DESIGN.md 6h states in full: binary64 from the binary32 state,
+ * one rounding per operation, no contraction:
+ *   counted   a body takes part when its position, mass and velocity are all
+ *             finite (the predicate of nb_sim_diagnostics); every other body is
+ *             `nonfinite`, has label NB_FOF_NONE and belongs to no group
+ *   friends   bodies i != j are friends iff d2 <= b2, with
+ *             dx = (double)x_i - (double)x_j, dy and dz likewise,
+ *             d2 = (dx dx + dy dy) + dz dz, b2 = link * link formed once;
+ *             the rule is symmetric in i and j
+ *   groups    a group is a connected component of the friends graph; a body's
+ *             label is the smallest body index of its component.  The index is the
+ *             one in the order nb_sim_read_particles returns at that moment: a
+ *             TreeSim reorders its bodies at every step, so labels of different
+ *             steps do not name the same bodies
+ *   catalogue the components with count >= min_members, numbered in ascending
+ *             label order; a row holds label, count and nine sums over the members:
+ *             m, m x, m y, m z, m vx, m vy, m vz, m ((x x + y y) + z z),
+ *             m ((vx vx + vy vy) + vz vz); group_of[i] is body i's row or NB_FOF_NONE
+ * The partition is unique, so labels, group_of, counts and every integer of the
+ * stats are exact and bit-identical between calls, whatever order the device's
+ * threads ran in.  The sums are added in a fixed order (the members in body order
+ * in runs of 64, a run by a fixed butterfly, the runs then in order): two calls
+ * return bit-identical doubles, each within 1e-10 of its sum of |term| of the
+ * binary64 sum.  No float atomics.
+ * nonfinite + sum of all component sizes == n; sum of the catalogue's counts ==
+ * grouped_bodies.  largest_label is the smallest label among the components of
+ * largest_count (NB_FOF_NONE, 0 without components).
+ * The bodies are sorted into cubic cells of side (link / sqrt(3)) (1 - 2^-20)
+ * from the smallest counted coordinate of every axis; a state that needs more than
+ * NB_FOF_MAX_CELLS_PER_AXIS cells on an axis is refused (NB_ERR_INVALID, after the
+ * call's one synchronisation, outputs untouched): such a link is below the
+ * resolution of binary32 coordinates over that extent.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.
+ * "fof_chunk_len" (nb_sim_set_tuning, 64..65536, a multiple of 64; default 1024;
+ * speed and testing only): the bodies of a cell, and of a catalogue row, one work
+ * item takes.  "fof_cell_boxes" (0 or 1, default 1; speed and testing only): use
+ * per-cell bounding boxes to skip or link neighbour cells without pair tests.
+ * Neither changes a bit of the result. */
+#define NB_FOF_NONE 0xFFFFFFFFu
+#define NB_FOF_MAX_CELLS_PER_AXIS (1u << 21)
+
+typedef struct nb_fof_params {
+    double link;          /* b: finite, > 0 */
+    uint32_t min_members; /* >= 1: the smallest component the catalogue holds */
+    uint32_t flags;       /* 0 */
+    uint64_t reserved;    /* 0 */
+} nb_fof_params;
+
+typedef struct nb_fof_group {
+    uint32_t label, count;
+    double mass, mx[3], mv[3], mr2, mv2; /* the nine sums, in the order above */
+} nb_fof_group;
+
+typedef struct nb_fof_stats {
+    uint64_t step_num, n, nonfinite;
+    uint64_t components;     /* all of them, singletons included */
+    uint64_t groups;         /* the catalogued ones, even when group_capacity is smaller */
+    uint64_t grouped_bodies; /* bodies of catalogued components */
+    uint32_t largest_count, largest_label;
+    uint32_t cells[3];       /* cells per axis that were used (0 without counted bodies) */
+    uint32_t reserved;
+    double cell_side;        /* the cell side that was used */
+} nb_fof_stats;
+
+/* The groups of a simulator's current state.  labels and group_of: n values each; groups: room for
+ * group_capacity rows, of which the first min(stats->groups, group_capacity) are written.  Every output
+ * pointer may be null: what is not asked for is not copied (and without `groups` no sum is formed); a call
+ * with none of them synchronises and measures nothing.  NB_ERR_INVALID for a null handle or params, a
+ * non-finite or non-positive link or one whose square is not a positive finite double (it under- or
+ * overflows), min_members == 0, unknown flags or reserved != 0 -- all checked before any device call --
+ * and for a state that needs too many cells (above); NB_ERR_UNSUPPORTED for a sharded simulator (placement
+ * world > 1). */
+int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of,
+               nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -788,6 +871,10 @@ int nb_runner_field(nb_runner *runner, const float *points, size_t m, uint32_t f
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *counts, double *planes,
                   nb_map_stats *stats);
+/* nb_sim_fof of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of,
+                  nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -36,6 +36,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
+           "FofGroups", "FofStats", "FOF_NONE",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -436,6 +437,100 @@ def _projected_map(call, handle, width, height, extent, axis, center, velocity, 
                         vec(st.velocity), vec(st.n_hat), vec(st.e1), vec(st.e2), int(st.flags), int(st.max_count))
 
 
+FOF_NONE = _lib.NB_FOF_NONE
+
+
+@dataclass(frozen=True)
+class FofStats:
+    """nb_fof_stats (include/nbody.h "Friends-of-friends groups")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    components: int       # all of them, singletons included
+    groups: int           # the catalogued ones
+    grouped_bodies: int
+    largest_count: int
+    largest_label: int
+    cells: tuple          # cells per axis that were used
+    cell_side: float
+
+
+@dataclass(frozen=True)
+class FofGroups:
+    """nb_sim_fof's partition and catalogue (include/nbody.h "Friends-of-friends groups"; no reference
+    counterpart): bodies closer than `link` are friends, a group is a connected component of the friends
+    graph of the state read_particles would return, its label the smallest body index in it.  labels and
+    group_of: (n,) uint32, FOF_NONE for a non-finite body / a body of no catalogued group (labels None when
+    not asked for).  rows: the catalogue, _lib.FOF_GROUP_DTYPE records in ascending label order -- the
+    components with at least min_members bodies."""
+    labels: Optional[np.ndarray]
+    group_of: np.ndarray
+    rows: np.ndarray
+    link: float
+    min_members: int
+    stats: FofStats
+
+    def _per_mass(self, a):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return a / (self.mass if a.ndim == 1 else self.mass[:, None])
+
+    @property
+    def label(self) -> np.ndarray:
+        return self.rows["label"]
+
+    @property
+    def count(self) -> np.ndarray:
+        return self.rows["count"]
+
+    @property
+    def mass(self) -> np.ndarray:
+        return self.rows["mass"]
+
+    @property
+    def com(self) -> np.ndarray:
+        """(groups, 3): sum m x / sum m."""
+        return self._per_mass(self.rows["mx"])
+
+    @property
+    def velocity(self) -> np.ndarray:
+        """(groups, 3): sum m v / sum m."""
+        return self._per_mass(self.rows["mv"])
+
+    @property
+    def rms_radius(self) -> np.ndarray:
+        """Mass-weighted rms distance of the members from com: sqrt(max(0, sum m |x|^2 / mass - |com|^2))."""
+        c = self.com
+        return np.sqrt(np.maximum(self._per_mass(self.rows["mr2"]) - (c * c).sum(axis=1), 0.0))
+
+    @property
+    def sigma(self) -> np.ndarray:
+        """Mass-weighted 3-D velocity dispersion about the group's velocity."""
+        v = self.velocity
+        return np.sqrt(np.maximum(self._per_mass(self.rows["mv2"]) - (v * v).sum(axis=1), 0.0))
+
+    def by_size(self) -> np.ndarray:
+        """The rows' numbers by count, descending, ties by label (ascending)."""
+        return np.lexsort((self.rows["label"], -self.rows["count"].astype(np.int64)))
+
+
+def _fof_groups(call, handle, n, link, min_members, labels) -> FofGroups:
+    p = _lib.nb_fof_params()
+    p.link, p.flags, p.reserved = float(link), 0, 0
+    mm = int(min_members)
+    p.min_members = mm if 0 <= mm <= 0xFFFFFFFF else 0  # (the call refuses 0 itself)
+    cap = n // mm if mm >= 1 else 0  # the most there can be
+    lab = np.empty(n, dtype=np.uint32) if labels else None
+    gof = np.empty(n, dtype=np.uint32)
+    rows = np.zeros(cap, dtype=_lib.FOF_GROUP_DTYPE)
+    st = _lib.nb_fof_stats()
+    check(call(handle, C.byref(p), lab.ctypes.data if labels else None, gof.ctypes.data, rows.ctypes.data, cap,
+               C.byref(st)))
+    stats = FofStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.components), int(st.groups),
+                     int(st.grouped_bodies), int(st.largest_count), int(st.largest_label),
+                     tuple(int(c) for c in st.cells), float(st.cell_side))
+    return FofGroups(lab, gof, rows[:stats.groups], float(link), mm, stats)
+
+
 @dataclass(frozen=True)
 class Camera:
     """nb_camera (`Camera`, online_renderer.rs:12-20)."""
@@ -782,6 +877,14 @@ class Simulator:
         return _projected_map(_lib.lib().nb_sim_map, self._h, width, height, extent, axis, center, velocity, depth,
                               velocities)
 
+    def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
+        """The friends-of-friends groups of the current state (nb_sim_fof): bodies within `link` of each
+        other are friends, a group is a connected component; the catalogue holds the groups of at least
+        min_members bodies.  The body indices are those of read_particles() now: a TreeSim reorders its
+        bodies at every step.  labels=False leaves the per-body labels on the device."""
+        return _fof_groups(_lib.lib().nb_sim_fof, self._h, int(self.sim_params().particle_num), link, min_members,
+                           labels)
+
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
         """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
@@ -967,6 +1070,11 @@ class OfflineHeadless:
         """nb_runner_map: Simulator.projected_map of the runner's simulator (one device only)."""
         return _projected_map(_lib.lib().nb_runner_map, self._h, width, height, extent, axis, center, velocity, depth,
                               velocities)
+
+    def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
+        """nb_runner_fof: Simulator.fof_groups of the runner's simulator (one device only)."""
+        return _fof_groups(_lib.lib().nb_runner_fof, self._h, int(self.sim_params().particle_num), link, min_members,
+                           labels)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

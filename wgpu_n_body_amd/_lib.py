@@ -111,6 +111,26 @@ class nb_map_stats(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_count", C.c_uint32)]
 
 
+class nb_fof_params(C.Structure):
+    _fields_ = [("link", C.c_double), ("min_members", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_fof_group(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("count", C.c_uint32), ("mass", C.c_double), ("mx", C.c_double * 3),
+                ("mv", C.c_double * 3), ("mr2", C.c_double), ("mv2", C.c_double)]
+
+
+class nb_fof_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("components", C.c_uint64), ("groups", C.c_uint64), ("grouped_bodies", C.c_uint64),
+                ("largest_count", C.c_uint32), ("largest_label", C.c_uint32), ("cells", C.c_uint32 * 3),
+                ("reserved", C.c_uint32), ("cell_side", C.c_double)]
+
+
+# nb_fof_group[] as a numpy record array
+FOF_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
+                            ("mv", "<f8", (3,)), ("mr2", "<f8"), ("mv2", "<f8")])
+
 # nb_field_sample[] and nb_field_ring[] as numpy record arrays
 FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
 FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
@@ -126,6 +146,8 @@ assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
 assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.sizeof(nb_field_stats) == 48
 assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
+assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
+assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -140,6 +162,7 @@ NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
+NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -155,6 +178,7 @@ ABI_SYMBOLS = [
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
+    "nb_sim_fof", "nb_runner_fof",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
@@ -228,6 +252,8 @@ def lib() -> C.CDLL:
                                       vp]
     L.nb_sim_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
     L.nb_runner_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
+    L.nb_sim_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
+    L.nb_runner_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
     L.nb_map_frame.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_map_edges.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]

@@ -10,6 +10,7 @@
 //             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
+//            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -43,6 +44,13 @@
 // row 0 the smallest b; --map-depth keeps LO <= h < HI along the line of sight.  One line per map
 // "map <step> <binned> <outside> <nonfinite> <max_count>".  DIR must exist.  The time they take is not
 // part of any "Step Duration"; without --maps the output is unchanged.
+//
+// --fof K finds the friends-of-friends groups (nb_runner_fof) of step 0 and of every K-th step: bodies within
+// --fof-link B of each other are friends, the catalogue holds the groups of at least M bodies (--fof-min,
+// default 20).  One line "fof <step> <groups> <grouped_bodies> <largest_count>", then the T largest rows
+// (--fof-top, default 0) as "fof_group <step> <row> <label> <count> <mass> <x> <y> <z>" (%.9e: the mass and the
+// centre of mass).  The time they take is not part of any "Step Duration"; without --fof the output is
+// unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
 // default camera, src/runners/online_renderer.rs:224-367) at step 0 and after every K-th step
@@ -181,6 +189,26 @@ static bool write_map(nbody::OfflineHeadless<Sim> &runner, const MapOptions &mo)
     return true;
 }
 
+struct FofOptions {
+    int every = 0, top = 0;
+    double link = 0.0;
+    uint32_t min_members = 20;
+};
+
+template <class Sim>
+static void print_fof(nbody::OfflineHeadless<Sim> &runner, const FofOptions &fo) {
+    const nbody::FofGroups g = runner.fof_groups(fo.link, fo.min_members, false);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("fof %llu %llu %llu %u\n", step, (unsigned long long)g.stats.groups,
+                (unsigned long long)g.stats.grouped_bodies, g.stats.largest_count);
+    const std::vector<uint32_t> order = g.by_size();
+    for (size_t k = 0; k < order.size() && k < (size_t)fo.top; ++k) {
+        const nbody::FofGroup &r = g.groups[order[k]];
+        std::printf("fof_group %llu %u %u %u %.9e %.9e %.9e %.9e\n", step, order[k], r.label, r.count, r.mass,
+                    r.mx[0] / r.mass, r.mx[1] / r.mass, r.mx[2] / r.mass);
+    }
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -218,7 +246,7 @@ template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
-               const RotcurveOptions &rotcurve, const MapOptions &maps) {
+               const RotcurveOptions &rotcurve, const MapOptions &maps, const FofOptions &fof) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -227,6 +255,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (radial.every > 0) print_radial(runner, radial);
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
+    if (fof.every > 0) print_fof(runner, fof);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -238,6 +267,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
+        if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -262,6 +292,7 @@ int main(int argc, char **argv) {
     RadialOptions radial;
     RotcurveOptions rotcurve;
     MapOptions maps;
+    FofOptions fof;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -376,6 +407,10 @@ int main(int argc, char **argv) {
             frames.width = w;
             frames.height = h;
         }
+        else if (k == "--fof") fof.every = std::atoi(v.c_str());
+        else if (k == "--fof-link") fof.link = std::atof(v.c_str());
+        else if (k == "--fof-min") fof.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--fof-top") fof.top = std::atoi(v.c_str());
         else if (k == "--devices") {
             for (size_t a = 0; a <= v.size();) {
                 const size_t b = std::min(v.find(',', a), v.size());
@@ -397,15 +432,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--maps needs --map-size WxH and --map-extent X0,X1,Y0,Y1\n");
         return 2;
     }
+    if (fof.every > 0 && !(fof.link > 0.0)) {
+        std::fprintf(stderr, "--fof needs --fof-link B > 0\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps);
+                                        diag_potential, frames, radial, rotcurve, maps, fof);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, fof);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -572,6 +572,32 @@ static int ring_basis(const char *what, const double *center, const double *axis
     return NB_OK;
 }
 
+// nb_sim_fof: everything that can be refused without a device
+static int fof_check_params(const nb_fof_params *p) {
+    if (!p) {
+        set_error("fof: null params");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->link) || !(p->link > 0.0)) {
+        set_error("fof: link must be finite and > 0 (got %g)", p->link);
+        return NB_ERR_INVALID;
+    }
+    const double b2 = p->link * p->link;  // what the rule compares with
+    if (!(b2 > 0.0) || !std::isfinite(b2)) {
+        set_error("fof: link %g squared is not a positive finite double", p->link);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("fof: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved) {
+        set_error("fof: unknown flag bits 0x%x or reserved %llu != 0", p->flags, (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_map_edges / nb_sim_map: the cell size of `cells` cells in [lo, hi), refused unless the edges
 // lo + i * size (i < cells), hi come out strictly ascending
 static int map_cell_size(const char *what, double lo, double hi, uint32_t cells, double *size) {
@@ -829,6 +855,30 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->map_segment_len = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "fof_chunk_len")) {  // the group finder's, whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 64 || value > 65536 || value % 64) {
+            set_error("fof_chunk_len: a multiple of 64 in 64..65536, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->fof_chunk_len = value;
+        return NB_OK;
+    }
+    if (!std::strcmp(key, "fof_cell_boxes")) {
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value != 0 && value != 1) {
+            set_error("fof_cell_boxes: 0 or 1, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->fof_cell_boxes = value;
+        return NB_OK;
+    }
     NB_SIM_CALL(sim, set_tuning(key, value))
 }
 
@@ -959,6 +1009,12 @@ int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, doubl
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
     NB_SIM_PASS(sim, sim_map, *params, plan, counts, planes, stats)
+}
+
+int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+               size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = fof_check_params(params)) return rc;
+    NB_SIM_PASS(sim, sim_fof, *params, labels, group_of, groups, group_capacity, stats)
 }
 
 int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
@@ -1214,6 +1270,14 @@ int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *coun
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "map")) return rc;
     return nb_sim_map(runner->sim, params, counts, planes, stats);
+}
+
+int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of,
+                  nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = fof_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "fof")) return rc;
+    return nb_sim_fof(runner->sim, params, labels, group_of, groups, group_capacity, stats);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -1,0 +1,988 @@
+// nb_fof.hip -- nb_sim_fof: the friends-of-friends groups of a simulator's current state (include/nbody.h
+// "Friends-of-friends groups"; no reference counterpart).
+//
+// Bodies i != j are friends iff d2 <= link * link in binary64; a group is a connected component of that
+// graph, its label the smallest body index in it.  The graph is fixed by the state, so the partition is
+// unique and everything integer here is exact, whatever order the threads ran in.
+//   bounds  -- one thread per body over the float4 SoA state (SimBase::diag_state): the per-axis minimum and
+//              maximum of the counted bodies (body_ok) and their number, through per-block slabs (block_row,
+//              nb_analysis.hpp); one block finishes them into the plan on the device: the grid's origin, the
+//              cells per axis of side h = (link / sqrt(3)) (1 - 2^-20), the key bits in use -- or the refusal
+//              of a state that needs more than 2^21 cells on an axis.  Every later kernel reads the plan;
+//              after a refusal they all return at once.  No host round trip;
+//   key     -- one 64-bit linear cell key per body, (cz ny + cy) nx + cx, or the key past the last cell
+//              for a body that does not count;
+//   sort    -- a stable LSD radix sort of (key, body index), 8 bits a pass: count / scan / scatter, one
+//              wave per chunk of bodies, the rank inside a chunk by wave ballots in body order (the design
+//              of nb_map.hip's sort on 64-bit keys).  Eight passes are enqueued, those the plan does not need
+//              return at once.  A cell's bodies end up consecutive and in body order;
+//   cells   -- the occupied cells (key, start) from neighbouring keys and a scan, every body's position
+//              gathered in sorted order, parent[i] = the first body of i's cell -- all bodies of a cell are
+//              friends without a test (the cell's diagonal is below link) -- and the cells' bounding boxes by
+//              integer atomic minima and maxima of the order-preserving encoding of a float;
+//   union   -- one wave per chunk of at most "fof_chunk_len" bodies of an occupied cell A.  Lane l looks
+//              up the l-th of the 62 forward neighbours within +-2 cells per axis by binary search in the
+//              cell table and classes it by the boxes: apart (nearest corners beyond link), all friends
+//              (farthest corners within link), or to be tested.  A neighbour whose representative already
+//              shares A's root is skipped; otherwise the pairs of A x B are tested by the rule, lanes over
+//              A's bodies, until a wave ballot finds a hit; then the roots are united lock-free by
+//              atomicCAS(&parent[max], max, min), retried on failure.  No locks, no waiting on other threads;
+//   labels  -- every body follows parent to its root, which hooking to the smaller makes the component's
+//              smallest index; component sizes by integer atomics on the root;
+//   rows    -- roots with count >= min_members flagged and scanned into catalogue rows, group_of, and the
+//              integer stats by integer atomics;
+//   sums    -- (only when the catalogue is asked for) the grouped bodies sorted stably by row, then one
+//              wave per chunk of a row's list: runs of 64 members by the fixed butterfly, one slot per run;
+//              then 16 lanes per row add the row's runs in order.  The chunk length decides who adds a run,
+//              never in which order: the sums do not depend on it.
+// No float atomics anywhere.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+#include "nb_analysis.hpp"
+#include "nb_common.hpp"
+#include "nb_sim.hpp"
+
+namespace nb {
+
+namespace {
+
+constexpr uint32_t kThreads = kBlock;
+constexpr uint32_t kRadix = 256;         // 8 bits of the key per sort pass
+constexpr uint32_t kSortBlocks = 2048;   // at most this many chunks (one wave each) per sort pass
+constexpr uint32_t kScanThreads = 1024;  // the scans: elements per block of the local scan
+constexpr uint32_t kMaxPasses = 8;       // a 64-bit key
+constexpr uint32_t kBoundFields = 8, kBoundLive = 7;  // max(-x, -y, -z, x, y, z), counted bodies
+constexpr uint32_t kBoundMax = 0x3f;
+constexpr uint32_t kTerms = 9;           // the sums of a catalogue row
+constexpr uint32_t kRowLanes = 16;       // lanes per row of the combine kernel
+constexpr uint32_t kNeighbours = 62;     // forward neighbours within +-2 cells per axis: (5^3 - 1) / 2
+constexpr double kMaxCells = (double)NB_FOF_MAX_CELLS_PER_AXIS;
+
+// The plan and the integer results of a call, on the device.  Written by single threads or integer atomics.
+struct FofInfo {
+    double lo[3];
+    double h;
+    unsigned long long total;      // cells of the grid = the key of a body that does not count
+    unsigned long long nx, ny, nz;
+    unsigned long long grouped_bodies, largest;  // largest: count << 32 | ~label
+    uint32_t status;               // 1: refused, too many cells on an axis
+    uint32_t n_ok, ncells;
+    uint32_t passes[2];            // sort passes in use: the cell keys', the rows'
+    uint32_t components, groups, rows;  // rows = min(groups, capacity): the key past the last row
+    uint32_t row_bodies;           // bodies of the rows below `rows`
+};
+
+__host__ __device__ inline uint32_t bits_of(unsigned long long x) {
+    uint32_t b = 0;
+    while (x) {
+        ++b;
+        x >>= 1;
+    }
+    return b;
+}
+
+// the order-preserving encoding of a finite float as an unsigned integer
+__device__ inline uint32_t ordered(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float unordered(uint32_t e) {
+    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
+}
+
+// ---- bounds ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void fof_bounds_kernel(const float4 *__restrict__ posm,
+                                                              const float4 *__restrict__ vel, uint32_t n,
+                                                              double *__restrict__ slabs) {
+    __shared__ double part[kThreads / kWave][kBoundFields];
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    double v[kBoundLive];
+    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
+    v[6] = 0.0;
+    if (i < n) {
+        const float4 p = posm[i];
+        if (body_ok(p, vel[i])) {
+            v[0] = -(double)p.x;
+            v[1] = -(double)p.y;
+            v[2] = -(double)p.z;
+            v[3] = p.x;
+            v[4] = p.y;
+            v[5] = p.z;
+            v[6] = 1.0;
+        }
+    }
+    block_row<kBoundFields, kBoundLive, kBoundMax>(v, part, slabs + (size_t)blockIdx.x * kBoundFields);
+}
+
+// One block: the slabs into the plan.  Maxima and a sum of small integers: exact in any order.
+__global__ __launch_bounds__(kThreads) void fof_plan_kernel(const double *__restrict__ slabs, uint32_t blocks,
+                                                            double h, FofInfo *__restrict__ info) {
+    __shared__ double red[kBoundLive][kThreads];
+    const uint32_t tid = threadIdx.x;
+    double v[kBoundLive];
+    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
+    v[6] = 0.0;
+    for (uint32_t b = tid; b < blocks; b += kThreads) {
+        const double *row = slabs + (size_t)b * kBoundFields;
+        for (uint32_t f = 0; f < 6; ++f) v[f] = fmax(v[f], row[f]);
+        v[6] += row[6];
+    }
+    for (uint32_t f = 0; f < kBoundLive; ++f) red[f][tid] = v[f];
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            for (uint32_t f = 0; f < 6; ++f) red[f][tid] = fmax(red[f][tid], red[f][tid + o]);
+            red[6][tid] += red[6][tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    FofInfo o{};
+    o.h = h;
+    o.n_ok = (uint32_t)red[6][0];
+    if (o.n_ok > 0) {
+        unsigned long long cells[3];
+        for (int a = 0; a < 3; ++a) {
+            o.lo[a] = -red[a][0];
+            const double c = floor((red[3 + a][0] - o.lo[a]) / h) + 1.0;
+            if (!(c <= kMaxCells)) o.status = 1;
+            cells[a] = o.status ? 0ull : (unsigned long long)c;
+        }
+        o.nx = cells[0];
+        o.ny = cells[1];
+        o.nz = cells[2];
+        o.total = o.status ? 0ull : o.nx * o.ny * o.nz;  // (at most 2^63)
+    }
+    o.passes[0] = std::max(1u, (bits_of(o.total) + 7) / 8);  // keys run 0 .. total
+    *info = o;
+}
+
+// ---- key ------------------------------------------------------------------------------------------
+// The cell of coordinate x on an axis of `cells` cells from lo: floor((x - lo) / h), x >= lo
+__device__ inline unsigned long long cell_of(float x, double lo, double h, unsigned long long cells) {
+    const double q = floor(((double)x - lo) / h);
+    const unsigned long long c = (unsigned long long)q;
+    return c < cells ? c : cells - 1;  // (q < cells by the plan's own division; the clamp never binds)
+}
+
+__global__ __launch_bounds__(kThreads) void fof_key_kernel(const float4 *__restrict__ posm,
+                                                           const float4 *__restrict__ vel, uint32_t n,
+                                                           const FofInfo *__restrict__ info,
+                                                           unsigned long long *__restrict__ keys) {
+    if (info->status) return;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = posm[i];
+    unsigned long long key = info->total;
+    if (body_ok(p, vel[i])) {
+        const unsigned long long cx = cell_of(p.x, info->lo[0], info->h, info->nx);
+        const unsigned long long cy = cell_of(p.y, info->lo[1], info->h, info->ny);
+        const unsigned long long cz = cell_of(p.z, info->lo[2], info->h, info->nz);
+        key = (cz * info->ny + cy) * info->nx + cx;
+    }
+    keys[i] = key;
+}
+
+// ---- sort: one pass of the stable sort, digit = (key >> 8 pass) & 255 ----------------------------------
+// Pass p reads side p & 1 and writes the other; the sorted keys are on side passes & 1.  A pass at or past
+// info->passes[which] returns at once.  Chunk b = elements [b * chunk, (b + 1) * chunk), one wave each.
+__global__ __launch_bounds__(kWave) void fof_sort_count_kernel(const FofInfo *__restrict__ info, uint32_t which,
+                                                               uint32_t pass,
+                                                               const unsigned long long *__restrict__ k0,
+                                                               const unsigned long long *__restrict__ k1, uint32_t n,
+                                                               uint32_t chunk, uint32_t *__restrict__ hist) {
+    if (info->status || pass >= info->passes[which]) return;
+    __shared__ uint32_t cnt[kRadix];
+    const unsigned long long *keys = pass & 1 ? k1 : k0;
+    const uint32_t lane = threadIdx.x, shift = 8 * pass;
+    for (uint32_t d = lane; d < kRadix; d += kWave) cnt[d] = 0;
+    __syncthreads();
+    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
+    for (size_t i = lo + lane; i < hi; i += kWave) atomicAdd(&cnt[(uint32_t)(keys[i] >> shift) & (kRadix - 1)], 1u);
+    __syncthreads();
+    for (uint32_t d = lane; d < kRadix; d += kWave) hist[(size_t)d * gridDim.x + blockIdx.x] = cnt[d];
+}
+
+// An exclusive scan of v[0 .. count) in place by one block of kScanThreads, thread t owning a run of elements;
+// returns the sum of all of them.
+__device__ inline uint32_t block_scan_runs(uint32_t *v, uint32_t count, uint32_t *lds /* [2][kScanThreads] */) {
+    const uint32_t tid = threadIdx.x, per = (count + kScanThreads - 1) / kScanThreads;
+    const size_t lo = std::min<size_t>(count, (size_t)tid * per), hi = std::min<size_t>(count, lo + per);
+    uint32_t s = 0;
+    for (size_t i = lo; i < hi; ++i) s += v[i];
+    uint32_t *a = lds, *b = lds + kScanThreads;
+    a[tid] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele
+        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
+        __syncthreads();
+        uint32_t *t = a;
+        a = b;
+        b = t;
+    }
+    uint32_t run = a[tid] - s;  // exclusive
+    const uint32_t total = a[kScanThreads - 1];
+    for (size_t i = lo; i < hi; ++i) {
+        const uint32_t x = v[i];
+        v[i] = run;
+        run += x;
+    }
+    __syncthreads();
+    return total;
+}
+
+// scan: block d scans the row of digit d over the chunks in place and writes the row's sum to totals[d]
+__global__ __launch_bounds__(kScanThreads) void fof_sort_scan_kernel(const FofInfo *__restrict__ info, uint32_t which,
+                                                                     uint32_t pass, uint32_t *__restrict__ hist,
+                                                                     uint32_t blocks, uint32_t *__restrict__ totals) {
+    if (info->status || pass >= info->passes[which]) return;
+    __shared__ uint32_t lds[2 * kScanThreads];
+    const uint32_t total = block_scan_runs(hist + (size_t)blockIdx.x * blocks, blocks, lds);
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+// scatter: element i of chunk b goes to (elements with a lower digit) + offs[d * blocks + b] + (elements of
+// the chunk before i with digit d).  Pass 0 takes the identity for the indices.
+__global__ __launch_bounds__(kWave) void fof_sort_scatter_kernel(const FofInfo *__restrict__ info, uint32_t which,
+                                                                 uint32_t pass, unsigned long long *__restrict__ k0,
+                                                                 unsigned long long *__restrict__ k1,
+                                                                 uint32_t *__restrict__ i0p, uint32_t *__restrict__ i1p,
+                                                                 uint32_t n, uint32_t chunk,
+                                                                 const uint32_t *__restrict__ offs,
+                                                                 const uint32_t *__restrict__ totals) {
+    if (info->status || pass >= info->passes[which]) return;
+    __shared__ uint32_t base[kRadix];
+    const unsigned long long *key_in = pass & 1 ? k1 : k0;
+    unsigned long long *key_out = pass & 1 ? k0 : k1;
+    const uint32_t *idx_in = pass & 1 ? i1p : i0p;
+    uint32_t *idx_out = pass & 1 ? i0p : i1p;
+    const uint32_t lane = threadIdx.x, shift = 8 * pass;
+    {  // lane l owns digits 4 l .. 4 l + 3: an exclusive scan of the 256 totals, four a lane, then over the wave
+        constexpr uint32_t kPer = kRadix / kWave;
+        uint32_t t[kPer], sum = 0;
+        for (uint32_t q = 0; q < kPer; ++q) {
+            t[q] = totals[lane * kPer + q];
+            sum += t[q];
+        }
+        uint32_t inc = sum;
+        for (uint32_t o = 1; o < kWave; o <<= 1) {
+            const uint32_t y = __shfl_up(inc, o);
+            if (lane >= o) inc += y;
+        }
+        uint32_t run = inc - sum;
+        for (uint32_t q = 0; q < kPer; ++q) {
+            const uint32_t d = lane * kPer + q;
+            base[d] = run + offs[(size_t)d * gridDim.x + blockIdx.x];
+            run += t[q];
+        }
+    }
+    __syncthreads();
+    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (size_t i0 = lo; i0 < hi; i0 += kWave) {
+        const size_t i = i0 + lane;
+        const bool valid = i < hi;
+        const unsigned long long key = valid ? key_in[i] : 0ull;
+        const uint32_t src = valid ? (pass ? idx_in[i] : (uint32_t)i) : 0u;
+        const uint32_t d = (uint32_t)(key >> shift) & (kRadix - 1);
+        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & below), group = (uint32_t)__popcll(same);
+        const uint32_t pos = base[d] + rank;
+        __syncthreads();
+        if (valid && rank + 1 == group) base[d] += group;  // one lane per digit present
+        __syncthreads();
+        if (valid && pos < n) {
+            key_out[pos] = key;
+            idx_out[pos] = src;
+        }
+    }
+}
+
+// ---- scans over n elements: kScanThreads elements per block, then the blocks' sums by one block --------
+// excl[i] = flags before i in i's block; block_tot[b] = the flags of block b
+__global__ __launch_bounds__(kScanThreads) void fof_scan_local_kernel(const FofInfo *__restrict__ info,
+                                                                      const uint32_t *__restrict__ flags, uint32_t n,
+                                                                      uint32_t *__restrict__ excl,
+                                                                      uint32_t *__restrict__ block_tot) {
+    if (info->status) return;
+    __shared__ uint32_t lds[2 * kScanThreads];
+    const uint32_t tid = threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * kScanThreads + tid;
+    const uint32_t s = i < n ? flags[i] : 0u;
+    uint32_t *a = lds, *b = lds + kScanThreads;
+    a[tid] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {
+        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
+        __syncthreads();
+        uint32_t *t = a;
+        a = b;
+        b = t;
+    }
+    if (i < n) excl[i] = a[tid] - s;
+    if (tid == kScanThreads - 1) block_tot[blockIdx.x] = a[tid];
+}
+
+// block_tot scanned in place (exclusive); the sum of all to *total
+__global__ __launch_bounds__(kScanThreads) void fof_scan_blocks_kernel(const FofInfo *__restrict__ info,
+                                                                       uint32_t *__restrict__ block_tot,
+                                                                       uint32_t blocks, uint32_t *__restrict__ total) {
+    if (info->status) return;
+    __shared__ uint32_t lds[2 * kScanThreads];
+    const uint32_t t = block_scan_runs(block_tot, blocks, lds);
+    if (threadIdx.x == 0) *total = t;
+}
+
+__device__ inline uint32_t scanned(const uint32_t *excl, const uint32_t *block_tot, size_t i) {
+    return excl[i] + block_tot[i / kScanThreads];
+}
+
+// ---- cells ----------------------------------------------------------------------------------------
+// flags[p] = 1 where a cell starts in the sorted keys
+__global__ __launch_bounds__(kThreads) void fof_heads_kernel(const FofInfo *__restrict__ info,
+                                                             const unsigned long long *__restrict__ k0,
+                                                             const unsigned long long *__restrict__ k1, uint32_t n,
+                                                             uint32_t *__restrict__ flags) {
+    if (info->status) return;
+    const size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= n) return;
+    const unsigned long long *keys = info->passes[0] & 1 ? k1 : k0;
+    const unsigned long long key = keys[p];
+    flags[p] = key < info->total && (p == 0 || keys[p - 1] != key);
+}
+
+// the cell table: cell_key[c], cell_start[c] for the c-th occupied cell, cell_start[ncells] = counted bodies;
+// flags[p] becomes the cell of sorted position p
+__global__ __launch_bounds__(kThreads) void fof_cells_kernel(const FofInfo *__restrict__ info,
+                                                             const unsigned long long *__restrict__ k0,
+                                                             const unsigned long long *__restrict__ k1, uint32_t n,
+                                                             const uint32_t *__restrict__ excl,
+                                                             const uint32_t *__restrict__ block_tot,
+                                                             uint32_t *__restrict__ flags,
+                                                             unsigned long long *__restrict__ cell_key,
+                                                             uint32_t *__restrict__ cell_start) {
+    if (info->status) return;
+    const size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= info->n_ok) return;
+    const unsigned long long *keys = info->passes[0] & 1 ? k1 : k0;
+    const uint32_t head = flags[p], c = scanned(excl, block_tot, p) + head - 1;
+    if (head) {
+        cell_key[c] = keys[p];
+        cell_start[c] = (uint32_t)p;
+    }
+    if (p + 1 == info->n_ok) cell_start[c + 1] = info->n_ok;
+    flags[p] = c;
+}
+
+// parent, the gathered positions and the cells' boxes.  boxes[6 c + a]: a < 3 the maximum of ~ordered(x_a)
+// (the minimum, complemented), else the maximum of ordered(x_a); cleared to 0 beforehand.
+__global__ __launch_bounds__(kThreads) void fof_parent_kernel(FofInfo *__restrict__ info,
+                                                              const float4 *__restrict__ posm,
+                                                              const uint32_t *__restrict__ i0p,
+                                                              const uint32_t *__restrict__ i1p, uint32_t n,
+                                                              const uint32_t *__restrict__ cell_of_pos,
+                                                              const uint32_t *__restrict__ cell_start,
+                                                              const uint32_t *__restrict__ block_tot_total,
+                                                              float4 *__restrict__ spos, uint32_t *__restrict__ parent,
+                                                              uint32_t *__restrict__ boxes, uint32_t use_boxes) {
+    if (info->status) return;
+    const size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p == 0) info->ncells = *block_tot_total;
+    if (p >= n) return;
+    const uint32_t *idx = info->passes[0] & 1 ? i1p : i0p;
+    const uint32_t body = idx[p];
+    if (p >= info->n_ok) {
+        parent[body] = NB_FOF_NONE;
+        return;
+    }
+    const uint32_t c = cell_of_pos[p];
+    parent[body] = idx[cell_start[c]];
+    const float4 q = posm[body];
+    spos[p] = q;
+    if (!use_boxes) return;
+    uint32_t e[6] = {~ordered(q.x), ~ordered(q.y), ~ordered(q.z), ordered(q.x), ordered(q.y), ordered(q.z)};
+    // a wave whose active lanes share one cell sends one lane's six atomics
+    const unsigned long long active = __ballot(true);
+    const int first = __ffsll((long long)active) - 1;
+    const uint32_t c0 = __shfl(c, first);
+    if (__ballot(c != c0) == 0ull && active == ~0ull) {
+        for (int o = 32; o > 0; o >>= 1)
+            for (int a = 0; a < 6; ++a) e[a] = std::max(e[a], (uint32_t)__shfl_xor(e[a], o));
+        if (threadIdx.x % kWave == 0)
+            for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
+    } else {
+        for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
+    }
+}
+
+// ---- union ----------------------------------------------------------------------------------------
+__device__ inline uint32_t load_parent(const uint32_t *parent, uint32_t i) {
+    return __atomic_load_n(parent + i, __ATOMIC_RELAXED);
+}
+// parent[x] < x unless x is a root: the walk ends
+__device__ inline uint32_t find_root(const uint32_t *parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = load_parent(parent, x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+// ... and on the way points every second node at its grandparent (path halving).  Only a node that is not a
+// root is written, with a smaller ancestor of its own tree, and a node never becomes a root again: the
+// exchange in unite, which expects a root, is not disturbed, and parent[x] < x holds on.
+__device__ inline uint32_t find_root_halving(uint32_t *parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = load_parent(parent, x);
+        if (p == x) return x;
+        const uint32_t g = load_parent(parent, p);
+        if (g != p) __atomic_store_n(parent + x, g, __ATOMIC_RELAXED);
+        x = g;
+    }
+}
+// Hook the larger root under the smaller.  A failed exchange means another thread hooked that root first:
+// find both roots again.  Nothing waits on another thread.
+__device__ inline void unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = find_root_halving(parent, a);
+        b = find_root_halving(parent, b);
+        if (a == b) return;
+        const uint32_t hi = std::max(a, b), lo = std::min(a, b);
+        if (atomicCAS(parent + hi, hi, lo) == hi) return;
+        a = hi;
+        b = lo;
+    }
+}
+
+// the rule of include/nbody.h
+__device__ inline bool friends(float4 p, float4 q, double b2) {
+#pragma clang fp contract(off)
+    const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
+    return (dx * dx + dy * dy) + dz * dz <= b2;
+}
+
+// The list of work item g among lists l = 0 .. count - 1 of positions [start[l], start[l + 1]), cut into chunks
+// of len: list l owns the items start[l] / len + l onwards, which are at least its chunks.  False for an item
+// no list owns.  *a0, *a1: the chunk's positions; *s: its number in the list.
+__device__ inline bool item_chunk(const uint32_t *__restrict__ start, uint32_t count, uint32_t len, uint32_t g,
+                                  uint32_t *l_out, uint32_t *s_out, uint32_t *a0, uint32_t *a1) {
+    if (count == 0) return false;
+    uint32_t lo = 0, hi = count;  // start[0] / len + 0 = 0 <= g
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if ((unsigned long long)start[mid] / len + mid <= g) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t s = g - (start[lo] / len + lo);
+    const unsigned long long first = (unsigned long long)start[lo] + (unsigned long long)s * len;
+    const uint32_t end = start[lo + 1];
+    if (first >= end) return false;
+    *l_out = lo;
+    *s_out = s;
+    *a0 = (uint32_t)first;
+    *a1 = (uint32_t)std::min<unsigned long long>(end, first + len);
+    return true;
+}
+
+__global__ __launch_bounds__(kWave) void fof_union_kernel(const FofInfo *__restrict__ info,
+                                                          const unsigned long long *__restrict__ cell_key,
+                                                          const uint32_t *__restrict__ cell_start,
+                                                          const uint32_t *__restrict__ boxes,
+                                                          const uint32_t *__restrict__ i0p,
+                                                          const uint32_t *__restrict__ i1p,
+                                                          const float4 *__restrict__ spos, uint32_t *parent,
+                                                          uint32_t len, double b2, uint32_t use_boxes) {
+#pragma clang fp contract(off)
+    if (info->status) return;
+    const uint32_t ncells = info->ncells, lane = threadIdx.x;
+    uint32_t c, s, a0, a1;
+    if (!item_chunk(cell_start, ncells, len, blockIdx.x, &c, &s, &a0, &a1)) return;  // (uniform over the wave)
+    const uint32_t *idx = info->passes[0] & 1 ? i1p : i0p;
+    const uint32_t rep_a = idx[cell_start[c]];
+
+    // lane l: the l-th forward neighbour, its place in the cell table and its class by the boxes
+    uint32_t nb = 0, cls = 0;  // 0 none or apart, 1 test the pairs, 2 all friends
+    if (lane < kNeighbours) {
+        const unsigned long long nx = info->nx, ny = info->ny, nz = info->nz, key = cell_key[c];
+        const long long cx = (long long)(key % nx), cy = (long long)((key / nx) % ny), cz = (long long)(key / (nx * ny));
+        const uint32_t t = lane + kNeighbours + 1;  // offsets after (0, 0, 0) in (z, y, x) order
+        const long long ox = (long long)(t % 5) - 2, oy = (long long)((t / 5) % 5) - 2, oz = (long long)(t / 25) - 2;
+        const long long x = cx + ox, y = cy + oy, z = cz + oz;
+        if (x >= 0 && x < (long long)nx && y >= 0 && y < (long long)ny && z >= 0 && z < (long long)nz) {
+            const unsigned long long want = ((unsigned long long)z * ny + (unsigned long long)y) * nx + (unsigned long long)x;
+            uint32_t lo = c + 1, hi = ncells;  // (a forward neighbour has a larger key)
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (cell_key[mid] < want) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < ncells && cell_key[lo] == want) {
+                nb = lo;
+                cls = 1;
+                if (use_boxes) {
+                    // per axis the gap between the boxes and their farthest extent; the pair rule's own
+                    // operations on them bound every pair's d2 from below and from above (rounding is monotone)
+                    double gap[3], far[3];
+                    for (int a = 0; a < 3; ++a) {
+                        const double alo = unordered(~boxes[(size_t)6 * c + a]), ahi = unordered(boxes[(size_t)6 * c + 3 + a]);
+                        const double blo = unordered(~boxes[(size_t)6 * nb + a]), bhi = unordered(boxes[(size_t)6 * nb + 3 + a]);
+                        gap[a] = fmax(0.0, fmax(blo - ahi, alo - bhi));
+                        far[a] = fmax(bhi - alo, ahi - blo);
+                    }
+                    if ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2] > b2) cls = 0;
+                    else if ((far[0] * far[0] + far[1] * far[1]) + far[2] * far[2] <= b2) cls = 2;
+                }
+            }
+        }
+    }
+    // all friends: united by the cell's first chunk alone
+    unsigned long long direct = __ballot(cls == 2), test = __ballot(cls == 1);
+    if (s != 0) direct = 0ull;
+    while (direct) {
+        const int l = __ffsll((long long)direct) - 1;
+        direct &= direct - 1;
+        const uint32_t b = __shfl(nb, l);
+        if (lane == 0) unite(parent, rep_a, idx[cell_start[b]]);
+    }
+    while (test) {
+        const int l = __ffsll((long long)test) - 1;
+        test &= test - 1;
+        const uint32_t b = __shfl(nb, l);
+        const uint32_t rep_b = idx[cell_start[b]];
+        uint32_t same = 0;
+        if (lane == 0) same = find_root_halving(parent, rep_a) == find_root_halving(parent, rep_b);
+        if (__shfl(same, 0)) continue;
+        const uint32_t b0 = cell_start[b], b1 = cell_start[b + 1];
+        bool hit = false;
+        for (uint32_t a = a0; a < a1 && !hit; a += kWave) {
+            const bool valid = a + lane < a1;
+            const float4 pa = spos[valid ? a + lane : a];
+            for (uint32_t j = b0; j < b1; ++j) {
+                const float4 pb = spos[j];
+                if (__ballot(valid && friends(pa, pb, b2))) {
+                    hit = true;
+                    break;
+                }
+            }
+        }
+        if (hit && lane == 0) unite(parent, rep_a, rep_b);
+    }
+}
+
+// ---- labels, component sizes ----------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void fof_label_kernel(const FofInfo *__restrict__ info,
+                                                             const uint32_t *__restrict__ parent, uint32_t n,
+                                                             uint32_t *__restrict__ labels, uint32_t *__restrict__ count) {
+    if (info->status) return;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    uint32_t r = parent[i];
+    if (r != NB_FOF_NONE) r = find_root(parent, (uint32_t)i);
+    labels[i] = r;
+    // the lanes that share the first counted lane's root send one atomic (a large component: most of the wave)
+    const bool counted = r != NB_FOF_NONE;
+    const unsigned long long any = __ballot(counted);
+    if (!any) return;
+    const uint32_t r0 = __shfl(r, __ffsll((long long)any) - 1);
+    const unsigned long long same = __ballot(counted && r == r0);
+    if (counted && r != r0) atomicAdd(&count[r], 1u);
+    if (threadIdx.x % kWave == (uint32_t)(__ffsll((long long)same) - 1)) atomicAdd(&count[r0], (uint32_t)__popcll(same));
+}
+
+// flags[i] = 1 for the root of a catalogued component; the integer stats
+__global__ __launch_bounds__(kThreads) void fof_roots_kernel(FofInfo *__restrict__ info,
+                                                             const uint32_t *__restrict__ labels,
+                                                             const uint32_t *__restrict__ count, uint32_t n,
+                                                             uint32_t min_members, uint32_t *__restrict__ flags) {
+    if (info->status) return;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    const bool root = i < n && labels[i] == (uint32_t)i;
+    const uint32_t cnt = root ? count[i] : 0u;
+    const bool listed = root && cnt >= min_members;
+    if (i < n) flags[i] = listed;
+    // one lane per wave sends the wave's share: integers, so the order is irrelevant
+    const unsigned long long roots = __ballot(root);
+    if (!roots) return;
+    unsigned long long bodies = listed ? cnt : 0u;
+    unsigned long long largest = root ? ((unsigned long long)cnt << 32) | (uint32_t)~(uint32_t)i : 0ull;
+    for (int o = 32; o > 0; o >>= 1) {
+        bodies += __shfl_xor(bodies, o);
+        largest = std::max(largest, (unsigned long long)__shfl_xor(largest, o));
+    }
+    if (threadIdx.x % kWave == 0) {
+        atomicAdd(&info->components, (uint32_t)__popcll(roots));
+        if (bodies) atomicAdd(&info->grouped_bodies, bodies);
+        atomicMax(&info->largest, largest);
+    }
+}
+
+// the key past the last row and the passes of the sort by row
+__global__ void fof_rows_plan_kernel(FofInfo *__restrict__ info, uint32_t capacity) {
+    if (info->status) return;
+    info->rows = std::min(info->groups, capacity);
+    info->passes[1] = std::max(1u, (bits_of(info->rows) + 7) / 8);
+}
+
+// row_of[i] = the row of root i (NB_FOF_NONE for every other body); label and count of the rows below `rows`
+__global__ __launch_bounds__(kThreads) void fof_rows_kernel(const FofInfo *__restrict__ info,
+                                                            const uint32_t *__restrict__ flags,
+                                                            const uint32_t *__restrict__ excl,
+                                                            const uint32_t *__restrict__ block_tot,
+                                                            const uint32_t *__restrict__ count, uint32_t n,
+                                                            uint32_t *__restrict__ row_of,
+                                                            nb_fof_group *__restrict__ rows) {
+    if (info->status) return;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    uint32_t row = NB_FOF_NONE;
+    if (flags[i]) {
+        row = scanned(excl, block_tot, i);
+        if (rows && row < info->rows) {
+            rows[row].label = (uint32_t)i;
+            rows[row].count = count[i];
+        }
+    }
+    row_of[i] = row;
+}
+
+// group_of, and (keys non-null) the key of the sort by row: the row, or `rows` for a body of none below it
+__global__ __launch_bounds__(kThreads) void fof_group_of_kernel(const FofInfo *__restrict__ info,
+                                                                const uint32_t *__restrict__ labels,
+                                                                const uint32_t *__restrict__ row_of, uint32_t n,
+                                                                uint32_t *__restrict__ group_of,
+                                                                unsigned long long *__restrict__ keys) {
+    if (info->status) return;
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t label = labels[i], row = label == NB_FOF_NONE ? NB_FOF_NONE : row_of[label];
+    group_of[i] = row;
+    if (keys) keys[i] = row < info->rows ? row : info->rows;
+}
+
+// ---- sums -----------------------------------------------------------------------------------------
+// row_start[r] = the first sorted position of row r, row_start[rows] = the bodies of all rows
+__global__ __launch_bounds__(kThreads) void fof_row_start_kernel(const FofInfo *__restrict__ info,
+                                                                 const unsigned long long *__restrict__ k0,
+                                                                 const unsigned long long *__restrict__ k1, uint32_t n,
+                                                                 uint32_t *__restrict__ row_start) {
+    if (info->status) return;
+    const size_t p = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= n) return;
+    const unsigned long long *keys = info->passes[1] & 1 ? k1 : k0;
+    const unsigned long long key = keys[p], rows = info->rows;
+    if (key < rows) {
+        if (p == 0 || keys[p - 1] != key) row_start[key] = (uint32_t)p;
+        if (p + 1 == n || keys[p + 1] >= rows) row_start[rows] = (uint32_t)(p + 1);
+    }
+}
+
+// the terms of a member
+__device__ inline void terms(float4 p, float4 v, double (&t)[kTerms]) {
+#pragma clang fp contract(off)
+    const double m = p.w, x = p.x, y = p.y, z = p.z, vx = v.x, vy = v.y, vz = v.z;
+    t[0] = m;
+    t[1] = m * x;
+    t[2] = m * y;
+    t[3] = m * z;
+    t[4] = m * vx;
+    t[5] = m * vy;
+    t[6] = m * vz;
+    t[7] = m * ((x * x + y * y) + z * z);
+    t[8] = m * ((vx * vx + vy * vy) + vz * vz);
+}
+
+// the first run slot of row r: rows before it hold at most start / 64 + r runs
+__device__ inline size_t run_slot(uint32_t start, uint32_t r) { return (size_t)start / kWave + r; }
+
+// One wave per chunk of a row's list: every run of 64 members (from the row's start) through the butterfly
+// into its slot.
+__global__ __launch_bounds__(kWave) void fof_sum_kernel(const FofInfo *__restrict__ info,
+                                                        const float4 *__restrict__ posm,
+                                                        const float4 *__restrict__ vel,
+                                                        const uint32_t *__restrict__ i0p,
+                                                        const uint32_t *__restrict__ i1p,
+                                                        const uint32_t *__restrict__ row_start, uint32_t len,
+                                                        double *__restrict__ runs) {
+    if (info->status) return;
+    const uint32_t lane = threadIdx.x;
+    uint32_t r, s, a0, a1;
+    if (!item_chunk(row_start, info->rows, len, blockIdx.x, &r, &s, &a0, &a1)) return;
+    const uint32_t *idx = info->passes[1] & 1 ? i1p : i0p;
+    const uint32_t start = row_start[r];
+    for (uint32_t a = a0; a < a1; a += kWave) {  // (len is a multiple of 64: a - start too)
+        double t[kTerms];
+        for (uint32_t f = 0; f < kTerms; ++f) t[f] = 0.0;
+        if (a + lane < a1) {
+            const uint32_t body = idx[a + lane];
+            terms(posm[body], vel[body], t);
+        }
+        for (uint32_t f = 0; f < kTerms; ++f) t[f] = wave_sum(t[f]);
+        if (lane < kTerms) {
+            double mine = t[0];
+            for (uint32_t f = 1; f < kTerms; ++f) mine = lane == f ? t[f] : mine;
+            runs[(run_slot(start, r) + (a - start) / kWave) * kTerms + lane] = mine;
+        }
+    }
+}
+
+// 16 lanes per row, lane f < 9 adds term f of the row's runs in order
+__global__ __launch_bounds__(kThreads) void fof_combine_kernel(const FofInfo *__restrict__ info,
+                                                               const uint32_t *__restrict__ row_start,
+                                                               const double *__restrict__ runs,
+                                                               nb_fof_group *__restrict__ rows) {
+    if (info->status) return;
+    const size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t f = (uint32_t)(g % kRowLanes);
+    const size_t r = g / kRowLanes;
+    if (r >= info->rows || f >= kTerms) return;
+    const uint32_t start = row_start[r], count = row_start[r + 1] - start;
+    const double *p = runs + run_slot(start, (uint32_t)r) * kTerms + f;
+    double sum = 0.0;
+    for (uint32_t q = 0; q < (count + kWave - 1) / kWave; ++q) sum += p[(size_t)q * kTerms];
+    (&rows[r].mass)[f] = sum;
+}
+
+}  // namespace
+
+static_assert(sizeof(nb_fof_group) == 8 + 8 * kTerms && offsetof(nb_fof_group, mass) == 8, "nine doubles after the header");
+
+struct FofWork : Workspace {  // (all but the last two grow to the largest call so far)
+    DeviceBuf<unsigned long long> keys[2];  // [n] each: the sorts' two sides
+    DeviceBuf<uint32_t> idx[2];             // [n] each
+    DeviceBuf<uint32_t> hist;               // [256][chunks], then the 256 digit totals
+    DeviceBuf<double> slabs;                // [bounds blocks][kBoundFields]
+    DeviceBuf<uint32_t> flags, excl;        // [n]: what a scan reads and writes
+    DeviceBuf<uint32_t> block_tot;          // [scan blocks + 1]: the blocks' sums, then the sum of all
+    DeviceBuf<unsigned long long> cell_key; // [n]
+    DeviceBuf<uint32_t> cell_start;         // [n + 1]
+    DeviceBuf<uint32_t> boxes;              // [n][6]
+    DeviceBuf<float4> spos;                 // [n]: positions in sorted order
+    DeviceBuf<uint32_t> parent, labels, count, row_of, group_of;  // [n]
+    DeviceBuf<uint32_t> row_start;          // [rows possible + 1]
+    DeviceBuf<double> runs;                 // [run slots][kTerms]
+    DeviceBuf<nb_fof_group> rows;           // [rows possible]
+    PinnedBuf<uint32_t> h_labels, h_group_of;  // [n]: staged, so that a refused call leaves the outputs alone
+    PinnedBuf<nb_fof_group> h_rows;
+    DeviceBuf<FofInfo> info;                // [1]
+    PinnedBuf<FofInfo> h_info;              // [1]
+};
+
+namespace {
+
+template <class B>
+int fof_reserve(B &b, size_t count) {
+    if (b.reserve(std::max<size_t>(1, count)) == hipSuccess) return NB_OK;
+    (void)hipGetLastError();
+    set_error("fof: cannot allocate the workspace (%zu elements)", count);
+    return NB_ERR_ALLOC;
+}
+
+// the stable sort of (keys[0], identity) on the bits info->passes[which] covers; at most max_passes enqueued
+int enqueue_sort(SimBase &sim, FofWork &w, uint32_t which, uint32_t max_passes, uint32_t chunk, uint32_t sort_blocks) {
+    const uint32_t n = sim.n;
+    uint32_t *totals = w.hist + (size_t)kRadix * sort_blocks;
+    for (uint32_t pass = 0; pass < max_passes; ++pass) {
+        hipLaunchKernelGGL(fof_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.info, which, pass,
+                           w.keys[0], w.keys[1], n, chunk, w.hist);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream, w.info, which, pass,
+                           w.hist, sort_blocks, totals);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.info, which, pass,
+                           w.keys[0], w.keys[1], w.idx[0], w.idx[1], n, chunk, w.hist, totals);
+        NB_HIP_TRY(hipGetLastError());
+    }
+    return NB_OK;
+}
+
+int enqueue_scan(SimBase &sim, FofWork &w, uint32_t scan_blocks, uint32_t *total) {
+    hipLaunchKernelGGL(fof_scan_local_kernel, dim3(scan_blocks), dim3(kScanThreads), 0, sim.stream, w.info, w.flags,
+                       sim.n, w.excl, w.block_tot);
+    NB_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fof_scan_blocks_kernel, dim3(1), dim3(kScanThreads), 0, sim.stream, w.info, w.block_tot,
+                       scan_blocks, total);
+    NB_HIP_TRY(hipGetLastError());
+    return NB_OK;
+}
+
+}  // namespace
+
+int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+            size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = analysis_begin(sim, "fof")) return rc;
+    if (!groups) group_capacity = 0;
+    if (!labels && !group_of && !groups && !stats) {  // nothing to measure
+        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+        return sim.diag_status();
+    }
+    const uint32_t n = sim.n;
+    const double b2 = params.link * params.link;  // (positive and finite: fof_check_params)
+    const double h = (params.link / std::sqrt(3.0)) * (1.0 - 0x1p-20);
+    const uint32_t len = (uint32_t)sim.fof_chunk_len, use_boxes = (uint32_t)sim.fof_cell_boxes;
+    // the most rows there can be, and those the caller has room for
+    const uint32_t rows_cap = (uint32_t)std::min<size_t>(group_capacity, n / params.min_members);
+    const unsigned long long union_items = (unsigned long long)n / len + n + 1;
+    const unsigned long long sum_items = (unsigned long long)n / len + rows_cap + 1;
+    if (union_items > 0x7fffffffull) {
+        set_error("fof: %u bodies are more than one call takes", n);
+        return NB_ERR_UNSUPPORTED;
+    }
+    FofWork *work = nullptr;
+    if (int rc = workspace(sim, kWorkFof, &work, [](FofWork &f) {
+            if (f.info.reserve(1) != hipSuccess || f.h_info.reserve(1) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("fof: cannot allocate the result workspace");
+                return NB_ERR_ALLOC;
+            }
+            return NB_OK;
+        }))
+        return rc;
+    FofWork &w = *work;
+    FofInfo &res = *static_cast<FofInfo *>(w.h_info);
+    std::memset(&res, 0, sizeof res);
+    res.h = h;  // (largest = 0: count 0, label NB_FOF_NONE)
+
+    if (n > 0) {
+        const uint32_t blocks = (n + kThreads - 1) / kThreads;
+        const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
+        const uint32_t chunk = std::max(256u, ((n + kSortBlocks - 1) / kSortBlocks + kWave - 1) / kWave * kWave);
+        const uint32_t sort_blocks = (n + chunk - 1) / chunk;
+        const size_t run_slots = (size_t)n / kWave + rows_cap + 1;
+        for (int s = 0; s < 2; ++s) {
+            if (int rc = fof_reserve(w.keys[s], n)) return rc;
+            if (int rc = fof_reserve(w.idx[s], n)) return rc;
+        }
+        if (int rc = fof_reserve(w.hist, (size_t)kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = fof_reserve(w.slabs, (size_t)kBoundFields * blocks)) return rc;
+        if (int rc = fof_reserve(w.flags, n)) return rc;
+        if (int rc = fof_reserve(w.excl, n)) return rc;
+        if (int rc = fof_reserve(w.block_tot, (size_t)scan_blocks + 1)) return rc;
+        if (int rc = fof_reserve(w.cell_key, n)) return rc;
+        if (int rc = fof_reserve(w.cell_start, (size_t)n + 1)) return rc;
+        if (int rc = fof_reserve(w.boxes, (size_t)6 * n)) return rc;
+        if (int rc = fof_reserve(w.spos, n)) return rc;
+        if (int rc = fof_reserve(w.parent, n)) return rc;
+        if (int rc = fof_reserve(w.labels, n)) return rc;
+        if (int rc = fof_reserve(w.count, n)) return rc;
+        if (int rc = fof_reserve(w.row_of, n)) return rc;
+        if (int rc = fof_reserve(w.group_of, n)) return rc;
+        if (labels)
+            if (int rc = fof_reserve(w.h_labels, n)) return rc;
+        if (group_of)
+            if (int rc = fof_reserve(w.h_group_of, n)) return rc;
+        if (rows_cap > 0) {
+            if (int rc = fof_reserve(w.row_start, (size_t)rows_cap + 1)) return rc;
+            if (int rc = fof_reserve(w.runs, run_slots * kTerms)) return rc;
+            if (int rc = fof_reserve(w.rows, rows_cap)) return rc;
+            if (int rc = fof_reserve(w.h_rows, rows_cap)) return rc;
+        }
+
+        const float4 *posm = nullptr, *vel = nullptr;
+        sim.diag_state(&posm, &vel);
+        FofInfo *info = w.info;
+        uint32_t *scan_total = w.block_tot + scan_blocks;
+        hipLaunchKernelGGL(fof_bounds_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_plan_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, blocks, h, info);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, w.keys[0]);
+        NB_HIP_TRY(hipGetLastError());
+        if (int rc = enqueue_sort(sim, w, 0, kMaxPasses, chunk, sort_blocks)) return rc;
+        // the cell table
+        hipLaunchKernelGGL(fof_heads_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0], w.keys[1], n,
+                           w.flags);
+        NB_HIP_TRY(hipGetLastError());
+        if (int rc = enqueue_scan(sim, w, scan_blocks, scan_total)) return rc;
+        hipLaunchKernelGGL(fof_cells_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0], w.keys[1], n,
+                           w.excl, w.block_tot, w.flags, w.cell_key, w.cell_start);
+        NB_HIP_TRY(hipGetLastError());
+        if (use_boxes) NB_HIP_TRY(hipMemsetAsync(w.boxes, 0, sizeof(uint32_t) * 6 * n, sim.stream));
+        hipLaunchKernelGGL(fof_parent_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, posm, w.idx[0], w.idx[1],
+                           n, w.flags, w.cell_start, scan_total, w.spos, w.parent, w.boxes, use_boxes);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_union_kernel, dim3((uint32_t)union_items), dim3(kWave), 0, sim.stream, info, w.cell_key,
+                           w.cell_start, w.boxes, w.idx[0], w.idx[1], w.spos, w.parent, len, b2, use_boxes);
+        NB_HIP_TRY(hipGetLastError());
+        // labels, sizes, rows
+        NB_HIP_TRY(hipMemsetAsync(w.count, 0, sizeof(uint32_t) * n, sim.stream));
+        hipLaunchKernelGGL(fof_label_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.parent, n, w.labels,
+                           w.count);
+        NB_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fof_roots_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.count, n,
+                           params.min_members, w.flags);
+        NB_HIP_TRY(hipGetLastError());
+        if (int rc = enqueue_scan(sim, w, scan_blocks, &info->groups)) return rc;
+        hipLaunchKernelGGL(fof_rows_plan_kernel, dim3(1), dim3(1), 0, sim.stream, info, rows_cap);
+        NB_HIP_TRY(hipGetLastError());
+        nb_fof_group *rows = rows_cap > 0 ? (nb_fof_group *)w.rows : nullptr;
+        hipLaunchKernelGGL(fof_rows_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.flags, w.excl,
+                           w.block_tot, w.count, n, w.row_of, rows);
+        NB_HIP_TRY(hipGetLastError());
+        if (group_of || rows_cap > 0) {
+            hipLaunchKernelGGL(fof_group_of_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.row_of,
+                               n, w.group_of, rows_cap > 0 ? (unsigned long long *)w.keys[0] : nullptr);
+            NB_HIP_TRY(hipGetLastError());
+        }
+        if (rows_cap > 0) {  // the catalogue's sums
+            if (int rc = enqueue_sort(sim, w, 1, (bits_of(rows_cap) + 7) / 8, chunk, sort_blocks)) return rc;
+            hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0],
+                               w.keys[1], n, w.row_start);
+            NB_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm, vel,
+                               w.idx[0], w.idx[1], w.row_start, len, w.runs);
+            NB_HIP_TRY(hipGetLastError());
+            const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
+            hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info, w.row_start,
+                               w.runs, rows);
+            NB_HIP_TRY(hipGetLastError());
+        }
+        NB_HIP_TRY(hipMemcpyAsync(w.h_info, info, sizeof(FofInfo), hipMemcpyDeviceToHost, sim.stream));
+        if (labels)
+            NB_HIP_TRY(hipMemcpyAsync(w.h_labels, w.labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, sim.stream));
+        if (group_of)
+            NB_HIP_TRY(hipMemcpyAsync(w.h_group_of, w.group_of, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, sim.stream));
+        if (rows_cap > 0)
+            NB_HIP_TRY(hipMemcpyAsync(w.h_rows, w.rows, sizeof(nb_fof_group) * rows_cap, hipMemcpyDeviceToHost,
+                                      sim.stream));
+    }
+    NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+    if (int rc = sim.diag_status()) return rc;
+    if (res.status) {
+        set_error("fof: link %g needs more than %u cells on an axis over this state's extent: it is below the "
+                  "resolution of binary32 coordinates there",
+                  params.link, NB_FOF_MAX_CELLS_PER_AXIS);
+        return NB_ERR_INVALID;
+    }
+    if (n > 0) {
+        if (labels) std::memcpy(labels, w.h_labels, sizeof(uint32_t) * n);
+        if (group_of) std::memcpy(group_of, w.h_group_of, sizeof(uint32_t) * n);
+        if (res.rows > 0) std::memcpy(groups, w.h_rows, sizeof(nb_fof_group) * res.rows);
+    }
+    if (stats) {
+        nb_fof_stats o{};
+        o.step_num = sim.step_num;
+        o.n = n;
+        o.nonfinite = n - res.n_ok;
+        o.components = res.components;
+        o.groups = res.groups;
+        o.grouped_bodies = res.grouped_bodies;
+        o.largest_count = (uint32_t)(res.largest >> 32);
+        o.largest_label = ~(uint32_t)res.largest;
+        o.cells[0] = (uint32_t)res.nx;
+        o.cells[1] = (uint32_t)res.ny;
+        o.cells[2] = (uint32_t)res.nz;
+        o.cell_side = h;
+        *stats = o;
+    }
+    return NB_OK;
+}
+
+}  // namespace nb

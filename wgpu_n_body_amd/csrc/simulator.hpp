@@ -14,6 +14,7 @@
 // (src/sims/tree.rs:278-280); here it throws.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -37,6 +38,8 @@ using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and c
 using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
 using MapParams = nb_map_params;          // grid, window, line of sight and centre of a projected map
 using MapStats = nb_map_stats;
+using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sums of a catalogued group
+using FofStats = nb_fof_stats;
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -209,6 +212,42 @@ ProjectedMap projected_map(int (*call)(H *, const nb_map_params *, uint32_t *, d
 }
 }  // namespace detail
 
+// The friends-of-friends groups of a state (no reference counterpart): per body the label (the smallest body
+// index of its group) and the catalogue row (NB_FOF_NONE: none), the catalogue in ascending label order
+struct FofGroups {
+    std::vector<uint32_t> labels, group_of;
+    std::vector<FofGroup> groups;
+    FofStats stats{};
+    // the rows by count, descending, ties by label
+    std::vector<uint32_t> by_size() const {
+        std::vector<uint32_t> o(groups.size());
+        for (size_t i = 0; i < o.size(); ++i) o[i] = (uint32_t)i;
+        std::sort(o.begin(), o.end(), [this](uint32_t a, uint32_t b) {
+            return groups[a].count != groups[b].count ? groups[a].count > groups[b].count : groups[a].label < groups[b].label;
+        });
+        return o;
+    }
+};
+
+namespace detail {
+template <class H>
+FofGroups fof_groups(int (*call)(H *, const nb_fof_params *, uint32_t *, uint32_t *, nb_fof_group *, size_t,
+                                 nb_fof_stats *),
+                     H *h, size_t n, double link, uint32_t min_members, bool labels) {
+    FofGroups g;
+    nb_fof_params p{};
+    p.link = link;
+    p.min_members = min_members;
+    const size_t cap = min_members ? n / min_members : 0;  // the most there can be (the call refuses 0 itself)
+    if (labels) g.labels.resize(n);
+    g.group_of.resize(n);
+    g.groups.resize(cap);
+    check(call(h, &p, labels ? g.labels.data() : nullptr, g.group_of.data(), g.groups.data(), cap, &g.stats));
+    g.groups.resize((size_t)g.stats.groups);
+    return g;
+}
+}  // namespace detail
+
 // A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
 struct Frame {
     uint32_t width = 0, height = 0;
@@ -301,6 +340,10 @@ class Simulator {
     }
     // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
     ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(nb_sim_map, h_, p); }
+    // the friends-of-friends groups of the current state: bodies within `link` are friends
+    FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
+        return detail::fof_groups(nb_sim_fof, h_, sim_params().particle_num, link, min_members, labels);
+    }
     Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
         return detail::field(nb_sim_field, h_, points, flags);
     }
@@ -430,6 +473,11 @@ class OfflineHeadless {
     }
     ProjectedMap projected_map(const MapParams &p) {  // one device only
         return detail::projected_map(nb_runner_map, r_, p);
+    }
+    FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::fof_groups(nb_runner_fof, r_, sp.particle_num, link, min_members, labels);
     }
     Field field(const std::vector<float> &points,  // one device only
                 uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
