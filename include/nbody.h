@@ -713,6 +713,81 @@ int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint3
                nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* k-nearest-neighbour density -- how dense the state is at every body, and    */
+/* the density centre (no reference counterpart)                              */
+/* ------------------------------------------------------------------------- */
+/* For every body of the state nb_sim_read_particles would return: the squared
+ * distance to its k-th nearest neighbour, that neighbour, the mass inside it and
+ * the density of Casertano & Hut (1985) from them; and the density-weighted sums
+ * that give the density centre.  The rule, which DESIGN.md 6i states in full:
+ * binary64 from the binary32 state, one rounding per operation, no contraction:
+ *   counted   a body takes part when its position, mass and velocity are all
+ *             finite (the predicate of nb_sim_diagnostics); c is their number
+ *   distance  d2(i, j) = (dx dx + dy dy) + dz dz with dx = (double)x_i - (double)x_j,
+ *             dy and dz likewise (the expression of nb_sim_fof); finite for
+ *             counted bodies
+ *   order     for a counted body i the other counted bodies in ascending
+ *             (d2(i, j), j): equal d2 are ordered by the smaller body index, the
+ *             index in the order nb_sim_read_particles returns at that moment (a
+ *             TreeSim reorders its bodies at every step)
+ *   per body  for 1 <= k <= NB_KNN_MAX_K and c > k:
+ *             r2[i]      the d2 of the k-th body of that order
+ *             kth[i]     its index
+ *             mass_in[i] the binary64 sum of (double)m_j over the first k - 1 bodies,
+ *                        added in that order from 0 (0 for k = 1)
+ *             density[i] mass_in[i] / (C (r2[i] sqrt(r2[i]))), C = NB_KNN_SPHERE,
+ *                        evaluated as written: sqrt, multiply, multiply, divide
+ *   special   r2[i] == 0 (at least k bodies coincide with i): density[i] = +inf and
+ *             the body is one of `degenerate`;
+ *             a body that is not counted: r2 = NaN, kth = NB_KNN_NONE, mass_in = 0,
+ *             density = 0;
+ *             c <= k: every counted body has r2 = +inf, kth = NB_KNN_NONE, mass_in = 0,
+ *             density = 0; short_of_k = c (0 otherwise), sums 0, no peak
+ *   sums      over the counted bodies with finite, non-zero r2, rho = density[i]:
+ *             rho, rho x, rho y, rho z, rho vx, rho vy, rho vz, rho rho, each term one
+ *             binary64 product of rho and the widened coordinate, added in body order
+ *             in a fixed order (blocks of 256 bodies by a fixed butterfly, the blocks
+ *             then in 16 interleaved groups): two calls return bit-identical doubles,
+ *             each within 1e-10 of its sum of |term| of the binary64 sum
+ *   peak      over the same bodies, those of finite density: peak_density is the
+ *             largest density and peak_index the smallest index that holds it
+ *             (0 and NB_KNN_NONE when there is none)
+ * Everything per body is unique given the state, so r2, kth, mass_in, density, the peak
+ * and every integer of the stats are exact and bit-identical between calls, whatever
+ * order the device's threads ran in.  No float atomics.  The density centre is
+ * sum_rho_x / sum_rho, its velocity sum_rho_v / sum_rho.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.
+ * "knn_span_cells" (nb_sim_set_tuning, 1..8, default 3; speed and testing only): the
+ * octree cells per axis the search opens around a body.  "knn_block_queries" (1, 2
+ * or 4, default 4; speed and testing only): the bodies one block of the search
+ * serves, a wave each.  Neither changes a bit of the result. */
+#define NB_KNN_NONE 0xFFFFFFFFu
+#define NB_KNN_MAX_K 64u
+#define NB_KNN_SPHERE 4.1887902047863909846 /* C = 4 pi / 3, to binary64 0x1.0c152382d7366p+2 */
+
+typedef struct nb_knn_params {
+    uint32_t k;        /* 1 .. NB_KNN_MAX_K */
+    uint32_t flags;    /* 0 */
+    uint64_t reserved; /* 0 */
+} nb_knn_params;
+
+typedef struct nb_knn_stats {
+    uint64_t step_num, n, nonfinite, counted, degenerate, short_of_k;
+    double sum_rho, sum_rho_x[3], sum_rho_v[3], sum_rho2, peak_density;
+    uint32_t peak_index, reserved;
+} nb_knn_stats;
+
+/* The per-body values (n each) and the stats of a simulator's current state.  Every output pointer may be
+ * null: what is not asked for is not copied; a call with none of them synchronises and measures nothing.
+ * The outputs are written only by a call that succeeds.  NB_ERR_INVALID for a null handle or params,
+ * k == 0, k > NB_KNN_MAX_K, unknown flags or reserved != 0 -- all checked before any device call;
+ * NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
+               double *density, nb_knn_stats *stats);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -875,6 +950,10 @@ int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *coun
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of,
                   nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
+/* nb_sim_knn of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
+                  double *density, nb_knn_stats *stats);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -37,6 +37,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
            "FofGroups", "FofStats", "FOF_NONE",
+           "KnnDensity", "KnnStats", "KNN_NONE",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -531,6 +532,89 @@ def _fof_groups(call, handle, n, link, min_members, labels) -> FofGroups:
     return FofGroups(lab, gof, rows[:stats.groups], float(link), mm, stats)
 
 
+KNN_NONE = _lib.NB_KNN_NONE
+
+
+@dataclass(frozen=True)
+class KnnStats:
+    """nb_knn_stats (include/nbody.h "k-nearest-neighbour density")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    counted: int
+    degenerate: int       # counted bodies with at least k others at their own position: density +inf
+    short_of_k: int       # the counted bodies when there are no more than k of them, else 0
+    sum_rho: float
+    sum_rho_x: np.ndarray
+    sum_rho_v: np.ndarray
+    sum_rho2: float
+    peak_density: float
+    peak_index: int
+
+
+@dataclass(frozen=True)
+class KnnDensity:
+    """nb_sim_knn's per-body values and sums (include/nbody.h "k-nearest-neighbour density"; no reference
+    counterpart).  For body i of the state read_particles would return: r2[i] the squared distance to its
+    k-th nearest counted neighbour (ties by the smaller index), kth[i] that neighbour (KNN_NONE: none),
+    mass_in[i] the mass of the k - 1 nearer ones, density[i] = mass_in / (4 pi / 3 r_k^3) (Casertano & Hut
+    1985).  An array that was not asked for is None."""
+    k: int
+    r2: Optional[np.ndarray]
+    kth: Optional[np.ndarray]
+    mass_in: Optional[np.ndarray]
+    density: Optional[np.ndarray]
+    stats: KnnStats
+
+    @property
+    def r_k(self) -> Optional[np.ndarray]:
+        """sqrt(r2): the distance to the k-th neighbour."""
+        return None if self.r2 is None else np.sqrt(self.r2)
+
+    def _per_rho(self, a) -> np.ndarray:
+        s = self.stats.sum_rho
+        return a / s if s != 0.0 else np.full(3, np.nan)
+
+    @property
+    def center(self) -> np.ndarray:
+        """The density centre sum rho x / sum rho (NaN when sum rho is 0)."""
+        return self._per_rho(self.stats.sum_rho_x)
+
+    @property
+    def center_velocity(self) -> np.ndarray:
+        """sum rho v / sum rho (NaN when sum rho is 0)."""
+        return self._per_rho(self.stats.sum_rho_v)
+
+    @property
+    def peak_index(self) -> int:
+        return self.stats.peak_index
+
+    @property
+    def peak_density(self) -> float:
+        return self.stats.peak_density
+
+
+def _knn_stats(st) -> KnnStats:
+    return KnnStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.counted), int(st.degenerate),
+                    int(st.short_of_k), float(st.sum_rho), np.array(st.sum_rho_x[:], dtype=np.float64),
+                    np.array(st.sum_rho_v[:], dtype=np.float64), float(st.sum_rho2), float(st.peak_density),
+                    int(st.peak_index))
+
+
+def _knn_density(call, handle, n, k, density, neighbours) -> KnnDensity:
+    p = _lib.nb_knn_params()
+    kk = int(k)
+    p.k, p.flags, p.reserved = (kk if 0 <= kk <= 0xFFFFFFFF else 0), 0, 0  # (the call refuses 0 itself)
+    r2 = np.empty(n, dtype=np.float64) if neighbours else None
+    kth = np.empty(n, dtype=np.uint32) if neighbours else None
+    mass_in = np.empty(n, dtype=np.float64) if density else None
+    rho = np.empty(n, dtype=np.float64) if density else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    st = _lib.nb_knn_stats()
+    check(call(handle, C.byref(p), ptr(r2), ptr(kth), ptr(mass_in), ptr(rho), C.byref(st)))
+    return KnnDensity(kk, r2, kth, mass_in, rho, _knn_stats(st))
+
+
 @dataclass(frozen=True)
 class Camera:
     """nb_camera (`Camera`, online_renderer.rs:12-20)."""
@@ -850,7 +934,11 @@ class Simulator:
         nbins + 1 radii, or rmin, rmax, nbins and log for radial_edges().  cylindrical: bin by distance
         from `axis` through the centre (a disc's annuli) instead of from the centre.  center: "com" (the
         centre of mass and its velocity P/M, as diagnostics() returns them) or three coordinates, then
-        with `velocity` as the centre's velocity."""
+        with `velocity` as the centre's velocity; "density": the density centre and its velocity of
+        knn_density(6), passed on as explicit values."""
+        if isinstance(center, str) and center == "density":
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
         return _radial_profile(_lib.lib().nb_sim_radial_profile, self._h, edges, nbins, rmin, rmax, log,
                                cylindrical, axis, center, velocity)
 
@@ -872,8 +960,14 @@ class Simulator:
         along `axis` (nb_sim_map).  extent: (x0, x1, y0, y1), the window [x0, x1) x [y0, y1) in the plane
         coordinates of map_frame(axis) about the centre.  center: "com" (the centre of mass and its
         velocity P/M, as diagnostics() returns them) or three coordinates, then with `velocity` (default:
-        at rest).  depth: (lo, hi) keeps the bodies with lo <= h < hi along the line of sight.
+        at rest); "density": the density centre and its velocity of knn_density(6), passed on as explicit
+        values.  depth: (lo, hi) keeps the bodies with lo <= h < hi along the line of sight.
         velocities=False returns the counts and the mass alone."""
+        if isinstance(center, str) and center == "density":
+            if velocity is not None:
+                raise ValueError('center="density" brings its own velocity')
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
         return _projected_map(_lib.lib().nb_sim_map, self._h, width, height, extent, axis, center, velocity, depth,
                               velocities)
 
@@ -884,6 +978,14 @@ class Simulator:
         bodies at every step.  labels=False leaves the per-body labels on the device."""
         return _fof_groups(_lib.lib().nb_sim_fof, self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
+
+    def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
+        """The k-th nearest neighbour of every body of the current state, the mass inside it and the density
+        from them (nb_sim_knn), with the density-weighted sums: .center is the density centre of Casertano &
+        Hut (1985).  The body indices are those of read_particles() now: a TreeSim reorders its bodies at
+        every step.  density=False leaves mass_in and density on the device, neighbours=False r2 and kth."""
+        return _knn_density(_lib.lib().nb_sim_knn, self._h, int(self.sim_params().particle_num), k, density,
+                            neighbours)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
@@ -1075,6 +1177,11 @@ class OfflineHeadless:
         """nb_runner_fof: Simulator.fof_groups of the runner's simulator (one device only)."""
         return _fof_groups(_lib.lib().nb_runner_fof, self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
+
+    def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
+        """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""
+        return _knn_density(_lib.lib().nb_runner_knn, self._h, int(self.sim_params().particle_num), k, density,
+                            neighbours)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

@@ -127,6 +127,18 @@ class nb_fof_stats(C.Structure):
                 ("reserved", C.c_uint32), ("cell_side", C.c_double)]
 
 
+class nb_knn_params(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_knn_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("counted", C.c_uint64),
+                ("degenerate", C.c_uint64), ("short_of_k", C.c_uint64),
+                ("sum_rho", C.c_double), ("sum_rho_x", C.c_double * 3), ("sum_rho_v", C.c_double * 3),
+                ("sum_rho2", C.c_double), ("peak_density", C.c_double),
+                ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # nb_fof_group[] as a numpy record array
 FOF_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
                             ("mv", "<f8", (3,)), ("mr2", "<f8"), ("mv2", "<f8")])
@@ -148,6 +160,7 @@ assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
 assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
+assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -163,6 +176,8 @@ NB_FIELD_MAX_POINTS = 1 << 24
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
+NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_KNN_SPHERE = float("4.1887902047863909846")  # C = 4 pi / 3, the header's literal
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -179,6 +194,7 @@ ABI_SYMBOLS = [
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_sim_fof", "nb_runner_fof",
+    "nb_sim_knn", "nb_runner_knn",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
@@ -254,6 +270,8 @@ def lib() -> C.CDLL:
     L.nb_runner_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
     L.nb_sim_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
     L.nb_runner_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
+    L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
+    L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_map_frame.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_map_edges.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]

@@ -11,6 +11,7 @@
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
+//            [--knn K [--knn-k 6]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -50,6 +51,12 @@
 // default 20).  One line "fof <step> <groups> <grouped_bodies> <largest_count>", then the T largest rows
 // (--fof-top, default 0) as "fof_group <step> <row> <label> <count> <mass> <x> <y> <z>" (%.9e: the mass and the
 // centre of mass).  The time they take is not part of any "Step Duration"; without --fof the output is
+// unchanged.
+//
+// --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
+// every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
+// <peak_density> <peak_index>" (every real %.17g): the density centre and its velocity, the largest density and
+// the body that holds it.  The time it takes is not part of any "Step Duration"; without --knn the output is
 // unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
@@ -209,6 +216,21 @@ static void print_fof(nbody::OfflineHeadless<Sim> &runner, const FofOptions &fo)
     }
 }
 
+struct KnnOptions {
+    int every = 0;
+    uint32_t k = 6;
+};
+
+template <class Sim>
+static void print_knn(nbody::OfflineHeadless<Sim> &runner, const KnnOptions &ko) {
+    const nbody::KnnDensity d = runner.knn_density(ko.k, false, false);
+    const std::array<double, 3> c = d.center(), v = d.center_velocity();
+    std::printf("knn %llu %llu %llu %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u\n",
+                (unsigned long long)d.stats.step_num, (unsigned long long)d.stats.counted,
+                (unsigned long long)d.stats.degenerate, c[0], c[1], c[2], v[0], v[1], v[2], d.stats.peak_density,
+                d.stats.peak_index);
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -246,7 +268,7 @@ template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
-               const RotcurveOptions &rotcurve, const MapOptions &maps, const FofOptions &fof) {
+               const RotcurveOptions &rotcurve, const MapOptions &maps, const FofOptions &fof, const KnnOptions &knn) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -256,6 +278,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
+    if (knn.every > 0) print_knn(runner, knn);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -268,6 +291,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
+        if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -293,6 +317,7 @@ int main(int argc, char **argv) {
     RotcurveOptions rotcurve;
     MapOptions maps;
     FofOptions fof;
+    KnnOptions knn;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -411,6 +436,8 @@ int main(int argc, char **argv) {
         else if (k == "--fof-link") fof.link = std::atof(v.c_str());
         else if (k == "--fof-min") fof.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--fof-top") fof.top = std::atoi(v.c_str());
+        else if (k == "--knn") knn.every = std::atoi(v.c_str());
+        else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--devices") {
             for (size_t a = 0; a <= v.size();) {
                 const size_t b = std::min(v.find(',', a), v.size());
@@ -442,9 +469,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, fof);
+                                        diag_potential, frames, radial, rotcurve, maps, fof, knn);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, fof);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, fof, knn);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -598,6 +598,23 @@ static int fof_check_params(const nb_fof_params *p) {
     return NB_OK;
 }
 
+// nb_sim_knn: everything that can be refused without a device
+static int knn_check_params(const nb_knn_params *p) {
+    if (!p) {
+        set_error("knn: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->k < 1 || p->k > NB_KNN_MAX_K) {
+        set_error("knn: k must be 1..%u (got %u)", NB_KNN_MAX_K, p->k);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved) {
+        set_error("knn: unknown flag bits 0x%x or reserved %llu != 0", p->flags, (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_map_edges / nb_sim_map: the cell size of `cells` cells in [lo, hi), refused unless the edges
 // lo + i * size (i < cells), hi come out strictly ascending
 static int map_cell_size(const char *what, double lo, double hi, uint32_t cells, double *size) {
@@ -879,6 +896,30 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->fof_cell_boxes = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "knn_span_cells")) {  // the neighbour search's, whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 1 || value > 8) {
+            set_error("knn_span_cells: 1..8, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->knn_span_cells = value;
+        return NB_OK;
+    }
+    if (!std::strcmp(key, "knn_block_queries")) {
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value != 1 && value != 2 && value != 4) {
+            set_error("knn_block_queries: 1, 2 or 4, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->knn_block_queries = value;
+        return NB_OK;
+    }
     NB_SIM_CALL(sim, set_tuning(key, value))
 }
 
@@ -1015,6 +1056,12 @@ int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint3
                size_t group_capacity, nb_fof_stats *stats) {
     if (int rc = fof_check_params(params)) return rc;
     NB_SIM_PASS(sim, sim_fof, *params, labels, group_of, groups, group_capacity, stats)
+}
+
+int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in, double *density,
+               nb_knn_stats *stats) {
+    if (int rc = knn_check_params(params)) return rc;
+    NB_SIM_PASS(sim, sim_knn, *params, r2, kth, mass_in, density, stats)
 }
 
 int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
@@ -1278,6 +1325,14 @@ int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labe
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "fof")) return rc;
     return nb_sim_fof(runner->sim, params, labels, group_of, groups, group_capacity, stats);
+}
+
+int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
+                  double *density, nb_knn_stats *stats) {
+    if (int rc = knn_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "knn")) return rc;
+    return nb_sim_knn(runner->sim, params, r2, kth, mass_in, density, stats);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

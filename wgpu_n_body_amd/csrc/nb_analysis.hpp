@@ -1,5 +1,5 @@
 // nb_analysis.hpp -- what the analysis passes over a simulator's current state share (nb_diag.hip,
-// nb_render.hip, nb_radial.hip, nb_field.hip, nb_map.hip, nb_fof.hip):
+// nb_render.hip, nb_radial.hip, nb_field.hip, nb_map.hip, nb_fof.hip, nb_knn.hip):
 //   host    -- the buffers a workspace is made of, the workspace of a pass behind its slot of SimBase, the
 //              preamble of every entry point, and the centre a pass over no bodies reports;
 //   device  -- the predicate that decides which bodies count, the fixed-order reductions that make the sums

@@ -13,7 +13,7 @@ namespace nb {
 struct Workspace {
     virtual ~Workspace() = default;
 };
-enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkSlots };
+enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -126,6 +126,8 @@ class SimBase {
     int map_segment_len = 4096;  // "map_segment_len": bodies of a tile summed by one block of nb_sim_map
     int fof_chunk_len = 1024;    // "fof_chunk_len": bodies of a cell or a catalogue row per work item of nb_sim_fof
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
+    int knn_span_cells = 3;      // "knn_span_cells": octree cells per axis the search of nb_sim_knn opens around a body
+    int knn_block_queries = 4;   // "knn_block_queries": bodies (a wave each) per block of that search
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle
@@ -160,6 +162,9 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
 // nb_fof.hip: nb_sim_fof behind the handle (arguments already checked by fof_check_params, nb_abi.cpp)
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
             size_t group_capacity, nb_fof_stats *stats);
+// nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
+int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
+            nb_knn_stats *stats);
 // nb_abi.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
 // rule of include/nbody.h); false for an axis without a finite, non-zero length
 bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]);

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -40,6 +41,7 @@ using MapParams = nb_map_params;          // grid, window, line of sight and cen
 using MapStats = nb_map_stats;
 using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sums of a catalogued group
 using FofStats = nb_fof_stats;
+using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -248,6 +250,46 @@ FofGroups fof_groups(int (*call)(H *, const nb_fof_params *, uint32_t *, uint32_
 }
 }  // namespace detail
 
+// The k-th nearest neighbour of every body of a state, the mass inside it and the density from them (no
+// reference counterpart); a vector that was not asked for is empty
+struct KnnDensity {
+    uint32_t k = 0;
+    std::vector<double> r2, mass_in, density;
+    std::vector<uint32_t> kth;  // NB_KNN_NONE: none
+    KnnStats stats{};
+    // the density centre sum rho x / sum rho and its velocity (NaN when sum rho is 0)
+    std::array<double, 3> center() const { return per_rho(stats.sum_rho_x); }
+    std::array<double, 3> center_velocity() const { return per_rho(stats.sum_rho_v); }
+
+   private:
+    std::array<double, 3> per_rho(const double (&s)[3]) const {
+        const double nan = std::numeric_limits<double>::quiet_NaN(), w = stats.sum_rho;
+        if (w == 0.0) return {nan, nan, nan};
+        return {s[0] / w, s[1] / w, s[2] / w};
+    }
+};
+
+namespace detail {
+template <class H>
+KnnDensity knn_density(int (*call)(H *, const nb_knn_params *, double *, uint32_t *, double *, double *, nb_knn_stats *),
+                       H *h, size_t n, uint32_t k, bool density, bool neighbours) {
+    KnnDensity d;
+    nb_knn_params p{};
+    p.k = d.k = k;
+    if (neighbours) {
+        d.r2.resize(n);
+        d.kth.resize(n);
+    }
+    if (density) {
+        d.mass_in.resize(n);
+        d.density.resize(n);
+    }
+    check(call(h, &p, neighbours ? d.r2.data() : nullptr, neighbours ? d.kth.data() : nullptr,
+               density ? d.mass_in.data() : nullptr, density ? d.density.data() : nullptr, &d.stats));
+    return d;
+}
+}  // namespace detail
+
 // A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
 struct Frame {
     uint32_t width = 0, height = 0;
@@ -343,6 +385,10 @@ class Simulator {
     // the friends-of-friends groups of the current state: bodies within `link` are friends
     FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
         return detail::fof_groups(nb_sim_fof, h_, sim_params().particle_num, link, min_members, labels);
+    }
+    // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
+    KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
+        return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
     }
     Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
         return detail::field(nb_sim_field, h_, points, flags);
@@ -478,6 +524,11 @@ class OfflineHeadless {
         SimParams sp{};
         check(nb_runner_sim_params(r_, &sp));
         return detail::fof_groups(nb_runner_fof, r_, sp.particle_num, link, min_members, labels);
+    }
+    KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::knn_density(nb_runner_knn, r_, sp.particle_num, k, density, neighbours);
     }
     Field field(const std::vector<float> &points,  // one device only
                 uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
