@@ -94,14 +94,19 @@ def knn_vectorised(pos, mass, vel, k: int, queries=None, rows: int = 256) -> Knn
     m = mass[idx].astype(np.float64)
     whole = queries is None
     qs = idx if whole else np.array([q for q in np.asarray(queries, dtype=np.int64) if ok[q]], dtype=np.int64)
-    cols = np.broadcast_to(idx, (rows, idx.size))
     for lo in range(0, qs.size, rows):
         q = qs[lo:lo + rows]
         xq = x[place[q]]
         dx, dy, dz = (xq[:, None, a] - x[None, :, a] for a in range(3))
         d2 = (dx * dx + dy * dy) + dz * dz
         d2[np.arange(q.size), place[q]] = np.inf  # the body itself is not in its order (the others are finite)
-        order = np.lexsort((cols[:q.size], d2), axis=-1)[:, :k]
+        # the first k of the order (d2, index): only the bodies at or inside a row's k-th smallest d2 can be among
+        # them, so those alone are sorted (ascending position is ascending index)
+        kd = np.partition(d2, k - 1, axis=-1)[:, k - 1]
+        order = np.empty((q.size, k), dtype=np.int64)
+        for t, row in enumerate(d2):
+            cand = np.nonzero(row <= kd[t])[0]
+            order[t] = cand[np.lexsort((cand, row[cand]))[:k]]
         r = np.arange(q.size)
         ref.r2[q] = d2[r, order[:, k - 1]]
         ref.kth[q] = idx[order[:, k - 1]]

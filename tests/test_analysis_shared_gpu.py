@@ -1,6 +1,6 @@
-"""What the five analysis passes share (csrc/nb_analysis.hpp: the workspace slots of a simulator, the moments
-pass behind every centre of mass, the buffers that grow) must not let one pass leak into another: every entry
-point returns the same bytes whichever pass touched the simulator first and whatever ran in between.  And the
+"""What the seven analysis passes share (csrc/nb_analysis.hpp: the workspace slots of a simulator, the moments
+pass behind every centre of mass, the buffers that grow; csrc/nb_analysis_sort.hpp: the sort of the three that sort
+their bodies) must not let one pass leak into another: every entry point returns the same bytes whichever pass touched the simulator first and whatever ran in between.  And the
 one state the centre rule treats on the host, a simulator without bodies, for the two passes whose suites do
 not cover it.  `-m gpu`."""
 import dataclasses
@@ -44,6 +44,8 @@ def _passes(pts):
         "radial": lambda s: s.radial_profile(nbins=7, rmin=0.02, rmax=1.5),
         "field": lambda s: s.field(pts),
         "map": lambda s: s.projected_map(17, 33, extent=(-1.0, 1.0, -1.0, 1.0)),
+        "fof": lambda s: s.fof_groups(0.02, min_members=2),
+        "knn": lambda s: s.knn_density(6),
     }
 
 

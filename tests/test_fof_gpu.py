@@ -203,6 +203,23 @@ def test_multi_pass_sort(gpu):
     sim.destroy()
 
 
+def test_sort_chunks_beyond_the_other_suites(gpu):
+    """524,289 bodies, uniform in a cube, over 200^3 cells: 1,639 sort chunks of 320 bodies, the last of one body,
+    so a thread of the shared sort's scan (csrc/nb_analysis_sort.hpp) owns two chunks; three of the eight enqueued
+    passes run, the rest are gated off by the plan."""
+    nb = gpu
+    n = 524289
+    state = make_state("uniform", n, seed=5)
+    sim = _sim(nb, "naive", state)
+    ext = state[:, 0:3].max(axis=0) - state[:, 0:3].min(axis=0)
+    link = 0.7 * float((ext.prod() / n) ** (1.0 / 3.0))
+    g = _fof(sim, link, 2)
+    sim.destroy()
+    assert 1 << 16 < int(g.st.cells[0]) * int(g.st.cells[1]) * int(g.st.cells[2]) < 1 << 24  # three passes
+    _check(g, F.fof_grid(state, link, 2))
+    assert 100 < g.st.groups and g.st.components < n
+
+
 def test_tuning_keys_do_not_change_a_bit(gpu):
     """One cell of 5,000 bodies beside scattered ones: the shortest chunks, and no boxes, give the default's bytes."""
     nb = gpu
@@ -311,6 +328,9 @@ def test_refusals(gpu):
     assert bytes(g.st) == bytes(_lib.nb_fof_stats())
     ok = _fof(sim, 0.1, 1)  # the simulator stays usable, and a link the grid can carry goes through
     _check(ok, F.fof_brute(far, 0.1, 1))
+    fresh = _sim(nb, "naive", far)  # ... with the bytes of a simulator that never refused: the refusal left nothing
+    assert _fof(fresh, 0.1, 1).bytes == ok.bytes
+    fresh.destroy()
     with pytest.raises(nb.NBodyError) as ex:
         sim.fof_groups(0.01)
     assert ex.value.code == _lib.NB_ERR_INVALID

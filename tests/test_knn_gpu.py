@@ -194,6 +194,32 @@ def test_large_case_against_a_sample(gpu, kind, k):
     assert np.all(g.kth < n) and np.all(g.kth != np.arange(n)) and np.all(np.isfinite(g.density[g.r2 > 0]))
 
 
+def test_sort_chunks_beyond_the_other_suites(gpu):
+    """524,289 bodies, k = 6: 1,639 sort chunks of 320 bodies, the last of one body, so a thread of the shared sort's
+    scan (csrc/nb_analysis_sort.hpp) owns two chunks, in all eight passes.  As the large case above: the restatement
+    for 128 seeded bodies, the 32 of smallest and of largest device r2 and the peak's, each against all bodies; the
+    sums in full from the device's own density by a binary64 host sum."""
+    nb = gpu
+    n, k = 524289, 6
+    sim, state = _prepared(nb, "naive", make_state("spherical", n, seed=11))
+    g = _knn(sim, k)
+    sim.destroy()
+    order = np.argsort(g.r2, kind="stable")
+    sample = np.unique(np.concatenate([np.random.default_rng(k).choice(n, 128, replace=False), order[:32], order[-32:],
+                                       [g.st.peak_index]]))
+    assert 128 <= sample.size <= 193 and g.st.peak_index in sample
+    ref = K.knn_vectorised(*K.split(state), k, queries=sample, rows=48)
+    _check_bodies(g, ref, sample)
+    assert (g.st.n, g.st.counted, g.st.nonfinite, g.st.short_of_k) == (n, n, 0, 0)
+    assert g.st.degenerate == np.count_nonzero(g.r2 == 0.0)
+    full = K.KnnRef(k, g.r2, g.kth, g.mass_in, g.density, n, 0, n)
+    K.finish(full, state[:, 0:3], state[:, 3:6], np.ones(n, bool), True)
+    err = np.abs(_sums_of(g.st) - full.sums)
+    assert np.all(err <= TOL * full.sums_abs), (err, full.sums_abs)
+    assert (g.st.peak_density, g.st.peak_index) == (full.peak_density, full.peak_index)
+    assert np.all(g.kth < n) and np.all(g.kth != np.arange(n)) and np.all(np.isfinite(g.density[g.r2 > 0]))
+
+
 def test_tuning_keys_do_not_change_a_bit(gpu):
     """A crowded cell beside scattered bodies: every span and every cut of the work gives the default's bytes."""
     nb = gpu

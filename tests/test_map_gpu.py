@@ -229,6 +229,22 @@ def test_concentrated_states(gpu, mode, n, segment):
         assert int(tile.sum()) >= n // 2 > 2 * (segment or 4096)
 
 
+@pytest.mark.parametrize("n", [262145, 524289])
+def test_sort_chunks_beyond_the_other_suites(gpu, n):
+    """The shared sort (csrc/nb_analysis_sort.hpp) where no other test takes it: 262,145 bodies are 1,025 chunks of
+    256, the last of one body, and the first size at which a thread of the scan owns two chunks; 524,289 are 1,639
+    chunks of 320.  Uniform bodies, 256 x 256 cells (two passes), velocities on, a window that cuts."""
+    nb = gpu
+    state = make_state("uniform", n, seed=13)
+    sim = _sim(nb, "naive", state)
+    extent, axis = (-0.5, 0.5, -0.5, 0.5), (0.0, 0.0, 1.0)
+    m = _map(sim, 256, 256, extent, axis, (0.0, 0.0, 0.0))
+    sim.destroy()
+    worst = _check(m, M.map64(state, 256, 256, extent, axis=axis))
+    print(f"binned {m.st.binned_count} outside {m.st.outside_count} worst error / bound {worst / TOL:.3g}")
+    assert 0 < m.st.binned_count and 0 < m.st.outside_count
+
+
 def test_segment_length_key_is_checked(gpu):
     nb = gpu
     sim = _sim(nb, "naive", make_state("uniform", 64, seed=1))

@@ -7,6 +7,8 @@
 // The device part only adds, takes maxima and divides: there is nothing to contract, so it is the same
 // arithmetic in the units built with -ffp-contract=off and in those built without.  The terms that are summed
 // stay in their units, whose contraction setting is part of their specification.
+// What only the passes that sort their bodies by a spatial key share (nb_map.hip, nb_fof.hip, nb_knn.hip) -- the
+// radix sort and, for the last two, the bounds of the counted bodies -- is in nb_analysis_sort.hpp, on top of this.
 #pragma once
 
 #include <cmath>

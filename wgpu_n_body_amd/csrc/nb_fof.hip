@@ -4,18 +4,17 @@
 // Bodies i != j are friends iff d2 <= link * link in binary64; a group is a connected component of that
 // graph, its label the smallest body index in it.  The graph is fixed by the state, so the partition is
 // unique and everything integer here is exact, whatever order the threads ran in.
-//   bounds  -- one thread per body over the float4 SoA state (SimBase::diag_state): the per-axis minimum and
-//              maximum of the counted bodies (body_ok) and their number, through per-block slabs (block_row,
-//              nb_analysis.hpp); one block finishes them into the plan on the device: the grid's origin, the
-//              cells per axis of side h = (link / sqrt(3)) (1 - 2^-20), the key bits in use -- or the refusal
-//              of a state that needs more than 2^21 cells on an axis.  Every later kernel reads the plan;
-//              after a refusal they all return at once.  No host round trip;
+//   bounds  -- the per-axis minimum and maximum of the counted bodies (body_ok) and their number over the float4
+//              SoA state (SimBase::diag_state), by the bounds pass of nb_analysis_sort.hpp; the one block that
+//              finishes them makes the plan on the device: the grid's origin, the cells per axis of side
+//              h = (link / sqrt(3)) (1 - 2^-20), the key bits in use -- or the refusal of a state that needs
+//              more than 2^21 cells on an axis.  Every later kernel reads the plan; after a refusal they all
+//              return at once.  No host round trip;
 //   key     -- one 64-bit linear cell key per body, (cz ny + cy) nx + cx, or the key past the last cell
 //              for a body that does not count;
-//   sort    -- a stable LSD radix sort of (key, body index), 8 bits a pass: count / scan / scatter, one
-//              wave per chunk of bodies, the rank inside a chunk by wave ballots in body order (the design
-//              of nb_map.hip's sort on 64-bit keys).  Eight passes are enqueued, those the plan does not need
-//              return at once.  A cell's bodies end up consecutive and in body order;
+//   sort    -- the stable sort of nb_analysis_sort.hpp on (key, body index).  Eight passes are enqueued, those
+//              the plan does not need (passes[0]; all of them after a refusal) return at once, and the sorted
+//              arrays are on side passes[0] & 1.  A cell's bodies end up consecutive and in body order;
 //   cells   -- the occupied cells (key, start) from neighbouring keys and a scan, every body's position
 //              gathered in sorted order, parent[i] = the first body of i's cell -- all bodies of a cell are
 //              friends without a test (the cell's diagonal is below link) -- and the cells' bounding boxes by
@@ -42,6 +41,7 @@
 #include <cstring>
 
 #include "nb_analysis.hpp"
+#include "nb_analysis_sort.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -50,12 +50,7 @@ namespace nb {
 namespace {
 
 constexpr uint32_t kThreads = kBlock;
-constexpr uint32_t kRadix = 256;         // 8 bits of the key per sort pass
-constexpr uint32_t kSortBlocks = 2048;   // at most this many chunks (one wave each) per sort pass
-constexpr uint32_t kScanThreads = 1024;  // the scans: elements per block of the local scan
 constexpr uint32_t kMaxPasses = 8;       // a 64-bit key
-constexpr uint32_t kBoundFields = 8, kBoundLive = 7;  // max(-x, -y, -z, x, y, z), counted bodies
-constexpr uint32_t kBoundMax = 0x3f;
 constexpr uint32_t kTerms = 9;           // the sums of a catalogue row
 constexpr uint32_t kRowLanes = 16;       // lanes per row of the combine kernel
 constexpr uint32_t kNeighbours = 62;     // forward neighbours within +-2 cells per axis: (5^3 - 1) / 2
@@ -93,61 +88,19 @@ __device__ inline float unordered(uint32_t e) {
     return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
 }
 
-// ---- bounds ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void fof_bounds_kernel(const float4 *__restrict__ posm,
-                                                              const float4 *__restrict__ vel, uint32_t n,
-                                                              double *__restrict__ slabs) {
-    __shared__ double part[kThreads / kWave][kBoundFields];
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-    double v[kBoundLive];
-    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
-    v[6] = 0.0;
-    if (i < n) {
-        const float4 p = posm[i];
-        if (body_ok(p, vel[i])) {
-            v[0] = -(double)p.x;
-            v[1] = -(double)p.y;
-            v[2] = -(double)p.z;
-            v[3] = p.x;
-            v[4] = p.y;
-            v[5] = p.z;
-            v[6] = 1.0;
-        }
-    }
-    block_row<kBoundFields, kBoundLive, kBoundMax>(v, part, slabs + (size_t)blockIdx.x * kBoundFields);
-}
-
-// One block: the slabs into the plan.  Maxima and a sum of small integers: exact in any order.
+// One block: the bounds into the plan.  A refusal leaves no sort pass to run (passes[1] stays 0: the rows' plan
+// returns first); every other kernel tests status itself.
 __global__ __launch_bounds__(kThreads) void fof_plan_kernel(const double *__restrict__ slabs, uint32_t blocks,
                                                             double h, FofInfo *__restrict__ info) {
-    __shared__ double red[kBoundLive][kThreads];
-    const uint32_t tid = threadIdx.x;
-    double v[kBoundLive];
-    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
-    v[6] = 0.0;
-    for (uint32_t b = tid; b < blocks; b += kThreads) {
-        const double *row = slabs + (size_t)b * kBoundFields;
-        for (uint32_t f = 0; f < 6; ++f) v[f] = fmax(v[f], row[f]);
-        v[6] += row[6];
-    }
-    for (uint32_t f = 0; f < kBoundLive; ++f) red[f][tid] = v[f];
-    __syncthreads();
-    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            for (uint32_t f = 0; f < 6; ++f) red[f][tid] = fmax(red[f][tid], red[f][tid + o]);
-            red[6][tid] += red[6][tid + o];
-        }
-        __syncthreads();
-    }
-    if (tid != 0) return;
+    double lo[3], hi[3];
     FofInfo o{};
+    if (!bounds_finish(slabs, blocks, lo, hi, &o.n_ok)) return;
     o.h = h;
-    o.n_ok = (uint32_t)red[6][0];
     if (o.n_ok > 0) {
         unsigned long long cells[3];
         for (int a = 0; a < 3; ++a) {
-            o.lo[a] = -red[a][0];
-            const double c = floor((red[3 + a][0] - o.lo[a]) / h) + 1.0;
+            o.lo[a] = lo[a];
+            const double c = floor((hi[a] - lo[a]) / h) + 1.0;
             if (!(c <= kMaxCells)) o.status = 1;
             cells[a] = o.status ? 0ull : (unsigned long long)c;
         }
@@ -156,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void fof_plan_kernel(const double *__rest
         o.nz = cells[2];
         o.total = o.status ? 0ull : o.nx * o.ny * o.nz;  // (at most 2^63)
     }
-    o.passes[0] = std::max(1u, (bits_of(o.total) + 7) / 8);  // keys run 0 .. total
+    o.passes[0] = o.status ? 0u : std::max(1u, (bits_of(o.total) + 7) / 8);  // keys run 0 .. total
     *info = o;
 }
 
@@ -184,127 +137,6 @@ __global__ __launch_bounds__(kThreads) void fof_key_kernel(const float4 *__restr
         key = (cz * info->ny + cy) * info->nx + cx;
     }
     keys[i] = key;
-}
-
-// ---- sort: one pass of the stable sort, digit = (key >> 8 pass) & 255 ----------------------------------
-// Pass p reads side p & 1 and writes the other; the sorted keys are on side passes & 1.  A pass at or past
-// info->passes[which] returns at once.  Chunk b = elements [b * chunk, (b + 1) * chunk), one wave each.
-__global__ __launch_bounds__(kWave) void fof_sort_count_kernel(const FofInfo *__restrict__ info, uint32_t which,
-                                                               uint32_t pass,
-                                                               const unsigned long long *__restrict__ k0,
-                                                               const unsigned long long *__restrict__ k1, uint32_t n,
-                                                               uint32_t chunk, uint32_t *__restrict__ hist) {
-    if (info->status || pass >= info->passes[which]) return;
-    __shared__ uint32_t cnt[kRadix];
-    const unsigned long long *keys = pass & 1 ? k1 : k0;
-    const uint32_t lane = threadIdx.x, shift = 8 * pass;
-    for (uint32_t d = lane; d < kRadix; d += kWave) cnt[d] = 0;
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    for (size_t i = lo + lane; i < hi; i += kWave) atomicAdd(&cnt[(uint32_t)(keys[i] >> shift) & (kRadix - 1)], 1u);
-    __syncthreads();
-    for (uint32_t d = lane; d < kRadix; d += kWave) hist[(size_t)d * gridDim.x + blockIdx.x] = cnt[d];
-}
-
-// An exclusive scan of v[0 .. count) in place by one block of kScanThreads, thread t owning a run of elements;
-// returns the sum of all of them.
-__device__ inline uint32_t block_scan_runs(uint32_t *v, uint32_t count, uint32_t *lds /* [2][kScanThreads] */) {
-    const uint32_t tid = threadIdx.x, per = (count + kScanThreads - 1) / kScanThreads;
-    const size_t lo = std::min<size_t>(count, (size_t)tid * per), hi = std::min<size_t>(count, lo + per);
-    uint32_t s = 0;
-    for (size_t i = lo; i < hi; ++i) s += v[i];
-    uint32_t *a = lds, *b = lds + kScanThreads;
-    a[tid] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele
-        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
-        __syncthreads();
-        uint32_t *t = a;
-        a = b;
-        b = t;
-    }
-    uint32_t run = a[tid] - s;  // exclusive
-    const uint32_t total = a[kScanThreads - 1];
-    for (size_t i = lo; i < hi; ++i) {
-        const uint32_t x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    __syncthreads();
-    return total;
-}
-
-// scan: block d scans the row of digit d over the chunks in place and writes the row's sum to totals[d]
-__global__ __launch_bounds__(kScanThreads) void fof_sort_scan_kernel(const FofInfo *__restrict__ info, uint32_t which,
-                                                                     uint32_t pass, uint32_t *__restrict__ hist,
-                                                                     uint32_t blocks, uint32_t *__restrict__ totals) {
-    if (info->status || pass >= info->passes[which]) return;
-    __shared__ uint32_t lds[2 * kScanThreads];
-    const uint32_t total = block_scan_runs(hist + (size_t)blockIdx.x * blocks, blocks, lds);
-    if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-
-// scatter: element i of chunk b goes to (elements with a lower digit) + offs[d * blocks + b] + (elements of
-// the chunk before i with digit d).  Pass 0 takes the identity for the indices.
-__global__ __launch_bounds__(kWave) void fof_sort_scatter_kernel(const FofInfo *__restrict__ info, uint32_t which,
-                                                                 uint32_t pass, unsigned long long *__restrict__ k0,
-                                                                 unsigned long long *__restrict__ k1,
-                                                                 uint32_t *__restrict__ i0p, uint32_t *__restrict__ i1p,
-                                                                 uint32_t n, uint32_t chunk,
-                                                                 const uint32_t *__restrict__ offs,
-                                                                 const uint32_t *__restrict__ totals) {
-    if (info->status || pass >= info->passes[which]) return;
-    __shared__ uint32_t base[kRadix];
-    const unsigned long long *key_in = pass & 1 ? k1 : k0;
-    unsigned long long *key_out = pass & 1 ? k0 : k1;
-    const uint32_t *idx_in = pass & 1 ? i1p : i0p;
-    uint32_t *idx_out = pass & 1 ? i0p : i1p;
-    const uint32_t lane = threadIdx.x, shift = 8 * pass;
-    {  // lane l owns digits 4 l .. 4 l + 3: an exclusive scan of the 256 totals, four a lane, then over the wave
-        constexpr uint32_t kPer = kRadix / kWave;
-        uint32_t t[kPer], sum = 0;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            t[q] = totals[lane * kPer + q];
-            sum += t[q];
-        }
-        uint32_t inc = sum;
-        for (uint32_t o = 1; o < kWave; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        uint32_t run = inc - sum;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            const uint32_t d = lane * kPer + q;
-            base[d] = run + offs[(size_t)d * gridDim.x + blockIdx.x];
-            run += t[q];
-        }
-    }
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (size_t i0 = lo; i0 < hi; i0 += kWave) {
-        const size_t i = i0 + lane;
-        const bool valid = i < hi;
-        const unsigned long long key = valid ? key_in[i] : 0ull;
-        const uint32_t src = valid ? (pass ? idx_in[i] : (uint32_t)i) : 0u;
-        const uint32_t d = (uint32_t)(key >> shift) & (kRadix - 1);
-        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(same & below), group = (uint32_t)__popcll(same);
-        const uint32_t pos = base[d] + rank;
-        __syncthreads();
-        if (valid && rank + 1 == group) base[d] += group;  // one lane per digit present
-        __syncthreads();
-        if (valid && pos < n) {
-            key_out[pos] = key;
-            idx_out[pos] = src;
-        }
-    }
 }
 
 // ---- scans over n elements: kScanThreads elements per block, then the blocks' sums by one block --------
@@ -755,9 +587,7 @@ __global__ __launch_bounds__(kThreads) void fof_combine_kernel(const FofInfo *__
 static_assert(sizeof(nb_fof_group) == 8 + 8 * kTerms && offsetof(nb_fof_group, mass) == 8, "nine doubles after the header");
 
 struct FofWork : Workspace {  // (all but the last two grow to the largest call so far)
-    DeviceBuf<unsigned long long> keys[2];  // [n] each: the sorts' two sides
-    DeviceBuf<uint32_t> idx[2];             // [n] each
-    DeviceBuf<uint32_t> hist;               // [256][chunks], then the 256 digit totals
+    SortBufs<unsigned long long> sort;      // the two sides of both sorts, the histogram
     DeviceBuf<double> slabs;                // [bounds blocks][kBoundFields]
     DeviceBuf<uint32_t> flags, excl;        // [n]: what a scan reads and writes
     DeviceBuf<uint32_t> block_tot;          // [scan blocks + 1]: the blocks' sums, then the sum of all
@@ -783,24 +613,6 @@ int fof_reserve(B &b, size_t count) {
     (void)hipGetLastError();
     set_error("fof: cannot allocate the workspace (%zu elements)", count);
     return NB_ERR_ALLOC;
-}
-
-// the stable sort of (keys[0], identity) on the bits info->passes[which] covers; at most max_passes enqueued
-int enqueue_sort(SimBase &sim, FofWork &w, uint32_t which, uint32_t max_passes, uint32_t chunk, uint32_t sort_blocks) {
-    const uint32_t n = sim.n;
-    uint32_t *totals = w.hist + (size_t)kRadix * sort_blocks;
-    for (uint32_t pass = 0; pass < max_passes; ++pass) {
-        hipLaunchKernelGGL(fof_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.info, which, pass,
-                           w.keys[0], w.keys[1], n, chunk, w.hist);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream, w.info, which, pass,
-                           w.hist, sort_blocks, totals);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.info, which, pass,
-                           w.keys[0], w.keys[1], w.idx[0], w.idx[1], n, chunk, w.hist, totals);
-        NB_HIP_TRY(hipGetLastError());
-    }
-    return NB_OK;
 }
 
 int enqueue_scan(SimBase &sim, FofWork &w, uint32_t scan_blocks, uint32_t *total) {
@@ -853,14 +665,9 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
     if (n > 0) {
         const uint32_t blocks = (n + kThreads - 1) / kThreads;
         const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
-        const uint32_t chunk = std::max(256u, ((n + kSortBlocks - 1) / kSortBlocks + kWave - 1) / kWave * kWave);
-        const uint32_t sort_blocks = (n + chunk - 1) / chunk;
+        const SortShape shape = sort_shape(n);
         const size_t run_slots = (size_t)n / kWave + rows_cap + 1;
-        for (int s = 0; s < 2; ++s) {
-            if (int rc = fof_reserve(w.keys[s], n)) return rc;
-            if (int rc = fof_reserve(w.idx[s], n)) return rc;
-        }
-        if (int rc = fof_reserve(w.hist, (size_t)kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return fof_reserve(b, count); })) return rc;
         if (int rc = fof_reserve(w.slabs, (size_t)kBoundFields * blocks)) return rc;
         if (int rc = fof_reserve(w.flags, n)) return rc;
         if (int rc = fof_reserve(w.excl, n)) return rc;
@@ -888,28 +695,30 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
         const float4 *posm = nullptr, *vel = nullptr;
         sim.diag_state(&posm, &vel);
         FofInfo *info = w.info;
+        const auto &keys = w.sort.keys;  // both sides go to the kernels: the plan says where the sorted arrays are
+        const auto &idx = w.sort.idx;
         uint32_t *scan_total = w.block_tot + scan_blocks;
-        hipLaunchKernelGGL(fof_bounds_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
+        hipLaunchKernelGGL(bounds_kernel<>, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(fof_plan_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, blocks, h, info);
         NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, w.keys[0]);
+        hipLaunchKernelGGL(fof_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, keys[0]);
         NB_HIP_TRY(hipGetLastError());
-        if (int rc = enqueue_sort(sim, w, 0, kMaxPasses, chunk, sort_blocks)) return rc;
+        if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, kMaxPasses, 0, &info->passes[0])) return rc;
         // the cell table
-        hipLaunchKernelGGL(fof_heads_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0], w.keys[1], n,
+        hipLaunchKernelGGL(fof_heads_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
                            w.flags);
         NB_HIP_TRY(hipGetLastError());
         if (int rc = enqueue_scan(sim, w, scan_blocks, scan_total)) return rc;
-        hipLaunchKernelGGL(fof_cells_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0], w.keys[1], n,
+        hipLaunchKernelGGL(fof_cells_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
                            w.excl, w.block_tot, w.flags, w.cell_key, w.cell_start);
         NB_HIP_TRY(hipGetLastError());
         if (use_boxes) NB_HIP_TRY(hipMemsetAsync(w.boxes, 0, sizeof(uint32_t) * 6 * n, sim.stream));
-        hipLaunchKernelGGL(fof_parent_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, posm, w.idx[0], w.idx[1],
+        hipLaunchKernelGGL(fof_parent_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, posm, idx[0], idx[1],
                            n, w.flags, w.cell_start, scan_total, w.spos, w.parent, w.boxes, use_boxes);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(fof_union_kernel, dim3((uint32_t)union_items), dim3(kWave), 0, sim.stream, info, w.cell_key,
-                           w.cell_start, w.boxes, w.idx[0], w.idx[1], w.spos, w.parent, len, b2, use_boxes);
+                           w.cell_start, w.boxes, idx[0], idx[1], w.spos, w.parent, len, b2, use_boxes);
         NB_HIP_TRY(hipGetLastError());
         // labels, sizes, rows
         NB_HIP_TRY(hipMemsetAsync(w.count, 0, sizeof(uint32_t) * n, sim.stream));
@@ -928,16 +737,17 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
         NB_HIP_TRY(hipGetLastError());
         if (group_of || rows_cap > 0) {
             hipLaunchKernelGGL(fof_group_of_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.row_of,
-                               n, w.group_of, rows_cap > 0 ? (unsigned long long *)w.keys[0] : nullptr);
+                               n, w.group_of, rows_cap > 0 ? (unsigned long long *)keys[0] : nullptr);
             NB_HIP_TRY(hipGetLastError());
         }
         if (rows_cap > 0) {  // the catalogue's sums
-            if (int rc = enqueue_sort(sim, w, 1, (bits_of(rows_cap) + 7) / 8, chunk, sort_blocks)) return rc;
-            hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.keys[0],
-                               w.keys[1], n, w.row_start);
+            if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, (bits_of(rows_cap) + 7) / 8, 0, &info->passes[1]))
+                return rc;
+            hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0],
+                               keys[1], n, w.row_start);
             NB_HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm, vel,
-                               w.idx[0], w.idx[1], w.row_start, len, w.runs);
+                               idx[0], idx[1], w.row_start, len, w.runs);
             NB_HIP_TRY(hipGetLastError());
             const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
             hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info, w.row_start,

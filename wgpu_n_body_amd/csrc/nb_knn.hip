@@ -5,18 +5,16 @@
 // For a counted body i the other counted bodies are ordered by (d2(i, j), j); the k-th of them fixes r2, kth,
 // mass_in and density.  The order is total (j is unique), so everything per body is unique given the state,
 // whatever order the threads ran in.
-//   bounds  -- one thread per body over the float4 SoA state (SimBase::diag_state): the per-axis minimum and
-//              maximum of the counted bodies (body_ok) and their number c, through per-block slabs (block_row,
-//              nb_analysis.hpp); one block finishes them into the plan on the device: lo, hi and the side
-//              h = (largest extent) 2^-21 of the finest cells.  Every later kernel reads the plan;
+//   bounds  -- the per-axis minimum and maximum of the counted bodies (body_ok) and their number c over the float4
+//              SoA state (SimBase::diag_state), by the bounds pass of nb_analysis_sort.hpp; the one block that
+//              finishes them makes the plan on the device: lo, hi and the side h = (largest extent) 2^-21 of
+//              the finest cells.  Every later kernel reads the plan;
 //   key     -- a body's cell on an axis is the q with e(q) <= x < e(q + 1), e(q) = lo + q h: found by a
 //              division and then corrected by comparing x with the edges themselves, so that membership is a
 //              comparison and not an arithmetic identity.  The key is the 63-bit Morton code of (qx, qy, qz),
 //              or 2^63 for a body that does not count;
-//   sort    -- a stable LSD radix sort of (key, body index), 8 bits a pass, eight passes: a sibling of
-//              nb_fof.hip's (count / scan / scatter, one wave per chunk, ranks by wave ballots), without its
-//              plan.  A cell of any octree level is then a contiguous run of positions, its bodies of equal
-//              key in body order;
+//   sort    -- the stable sort of nb_analysis_sort.hpp on (key, body index), all eight passes.  A cell of any
+//              octree level is then a contiguous run of positions, its bodies of equal key in body order;
 //   gather  -- positions and masses in sorted order; every body's outputs preset to those of a body that is
 //              not counted, or of a state short of k;
 //   search  -- one wave per counted body, "knn_block_queries" waves a block.  The k best (d2, j) sit one per
@@ -43,6 +41,7 @@
 #include <cstring>
 
 #include "nb_analysis.hpp"
+#include "nb_analysis_sort.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -51,12 +50,7 @@ namespace nb {
 namespace {
 
 constexpr uint32_t kThreads = kBlock;
-constexpr uint32_t kRadix = 256;         // 8 bits of the key per sort pass
-constexpr uint32_t kSortBlocks = 2048;   // at most this many chunks (one wave each) per sort pass
-constexpr uint32_t kScanThreads = 1024;  // the scan of a digit's row over the chunks
 constexpr uint32_t kPasses = 8;          // a 64-bit key; even, so the sorted arrays are on side 0
-constexpr uint32_t kBoundFields = 8, kBoundLive = 7;  // max(-x, -y, -z, x, y, z), counted bodies
-constexpr uint32_t kBoundMax = 0x3f;
 constexpr uint32_t kAxisBits = 21;
 constexpr uint32_t kAxisMax = (1u << kAxisBits) - 1;       // the last finest cell of an axis
 constexpr unsigned long long kKeyNone = 1ull << 63;        // past every Morton code
@@ -91,61 +85,18 @@ __device__ inline double wave_min(double v) {
     return v;
 }
 
-// ---- bounds ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void knn_bounds_kernel(const float4 *__restrict__ posm,
-                                                              const float4 *__restrict__ vel, uint32_t n,
-                                                              double *__restrict__ slabs) {
-    __shared__ double part[kThreads / kWave][kBoundFields];
-    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-    double v[kBoundLive];
-    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
-    v[6] = 0.0;
-    if (i < n) {
-        const float4 p = posm[i];
-        if (body_ok(p, vel[i])) {
-            v[0] = -(double)p.x;
-            v[1] = -(double)p.y;
-            v[2] = -(double)p.z;
-            v[3] = p.x;
-            v[4] = p.y;
-            v[5] = p.z;
-            v[6] = 1.0;
-        }
-    }
-    block_row<kBoundFields, kBoundLive, kBoundMax>(v, part, slabs + (size_t)blockIdx.x * kBoundFields);
-}
-
-// One block: the slabs into the plan.  Maxima and a sum of small integers: exact in any order.
+// One block: the bounds into the plan.
 __global__ __launch_bounds__(kThreads) void knn_plan_kernel(const double *__restrict__ slabs, uint32_t blocks,
                                                             KnnInfo *__restrict__ info) {
-    __shared__ double red[kBoundLive][kThreads];
-    const uint32_t tid = threadIdx.x;
-    double v[kBoundLive];
-    for (uint32_t f = 0; f < 6; ++f) v[f] = -INFINITY;
-    v[6] = 0.0;
-    for (uint32_t b = tid; b < blocks; b += kThreads) {
-        const double *row = slabs + (size_t)b * kBoundFields;
-        for (uint32_t f = 0; f < 6; ++f) v[f] = fmax(v[f], row[f]);
-        v[6] += row[6];
-    }
-    for (uint32_t f = 0; f < kBoundLive; ++f) red[f][tid] = v[f];
-    __syncthreads();
-    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            for (uint32_t f = 0; f < 6; ++f) red[f][tid] = fmax(red[f][tid], red[f][tid + o]);
-            red[6][tid] += red[6][tid + o];
-        }
-        __syncthreads();
-    }
-    if (tid != 0) return;
+    double lo[3], hi[3];
     KnnInfo o{};
-    o.n_ok = (uint32_t)red[6][0];
+    if (!bounds_finish(slabs, blocks, lo, hi, &o.n_ok)) return;
     o.peak_index = NB_KNN_NONE;
     if (o.n_ok > 0) {
         double extent = 0.0;
         for (int a = 0; a < 3; ++a) {
-            o.lo[a] = -red[a][0];
-            o.hi[a] = red[3 + a][0];
+            o.lo[a] = lo[a];
+            o.hi[a] = hi[a];
             extent = fmax(extent, o.hi[a] - o.lo[a]);  // finite: a difference of binary32 values
         }
         o.h = extent * 0x1p-21;  // exact; 0 only for a state at one point
@@ -201,113 +152,6 @@ __global__ __launch_bounds__(kThreads) void knn_key_kernel(const float4 *__restr
         key = morton(cell_of(p.x, info->lo[0], h), cell_of(p.y, info->lo[1], h), cell_of(p.z, info->lo[2], h));
     }
     keys[i] = key;
-}
-
-// ---- sort: one pass of the stable sort, digit = (key >> 8 pass) & 255 ----------------------------------
-// Pass p reads side p & 1 and writes the other.  Chunk b = elements [b * chunk, (b + 1) * chunk), one wave each.
-__global__ __launch_bounds__(kWave) void knn_sort_count_kernel(uint32_t pass,
-                                                               const unsigned long long *__restrict__ k0,
-                                                               const unsigned long long *__restrict__ k1, uint32_t n,
-                                                               uint32_t chunk, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t cnt[kRadix];
-    const unsigned long long *keys = pass & 1 ? k1 : k0;
-    const uint32_t lane = threadIdx.x, shift = 8 * pass;
-    for (uint32_t d = lane; d < kRadix; d += kWave) cnt[d] = 0;
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    for (size_t i = lo + lane; i < hi; i += kWave) atomicAdd(&cnt[(uint32_t)(keys[i] >> shift) & (kRadix - 1)], 1u);
-    __syncthreads();
-    for (uint32_t d = lane; d < kRadix; d += kWave) hist[(size_t)d * gridDim.x + blockIdx.x] = cnt[d];
-}
-
-// scan: block d scans the row of digit d over the chunks in place (exclusive, thread t owning a run of
-// elements) and writes the row's sum to totals[d]
-__global__ __launch_bounds__(kScanThreads) void knn_sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t blocks,
-                                                                     uint32_t *__restrict__ totals) {
-    __shared__ uint32_t lds[2 * kScanThreads];
-    uint32_t *v = hist + (size_t)blockIdx.x * blocks;
-    const uint32_t tid = threadIdx.x, per = (blocks + kScanThreads - 1) / kScanThreads;
-    const size_t lo = std::min<size_t>(blocks, (size_t)tid * per), hi = std::min<size_t>(blocks, lo + per);
-    uint32_t s = 0;
-    for (size_t i = lo; i < hi; ++i) s += v[i];
-    uint32_t *a = lds, *b = lds + kScanThreads;
-    a[tid] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele
-        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
-        __syncthreads();
-        uint32_t *t = a;
-        a = b;
-        b = t;
-    }
-    uint32_t run = a[tid] - s;  // exclusive
-    for (size_t i = lo; i < hi; ++i) {
-        const uint32_t x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    if (tid == kScanThreads - 1) totals[blockIdx.x] = a[tid];
-}
-
-// scatter: element i of chunk b goes to (elements with a lower digit) + offs[d * blocks + b] + (elements of
-// the chunk before i with digit d).  Pass 0 takes the identity for the indices.
-__global__ __launch_bounds__(kWave) void knn_sort_scatter_kernel(uint32_t pass, unsigned long long *__restrict__ k0,
-                                                                 unsigned long long *__restrict__ k1,
-                                                                 uint32_t *__restrict__ i0p, uint32_t *__restrict__ i1p,
-                                                                 uint32_t n, uint32_t chunk,
-                                                                 const uint32_t *__restrict__ offs,
-                                                                 const uint32_t *__restrict__ totals) {
-    __shared__ uint32_t base[kRadix];
-    const unsigned long long *key_in = pass & 1 ? k1 : k0;
-    unsigned long long *key_out = pass & 1 ? k0 : k1;
-    const uint32_t *idx_in = pass & 1 ? i1p : i0p;
-    uint32_t *idx_out = pass & 1 ? i0p : i1p;
-    const uint32_t lane = threadIdx.x, shift = 8 * pass;
-    {  // lane l owns digits 4 l .. 4 l + 3: an exclusive scan of the 256 totals, four a lane, then over the wave
-        constexpr uint32_t kPer = kRadix / kWave;
-        uint32_t t[kPer], sum = 0;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            t[q] = totals[lane * kPer + q];
-            sum += t[q];
-        }
-        uint32_t inc = sum;
-        for (uint32_t o = 1; o < kWave; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        uint32_t run = inc - sum;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            const uint32_t d = lane * kPer + q;
-            base[d] = run + offs[(size_t)d * gridDim.x + blockIdx.x];
-            run += t[q];
-        }
-    }
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (size_t i0 = lo; i0 < hi; i0 += kWave) {
-        const size_t i = i0 + lane;
-        const bool valid = i < hi;
-        const unsigned long long key = valid ? key_in[i] : 0ull;
-        const uint32_t src = valid ? (pass ? idx_in[i] : (uint32_t)i) : 0u;
-        const uint32_t d = (uint32_t)(key >> shift) & (kRadix - 1);
-        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(same & below), group = (uint32_t)__popcll(same);
-        const uint32_t pos = base[d] + rank;
-        __syncthreads();
-        if (valid && rank + 1 == group) base[d] += group;  // one lane per digit present
-        __syncthreads();
-        if (valid && pos < n) {
-            key_out[pos] = key;
-            idx_out[pos] = src;
-        }
-    }
 }
 
 // ---- gather ---------------------------------------------------------------------------------------
@@ -593,9 +437,7 @@ __global__ __launch_bounds__(kThreads) void knn_peak_kernel(const float4 *__rest
 }  // namespace
 
 struct KnnWork : Workspace {  // (all grow to the largest call so far)
-    DeviceBuf<unsigned long long> keys[2];  // [n] each: the sort's two sides
-    DeviceBuf<uint32_t> idx[2];             // [n] each
-    DeviceBuf<uint32_t> hist;               // [256][chunks], then the 256 digit totals
+    SortBufs<unsigned long long> sort;      // the two sides of (key, body index), the histogram
     DeviceBuf<double> slabs;                // [blocks][max(kBoundFields, kSumFields)]
     DeviceBuf<float4> spos;                 // [n]: positions and masses in sorted order
     DeviceBuf<double> r2, mass_in, density; // [n]
@@ -647,14 +489,9 @@ int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth
 
     if (n > 0) {
         const uint32_t blocks = (n + kThreads - 1) / kThreads;
-        const uint32_t chunk = std::max(256u, ((n + kSortBlocks - 1) / kSortBlocks + kWave - 1) / kWave * kWave);
-        const uint32_t sort_blocks = (n + chunk - 1) / chunk;
+        const SortShape shape = sort_shape(n);
         const uint32_t per_block = (uint32_t)sim.knn_block_queries, span = (uint32_t)sim.knn_span_cells;
-        for (int s = 0; s < 2; ++s) {
-            if (int rc = knn_reserve(w.keys[s], n)) return rc;
-            if (int rc = knn_reserve(w.idx[s], n)) return rc;
-        }
-        if (int rc = knn_reserve(w.hist, (size_t)kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return knn_reserve(b, count); })) return rc;
         if (int rc = knn_reserve(w.slabs, (size_t)std::max(kBoundFields, kSumFields) * blocks)) return rc;
         if (int rc = knn_reserve(w.spos, n)) return rc;
         if (int rc = knn_reserve(w.r2, n)) return rc;
@@ -673,32 +510,23 @@ int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth
         const float4 *posm = nullptr, *vel = nullptr;
         sim.diag_state(&posm, &vel);
         KnnInfo *info = w.info;
-        uint32_t *totals = w.hist + (size_t)kRadix * sort_blocks;
-        hipLaunchKernelGGL(knn_bounds_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
+        hipLaunchKernelGGL(bounds_kernel<>, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(knn_plan_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, blocks, info);
         NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(knn_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, w.keys[0]);
+        static_assert(kPasses % 2 == 0, "the sort starts from side 0 and its result is read from there");
+        unsigned long long *keys = w.sort.keys[0];
+        const uint32_t *sidx = w.sort.idx[0];
+        hipLaunchKernelGGL(knn_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, keys);
         NB_HIP_TRY(hipGetLastError());
-        for (uint32_t pass = 0; pass < kPasses; ++pass) {
-            hipLaunchKernelGGL(knn_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, pass, w.keys[0],
-                               w.keys[1], n, chunk, w.hist);
-            NB_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(knn_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream, w.hist,
-                               sort_blocks, totals);
-            NB_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(knn_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, pass, w.keys[0],
-                               w.keys[1], w.idx[0], w.idx[1], n, chunk, w.hist, totals);
-            NB_HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, w.idx[0],
+        if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, kPasses, 0, nullptr)) return rc;
+        hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, sidx,
                            w.spos, w.r2, w.kth, w.mass_in, w.density);
         NB_HIP_TRY(hipGetLastError());
         // one wave per sorted position; those past the counted bodies, and all of them in a state short of k,
         // return at once: no host round trip decides the launch
         hipLaunchKernelGGL(knn_search_kernel, dim3((n + per_block - 1) / per_block), dim3(per_block * kWave), 0,
-                           sim.stream, info, w.keys[0], w.idx[0], w.spos, posm, k, span, w.r2, w.kth, w.mass_in,
-                           w.density);
+                           sim.stream, info, keys, sidx, w.spos, posm, k, span, w.r2, w.kth, w.mass_in, w.density);
         NB_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(knn_sum_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, k, info, w.r2,
                            w.density, w.slabs);

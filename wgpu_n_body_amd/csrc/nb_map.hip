@@ -8,10 +8,9 @@
 //                body, (tile << 6) | cell in the tile, or the key of the tile past the last for a body
 //                that is outside or non-finite.  The global sums (class counts, masses) go through
 //                per-block slabs (block_row, nb_analysis.hpp) and a fixed-order finish;
-//   group     -- a stable LSD radix sort of (key, body index) on the tile bits, 8 bits a pass (one pass
-//                up to 255 tiles, two up to 65,535, else three): count / scan / scatter, one wave per
-//                chunk of bodies, the rank inside a chunk by wave ballots in body order, so the order
-//                of a tile's list is the order of the bodies.  No atomic reservation;
+//   group     -- the stable sort of nb_analysis_sort.hpp on (key, body index), on the tile bits (one pass
+//                up to 255 tiles, two up to 65,535, else three), so the order of a tile's list is the
+//                order of the bodies;
 //   lists     -- the first and last position of every tile in the sorted keys, the tiles' lists cut into
 //                segments of at most "map_segment_len" bodies, and the segments numbered by a scan
 //                (every block its 1,024 tiles, then the blocks before it added);
@@ -32,6 +31,7 @@
 #include <cstring>
 
 #include "nb_analysis.hpp"
+#include "nb_analysis_sort.hpp"
 #include "nb_common.hpp"
 #include "nb_sim.hpp"
 
@@ -42,9 +42,6 @@ namespace {
 constexpr uint32_t kThreads = kBlock;
 constexpr uint32_t kTile = 8, kTileCells = kTile * kTile;  // cells per tile = the low 6 bits of a key
 constexpr uint32_t kCellBits = 6;
-constexpr uint32_t kRadix = 256;          // 8 bits of the tile per sort pass
-constexpr uint32_t kSortBlocks = 2048;    // at most this many chunks (one wave each) per sort pass
-constexpr uint32_t kScanThreads = 1024;   // the one-block scans
 constexpr uint32_t kGlobalFields = 8;     // see GlobalField
 constexpr uint32_t kMaxFields = 6;        // planes with NB_MAP_VELOCITY
 constexpr uint32_t kMaxBlocks = 1024;     // the maximum over the counts: grid-stride beyond
@@ -140,117 +137,6 @@ __global__ __launch_bounds__(kThreads) void map_classify_kernel(const float4 *__
         keys[i] = key;
     }
     block_row<kGlobalFields, kGLive>(glob, part, slabs + (size_t)blockIdx.x * kGlobalFields);
-}
-
-// ---- group: one pass of the stable sort, digit = (key >> shift) & 255 ---------------------------
-// Chunk b = bodies [b * chunk, (b + 1) * chunk) of the pass's input, one wave each.
-// count: hist[d * blocks + b] = bodies of chunk b with digit d
-__global__ __launch_bounds__(kWave) void map_sort_count_kernel(const uint32_t *__restrict__ keys, uint32_t n,
-                                                               uint32_t chunk, uint32_t shift,
-                                                               uint32_t *__restrict__ hist) {
-    __shared__ uint32_t cnt[kRadix];
-    const uint32_t lane = threadIdx.x;
-    for (uint32_t d = lane; d < kRadix; d += kWave) cnt[d] = 0;
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    for (size_t i = lo + lane; i < hi; i += kWave) atomicAdd(&cnt[(keys[i] >> shift) & (kRadix - 1)], 1u);
-    __syncthreads();
-    for (uint32_t d = lane; d < kRadix; d += kWave) hist[(size_t)d * gridDim.x + blockIdx.x] = cnt[d];
-}
-
-// An exclusive scan of v[0 .. count) in place by one block, thread t owning a run of `per` elements; returns
-// the sum of all of them.
-__device__ inline uint32_t block_scan_runs(uint32_t *v, uint32_t count, uint32_t *lds /* [2][kScanThreads] */) {
-    const uint32_t tid = threadIdx.x, per = (count + kScanThreads - 1) / kScanThreads;
-    const size_t lo = std::min<size_t>(count, (size_t)tid * per), hi = std::min<size_t>(count, lo + per);
-    uint32_t s = 0;
-    for (size_t i = lo; i < hi; ++i) s += v[i];
-    uint32_t *a = lds, *b = lds + kScanThreads;
-    a[tid] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {  // inclusive, Hillis-Steele
-        b[tid] = tid >= o ? a[tid] + a[tid - o] : a[tid];
-        __syncthreads();
-        uint32_t *t = a;
-        a = b;
-        b = t;
-    }
-    uint32_t run = a[tid] - s;  // exclusive
-    const uint32_t total = a[kScanThreads - 1];
-    for (size_t i = lo; i < hi; ++i) {
-        const uint32_t x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    __syncthreads();
-    return total;
-}
-
-// scan: block d scans the row of digit d over the chunks in place and writes the row's sum to totals[d]; the
-// scatter adds the digits below itself
-__global__ __launch_bounds__(kScanThreads) void map_sort_scan_kernel(uint32_t *__restrict__ hist, uint32_t blocks,
-                                                                     uint32_t *__restrict__ totals) {
-    __shared__ uint32_t lds[2 * kScanThreads];
-    const uint32_t total = block_scan_runs(hist + (size_t)blockIdx.x * blocks, blocks, lds);
-    if (threadIdx.x == 0) totals[blockIdx.x] = total;
-}
-
-// scatter: body i of chunk b goes to (bodies with a lower digit) + offs[d * blocks + b] + (bodies of the chunk
-// before i with digit d).  idx_in null: the identity (the first pass).
-__global__ __launch_bounds__(kWave) void map_sort_scatter_kernel(const uint32_t *__restrict__ key_in,
-                                                                 const uint32_t *__restrict__ idx_in,
-                                                                 uint32_t *__restrict__ key_out,
-                                                                 uint32_t *__restrict__ idx_out, uint32_t n,
-                                                                 uint32_t chunk, uint32_t shift,
-                                                                 const uint32_t *__restrict__ offs,
-                                                                 const uint32_t *__restrict__ totals) {
-    __shared__ uint32_t base[kRadix];
-    const uint32_t lane = threadIdx.x;
-    {  // lane l owns digits 4 l .. 4 l + 3: an exclusive scan of the 256 totals, four a lane, then over the wave
-        constexpr uint32_t kPer = kRadix / kWave;
-        uint32_t t[kPer], sum = 0;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            t[q] = totals[lane * kPer + q];
-            sum += t[q];
-        }
-        uint32_t inc = sum;
-        for (uint32_t o = 1; o < kWave; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        uint32_t run = inc - sum;
-        for (uint32_t q = 0; q < kPer; ++q) {
-            const uint32_t d = lane * kPer + q;
-            base[d] = run + offs[(size_t)d * gridDim.x + blockIdx.x];
-            run += t[q];
-        }
-    }
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * chunk, hi = std::min<size_t>(n, lo + chunk);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (size_t i0 = lo; i0 < hi; i0 += kWave) {
-        const size_t i = i0 + lane;
-        const bool valid = i < hi;
-        const uint32_t key = valid ? key_in[i] : 0u;
-        const uint32_t src = valid ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
-        const uint32_t d = (key >> shift) & (kRadix - 1);
-        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(same & below), group = (uint32_t)__popcll(same);
-        const uint32_t pos = base[d] + rank;
-        __syncthreads();
-        if (valid && rank + 1 == group) base[d] += group;  // one lane per digit present
-        __syncthreads();
-        if (valid && pos < n) {
-            key_out[pos] = key;
-            idx_out[pos] = src;
-        }
-    }
 }
 
 // ---- lists: tile t's bodies are positions [first[t], last[t]) of the sorted keys (0, 0: none) ------
@@ -497,8 +383,7 @@ uint32_t bits_of(uint32_t x) {
 }  // namespace
 
 struct MapWork : Workspace {  // (all but the last three grow to the largest call so far)
-    DeviceBuf<uint32_t> keys[2], idx[2];    // [n] each: the sort's two sides
-    DeviceBuf<uint32_t> hist;               // [256][chunks], then the 256 digit totals
+    SortBufs<uint32_t> sort;                // the two sides of (key, body index), the histogram
     DeviceBuf<uint32_t> first, last;        // [tiles]
     DeviceBuf<uint32_t> seg_off, part_off;  // [tiles + 1]
     DeviceBuf<uint32_t> seg_tile;           // [segments possible]
@@ -592,19 +477,13 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
     if (n > 0) {
         const uint32_t seg_len = (uint32_t)sim.map_segment_len;
         const uint32_t class_blocks = (n + kThreads - 1) / kThreads;
-        // the sort: chunks of a multiple of 64 bodies, at least 256, at most kSortBlocks of them
-        const uint32_t chunk = std::max(256u, ((n + kSortBlocks - 1) / kSortBlocks + kWave - 1) / kWave * kWave);
-        const uint32_t sort_blocks = (n + chunk - 1) / chunk;
+        const SortShape shape = sort_shape(n);
         const uint32_t passes = (bits_of(k.tiles) + 7) / 8;  // keys' tiles run 0 .. tiles
         // segments: a tile with bodies has at most 1 + (len - 1) / seg_len; those of longer lists number
         // at most 2 (len / seg_len)
         const uint32_t seg_cap = std::min(k.tiles, n) + n / seg_len;
         const uint32_t part_cap = 2 * (n / seg_len);
-        for (int s = 0; s < 2; ++s) {
-            if (int rc = map_reserve(w.keys[s], n)) return rc;
-            if (int rc = map_reserve(w.idx[s], n)) return rc;
-        }
-        if (int rc = map_reserve(w.hist, (size_t)kRadix * (sort_blocks + 1))) return rc;
+        if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return map_reserve(b, count); })) return rc;
         if (int rc = map_reserve(w.first, k.tiles)) return rc;
         if (int rc = map_reserve(w.last, k.tiles)) return rc;
         if (int rc = map_reserve(w.seg_off, (size_t)k.tiles + 1)) return rc;
@@ -624,24 +503,10 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
         if (com)
             if (int rc = diag_enqueue_moments(sim, &mom)) return rc;
         hipLaunchKernelGGL(map_classify_kernel, dim3(class_blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, k, mom,
-                           w.keys[0], w.slabs, w.res);
+                           w.sort.keys[0], w.slabs, w.res);
         NB_HIP_TRY(hipGetLastError());
-        int side = 0;
-        for (uint32_t pass = 0; pass < passes; ++pass, side ^= 1) {
-            const uint32_t shift = kCellBits + 8 * pass;
-            hipLaunchKernelGGL(map_sort_count_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream, w.keys[side], n,
-                               chunk, shift, w.hist);
-            NB_HIP_TRY(hipGetLastError());
-            uint32_t *totals = w.hist + (size_t)kRadix * sort_blocks;
-            hipLaunchKernelGGL(map_sort_scan_kernel, dim3(kRadix), dim3(kScanThreads), 0, sim.stream, w.hist,
-                               sort_blocks, totals);
-            NB_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(map_sort_scatter_kernel, dim3(sort_blocks), dim3(kWave), 0, sim.stream,
-                               w.keys[side], pass ? (const uint32_t *)w.idx[side] : nullptr, w.keys[side ^ 1],
-                               w.idx[side ^ 1], n, chunk, shift, w.hist, totals);
-            NB_HIP_TRY(hipGetLastError());
-        }
-        const uint32_t *keys = w.keys[side], *idx = w.idx[side];
+        if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, passes, kCellBits, nullptr)) return rc;
+        const uint32_t *keys = w.sort.keys[passes & 1], *idx = w.sort.idx[passes & 1];
         NB_HIP_TRY(hipMemsetAsync(w.first, 0, sizeof(uint32_t) * k.tiles, sim.stream));
         NB_HIP_TRY(hipMemsetAsync(w.last, 0, sizeof(uint32_t) * k.tiles, sim.stream));
         NB_HIP_TRY(hipMemsetAsync(w.counts, 0, sizeof(uint32_t) * cells, sim.stream));
