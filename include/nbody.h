@@ -788,6 +788,104 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
                double *density, nb_knn_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
+/* kernel of its own radius (no reference counterpart: the image of the       */
+/* density estimate, where nb_sim_map gives shot noise)                       */
+/* ------------------------------------------------------------------------- */
+/* nb_sim_map puts a body into one cell; this pass spreads it over every pixel
+ * whose centre lies within the body's own smoothing length s[i] (typically the
+ * distance to its k-th neighbour, sqrt of nb_sim_knn's r2), with a compact
+ * kernel of unit integral.  The rule, which DESIGN.md 6j states in full:
+ * everything in binary64 from the binary32 state and the caller's binary64 s[],
+ * one rounding per operation, no contraction, in this order:
+ *   frame     n, e1, e2 exactly as nb_sim_map (nb_map_frame)
+ *   per body  d = (double)x - c, u = (double)v - v_c; a, b, h and ua, ub, w exactly as
+ *             nb_sim_map; the predicate for a counted body is nb_sim_map's; the slab
+ *             tests the body's own depth: lo <= h < hi (a NaN h is outside)
+ *   edges     xe[], ye[] exactly as nb_sim_map (nb_map_edges)
+ *   centres   xc[i] = 0.5 (xe[i] + xe[i+1]), yc[j] = 0.5 (ye[j] + ye[j+1])  (nb_smooth_centres)
+ *   length    s_eff = s < s_min ? s_min : (s > s_max ? s_max : s), 0 < s_min <= s_max finite.
+ *             s = 0 (nb_sim_knn's r_k at coincident bodies) and every s below s_min,
+ *             negative ones included, are `raised` to s_min; s = +inf (r_k when no more
+ *             than k bodies are counted) and every s above s_max are `lowered` to s_max;
+ *             both are counted over the counted bodies whose s is not NaN, whatever
+ *             their depth.  A NaN s stays NaN: the body deposits nothing and is counted
+ *             in `bad_smoothing`
+ *   weight    of body i at pixel (ix, jy): da = xc[ix] - a, db = yc[jy] - b,
+ *             r2 = da da + db db, s2 = s_eff s_eff.  The body reaches the pixel iff
+ *             r2 < s2 (strictly); then t = 1 - r2 / s2 and wgt = (K / s2) (t t),
+ *             K = NB_SMOOTH_K = 3 / pi: the 2-D kernel (3 / (pi s^2)) (1 - r^2 / s^2)^2 of
+ *             unit integral, the exact line-of-sight projection of the 3-D kernel
+ *             proportional to (1 - q^2)^(3/2).  A polynomial in r2: no sqrt
+ *   terms     wm = m wgt; the planes are the sums over the reaching bodies of wm, wm ua,
+ *             wm ub, wm w, (wm w) w, wm ((ux ux + uy uy) + uz uz)
+ *   counts    counts[jy][ix] = the number of bodies that reach the pixel: decided by the
+ *             one comparison above, so exact integers
+ * Plane 0 is a surface density already (mass per area of the plane coordinates).
+ * The kernel is point-sampled at the pixel centres, not integrated over the
+ * pixels: the sum of wgt times the pixel area over a body's pixels is 1 only up to
+ * the sampling error, which falls with s_eff in pixels (DESIGN.md 6j has the
+ * figures: within -0.7 % / +1.5 % at 2 pixels), and a body whose s_eff is below
+ * half a pixel diagonal can miss every centre.  s_min is that floor; an exact
+ * per-body renormalisation is a second pass per body and not done.
+ * stats: nonfinite + bad_smoothing + skipped + deposited == n, where `deposited`
+ * are the bodies that reach at least one pixel and `skipped` the counted bodies
+ * with a valid s that reach none (outside the depth slab, or no centre within
+ * s_eff); pairs = the sum of counts; mass = the mass of all counted bodies (a NaN
+ * s included), deposited_mass that of the deposited ones.  tile_entries is an
+ * implementation figure (the (8 x 8-pixel tile, body) entries the pass sorted)
+ * and not part of the rule.
+ * NB_SMOOTH_CENTER_COM works as NB_MAP_CENTER_COM.  No float atomics: two calls
+ * on one state return bit-identical counts, planes and stats, and every double is
+ * within 1e-10 of its sum of |term| of the binary64 sum.  The call is ordered
+ * after the enqueued steps on the simulator's stream, reports a TreeSim's status
+ * words as nb_sim_read_particles does, and does not change the trajectory.  It
+ * synchronises twice: once for the number of tile entries, which sizes its
+ * workspace, and once at the end.
+ * "smooth_segment_len" (nb_sim_set_tuning, 256..65536, a multiple of 256; default
+ * 4096; speed and testing only): a tile's entries are summed in runs of at most
+ * this many, the runs then in order. */
+#define NB_SMOOTH_CENTER_COM 1u /* as NB_MAP_CENTER_COM */
+#define NB_SMOOTH_VELOCITY 2u   /* add the five velocity planes */
+#define NB_SMOOTH_K 0.95492965855137201461 /* K = 3 / pi, to binary64 0x1.e8ec8a4aeacc4p-1 */
+#define NB_SMOOTH_MAX_ENTRIES (1ull << 28) /* (tile, body) entries of one call: 16 B each across the two sort sides */
+
+typedef struct nb_smooth_params {
+    uint32_t width, height, flags, reserved; /* sides 1..NB_MAP_MAX_SIDE, at most NB_MAP_MAX_CELLS pixels; reserved 0 */
+    double center[3], velocity[3];           /* ignored with NB_SMOOTH_CENTER_COM */
+    double axis[3];                          /* line of sight; any non-zero finite vector */
+    double x_range[2], y_range[2];           /* window in the plane coordinates a, b: [lo, hi) */
+    double depth_range[2];                   /* slab along the line of sight: lo <= h < hi; -inf, +inf = everything */
+    double s_min, s_max;                     /* 0 < s_min <= s_max, both finite */
+} nb_smooth_params;
+
+typedef struct nb_smooth_stats {
+    uint64_t step_num, n, nonfinite, bad_smoothing, skipped, deposited, raised, lowered, pairs;
+    uint64_t tile_entries;          /* implementation figure, not part of the rule */
+    double mass, deposited_mass;    /* mass: all counted bodies */
+    double center[3], velocity[3];  /* the values used */
+    double n_hat[3], e1[3], e2[3];  /* the frame used */
+    double s_min, s_max;
+    uint32_t width, height, flags, max_count;
+} nb_smooth_stats;
+
+/* The smoothed map of a simulator's current state.  s: n smoothing lengths on the host, s[i] that of body i
+ * in the order of nb_sim_read_particles now (a TreeSim reorders its bodies at every step).  counts: height *
+ * width values, row 0 the smallest b; planes: P planes of height * width doubles, plane-major: P = 1 without
+ * NB_SMOOTH_VELOCITY, P = 6 with it, in the order of `terms` above.  counts, planes and stats may each be
+ * null: what is not asked for is not copied, and a call with none of them synchronises and measures nothing.
+ * NB_ERR_INVALID for a null handle or params, what nb_sim_map refuses of the fields the two share, s_min or
+ * s_max not finite, s_min <= 0 or s_max < s_min, unknown flag bits or reserved != 0, a null s with n > 0 --
+ * all checked before any device call.  NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1), and
+ * for more than NB_SMOOTH_MAX_ENTRIES tile entries (a large s_max on a fine grid): the outputs are then
+ * untouched and the simulator stays usable. */
+int nb_sim_smooth_map(nb_sim *sim, const nb_smooth_params *params, const double *s, uint32_t *counts,
+                      double *planes, nb_smooth_stats *stats);
+/* Host only, no device: the `cells` pixel centres of a window [lo, hi) (see above).  NB_ERR_INVALID for what
+ * nb_map_edges refuses. */
+int nb_smooth_centres(double lo, double hi, uint32_t cells, double *out);
+
+/* ------------------------------------------------------------------------- */
 /* Renderer -- frames of the particle state, drawn off screen on the device   */
 /* (the draw pass of OnlineRenderer, src/runners/online_renderer.rs:224-367,  */
 /* and src/draw.wgsl; no window is opened)                                    */
@@ -954,6 +1052,10 @@ int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labe
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
                   double *density, nb_knn_stats *stats);
+/* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,
+                         double *planes, nb_smooth_stats *stats);
 /* nb_sim_render of the runner's simulator (OnlineRenderer::render, online_renderer.rs:331-367).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

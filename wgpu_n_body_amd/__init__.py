@@ -38,6 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
            "FofGroups", "FofStats", "FOF_NONE",
            "KnnDensity", "KnnStats", "KNN_NONE",
+           "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
 PARTICLES_PER_GROUP = 64  # sims/mod.rs:7
@@ -615,6 +616,134 @@ def _knn_density(call, handle, n, k, density, neighbours) -> KnnDensity:
     return KnnDensity(kk, r2, kth, mass_in, rho, _knn_stats(st))
 
 
+SMOOTH_K = _lib.NB_SMOOTH_K
+SMOOTH_PLANES = ("wm", "wm_ua", "wm_ub", "wm_w", "wm_w2", "wm_u2")
+
+
+def smooth_centres(lo: float, hi: float, cells: int) -> np.ndarray:
+    """nb_smooth_centres: the pixel centres of a smoothed map's window, the means of successive map_edges."""
+    out = np.empty(int(cells) if 1 <= int(cells) <= _lib.NB_MAP_MAX_SIDE else 1, dtype=np.float64)
+    check(_lib.lib().nb_smooth_centres(float(lo), float(hi), int(cells), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+@dataclass(frozen=True)
+class SmoothStats:
+    """nb_smooth_stats (include/nbody.h "Smoothed maps").  nonfinite + bad_smoothing + skipped + deposited == n."""
+    step_num: int
+    n: int
+    nonfinite: int
+    bad_smoothing: int    # counted bodies whose smoothing length is NaN
+    skipped: int          # outside the depth slab, or no pixel centre within the smoothing length
+    deposited: int
+    raised: int           # smoothing lengths below s_min
+    lowered: int          # ... above s_max
+    pairs: int            # the sum of counts
+    tile_entries: int     # implementation figure: the (tile, body) entries sorted
+    mass: float           # all counted bodies
+    deposited_mass: float
+    center: np.ndarray
+    velocity: np.ndarray
+    n_hat: np.ndarray
+    e1: np.ndarray
+    e2: np.ndarray
+    s_min: float
+    s_max: float
+    flags: int
+    max_count: int
+
+
+@dataclass(frozen=True)
+class SmoothedMap:
+    """nb_sim_smooth_map's counts, planes and stats (include/nbody.h "Smoothed maps"; no reference counterpart):
+    every body of the state read_particles would return spread over the pixels whose centre lies within its
+    smoothing length, with the kernel (3 / (pi s^2)) (1 - r^2 / s^2)^2.  counts: (H, W) uint32, the bodies that
+    reach a pixel.  planes: (P, H, W) float64, P = 1 or 6 in the order of SMOOTH_PLANES; plane 0 is the surface
+    density itself.  w is the velocity along the line of sight."""
+    counts: np.ndarray
+    planes: np.ndarray
+    x_centres: np.ndarray
+    y_centres: np.ndarray
+    smoothing: np.ndarray  # the n lengths passed to the call (before s_min and s_max)
+    stats: SmoothStats
+
+    def _plane(self, k):
+        if self.planes.shape[0] <= k:
+            raise ValueError("this map was taken without velocities")
+        return self.planes[k]
+
+    def _per_mass(self, k):
+        wm = self.planes[0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(wm != 0.0, self._plane(k) / wm, np.nan)
+
+    @property
+    def surface_density(self) -> np.ndarray:
+        """Plane 0: mass per area of the plane coordinates (0 where no body reaches)."""
+        return self.planes[0]
+
+    @property
+    def mean_w(self) -> np.ndarray:
+        """Kernel- and mass-weighted mean line-of-sight velocity per pixel (NaN where plane 0 is 0)."""
+        return self._per_mass(3)
+
+    @property
+    def sigma_w(self) -> np.ndarray:
+        """The line-of-sight velocity dispersion per pixel: sqrt(max(0, wm_w2 / wm - mean_w^2))."""
+        mean = self.mean_w
+        return np.sqrt(np.maximum(self._per_mass(4) - mean * mean, 0.0))
+
+
+def _smoothed_map(call, handle, n, s, width, height, extent, axis, center, velocity, depth, velocities, s_min,
+                  s_max) -> SmoothedMap:
+    p = _lib.nb_smooth_params()
+    p.width, p.height = int(width), int(height)
+    p.flags = _lib.NB_SMOOTH_VELOCITY if velocities else 0
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com" or three coordinates')
+        if velocity is not None:
+            raise ValueError('center="com" brings its own velocity')
+        p.flags |= _lib.NB_SMOOTH_CENTER_COM
+    else:
+        velocity = (0.0, 0.0, 0.0) if velocity is None else velocity
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    x0, x1, y0, y1 = (float(v) for v in extent)
+    p.x_range[0], p.x_range[1], p.y_range[0], p.y_range[1] = x0, x1, y0, y1
+    p.depth_range[0], p.depth_range[1] = (-np.inf, np.inf) if depth is None else (float(depth[0]), float(depth[1]))
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    ok = 1 <= p.width <= _lib.NB_MAP_MAX_SIDE and 1 <= p.height <= _lib.NB_MAP_MAX_SIDE and \
+        p.width * p.height <= _lib.NB_MAP_MAX_CELLS
+    h, w = (p.height, p.width) if ok else (1, 1)  # (the call refuses the sizes itself)
+    pixel = max(abs(x1 - x0) / w, abs(y1 - y0) / h)
+    p.s_min = 2.0 * pixel if s_min is None else float(s_min)
+    p.s_max = 64.0 * pixel if s_max is None else float(s_max)
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(s, dtype=np.float64), (n,)))
+    nplanes = len(SMOOTH_PLANES) if velocities else 1
+    counts = np.empty((h, w), dtype=np.uint32)
+    planes = np.empty((nplanes, h, w), dtype=np.float64)
+    st = _lib.nb_smooth_stats()
+    check(call(handle, C.byref(p), s.ctypes.data, counts.ctypes.data, planes.ctypes.data, C.byref(st)))
+    vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+    stats = SmoothStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.bad_smoothing), int(st.skipped),
+                        int(st.deposited), int(st.raised), int(st.lowered), int(st.pairs), int(st.tile_entries),
+                        float(st.mass), float(st.deposited_mass), vec(st.center), vec(st.velocity), vec(st.n_hat),
+                        vec(st.e1), vec(st.e2), float(st.s_min), float(st.s_max), int(st.flags), int(st.max_count))
+    return SmoothedMap(counts, planes, smooth_centres(x0, x1, w), smooth_centres(y0, y1, h), s, stats)
+
+
+def _smoothing_lengths(owner, smoothing, k, scale):
+    """The n smoothing lengths of smoothed_map(): "knn" composes knn_density on the host, as center="density"
+    does for the maps."""
+    if isinstance(smoothing, str):
+        if smoothing != "knn":
+            raise ValueError('smoothing is "knn", an array of n or a scalar')
+        return float(scale) * owner.knn_density(k, density=False).r_k
+    return smoothing
+
+
 @dataclass(frozen=True)
 class Camera:
     """nb_camera (`Camera`, online_renderer.rs:12-20)."""
@@ -987,6 +1116,20 @@ class Simulator:
         return _knn_density(_lib.lib().nb_sim_knn, self._h, int(self.sim_params().particle_num), k, density,
                             neighbours)
 
+    def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                     depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
+                     s_min=None, s_max=None) -> SmoothedMap:
+        """The smoothed image of the current state on a width x height grid seen along `axis`
+        (nb_sim_smooth_map): every body spread over the pixels whose centre lies within its smoothing length.
+        extent, axis, center, velocity, depth, velocities: as projected_map (center="density" is not offered).
+        smoothing: "knn" (scale times the distance to the k-th neighbour, from knn_density(k) on the same
+        state), an array of n lengths in the order of read_particles() now, or one length for all.  s_min,
+        s_max: the lengths are raised and lowered to these; default 2 and 64 times the larger side of a pixel."""
+        n = int(self.sim_params().particle_num)
+        s = _smoothing_lengths(self, smoothing, k, scale)
+        return _smoothed_map(_lib.lib().nb_sim_smooth_map, self._h, n, s, width, height, extent, axis, center,
+                             velocity, depth, velocities, s_min, s_max)
+
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):
         """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
@@ -1182,6 +1325,15 @@ class OfflineHeadless:
         """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""
         return _knn_density(_lib.lib().nb_runner_knn, self._h, int(self.sim_params().particle_num), k, density,
                             neighbours)
+
+    def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                     depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
+                     s_min=None, s_max=None) -> SmoothedMap:
+        """nb_runner_smooth_map: Simulator.smoothed_map of the runner's simulator (one device only)."""
+        n = int(self.sim_params().particle_num)
+        s = _smoothing_lengths(self, smoothing, k, scale)
+        return _smoothed_map(_lib.lib().nb_runner_smooth_map, self._h, n, s, width, height, extent, axis, center,
+                             velocity, depth, velocities, s_min, s_max)
 
     def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
                counts: bool = False, **params):

@@ -139,6 +139,24 @@ class nb_knn_stats(C.Structure):
                 ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_smooth_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("x_range", C.c_double * 2), ("y_range", C.c_double * 2), ("depth_range", C.c_double * 2),
+                ("s_min", C.c_double), ("s_max", C.c_double)]
+
+
+class nb_smooth_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("bad_smoothing", C.c_uint64), ("skipped", C.c_uint64), ("deposited", C.c_uint64),
+                ("raised", C.c_uint64), ("lowered", C.c_uint64), ("pairs", C.c_uint64), ("tile_entries", C.c_uint64),
+                ("mass", C.c_double), ("deposited_mass", C.c_double),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("n_hat", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3),
+                ("s_min", C.c_double), ("s_max", C.c_double),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_count", C.c_uint32)]
+
+
 # nb_fof_group[] as a numpy record array
 FOF_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
                             ("mv", "<f8", (3,)), ("mr2", "<f8"), ("mv2", "<f8")])
@@ -161,6 +179,7 @@ assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
 assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
+assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
 NB_INIT_FN = C.CFUNCTYPE(None, C.POINTER(nb_sim_params), C.c_void_p, C.c_void_p)
@@ -177,6 +196,9 @@ NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
+NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
+NB_SMOOTH_MAX_ENTRIES = 1 << 28
 NB_KNN_SPHERE = float("4.1887902047863909846")  # C = 4 pi / 3, the header's literal
 
 # every symbol include/nbody.h declares (tests check the library exports all of them)
@@ -195,6 +217,7 @@ ABI_SYMBOLS = [
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_sim_fof", "nb_runner_fof",
     "nb_sim_knn", "nb_runner_knn",
+    "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
     "nb_runner_set_profiling", "nb_runner_rank_times",
@@ -272,6 +295,9 @@ def lib() -> C.CDLL:
     L.nb_runner_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
     L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
+    L.nb_sim_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
+    L.nb_runner_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
+    L.nb_smooth_centres.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_map_frame.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_map_edges.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]

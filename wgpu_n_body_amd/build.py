@@ -36,6 +36,8 @@ SOURCES = [
     ("nb_fof.hip", ["-ffp-contract=off"]),
     # the neighbour order and the density are specified operation by operation: no FMA contraction
     ("nb_knn.hip", ["-ffp-contract=off"]),
+    # the weight rule is specified operation by operation: no FMA contraction
+    ("nb_smooth.hip", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

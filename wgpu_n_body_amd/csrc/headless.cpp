@@ -10,6 +10,8 @@
 //             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
+//            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
+//             [--smap-center com|X,Y,Z] [--smap-depth LO,HI] [--smap-k 32] [--smap-max PIXELS]]
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
 //            [--knn K [--knn-k 6]]
 //
@@ -45,6 +47,15 @@
 // row 0 the smallest b; --map-depth keeps LO <= h < HI along the line of sight.  One line per map
 // "map <step> <binned> <outside> <nonfinite> <max_count>".  DIR must exist.  The time they take is not
 // part of any "Step Duration"; without --maps the output is unchanged.
+//
+// --smaps DIR writes the smoothed map (nb_runner_knn, then nb_runner_smooth_map with the distance to the k-th
+// neighbour, k = --smap-k, as every body's smoothing length) of step 0 and of every K-th step (--smap-every,
+// default 1) as DIR/smap_<step, 6 digits>.npy: the layout of --maps, shape (7, H, W) -- the counts (the bodies
+// that reach a pixel) as doubles, then the planes wm, wm_ua, wm_ub, wm_w, wm_w2, wm_u2; plane 1 is the surface
+// density.  The lengths are held between 2 and --smap-max (default 64) times the larger side of a pixel; the
+// window, axis, centre and depth options read as those of --maps.  One line per map "smap <step> <deposited>
+// <skipped> <bad_smoothing> <nonfinite> <pairs> <max_count> <tile_entries>".  DIR must exist.  The time they
+// take is not part of any "Step Duration"; without --smaps the output is unchanged.
 //
 // --fof K finds the friends-of-friends groups (nb_runner_fof) of step 0 and of every K-th step: bodies within
 // --fof-link B of each other are friends, the catalogue holds the groups of at least M bodies (--fof-min,
@@ -150,6 +161,39 @@ static void print_rotcurve(nbody::OfflineHeadless<Sim> &runner, const RotcurveOp
                     r.rings[i].a_R, r.rings[i].a_n, r.rings[i].v_c);
 }
 
+// DIR/<name>: NumPy format 1.0, <f8, shape (1 + planes, H, W): the counts as doubles, then the planes
+static bool write_npy_planes(const std::string &path, uint32_t width, uint32_t height, const std::vector<uint32_t> &counts,
+                             const std::vector<double> &planes) {
+    std::FILE *out = std::fopen(path.c_str(), "wb");
+    if (!out) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    // magic, version, a little-endian uint16 header length, the header padded with spaces to a multiple of 64
+    // bytes in all and ended by a newline
+    const size_t cells = (size_t)width * height;
+    char dict[128];
+    const int len = std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (%zu, %u, %u), }",
+                                  1 + planes.size() / cells, height, width);
+    const size_t total = (10 + (size_t)len + 1 + 63) / 64 * 64, hlen = total - 10;
+    std::string head("\x93NUMPY\x01\x00", 8);
+    head += (char)(hlen & 0xff);
+    head += (char)(hlen >> 8);
+    head += dict;
+    head.append(total - 1 - head.size(), ' ');
+    head += '\n';
+    std::vector<double> cnt(cells);
+    for (size_t i = 0; i < cells; ++i) cnt[i] = (double)counts[i];
+    bool ok = std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
+              std::fwrite(cnt.data(), sizeof(double), cells, out) == cells &&
+              std::fwrite(planes.data(), sizeof(double), planes.size(), out) == planes.size();
+    if (std::fclose(out) != 0 || !ok) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    return true;
+}
+
 struct MapOptions {
     std::string dir;
     int every = 1;
@@ -163,36 +207,32 @@ static bool write_map(nbody::OfflineHeadless<Sim> &runner, const MapOptions &mo)
     char name[64];
     std::snprintf(name, sizeof name, "/map_%06llu.npy", (unsigned long long)m.stats.step_num);
     const std::string path = mo.dir + name;
-    std::FILE *out = std::fopen(path.c_str(), "wb");
-    if (!out) {
-        std::fprintf(stderr, "cannot write %s\n", path.c_str());
-        return false;
-    }
-    // NumPy format 1.0: magic, version, a little-endian uint16 header length, the header padded with spaces
-    // to a multiple of 64 bytes in all and ended by a newline
-    char dict[128];
-    const int len = std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (7, %u, %u), }",
-                                  m.height, m.width);
-    const size_t total = (10 + (size_t)len + 1 + 63) / 64 * 64, hlen = total - 10;
-    std::string head("\x93NUMPY\x01\x00", 8);
-    head += (char)(hlen & 0xff);
-    head += (char)(hlen >> 8);
-    head += dict;
-    head.append(total - 1 - head.size(), ' ');
-    head += '\n';
-    const size_t cells = (size_t)m.width * m.height;
-    std::vector<double> cnt(cells);
-    for (size_t i = 0; i < cells; ++i) cnt[i] = (double)m.counts[i];
-    bool ok = std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
-              std::fwrite(cnt.data(), sizeof(double), cells, out) == cells &&
-              std::fwrite(m.planes.data(), sizeof(double), m.planes.size(), out) == m.planes.size();
-    if (std::fclose(out) != 0 || !ok) {
-        std::fprintf(stderr, "cannot write %s\n", path.c_str());
-        return false;
-    }
+    if (!write_npy_planes(path, m.width, m.height, m.counts, m.planes)) return false;
     std::printf("map %llu %llu %llu %llu %u\n", (unsigned long long)m.stats.step_num,
                 (unsigned long long)m.stats.binned_count, (unsigned long long)m.stats.outside_count,
                 (unsigned long long)m.stats.nonfinite, m.stats.max_count);
+    return true;
+}
+
+struct SmapOptions {
+    std::string dir;
+    int every = 1;
+    bool have_size = false, have_extent = false;
+    uint32_t k = 32;
+    double max_pixels = 64.0;
+    nbody::SmoothParams params = nbody::smooth_params(0, 0, 0.0, 0.0, 0.0, 0.0);
+};
+
+template <class Sim>
+static bool write_smap(nbody::OfflineHeadless<Sim> &runner, const SmapOptions &so) {
+    const nbody::SmoothedMap m = runner.smoothed_map_knn(so.params, so.k);
+    char name[64];
+    std::snprintf(name, sizeof name, "/smap_%06llu.npy", (unsigned long long)m.stats.step_num);
+    if (!write_npy_planes(so.dir + name, m.width, m.height, m.counts, m.planes)) return false;
+    std::printf("smap %llu %llu %llu %llu %llu %llu %u %llu\n", (unsigned long long)m.stats.step_num,
+                (unsigned long long)m.stats.deposited, (unsigned long long)m.stats.skipped,
+                (unsigned long long)m.stats.bad_smoothing, (unsigned long long)m.stats.nonfinite,
+                (unsigned long long)m.stats.pairs, m.stats.max_count, (unsigned long long)m.stats.tile_entries);
     return true;
 }
 
@@ -268,7 +308,8 @@ template <class Sim>
 static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbody::InitFn &init,
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
-               const RotcurveOptions &rotcurve, const MapOptions &maps, const FofOptions &fof, const KnnOptions &knn) {
+               const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
+               const KnnOptions &knn) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -277,6 +318,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (radial.every > 0) print_radial(runner, radial);
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
+    if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
     if (knn.every > 0) print_knn(runner, knn);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
@@ -290,6 +332,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
+        if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
@@ -316,6 +359,7 @@ int main(int argc, char **argv) {
     RadialOptions radial;
     RotcurveOptions rotcurve;
     MapOptions maps;
+    SmapOptions smaps;
     FofOptions fof;
     KnnOptions knn;
     uint64_t seed = 0;
@@ -436,6 +480,48 @@ int main(int argc, char **argv) {
         else if (k == "--fof-link") fof.link = std::atof(v.c_str());
         else if (k == "--fof-min") fof.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--fof-top") fof.top = std::atoi(v.c_str());
+        else if (k == "--smaps") smaps.dir = v;
+        else if (k == "--smap-every") smaps.every = std::max(1, std::atoi(v.c_str()));
+        else if (k == "--smap-size") {
+            if (std::sscanf(v.c_str(), "%ux%u", &smaps.params.width, &smaps.params.height) != 2) {
+                std::fprintf(stderr, "--smap-size takes WxH, not %s\n", v.c_str());
+                return 2;
+            }
+            smaps.have_size = true;
+        }
+        else if (k == "--smap-extent") {
+            nbody::SmoothParams &mp = smaps.params;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf", &mp.x_range[0], &mp.x_range[1], &mp.y_range[0], &mp.y_range[1]) != 4) {
+                std::fprintf(stderr, "--smap-extent takes X0,X1,Y0,Y1, not %s\n", v.c_str());
+                return 2;
+            }
+            smaps.have_extent = true;
+        }
+        else if (k == "--smap-axis") {
+            double *a = smaps.params.axis;
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
+                std::fprintf(stderr, "--smap-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--smap-center") {
+            double *c = smaps.params.center;
+            if (v == "com") smaps.params.flags |= NB_SMOOTH_CENTER_COM;
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &c[0], &c[1], &c[2]) == 3)
+                smaps.params.flags &= ~NB_SMOOTH_CENTER_COM;
+            else {
+                std::fprintf(stderr, "--smap-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--smap-depth") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &smaps.params.depth_range[0], &smaps.params.depth_range[1]) != 2) {
+                std::fprintf(stderr, "--smap-depth takes LO,HI, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--smap-k") smaps.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--smap-max") smaps.max_pixels = std::atof(v.c_str());
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--devices") {
@@ -459,6 +545,22 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--maps needs --map-size WxH and --map-extent X0,X1,Y0,Y1\n");
         return 2;
     }
+    if (!smaps.dir.empty()) {
+        nbody::SmoothParams &mp = smaps.params;
+        if (!(smaps.have_size && smaps.have_extent) || mp.width == 0 || mp.height == 0) {
+            std::fprintf(stderr, "--smaps needs --smap-size WxH and --smap-extent X0,X1,Y0,Y1\n");
+            return 2;
+        }
+        if (!(smaps.max_pixels >= 2.0)) {
+            std::fprintf(stderr, "--smap-max takes at least 2 pixels, not %g\n", smaps.max_pixels);
+            return 2;
+        }
+        // the floor of two pixels and the cap, in the larger side of a pixel (nbody::smooth_params)
+        const double pixel = std::max(std::fabs(mp.x_range[1] - mp.x_range[0]) / mp.width,
+                                      std::fabs(mp.y_range[1] - mp.y_range[0]) / mp.height);
+        mp.s_min = 2.0 * pixel;
+        mp.s_max = smaps.max_pixels * pixel;
+    }
     if (fof.every > 0 && !(fof.link > 0.0)) {
         std::fprintf(stderr, "--fof needs --fof-link B > 0\n");
         return 2;
@@ -469,9 +571,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, fof, knn);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, fof, knn);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

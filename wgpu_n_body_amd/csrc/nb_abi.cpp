@@ -679,6 +679,59 @@ static int map_check_params(const nb_map_params *p, MapPlan *plan) {
     return NB_OK;
 }
 
+// nb_smooth_centres / nb_sim_smooth_map: the `cells` pixel centres of a window, from the edges of nb_map_edges
+static void smooth_centres(double lo, double hi, uint32_t cells, double size, double *out) {
+    double prev = lo;  // xe[i]
+    for (uint32_t i = 0; i < cells; ++i) {
+        const double next = i + 1 < cells ? lo + (double)(i + 1) * size : hi;
+        out[i] = 0.5 * (prev + next);
+        prev = next;
+    }
+}
+
+// nb_sim_smooth_map: everything that can be refused without a device, in the words of the pass; the frame, the
+// pixel sizes and the pixel centres on the way.  The fields the two share are checked by map_check_params.
+static int smooth_check_params(const nb_smooth_params *p, SmoothPlan *plan) {
+    if (!p) {
+        set_error("smooth_map: null params");
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~(NB_SMOOTH_CENTER_COM | NB_SMOOTH_VELOCITY)) || p->reserved) {
+        set_error("smooth_map: unknown flag bits 0x%x or reserved %u != 0",
+                  p->flags & ~(NB_SMOOTH_CENTER_COM | NB_SMOOTH_VELOCITY), p->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->s_min) || !std::isfinite(p->s_max) || !(p->s_min > 0.0) || !(p->s_max >= p->s_min)) {
+        set_error("smooth_map: needs finite 0 < s_min <= s_max (got %g, %g)", p->s_min, p->s_max);
+        return NB_ERR_INVALID;
+    }
+    static_assert(NB_SMOOTH_CENTER_COM == NB_MAP_CENTER_COM && NB_SMOOTH_VELOCITY == NB_MAP_VELOCITY, "shared flag bits");
+    nb_map_params m{};
+    m.width = p->width;
+    m.height = p->height;
+    m.flags = p->flags;
+    for (int k = 0; k < 3; ++k) {
+        m.center[k] = p->center[k];
+        m.velocity[k] = p->velocity[k];
+        m.axis[k] = p->axis[k];
+    }
+    for (int k = 0; k < 2; ++k) {
+        m.x_range[k] = p->x_range[k];
+        m.y_range[k] = p->y_range[k];
+        m.depth_range[k] = p->depth_range[k];
+    }
+    if (int rc = map_check_params(&m, &plan->frame)) {
+        const std::string why = g_last_error;  // "map: ..."
+        set_error("smooth_%s", why.c_str());
+        return rc;
+    }
+    plan->xc.resize(p->width);
+    plan->yc.resize(p->height);
+    smooth_centres(p->x_range[0], p->x_range[1], p->width, plan->frame.dx, plan->xc.data());
+    smooth_centres(p->y_range[0], p->y_range[1], p->height, plan->frame.dy, plan->yc.data());
+    return NB_OK;
+}
+
 #define NB_GUARD(body)                                            \
     try {                                                         \
         body                                                      \
@@ -872,6 +925,18 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->map_segment_len = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "smooth_segment_len")) {  // the smoothed maps', whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 256 || value > 65536 || value % 256) {
+            set_error("smooth_segment_len: a multiple of 256 in 256..65536, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->smooth_segment_len = value;
+        return NB_OK;
+    }
     if (!std::strcmp(key, "fof_chunk_len")) {  // the group finder's, whichever simulator holds the state
         if (!sim || !sim->impl) {
             set_error("null simulator");
@@ -1062,6 +1127,34 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
                nb_knn_stats *stats) {
     if (int rc = knn_check_params(params)) return rc;
     NB_SIM_PASS(sim, sim_knn, *params, r2, kth, mass_in, density, stats)
+}
+
+int nb_sim_smooth_map(nb_sim *sim, const nb_smooth_params *params, const double *s, uint32_t *counts, double *planes,
+                      nb_smooth_stats *stats) {
+    NB_GUARD({
+        SmoothPlan plan{};
+        if (int rc = smooth_check_params(params, &plan)) return rc;
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (!s && sim->impl->n > 0) {
+            set_error("smooth_map: null s for %u bodies", sim->impl->n);
+            return NB_ERR_INVALID;
+        }
+        return sim_smooth_map(*sim->impl, *params, plan, s, counts, planes, stats);
+    })
+}
+
+int nb_smooth_centres(double lo, double hi, uint32_t cells, double *out) {
+    if (!out) {
+        set_error("smooth_centres: out is null");
+        return NB_ERR_INVALID;
+    }
+    double d = 0.0;
+    if (int rc = map_cell_size("smooth_centres", lo, hi, cells, &d)) return rc;
+    smooth_centres(lo, hi, cells, d, out);
+    return NB_OK;
 }
 
 int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
@@ -1333,6 +1426,17 @@ int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, ui
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "knn")) return rc;
     return nb_sim_knn(runner->sim, params, r2, kth, mass_in, density, stats);
+}
+
+int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,
+                         double *planes, nb_smooth_stats *stats) {
+    NB_GUARD({
+        SmoothPlan plan{};
+        if (int rc = smooth_check_params(params, &plan)) return rc;
+    })
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "smooth_map")) return rc;
+    return nb_sim_smooth_map(runner->sim, params, s, counts, planes, stats);
 }
 
 int nb_runner_render(nb_runner *runner, const nb_render_params *params, uint8_t *rgba, uint32_t *counts,

@@ -13,7 +13,8 @@ namespace nb {
 struct Workspace {
     virtual ~Workspace() = default;
 };
-enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSlots };
+enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
+                      kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -124,6 +125,7 @@ class SimBase {
     std::unique_ptr<Workspace> work[kWorkSlots];  // the analysis passes' workspaces (nb_analysis.hpp)
     int field_pairs_log2 = 35;  // "field_launch_pairs_log2": pairs per launch of nb_sim_field, 2^16 .. 2^40
     int map_segment_len = 4096;  // "map_segment_len": bodies of a tile summed by one block of nb_sim_map
+    int smooth_segment_len = 4096;  // "smooth_segment_len": entries of a tile summed by one block of nb_sim_smooth_map
     int fof_chunk_len = 1024;    // "fof_chunk_len": bodies of a cell or a catalogue row per work item of nb_sim_fof
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
     int knn_span_cells = 3;      // "knn_span_cells": octree cells per axis the search of nb_sim_knn opens around a body
@@ -165,6 +167,14 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
 // nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);
+// nb_smooth.hip: nb_sim_smooth_map behind the handle (arguments already checked by smooth_check_params,
+// nb_abi.cpp, which also forms the frame, the pixel sizes and the pixel centres)
+struct SmoothPlan {
+    MapPlan frame;
+    std::vector<double> xc, yc;  // nb_smooth_centres of the two windows
+};
+int sim_smooth_map(SimBase &sim, const nb_smooth_params &params, const SmoothPlan &plan, const double *s,
+                   uint32_t *counts, double *planes, nb_smooth_stats *stats);
 // nb_abi.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
 // rule of include/nbody.h); false for an axis without a finite, non-zero length
 bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]);

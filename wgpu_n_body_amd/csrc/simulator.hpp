@@ -42,6 +42,8 @@ using MapStats = nb_map_stats;
 using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sums of a catalogued group
 using FofStats = nb_fof_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
+using SmoothParams = nb_smooth_params;    // a map's parameters and the bounds of the smoothing lengths
+using SmoothStats = nb_smooth_stats;
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
 using RenderParams = nb_render_params;  // size, view-projection matrix and constants of the draw pass
 using RenderStats = nb_render_stats;
@@ -290,6 +292,66 @@ KnnDensity knn_density(int (*call)(H *, const nb_knn_params *, double *, uint32_
 }
 }  // namespace detail
 
+// A smoothed map (no reference counterpart): width * height counts (the bodies that reach a pixel), row 0 the
+// smallest b, the planes (1, or 6 with NB_SMOOTH_VELOCITY: wm, wm_ua, wm_ub, wm_w, wm_w2, wm_u2; plane 0 is the
+// surface density) plane-major, the smoothing lengths that were passed and what the call measured
+struct SmoothedMap {
+    uint32_t width = 0, height = 0, nplanes = 0;
+    std::vector<uint32_t> counts;
+    std::vector<double> planes;
+    std::vector<double> smoothing;
+    SmoothStats stats{};
+    const double *plane(uint32_t k) const { return planes.data() + (size_t)k * width * height; }
+};
+
+// The parameters of a smoothed map of the window [x0, x1) x [y0, y1) about the centre of mass, seen along
+// `axis`, with the velocity planes, no depth cut, and the smoothing lengths held between 2 and 64 times the
+// larger side of a pixel
+inline SmoothParams smooth_params(uint32_t width, uint32_t height, double x0, double x1, double y0, double y1,
+                                  const std::array<double, 3> &axis = {0.0, 1.0, 0.0}) {
+    SmoothParams p{};
+    p.width = width;
+    p.height = height;
+    p.flags = NB_SMOOTH_CENTER_COM | NB_SMOOTH_VELOCITY;
+    for (int k = 0; k < 3; ++k) p.axis[k] = axis[(size_t)k];
+    p.x_range[0] = x0;
+    p.x_range[1] = x1;
+    p.y_range[0] = y0;
+    p.y_range[1] = y1;
+    p.depth_range[0] = -HUGE_VAL;
+    p.depth_range[1] = HUGE_VAL;
+    const double pixel = std::max(width ? std::fabs(x1 - x0) / width : 0.0, height ? std::fabs(y1 - y0) / height : 0.0);
+    p.s_min = 2.0 * pixel;
+    p.s_max = 64.0 * pixel;
+    return p;
+}
+
+namespace detail {
+template <class H>
+SmoothedMap smoothed_map(int (*call)(H *, const nb_smooth_params *, const double *, uint32_t *, double *,
+                                     nb_smooth_stats *),
+                         H *h, size_t n, const SmoothParams &p, std::vector<double> s) {
+    if (s.size() != n) throw Error(NB_ERR_INVALID, "nbody_hip: smoothed_map: one smoothing length per body");
+    SmoothedMap m;
+    const bool ok = p.width >= 1 && p.width <= NB_MAP_MAX_SIDE && p.height >= 1 && p.height <= NB_MAP_MAX_SIDE &&
+                    (uint64_t)p.width * p.height <= NB_MAP_MAX_CELLS;  // (the call refuses the sizes itself)
+    m.width = ok ? p.width : 1;
+    m.height = ok ? p.height : 1;
+    m.nplanes = (p.flags & NB_SMOOTH_VELOCITY) ? 6 : 1;
+    m.counts.resize((size_t)m.width * m.height);
+    m.planes.resize((size_t)m.nplanes * m.width * m.height);
+    m.smoothing = std::move(s);
+    check(call(h, &p, m.smoothing.empty() ? nullptr : m.smoothing.data(), m.counts.data(), m.planes.data(), &m.stats));
+    return m;
+}
+// scale times the distance to the k-th neighbour of every body: the lengths of a smoothed map, composed on the host
+inline std::vector<double> knn_lengths(const KnnDensity &d, double scale) {
+    std::vector<double> s(d.r2.size());
+    for (size_t i = 0; i < s.size(); ++i) s[i] = scale * std::sqrt(d.r2[i]);
+    return s;
+}
+}  // namespace detail
+
 // A frame drawn off screen: width * height RGBA8 pixels, rows top to bottom, and its statistics
 struct Frame {
     uint32_t width = 0, height = 0;
@@ -389,6 +451,14 @@ class Simulator {
     // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
+    }
+    // the smoothed map of the current state: s[i] the smoothing length of body i in the order of read_particles() now
+    SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {
+        return detail::smoothed_map(nb_sim_smooth_map, h_, sim_params().particle_num, p, std::move(s));
+    }
+    // ... with scale times the distance to the k-th neighbour (knn_density(k) on the same state)
+    SmoothedMap smoothed_map_knn(const SmoothParams &p, uint32_t k = 32, double scale = 1.0) {
+        return smoothed_map(p, detail::knn_lengths(knn_density(k, false, true), scale));
     }
     Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
         return detail::field(nb_sim_field, h_, points, flags);
@@ -529,6 +599,14 @@ class OfflineHeadless {
         SimParams sp{};
         check(nb_runner_sim_params(r_, &sp));
         return detail::knn_density(nb_runner_knn, r_, sp.particle_num, k, density, neighbours);
+    }
+    SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::smoothed_map(nb_runner_smooth_map, r_, sp.particle_num, p, std::move(s));
+    }
+    SmoothedMap smoothed_map_knn(const SmoothParams &p, uint32_t k = 32, double scale = 1.0) {  // one device only
+        return smoothed_map(p, detail::knn_lengths(knn_density(k, false, true), scale));
     }
     Field field(const std::vector<float> &points,  // one device only
                 uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
