@@ -713,6 +713,134 @@ int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint3
                nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Bound groups -- which friends-of-friends groups hold together (no reference */
+/* counterpart: every catalogued group unbound on the device)                 */
+/* ------------------------------------------------------------------------- */
+/* Finds the groups of the current state exactly as nb_sim_fof(link, min_members)
+ * does -- the same labels, rows and group_of -- and removes from every catalogued
+ * group, round by round, the members whose energy in the group's own frame is
+ * positive.  The rule, which DESIGN.md 6k states in full.  For catalogue row r the
+ * list L is the bodies with group_of == r in ascending body index; the coupling is
+ * c = (double)g * (double)dt (the convention of nb_sim_diagnostics: U = -g dt W);
+ * the active set starts as A = L; round t = 1, 2, ... does
+ *   1  M = sum_A (double)m and P = sum_A m v in binary64, in a fixed order (below);
+ *      unless M > 0 the group is DISSOLVED (B empty), `iterations` = t - 1
+ *   2  V = P / M
+ *   3  for every i in A: S_i = sum over j in A, j != i, of m_j psi(r_ij), psi the
+ *      potential of the pair force (psi(r) = integral_r^inf ds / (s^3 + e)); the
+ *      per-pair term is binary32 exactly as nb_sim_field and nb_sim_diagnostics
+ *      form it; runs of at most 64 consecutive terms are summed in binary32, every
+ *      run is folded into a binary64 sum and the partial sums are added in binary64
+ *      in a fixed order.  j is excluded by index: a distinct member at the same
+ *      coordinates adds m_j psi(0); with e == 0 a massless j at distance 0 adds 0.
+ *      phi_i = -c S_i
+ *   4  u = (double)v_i - V, k_i = 0.5 ((ux ux + uy uy) + uz uz), e_i = k_i + phi_i;
+ *      one rounding per operation, no contraction
+ *   5  R = { i in A : e_i > 0 }.  R empty: CONVERGED, B = A.  Otherwise A <- A \ R;
+ *      then |A| < min_bound: DISSOLVED, B empty; else t == max_iter: UNCONVERGED,
+ *      B = A after the removal with the values of round t; else round t + 1 runs.
+ *      `iterations` = t
+ * Massless members are tracers: they take part and attract nobody.  A group with
+ * count > max_group (max_group > 0) is SKIPPED: no round runs, its energies are NaN
+ * and its bound_count is 0 -- one round over a group costs count^2 pair terms, and
+ * the caller must be able to refuse that.
+ *   energy[i]    e_i of the last round in which body i was active: > 0 for a removed
+ *                body, <= 0 for one that stayed; NaN for a body of no analysed group
+ *                and where no round ran
+ *   bound_of[i]  the row for i in B, otherwise NB_FOF_NONE
+ *   a row        label and count are nb_sim_fof's.  Over B, with the last round's V
+ *                and phi: mass, mx, mv, mr2 (nb_fof_group's terms), kinetic =
+ *                sum m_i k_i, potential = 1/2 sum m_i phi_i, phi_min = the smallest
+ *                phi_i and most_bound = the smallest body index that has it (NaN and
+ *                NB_FOF_NONE for an empty B).  Over L in round 1: kinetic0 and
+ *                potential0, the same two sums (NaN where no round ran)
+ * The order of every sum is fixed by the group's own list alone.  Position p of a
+ * member is its place in L; a removed member keeps its place with its mass set to 0,
+ * so the runs of step 3 are the positions [64 q, 64 q + 64) whatever A is.  The
+ * j-range of a group of `count` members is cut into segments of
+ * max(1024, 256 ceil(ceil(count / 256) / 8)) positions: at most 8; inside a segment
+ * the runs are folded in order into one binary64 partial, and a row's partials are
+ * added in segment order.  The sums over members go through runs of 64 positions by
+ * the fixed butterfly of nb_sim_fof and the runs are added in order.  So a group's
+ * outputs are a function of its own list and state alone -- not of the other groups,
+ * of group_capacity or of the tuning keys -- and two calls return bit-identical
+ * outputs.  No float atomics.
+ * Against the same rule with S_i in binary64:
+ *   |S_i - S_i(64)| <= 5e-6 sum_j |m_j| psi(r_ij)            (nb_sim_field's bound)
+ * and the integers (bound_of, bound_count, iterations, status) equal the binary64
+ * rule's wherever each of its decisions is decisive:
+ *   |e_i| > 4 (5e-6 c sum_j |m_j| psi(r_ij) + 1e-12 (k_i + |V|^2))   in every round
+ * (by induction over the rounds: equal sets, then phi within the bound, then equal
+ * decisions).  A marginal decision is still deterministic on the device.
+ * Rows beyond group_capacity are not analysed: their bodies have bound_of
+ * NB_FOF_NONE and energy NaN.  group_capacity counts whether or not `groups` is null.
+ * The call is ordered after the enqueued steps on the simulator's stream, enqueues
+ * all max_iter rounds up front (the blocks of a finished group return at once), ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.
+ * "bound_chunk_len" (nb_sim_set_tuning, 64..1048576, a multiple of 64; default 1024):
+ * the j positions one work item takes -- whole segments, at least one.
+ * "bound_tile" (0, 64 or 256; default 0): the members of an i-tile; 0 takes 64 for
+ * groups of at most 256 members and 256 above.  Speed and testing only: neither
+ * changes a bit of the result. */
+#define NB_BOUND_CONVERGED 1u
+#define NB_BOUND_DISSOLVED 2u
+#define NB_BOUND_UNCONVERGED 4u
+#define NB_BOUND_SKIPPED 8u
+#define NB_BOUND_MAX_ITER 64u
+
+typedef struct nb_bound_params {
+    double link;          /* as nb_fof_params */
+    uint32_t min_members; /* as nb_fof_params */
+    uint32_t min_bound;   /* >= 1: a group left with fewer members is dissolved */
+    uint32_t max_iter;    /* 1 .. NB_BOUND_MAX_ITER */
+    uint32_t max_group;   /* 0: no limit; else groups with more members are skipped */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved32;  /* 0 */
+    uint64_t reserved;    /* 0 */
+} nb_bound_params;
+
+typedef struct nb_bound_group {
+    uint32_t label, count;            /* nb_fof_group's */
+    uint32_t bound_count, iterations; /* |B|; rounds that ran */
+    uint32_t status;                  /* one of NB_BOUND_CONVERGED .. NB_BOUND_SKIPPED */
+    uint32_t most_bound;              /* body index, or NB_FOF_NONE */
+    double mass, mx[3], mv[3], mr2;   /* over B */
+    double kinetic, potential, phi_min;
+    double kinetic0, potential0;      /* over L in round 1 */
+} nb_bound_group;
+
+typedef struct nb_bound_stats {
+    uint64_t step_num, n, nonfinite;
+    uint64_t components, groups, grouped_bodies; /* nb_fof_stats' */
+    uint32_t largest_count, largest_label;
+    uint64_t bound_groups; /* analysed rows with a non-empty B */
+    uint64_t bound_bodies; /* sum of their bound_count */
+    uint64_t dissolved, unconverged, skipped; /* analysed rows by status */
+    uint64_t pairs;        /* pair terms evaluated: sum over the rows of iterations * count * (count - 1) */
+    uint32_t rounds_max;   /* the largest `iterations` */
+    uint32_t reserved;
+} nb_bound_stats;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_bound_params) == 40 && sizeof(nb_bound_group) == 128 && sizeof(nb_bound_stats) == 112,
+              "nb_bound_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_bound_params) == 40 && sizeof(nb_bound_group) == 128 && sizeof(nb_bound_stats) == 112,
+               "nb_bound_* layouts");
+#endif
+
+/* The bound groups of a simulator's current state.  group_of and bound_of: n values each; energy: n doubles;
+ * groups: room for group_capacity rows, of which the first min(stats->groups, group_capacity) are written.
+ * Every output pointer may be null: what is not asked for is not copied; a call with none of them
+ * synchronises and measures nothing.  NB_ERR_INVALID for a null handle or params, everything nb_sim_fof
+ * refuses, softening e < 0, max_iter outside 1..NB_BOUND_MAX_ITER, min_bound == 0, unknown flags or a
+ * reserved field != 0 -- all checked before any device call -- and for a state that needs too many cells
+ * (nb_sim_fof); NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_bound(nb_sim *sim, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of, double *energy,
+                 nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
+
+/* ------------------------------------------------------------------------- */
 /* k-nearest-neighbour density -- how dense the state is at every body, and    */
 /* the density centre (no reference counterpart)                              */
 /* ------------------------------------------------------------------------- */
@@ -1048,6 +1176,10 @@ int nb_runner_map(nb_runner *runner, const nb_map_params *params, uint32_t *coun
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of,
                   nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
+/* nb_sim_bound of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
+int nb_runner_bound(nb_runner *runner, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of,
+                    double *energy, nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
 /* nb_sim_knn of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,

@@ -37,6 +37,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
            "FofGroups", "FofStats", "FOF_NONE",
+           "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
@@ -531,6 +532,124 @@ def _fof_groups(call, handle, n, link, min_members, labels) -> FofGroups:
                      int(st.grouped_bodies), int(st.largest_count), int(st.largest_label),
                      tuple(int(c) for c in st.cells), float(st.cell_side))
     return FofGroups(lab, gof, rows[:stats.groups], float(link), mm, stats)
+
+
+BOUND_CONVERGED, BOUND_DISSOLVED = _lib.NB_BOUND_CONVERGED, _lib.NB_BOUND_DISSOLVED
+BOUND_UNCONVERGED, BOUND_SKIPPED = _lib.NB_BOUND_UNCONVERGED, _lib.NB_BOUND_SKIPPED
+
+
+@dataclass(frozen=True)
+class BoundStats:
+    """nb_bound_stats (include/nbody.h "Bound groups")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    components: int
+    groups: int
+    grouped_bodies: int
+    largest_count: int
+    largest_label: int
+    bound_groups: int     # analysed rows with a non-empty bound set
+    bound_bodies: int
+    dissolved: int
+    unconverged: int
+    skipped: int
+    pairs: int            # pair terms evaluated
+    rounds_max: int
+
+
+@dataclass(frozen=True)
+class BoundGroups:
+    """nb_sim_bound's catalogue (include/nbody.h "Bound groups"; no reference counterpart): the
+    friends-of-friends groups of the state read_particles would return, each unbound round by round in its own
+    frame.  group_of: (n,) uint32, as FofGroups.  bound_of: (n,) uint32, the row for a body of the row's bound
+    set, FOF_NONE otherwise; energy: (n,) float64, a body's energy in the last round it was active in, NaN for
+    a body of no analysed group (both None when not asked for).  rows: _lib.BOUND_GROUP_DTYPE records in
+    ascending label order; the sums are over the bound set."""
+    group_of: np.ndarray
+    bound_of: Optional[np.ndarray]
+    energy: Optional[np.ndarray]
+    rows: np.ndarray
+    link: float
+    min_members: int
+    min_bound: int
+    max_iter: int
+    max_group: int
+    stats: BoundStats
+
+    def _per_mass(self, a):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return a / (self.mass if a.ndim == 1 else self.mass[:, None])
+
+    @property
+    def label(self) -> np.ndarray:
+        return self.rows["label"]
+
+    @property
+    def count(self) -> np.ndarray:
+        return self.rows["count"]
+
+    @property
+    def bound_count(self) -> np.ndarray:
+        return self.rows["bound_count"]
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.rows["status"]
+
+    @property
+    def mass(self) -> np.ndarray:
+        return self.rows["mass"]
+
+    @property
+    def com(self) -> np.ndarray:
+        """(groups, 3): sum m x / sum m over the bound set (NaN for an empty one)."""
+        return self._per_mass(self.rows["mx"])
+
+    @property
+    def velocity(self) -> np.ndarray:
+        """(groups, 3): sum m v / sum m over the bound set."""
+        return self._per_mass(self.rows["mv"])
+
+    @property
+    def bound_fraction(self) -> np.ndarray:
+        """bound_count / count."""
+        return self.rows["bound_count"] / self.rows["count"]
+
+    @property
+    def virial_ratio(self) -> np.ndarray:
+        """2 K / |U| of the whole friends-of-friends group in round 1 (kinetic0, potential0): 1 in virial
+        equilibrium, above 2 unbound as a whole; NaN where no round ran."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return 2.0 * self.rows["kinetic0"] / np.abs(self.rows["potential0"])
+
+    def by_bound_mass(self) -> np.ndarray:
+        """The rows' numbers by bound mass, descending, ties by label (ascending)."""
+        return np.lexsort((self.rows["label"], -self.rows["mass"]))
+
+
+def _bound_groups(call, handle, n, link, min_members, min_bound, max_iter, max_group, per_body) -> BoundGroups:
+    p = _lib.nb_bound_params()
+    mm = int(min_members)
+    mb = mm if min_bound is None else int(min_bound)
+    for name, v in (("min_members", mm), ("min_bound", mb), ("max_iter", max_iter), ("max_group", max_group)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:  # (the call itself refuses the zeros that mean nothing)
+            raise ValueError(f"bound_groups: {name} = {v} is not a 32-bit count")
+    p.link, p.flags, p.reserved32, p.reserved = float(link), 0, 0, 0
+    p.min_members, p.min_bound, p.max_iter, p.max_group = mm, mb, int(max_iter), int(max_group)
+    cap = n // mm if mm >= 1 else 0  # the most there can be
+    gof = np.empty(n, dtype=np.uint32)
+    bof = np.empty(n, dtype=np.uint32) if per_body else None
+    en = np.empty(n, dtype=np.float64) if per_body else None
+    rows = np.zeros(cap, dtype=_lib.BOUND_GROUP_DTYPE)
+    st = _lib.nb_bound_stats()
+    check(call(handle, C.byref(p), gof.ctypes.data, bof.ctypes.data if per_body else None,
+               en.ctypes.data if per_body else None, rows.ctypes.data, cap, C.byref(st)))
+    stats = BoundStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.components), int(st.groups),
+                       int(st.grouped_bodies), int(st.largest_count), int(st.largest_label), int(st.bound_groups),
+                       int(st.bound_bodies), int(st.dissolved), int(st.unconverged), int(st.skipped), int(st.pairs),
+                       int(st.rounds_max))
+    return BoundGroups(gof, bof, en, rows[:stats.groups], float(link), mm, mb, int(max_iter), int(max_group), stats)
 
 
 KNN_NONE = _lib.NB_KNN_NONE
@@ -1108,6 +1227,16 @@ class Simulator:
         return _fof_groups(_lib.lib().nb_sim_fof, self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
 
+    def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
+                     max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:
+        """The friends-of-friends groups of the current state (as fof_groups(link, min_members=...)), each
+        unbound on the device (nb_sim_bound): round by round the members with positive energy in the group's
+        own frame leave, until nobody does, fewer than min_bound (default min_members) are left, or max_iter
+        rounds have run.  A group of more than max_group members (0: no limit) is skipped: a round costs
+        count^2 pair terms.  per_body=False leaves bound_of and energy on the device."""
+        return _bound_groups(_lib.lib().nb_sim_bound, self._h, int(self.sim_params().particle_num), link,
+                             min_members, min_bound, max_iter, max_group, per_body)
+
     def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
         """The k-th nearest neighbour of every body of the current state, the mass inside it and the density
         from them (nb_sim_knn), with the density-weighted sums: .center is the density centre of Casertano &
@@ -1320,6 +1449,12 @@ class OfflineHeadless:
         """nb_runner_fof: Simulator.fof_groups of the runner's simulator (one device only)."""
         return _fof_groups(_lib.lib().nb_runner_fof, self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
+
+    def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
+                     max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:
+        """nb_runner_bound: Simulator.bound_groups of the runner's simulator (one device only)."""
+        return _bound_groups(_lib.lib().nb_runner_bound, self._h, int(self.sim_params().particle_num), link,
+                             min_members, min_bound, max_iter, max_group, per_body)
 
     def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
         """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""

@@ -127,6 +127,29 @@ class nb_fof_stats(C.Structure):
                 ("reserved", C.c_uint32), ("cell_side", C.c_double)]
 
 
+class nb_bound_params(C.Structure):
+    _fields_ = [("link", C.c_double), ("min_members", C.c_uint32), ("min_bound", C.c_uint32),
+                ("max_iter", C.c_uint32), ("max_group", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved32", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_bound_group(C.Structure):
+    _fields_ = [("label", C.c_uint32), ("count", C.c_uint32), ("bound_count", C.c_uint32),
+                ("iterations", C.c_uint32), ("status", C.c_uint32), ("most_bound", C.c_uint32),
+                ("mass", C.c_double), ("mx", C.c_double * 3), ("mv", C.c_double * 3), ("mr2", C.c_double),
+                ("kinetic", C.c_double), ("potential", C.c_double), ("phi_min", C.c_double),
+                ("kinetic0", C.c_double), ("potential0", C.c_double)]
+
+
+class nb_bound_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("components", C.c_uint64), ("groups", C.c_uint64), ("grouped_bodies", C.c_uint64),
+                ("largest_count", C.c_uint32), ("largest_label", C.c_uint32),
+                ("bound_groups", C.c_uint64), ("bound_bodies", C.c_uint64), ("dissolved", C.c_uint64),
+                ("unconverged", C.c_uint64), ("skipped", C.c_uint64), ("pairs", C.c_uint64),
+                ("rounds_max", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class nb_knn_params(C.Structure):
     _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
@@ -161,6 +184,12 @@ class nb_smooth_stats(C.Structure):
 FOF_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
                             ("mv", "<f8", (3,)), ("mr2", "<f8"), ("mv2", "<f8")])
 
+# nb_bound_group[] as a numpy record array
+BOUND_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("bound_count", "<u4"), ("iterations", "<u4"),
+                              ("status", "<u4"), ("most_bound", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
+                              ("mv", "<f8", (3,)), ("mr2", "<f8"), ("kinetic", "<f8"), ("potential", "<f8"),
+                              ("phi_min", "<f8"), ("kinetic0", "<f8"), ("potential0", "<f8")])
+
 # nb_field_sample[] and nb_field_ring[] as numpy record arrays
 FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
 FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
@@ -178,6 +207,8 @@ assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
 assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
+assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
+assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
@@ -195,6 +226,8 @@ NB_FIELD_MAX_POINTS = 1 << 24
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
+NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
+NB_BOUND_MAX_ITER = 64
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
@@ -216,6 +249,7 @@ ABI_SYMBOLS = [
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_sim_fof", "nb_runner_fof",
+    "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
@@ -293,6 +327,8 @@ def lib() -> C.CDLL:
     L.nb_runner_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
     L.nb_sim_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
     L.nb_runner_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
+    L.nb_sim_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
+    L.nb_runner_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
     L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_sim_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]

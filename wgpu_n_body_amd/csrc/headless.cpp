@@ -13,6 +13,7 @@
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
 //             [--smap-center com|X,Y,Z] [--smap-depth LO,HI] [--smap-k 32] [--smap-max PIXELS]]
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
+//            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
 //            [--knn K [--knn-k 6]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
@@ -63,6 +64,15 @@
 // (--fof-top, default 0) as "fof_group <step> <row> <label> <count> <mass> <x> <y> <z>" (%.9e: the mass and the
 // centre of mass).  The time they take is not part of any "Step Duration"; without --fof the output is
 // unchanged.
+//
+// --bound K unbinds the friends-of-friends groups (nb_runner_bound) of step 0 and of every K-th step: the groups of
+// --bound-link B and at least M bodies (--bound-min, default 20; also the fewest a bound set may keep), at most I
+// rounds (--bound-iter, default 32), groups of more than G bodies skipped (--bound-max-group, default 262144; 0:
+// none).  One line "bound <step> <groups> <bound_groups> <bound_bodies> <dissolved> <unconverged> <skipped>
+// <rounds_max> <pairs>", then the T rows of the largest bound mass (--bound-top, default 0) as "bound_group <step>
+// <row> <label> <count> <bound_count> <iterations> <status> <mass> <x> <y> <z> <kinetic> <potential>" (%.9e: the
+// bound mass, its centre of mass and its energies).  The time they take is not part of any "Step Duration";
+// without --bound the output is unchanged.
 //
 // --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
 // every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
@@ -256,6 +266,29 @@ static void print_fof(nbody::OfflineHeadless<Sim> &runner, const FofOptions &fo)
     }
 }
 
+struct BoundOptions {
+    int every = 0, top = 0;
+    double link = 0.0;
+    uint32_t min_members = 20, max_iter = 32, max_group = 262144;
+};
+
+template <class Sim>
+static void print_bound(nbody::OfflineHeadless<Sim> &runner, const BoundOptions &bo) {
+    const nbody::BoundGroups g = runner.bound_groups(bo.link, bo.min_members, 0, bo.max_iter, bo.max_group, false);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("bound %llu %llu %llu %llu %llu %llu %llu %u %llu\n", step, (unsigned long long)g.stats.groups,
+                (unsigned long long)g.stats.bound_groups, (unsigned long long)g.stats.bound_bodies,
+                (unsigned long long)g.stats.dissolved, (unsigned long long)g.stats.unconverged,
+                (unsigned long long)g.stats.skipped, g.stats.rounds_max, (unsigned long long)g.stats.pairs);
+    const std::vector<uint32_t> order = g.by_bound_mass();
+    for (size_t k = 0; k < order.size() && k < (size_t)bo.top; ++k) {
+        const nbody::BoundGroup &r = g.groups[order[k]];
+        std::printf("bound_group %llu %u %u %u %u %u %u %.9e %.9e %.9e %.9e %.9e %.9e\n", step, order[k], r.label,
+                    r.count, r.bound_count, r.iterations, r.status, r.mass, r.mx[0] / r.mass, r.mx[1] / r.mass,
+                    r.mx[2] / r.mass, r.kinetic, r.potential);
+    }
+}
+
 struct KnnOptions {
     int every = 0;
     uint32_t k = 6;
@@ -309,7 +342,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
-               const KnnOptions &knn) {
+               const KnnOptions &knn, const BoundOptions &bound) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -320,6 +353,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
+    if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
@@ -334,6 +368,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
+        if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
@@ -362,6 +397,7 @@ int main(int argc, char **argv) {
     SmapOptions smaps;
     FofOptions fof;
     KnnOptions knn;
+    BoundOptions bound;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -480,6 +516,12 @@ int main(int argc, char **argv) {
         else if (k == "--fof-link") fof.link = std::atof(v.c_str());
         else if (k == "--fof-min") fof.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--fof-top") fof.top = std::atoi(v.c_str());
+        else if (k == "--bound") bound.every = std::atoi(v.c_str());
+        else if (k == "--bound-link") bound.link = std::atof(v.c_str());
+        else if (k == "--bound-min") bound.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--bound-iter") bound.max_iter = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--bound-max-group") bound.max_group = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--bound-top") bound.top = std::atoi(v.c_str());
         else if (k == "--smaps") smaps.dir = v;
         else if (k == "--smap-every") smaps.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--smap-size") {
@@ -565,15 +607,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--fof needs --fof-link B > 0\n");
         return 2;
     }
+    if (bound.every > 0 && !(bound.link > 0.0)) {
+        std::fprintf(stderr, "--bound needs --bound-link B > 0\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -598,6 +598,42 @@ static int fof_check_params(const nb_fof_params *p) {
     return NB_OK;
 }
 
+// nb_sim_bound: everything that can be refused without a device (the softening is the simulator's: bound_check_e)
+static int bound_check_params(const nb_bound_params *p) {
+    if (!p) {
+        set_error("bound: null params");
+        return NB_ERR_INVALID;
+    }
+    nb_fof_params fp{};
+    fp.link = p->link;
+    fp.min_members = p->min_members;
+    if (int rc = fof_check_params(&fp)) return rc;
+    if (p->max_iter < 1 || p->max_iter > NB_BOUND_MAX_ITER) {
+        set_error("bound: max_iter must be 1..%u (got %u)", NB_BOUND_MAX_ITER, p->max_iter);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_bound < 1) {
+        set_error("bound: min_bound must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved32 || p->reserved) {
+        set_error("bound: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+static int bound_check_e(const nb_sim *sim) {
+    if (!sim || !sim->impl) {
+        set_error("null simulator");
+        return NB_ERR_INVALID;
+    }
+    if (!(sim->impl->params.e >= 0.f)) {
+        set_error("bound: the pair potential needs e >= 0 (e = %g)", (double)sim->impl->params.e);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_sim_knn: everything that can be refused without a device
 static int knn_check_params(const nb_knn_params *p) {
     if (!p) {
@@ -961,6 +997,30 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->fof_cell_boxes = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "bound_chunk_len")) {  // the unbinding's, whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 64 || value > 1048576 || value % 64) {
+            set_error("bound_chunk_len: a multiple of 64 in 64..1048576, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->bound_chunk_len = value;
+        return NB_OK;
+    }
+    if (!std::strcmp(key, "bound_tile")) {
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value != 0 && value != 64 && value != 256) {
+            set_error("bound_tile: 0, 64 or 256, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->bound_tile = value;
+        return NB_OK;
+    }
     if (!std::strcmp(key, "knn_span_cells")) {  // the neighbour search's, whichever simulator holds the state
         if (!sim || !sim->impl) {
             set_error("null simulator");
@@ -1121,6 +1181,13 @@ int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint3
                size_t group_capacity, nb_fof_stats *stats) {
     if (int rc = fof_check_params(params)) return rc;
     NB_SIM_PASS(sim, sim_fof, *params, labels, group_of, groups, group_capacity, stats)
+}
+
+int nb_sim_bound(nb_sim *sim, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of, double *energy,
+                 nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats) {
+    if (int rc = bound_check_params(params)) return rc;
+    if (int rc = bound_check_e(sim)) return rc;
+    NB_SIM_PASS(sim, sim_bound, *params, group_of, bound_of, energy, groups, group_capacity, stats)
 }
 
 int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in, double *density,
@@ -1418,6 +1485,14 @@ int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labe
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "fof")) return rc;
     return nb_sim_fof(runner->sim, params, labels, group_of, groups, group_capacity, stats);
+}
+
+int nb_runner_bound(nb_runner *runner, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of,
+                    double *energy, nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats) {
+    if (int rc = bound_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "bound")) return rc;
+    return nb_sim_bound(runner->sim, params, group_of, bound_of, energy, groups, group_capacity, stats);
 }
 
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,

@@ -43,6 +43,7 @@
 #include "nb_analysis.hpp"
 #include "nb_analysis_sort.hpp"
 #include "nb_common.hpp"
+#include "nb_fof.hpp"
 #include "nb_sim.hpp"
 
 namespace nb {
@@ -55,20 +56,6 @@ constexpr uint32_t kTerms = 9;           // the sums of a catalogue row
 constexpr uint32_t kRowLanes = 16;       // lanes per row of the combine kernel
 constexpr uint32_t kNeighbours = 62;     // forward neighbours within +-2 cells per axis: (5^3 - 1) / 2
 constexpr double kMaxCells = (double)NB_FOF_MAX_CELLS_PER_AXIS;
-
-// The plan and the integer results of a call, on the device.  Written by single threads or integer atomics.
-struct FofInfo {
-    double lo[3];
-    double h;
-    unsigned long long total;      // cells of the grid = the key of a body that does not count
-    unsigned long long nx, ny, nz;
-    unsigned long long grouped_bodies, largest;  // largest: count << 32 | ~label
-    uint32_t status;               // 1: refused, too many cells on an axis
-    uint32_t n_ok, ncells;
-    uint32_t passes[2];            // sort passes in use: the cell keys', the rows'
-    uint32_t components, groups, rows;  // rows = min(groups, capacity): the key past the last row
-    uint32_t row_bodies;           // bodies of the rows below `rows`
-};
 
 __host__ __device__ inline uint32_t bits_of(unsigned long long x) {
     uint32_t b = 0;
@@ -301,29 +288,6 @@ __device__ inline bool friends(float4 p, float4 q, double b2) {
     return (dx * dx + dy * dy) + dz * dz <= b2;
 }
 
-// The list of work item g among lists l = 0 .. count - 1 of positions [start[l], start[l + 1]), cut into chunks
-// of len: list l owns the items start[l] / len + l onwards, which are at least its chunks.  False for an item
-// no list owns.  *a0, *a1: the chunk's positions; *s: its number in the list.
-__device__ inline bool item_chunk(const uint32_t *__restrict__ start, uint32_t count, uint32_t len, uint32_t g,
-                                  uint32_t *l_out, uint32_t *s_out, uint32_t *a0, uint32_t *a1) {
-    if (count == 0) return false;
-    uint32_t lo = 0, hi = count;  // start[0] / len + 0 = 0 <= g
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if ((unsigned long long)start[mid] / len + mid <= g) lo = mid;
-        else hi = mid;
-    }
-    const uint32_t s = g - (start[lo] / len + lo);
-    const unsigned long long first = (unsigned long long)start[lo] + (unsigned long long)s * len;
-    const uint32_t end = start[lo + 1];
-    if (first >= end) return false;
-    *l_out = lo;
-    *s_out = s;
-    *a0 = (uint32_t)first;
-    *a1 = (uint32_t)std::min<unsigned long long>(end, first + len);
-    return true;
-}
-
 __global__ __launch_bounds__(kWave) void fof_union_kernel(const FofInfo *__restrict__ info,
                                                           const unsigned long long *__restrict__ cell_key,
                                                           const uint32_t *__restrict__ cell_start,
@@ -531,9 +495,6 @@ __device__ inline void terms(float4 p, float4 v, double (&t)[kTerms]) {
     t[8] = m * ((vx * vx + vy * vy) + vz * vz);
 }
 
-// the first run slot of row r: rows before it hold at most start / 64 + r runs
-__device__ inline size_t run_slot(uint32_t start, uint32_t r) { return (size_t)start / kWave + r; }
-
 // One wave per chunk of a row's list: every run of 64 members (from the row's start) through the butterfly
 // into its slot.
 __global__ __launch_bounds__(kWave) void fof_sum_kernel(const FofInfo *__restrict__ info,
@@ -586,25 +547,6 @@ __global__ __launch_bounds__(kThreads) void fof_combine_kernel(const FofInfo *__
 
 static_assert(sizeof(nb_fof_group) == 8 + 8 * kTerms && offsetof(nb_fof_group, mass) == 8, "nine doubles after the header");
 
-struct FofWork : Workspace {  // (all but the last two grow to the largest call so far)
-    SortBufs<unsigned long long> sort;      // the two sides of both sorts, the histogram
-    DeviceBuf<double> slabs;                // [bounds blocks][kBoundFields]
-    DeviceBuf<uint32_t> flags, excl;        // [n]: what a scan reads and writes
-    DeviceBuf<uint32_t> block_tot;          // [scan blocks + 1]: the blocks' sums, then the sum of all
-    DeviceBuf<unsigned long long> cell_key; // [n]
-    DeviceBuf<uint32_t> cell_start;         // [n + 1]
-    DeviceBuf<uint32_t> boxes;              // [n][6]
-    DeviceBuf<float4> spos;                 // [n]: positions in sorted order
-    DeviceBuf<uint32_t> parent, labels, count, row_of, group_of;  // [n]
-    DeviceBuf<uint32_t> row_start;          // [rows possible + 1]
-    DeviceBuf<double> runs;                 // [run slots][kTerms]
-    DeviceBuf<nb_fof_group> rows;           // [rows possible]
-    PinnedBuf<uint32_t> h_labels, h_group_of;  // [n]: staged, so that a refused call leaves the outputs alone
-    PinnedBuf<nb_fof_group> h_rows;
-    DeviceBuf<FofInfo> info;                // [1]
-    PinnedBuf<FofInfo> h_info;              // [1]
-};
-
 namespace {
 
 template <class B>
@@ -627,42 +569,39 @@ int enqueue_scan(SimBase &sim, FofWork &w, uint32_t scan_blocks, uint32_t *total
 
 }  // namespace
 
-int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
-            size_t group_capacity, nb_fof_stats *stats) {
-    if (int rc = analysis_begin(sim, "fof")) return rc;
-    if (!groups) group_capacity = 0;
-    if (!labels && !group_of && !groups && !stats) {  // nothing to measure
-        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
-        return sim.diag_status();
-    }
+static double fof_cell_side(double link) { return (link / std::sqrt(3.0)) * (1.0 - 0x1p-20); }
+
+int fof_work(SimBase &sim, FofWork **out) {
+    return workspace(sim, kWorkFof, out, [](FofWork &f) {
+        if (f.info.reserve(1) != hipSuccess || f.h_info.reserve(1) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("fof: cannot allocate the result workspace");
+            return NB_ERR_ALLOC;
+        }
+        return NB_OK;
+    });
+}
+
+int fof_refused(const nb_fof_params &params) {
+    set_error("fof: link %g needs more than %u cells on an axis over this state's extent: it is below the "
+              "resolution of binary32 coordinates there",
+              params.link, NB_FOF_MAX_CELLS_PER_AXIS);
+    return NB_ERR_INVALID;
+}
+
+int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t rows_cap, bool want_group_of,
+                bool sums) {
     const uint32_t n = sim.n;
     const double b2 = params.link * params.link;  // (positive and finite: fof_check_params)
-    const double h = (params.link / std::sqrt(3.0)) * (1.0 - 0x1p-20);
+    const double h = fof_cell_side(params.link);
     const uint32_t len = (uint32_t)sim.fof_chunk_len, use_boxes = (uint32_t)sim.fof_cell_boxes;
-    // the most rows there can be, and those the caller has room for
-    const uint32_t rows_cap = (uint32_t)std::min<size_t>(group_capacity, n / params.min_members);
     const unsigned long long union_items = (unsigned long long)n / len + n + 1;
     const unsigned long long sum_items = (unsigned long long)n / len + rows_cap + 1;
     if (union_items > 0x7fffffffull) {
         set_error("fof: %u bodies are more than one call takes", n);
         return NB_ERR_UNSUPPORTED;
     }
-    FofWork *work = nullptr;
-    if (int rc = workspace(sim, kWorkFof, &work, [](FofWork &f) {
-            if (f.info.reserve(1) != hipSuccess || f.h_info.reserve(1) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("fof: cannot allocate the result workspace");
-                return NB_ERR_ALLOC;
-            }
-            return NB_OK;
-        }))
-        return rc;
-    FofWork &w = *work;
-    FofInfo &res = *static_cast<FofInfo *>(w.h_info);
-    std::memset(&res, 0, sizeof res);
-    res.h = h;  // (largest = 0: count 0, label NB_FOF_NONE)
-
-    if (n > 0) {
+    {
         const uint32_t blocks = (n + kThreads - 1) / kThreads;
         const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
         const SortShape shape = sort_shape(n);
@@ -681,15 +620,10 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
         if (int rc = fof_reserve(w.count, n)) return rc;
         if (int rc = fof_reserve(w.row_of, n)) return rc;
         if (int rc = fof_reserve(w.group_of, n)) return rc;
-        if (labels)
-            if (int rc = fof_reserve(w.h_labels, n)) return rc;
-        if (group_of)
-            if (int rc = fof_reserve(w.h_group_of, n)) return rc;
         if (rows_cap > 0) {
             if (int rc = fof_reserve(w.row_start, (size_t)rows_cap + 1)) return rc;
             if (int rc = fof_reserve(w.runs, run_slots * kTerms)) return rc;
             if (int rc = fof_reserve(w.rows, rows_cap)) return rc;
-            if (int rc = fof_reserve(w.h_rows, rows_cap)) return rc;
         }
 
         const float4 *posm = nullptr, *vel = nullptr;
@@ -735,7 +669,7 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
         hipLaunchKernelGGL(fof_rows_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.flags, w.excl,
                            w.block_tot, w.count, n, w.row_of, rows);
         NB_HIP_TRY(hipGetLastError());
-        if (group_of || rows_cap > 0) {
+        if (want_group_of || rows_cap > 0) {
             hipLaunchKernelGGL(fof_group_of_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.row_of,
                                n, w.group_of, rows_cap > 0 ? (unsigned long long *)keys[0] : nullptr);
             NB_HIP_TRY(hipGetLastError());
@@ -746,15 +680,48 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
             hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0],
                                keys[1], n, w.row_start);
             NB_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm, vel,
-                               idx[0], idx[1], w.row_start, len, w.runs);
-            NB_HIP_TRY(hipGetLastError());
-            const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
-            hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info, w.row_start,
-                               w.runs, rows);
-            NB_HIP_TRY(hipGetLastError());
+            if (sums) {
+                hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm,
+                                   vel, idx[0], idx[1], w.row_start, len, w.runs);
+                NB_HIP_TRY(hipGetLastError());
+                const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
+                hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info,
+                                   w.row_start, w.runs, rows);
+                NB_HIP_TRY(hipGetLastError());
+            }
         }
-        NB_HIP_TRY(hipMemcpyAsync(w.h_info, info, sizeof(FofInfo), hipMemcpyDeviceToHost, sim.stream));
+    }
+    return NB_OK;
+}
+
+int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+            size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = analysis_begin(sim, "fof")) return rc;
+    if (!groups) group_capacity = 0;
+    if (!labels && !group_of && !groups && !stats) {  // nothing to measure
+        NB_HIP_TRY(hipStreamSynchronize(sim.stream));
+        return sim.diag_status();
+    }
+    const uint32_t n = sim.n;
+    const double h = fof_cell_side(params.link);
+    // the most rows there can be, and those the caller has room for
+    const uint32_t rows_cap = fof_rows_cap(n, group_capacity, params.min_members);
+    FofWork *work = nullptr;
+    if (int rc = fof_work(sim, &work)) return rc;
+    FofWork &w = *work;
+    FofInfo &res = *static_cast<FofInfo *>(w.h_info);
+    std::memset(&res, 0, sizeof res);
+    res.h = h;  // (largest = 0: count 0, label NB_FOF_NONE)
+
+    if (n > 0) {
+        if (labels)
+            if (int rc = fof_reserve(w.h_labels, n)) return rc;
+        if (group_of)
+            if (int rc = fof_reserve(w.h_group_of, n)) return rc;
+        if (rows_cap > 0)
+            if (int rc = fof_reserve(w.h_rows, rows_cap)) return rc;
+        if (int rc = fof_enqueue(sim, w, params, rows_cap, group_of != nullptr, true)) return rc;
+        NB_HIP_TRY(hipMemcpyAsync(w.h_info, w.info, sizeof(FofInfo), hipMemcpyDeviceToHost, sim.stream));
         if (labels)
             NB_HIP_TRY(hipMemcpyAsync(w.h_labels, w.labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, sim.stream));
         if (group_of)
@@ -765,12 +732,7 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
     }
     NB_HIP_TRY(hipStreamSynchronize(sim.stream));
     if (int rc = sim.diag_status()) return rc;
-    if (res.status) {
-        set_error("fof: link %g needs more than %u cells on an axis over this state's extent: it is below the "
-                  "resolution of binary32 coordinates there",
-                  params.link, NB_FOF_MAX_CELLS_PER_AXIS);
-        return NB_ERR_INVALID;
-    }
+    if (res.status) return fof_refused(params);
     if (n > 0) {
         if (labels) std::memcpy(labels, w.h_labels, sizeof(uint32_t) * n);
         if (group_of) std::memcpy(group_of, w.h_group_of, sizeof(uint32_t) * n);

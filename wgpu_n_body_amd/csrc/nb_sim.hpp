@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkSlots };
+                      kWorkBound, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -128,6 +128,8 @@ class SimBase {
     int smooth_segment_len = 4096;  // "smooth_segment_len": entries of a tile summed by one block of nb_sim_smooth_map
     int fof_chunk_len = 1024;    // "fof_chunk_len": bodies of a cell or a catalogue row per work item of nb_sim_fof
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
+    int bound_chunk_len = 1024;  // "bound_chunk_len": j positions of a group per work item of nb_sim_bound's pair pass
+    int bound_tile = 0;          // "bound_tile": members per i-tile of that pass, 64 or 256; 0 chooses by the group's size
     int knn_span_cells = 3;      // "knn_span_cells": octree cells per axis the search of nb_sim_knn opens around a body
     int knn_block_queries = 4;   // "knn_block_queries": bodies (a wave each) per block of that search
 };
@@ -164,6 +166,9 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
 // nb_fof.hip: nb_sim_fof behind the handle (arguments already checked by fof_check_params, nb_abi.cpp)
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
             size_t group_capacity, nb_fof_stats *stats);
+// nb_bound.hip: nb_sim_bound behind the handle (arguments already checked by bound_check_params, nb_abi.cpp)
+int sim_bound(SimBase &sim, const nb_bound_params &params, uint32_t *group_of, uint32_t *bound_of, double *energy,
+              nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
 // nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);

@@ -41,6 +41,8 @@ using MapParams = nb_map_params;          // grid, window, line of sight and cen
 using MapStats = nb_map_stats;
 using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sums of a catalogued group
 using FofStats = nb_fof_stats;
+using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound set
+using BoundStats = nb_bound_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
 using SmoothParams = nb_smooth_params;    // a map's parameters and the bounds of the smoothing lengths
 using SmoothStats = nb_smooth_stats;
@@ -252,6 +254,52 @@ FofGroups fof_groups(int (*call)(H *, const nb_fof_params *, uint32_t *, uint32_
 }
 }  // namespace detail
 
+// The bound groups of a state (nb_sim_bound; no reference counterpart): per body the catalogue row of its
+// friends-of-friends group, the row whose bound set it belongs to (NB_FOF_NONE: none) and its energy in the last
+// round it was active in; the catalogue in ascending label order.  bound_of and energy are empty when not asked for
+struct BoundGroups {
+    std::vector<uint32_t> group_of, bound_of;
+    std::vector<double> energy;
+    std::vector<BoundGroup> groups;
+    BoundStats stats{};
+    // the rows by bound mass, descending, ties by label
+    std::vector<uint32_t> by_bound_mass() const {
+        std::vector<uint32_t> o(groups.size());
+        for (size_t i = 0; i < o.size(); ++i) o[i] = (uint32_t)i;
+        std::sort(o.begin(), o.end(), [this](uint32_t a, uint32_t b) {
+            return groups[a].mass != groups[b].mass ? groups[a].mass > groups[b].mass : groups[a].label < groups[b].label;
+        });
+        return o;
+    }
+};
+
+namespace detail {
+template <class H>
+BoundGroups bound_groups(int (*call)(H *, const nb_bound_params *, uint32_t *, uint32_t *, double *, nb_bound_group *,
+                                     size_t, nb_bound_stats *),
+                         H *h, size_t n, double link, uint32_t min_members, uint32_t min_bound, uint32_t max_iter,
+                         uint32_t max_group, bool per_body) {
+    BoundGroups g;
+    nb_bound_params p{};
+    p.link = link;
+    p.min_members = min_members;
+    p.min_bound = min_bound;
+    p.max_iter = max_iter;
+    p.max_group = max_group;
+    const size_t cap = min_members ? n / min_members : 0;  // the most there can be (the call refuses 0 itself)
+    g.group_of.resize(n);
+    if (per_body) {
+        g.bound_of.resize(n);
+        g.energy.resize(n);
+    }
+    g.groups.resize(cap);
+    check(call(h, &p, g.group_of.data(), per_body ? g.bound_of.data() : nullptr, per_body ? g.energy.data() : nullptr,
+               g.groups.data(), cap, &g.stats));
+    g.groups.resize((size_t)g.stats.groups);
+    return g;
+}
+}  // namespace detail
+
 // The k-th nearest neighbour of every body of a state, the mass inside it and the density from them (no
 // reference counterpart); a vector that was not asked for is empty
 struct KnnDensity {
@@ -448,6 +496,12 @@ class Simulator {
     FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
         return detail::fof_groups(nb_sim_fof, h_, sim_params().particle_num, link, min_members, labels);
     }
+    // those groups unbound: min_bound 0 stands for min_members, max_group 0 for no limit
+    BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
+                             uint32_t max_group = 262144, bool per_body = true) {
+        return detail::bound_groups(nb_sim_bound, h_, sim_params().particle_num, link, min_members,
+                                    min_bound ? min_bound : min_members, max_iter, max_group, per_body);
+    }
     // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
@@ -594,6 +648,13 @@ class OfflineHeadless {
         SimParams sp{};
         check(nb_runner_sim_params(r_, &sp));
         return detail::fof_groups(nb_runner_fof, r_, sp.particle_num, link, min_members, labels);
+    }
+    BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
+                             uint32_t max_group = 262144, bool per_body = true) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::bound_groups(nb_runner_bound, r_, sp.particle_num, link, min_members,
+                                    min_bound ? min_bound : min_members, max_iter, max_group, per_body);
     }
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {  // one device only
         SimParams sp{};
