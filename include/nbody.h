@@ -916,6 +916,132 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
                double *density, nb_knn_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Halo profiles -- the spherical radial profile about many centres in one    */
+/* call (no reference counterpart)                                            */
+/* ------------------------------------------------------------------------- */
+/* For each of m centres: the bins of nb_sim_radial_profile's spherical mode over
+ * the state nb_sim_read_particles would return, with edges shared by all centres.
+ * A centre tests only the bodies of the grid cells its sphere can reach, so the
+ * cost follows the bodies near the centres, not m n.  The rule, which DESIGN.md 6l
+ * states in full:
+ *   per centre   exactly the spherical rule above ("Radial profiles"): binary64
+ *                from the binary32 state, one rounding per operation, no
+ *                contraction; d = (double)x - c, u = (double)v - v_c,
+ *                r2 = (dx dx + dy dy) + dz dz; the bin is the k with
+ *                edges[k]^2 <= r2 < edges[k+1]^2, the squares formed once on the
+ *                host; terms m, m r, m u_r, (m u_r) u_r, m |u|^2, m (d x u); u_r = 0
+ *                at r = 0; m_uphi = m_uphi2 = 0.  The predicate of
+ *                nb_sim_diagnostics decides which bodies count
+ *   not reported bodies with r2 >= edges[nbins]^2 (they are what the grid prunes):
+ *                there is no outside_count, total mass or shape.  inside_count and
+ *                inside_mass (r2 < edges[0]^2) are per centre
+ *   centres      m points centers[m][3] (binary64, all finite), or m body indices
+ *                bodies[m] (each < n): the centre is that body's widened position,
+ *                read on the device.  Exactly one of the two is non-null.
+ *                velocities[m][3] null: v_c = 0 for points, the body's own widened
+ *                velocity for body centres.  A body centre is itself a body at
+ *                r2 = 0 and is counted like any other.  A body centre that does not
+ *                count gives a zeroed row (center and velocity 0) with
+ *                NB_HALO_CENTER_NONFINITE in head.flags.  For a TreeSim the indices
+ *                are those of nb_sim_read_particles at the same moment
+ *   grid         with R = edges[nbins], lo and hi the per-axis bounds of the
+ *                counted bodies and E the largest hi - lo: cells of side
+ *                h = max(R, E 2^-10); axis a has min(1024, floor((hi_a - lo_a) / h) + 1)
+ *                cells with lower edges e(q) = lo_a + (double)q h; a body is in the
+ *                cell q with e(q) <= x (q > 0) and x < e(q + 1) (q not the last),
+ *                decided by those comparisons.  A centre looks at the cells
+ *                [t0, t1] of each axis: t0 the largest t with t = 0 or
+ *                (c >= e(t) and (c - e(t))^2 >= R^2), t1 the smallest t with t = last or
+ *                (e(t + 1) >= c and (e(t + 1) - c)^2 >= R^2), R^2 = edges[nbins]^2 as
+ *                formed on the host; no cell at all when on some axis
+ *                (c >= hi and (c - hi)^2 >= R^2) or (lo >= c and (lo - c)^2 >= R^2), or when R^2
+ *                underflows to 0.  Every body the per-centre rule bins or counts as
+ *                inside is in those cells (the proof is in DESIGN.md 6l)
+ *   candidates   a centre's candidates are the bodies of its cells in ascending
+ *                (iz, iy, ix, body index): T of them; `tested` is the sum of T
+ *   sums         the candidates in chunks of L = NB_HALO_CHUNK, a chunk in tiles of
+ *                256 summed per bin as nb_sim_radial_profile sums a tile, the tiles
+ *                of a chunk in order, then the chunks in order from 0.  The grid,
+ *                L and the order are part of the rule: a centre's row depends on
+ *                the state and the edges alone, not on m, the other centres or its
+ *                place in the list, and two calls return the same bits.  No float
+ *                atomics.  Counts are exact; every sum is within 1e-10 of its sum
+ *                of |term| of the binary64 sum
+ * Limits: m <= NB_HALO_MAX_CENTERS and m nbins <= NB_HALO_MAX_ROWS, else
+ * NB_ERR_INVALID before any device call.  A centre with T candidates costs
+ * ceil(T / L) work items, each with a partial of 2 + 9 nbins doubles in the
+ * workspace, and the workspace has room for m + NB_HALO_EXTRA_ITEMS of them: a
+ * call whose `items` would exceed that is NB_ERR_UNSUPPORTED, found on the device
+ * (nothing is written; split the centres over several calls).  Since items
+ * <= m + tested / L, no call with tested <= NB_HALO_EXTRA_ITEMS L = 2^28 is
+ * refused, whatever m is; one whose centres each see several chunks of
+ * candidates can be, from about 2^16 such chunks on.  m = 0 or n = 0 is a valid
+ * call that launches nothing: it synchronises, its rows are empty, and its stats
+ * carry nonfinite = tested = items = 0 and cells = 0.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory. */
+#define NB_HALO_MAX_BINS 64u
+#define NB_HALO_MAX_CENTERS (1u << 20)
+#define NB_HALO_MAX_ROWS (1u << 22)
+#define NB_HALO_MAX_CELLS_PER_AXIS 1024u
+#define NB_HALO_CHUNK 4096u           /* L: candidates per work item */
+#define NB_HALO_EXTRA_ITEMS (1u << 16) /* work items of one call beyond one a centre */
+#define NB_HALO_CENTER_NONFINITE 1u   /* nb_halo_head.flags: the body centre does not count */
+
+typedef struct nb_halo_params {
+    uint32_t nbins, flags;    /* 1..NB_HALO_MAX_BINS; 0 */
+    uint64_t m;               /* centres */
+    const double *edges;      /* nbins + 1 radii, as nb_radial_params */
+    const double *centers;    /* [m][3], or null */
+    const uint32_t *bodies;   /* [m], or null */
+    const double *velocities; /* [m][3], or null */
+} nb_halo_params;
+
+typedef struct nb_halo_head { /* 64 bytes */
+    uint32_t inside_count, flags;
+    double inside_mass;
+    double center[3], velocity[3]; /* the values used */
+} nb_halo_head;
+
+typedef struct nb_halo_stats {
+    uint64_t step_num, n, nonfinite;
+    uint64_t centers; /* m */
+    uint64_t tested;  /* candidate distance tests: the sum of T over the centres */
+    uint64_t items;   /* work items: the sum of ceil(T / L) */
+    uint32_t cells[3], reserved; /* cells per axis of the grid */
+} nb_halo_stats;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_halo_params) == 48 && sizeof(nb_halo_head) == 64 && sizeof(nb_halo_stats) == 64,
+              "nb_halo_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_halo_params) == 48 && sizeof(nb_halo_head) == 64 && sizeof(nb_halo_stats) == 64,
+               "nb_halo_* layouts");
+#endif
+
+/* heads: m rows; bins: [m][nbins] rows of nb_radial_bin; either may be null: what is not asked for is
+ * not copied.  The outputs are written only by a call that succeeds.  NB_ERR_INVALID for a null handle,
+ * params or edges, nbins outside 1..NB_HALO_MAX_BINS, flags != 0, edges nb_sim_radial_profile would
+ * refuse, both or neither of centers and bodies (m > 0), a non-finite centre or velocity, m or m nbins
+ * above the limits -- all checked before any device call -- and for a body index >= n;
+ * NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_halo_profiles(nb_sim *sim, const nb_halo_params *params, nb_halo_head *heads, nb_radial_bin *bins,
+                         nb_halo_stats *stats);
+/* Host only, pure functions of their arguments.
+ * nb_halo_enclosed: out[0] = head->inside_mass, out[k + 1] = out[k] + bins[k].mass: the mass inside edges[k].
+ * nb_halo_overdensity: the mean enclosed density at every edge with edges[k] > 0 is
+ * rho_k = out[k] / (NB_KNN_SPHERE ((e e) e)), e = edges[k].  For the first k with both edges > 0 and
+ * rho_{k-1} >= rho > rho_k: *r from ln rho linear in ln r between the two edges (the lower edge itself
+ * when rho_k = 0), *mass = rho NB_KNN_SPHERE r^3; both NaN when there is no such k.  Binned, like
+ * nb_radial_lagrangian: limited by the bins' resolution, and a crossing inside edges[0] or between
+ * edges that the profile does not bracket is not found.  NB_ERR_INVALID for a null pointer, nbins
+ * outside 1..NB_HALO_MAX_BINS or rho not finite and > 0. */
+int nb_halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out);
+int nb_halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, const double *edges, uint32_t nbins,
+                        double rho, double *r, double *mass);
+
+/* ------------------------------------------------------------------------- */
 /* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
 /* kernel of its own radius (no reference counterpart: the image of the       */
 /* density estimate, where nb_sim_map gives shot noise)                       */
@@ -1184,6 +1310,10 @@ int nb_runner_bound(nb_runner *runner, const nb_bound_params *params, uint32_t *
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
                   double *density, nb_knn_stats *stats);
+/* nb_sim_halo_profiles of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_runner_halo_profiles(nb_runner *runner, const nb_halo_params *params, nb_halo_head *heads,
+                            nb_radial_bin *bins, nb_halo_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

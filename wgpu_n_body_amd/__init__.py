@@ -39,6 +39,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
+           "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
@@ -735,6 +736,157 @@ def _knn_density(call, handle, n, k, density, neighbours) -> KnnDensity:
     return KnnDensity(kk, r2, kth, mass_in, rho, _knn_stats(st))
 
 
+HALO_CENTER_NONFINITE = _lib.NB_HALO_CENTER_NONFINITE
+
+
+@dataclass(frozen=True)
+class HaloStats:
+    """nb_halo_stats (include/nbody.h "Halo profiles")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    centers: int
+    tested: int           # candidate distance tests: what the grid did not prune
+    items: int            # work items of NB_HALO_CHUNK candidates
+    cells: tuple          # cells per axis of the grid
+
+
+@dataclass(frozen=True)
+class HaloProfiles:
+    """nb_sim_halo_profiles' rows (include/nbody.h "Halo profiles"; no reference counterpart): the spherical
+    profile of RadialProfile about m centres at once, with shared edges.  Per-bin fields are (m, nbins) arrays
+    (count: uint64, ang: (m, nbins, 3)); inside_count, inside_mass, center, velocity and flags are per centre.
+    Bodies at or beyond edges[-1] are not reported."""
+    edges: np.ndarray      # nbins + 1
+    count: np.ndarray
+    mass: np.ndarray       # sum m
+    m_r: np.ndarray        # sum m r
+    m_ur: np.ndarray       # sum m u_r
+    m_ur2: np.ndarray      # sum m u_r^2
+    m_u2: np.ndarray       # sum m |u|^2
+    ang: np.ndarray        # sum m (d x u)
+    inside_count: np.ndarray
+    inside_mass: np.ndarray
+    center: np.ndarray     # (m, 3): the centres used
+    velocity: np.ndarray   # (m, 3)
+    flags: np.ndarray      # HALO_CENTER_NONFINITE: a body centre that does not count (its row is zero)
+    stats: HaloStats
+
+    @property
+    def nbins(self) -> int:
+        return self.edges.shape[0] - 1
+
+    @property
+    def enclosed_mass(self) -> np.ndarray:
+        """(m, nbins + 1): the mass inside edges[k] (nb_halo_enclosed: inside_mass, then the bins in order)."""
+        return np.cumsum(np.concatenate([self.inside_mass[:, None], self.mass], axis=1), axis=1)
+
+    @property
+    def density(self) -> np.ndarray:
+        """mass over the shell's volume 4 pi (b^3 - a^3) / 3."""
+        a, b = self.edges[:-1], self.edges[1:]
+        return self.mass / (_lib.NB_KNN_SPHERE * (b ** 3 - a ** 3))
+
+    @property
+    def mean_ur(self) -> np.ndarray:
+        """Mass-weighted mean radial velocity per bin (NaN in a bin without mass)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.m_ur / self.mass
+
+    @property
+    def sigma_r(self) -> np.ndarray:
+        """Mass-weighted radial velocity dispersion per bin (NaN in a bin without mass)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = self.m_ur / self.mass
+            return np.sqrt(np.maximum(self.m_ur2 / self.mass - mean * mean, 0.0))
+
+    def vcirc(self, G: float) -> np.ndarray:
+        """(m, nbins + 1): sqrt(G M(<r) / r) at every edge (NaN at an edge of radius 0)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(float(G) * self.enclosed_mass / np.where(self.edges > 0.0, self.edges, np.nan))
+
+    def overdensity(self, rho: float):
+        """nb_halo_overdensity per centre: (r, mass), each (m,), where the mean enclosed density first falls
+        through rho, interpolated between two edges (binned: limited by the bins' resolution); NaN where the
+        profile has no such crossing."""
+        m, nbins = self.mass.shape
+        edges = np.ascontiguousarray(self.edges, dtype=np.float64)
+        head = np.zeros(1, dtype=_lib.HALO_HEAD_DTYPE)
+        bins = np.zeros(nbins, dtype=_lib.RADIAL_BIN_DTYPE)
+        r, mass = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        a, b = C.c_double(), C.c_double()
+        for j in range(m):
+            head["inside_mass"][0] = self.inside_mass[j]
+            bins["mass"] = self.mass[j]
+            check(_lib.lib().nb_halo_overdensity(head.ctypes.data, bins.ctypes.data,
+                                                 edges.ctypes.data_as(C.POINTER(C.c_double)), nbins, float(rho),
+                                                 C.byref(a), C.byref(b)))
+            r[j], mass[j] = a.value, b.value
+        return r, mass
+
+
+def _halo_profiles(call, handle, centers, bodies, velocities, edges, nbins, rmin, rmax, log) -> HaloProfiles:
+    if edges is None:
+        if rmin is None or rmax is None:
+            raise ValueError("halo_profiles needs edges, or rmin and rmax")
+        if not 1 <= int(nbins) <= _lib.NB_HALO_MAX_BINS:
+            raise ValueError(f"halo_profiles: nbins must be 1..{_lib.NB_HALO_MAX_BINS}")
+        edges = radial_edges(rmin, rmax, nbins, log)
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    dp = C.POINTER(C.c_double)
+    p = _lib.nb_halo_params()
+    p.nbins, p.flags = max(edges.shape[0] - 1, 0), 0
+    p.edges = edges.ctypes.data_as(dp)
+    m = 0
+    if centers is not None:
+        centers = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, 3)
+        m = centers.shape[0]
+        p.centers = centers.ctypes.data_as(dp)
+    if bodies is not None:
+        bodies = np.ascontiguousarray(bodies).reshape(-1)
+        if bodies.size and (bodies.min() < 0 or bodies.max() > 0xFFFFFFFF):
+            raise ValueError("halo_profiles: bodies are 32-bit body indices")
+        bodies = bodies.astype(np.uint32)
+        if centers is None:
+            m = bodies.shape[0]
+        p.bodies = bodies.ctypes.data_as(C.POINTER(C.c_uint32))
+    if velocities is not None:
+        velocities = np.ascontiguousarray(velocities, dtype=np.float64).reshape(-1, 3)
+        if velocities.shape[0] != m:
+            raise ValueError("halo_profiles: one velocity per centre")
+        p.velocities = velocities.ctypes.data_as(dp)
+    if centers is not None and bodies is not None and bodies.shape[0] != m:
+        raise ValueError("halo_profiles: centers and bodies differ in length (and only one may be given)")
+    p.m = m
+    nb = int(p.nbins)
+    heads = np.zeros(m, dtype=_lib.HALO_HEAD_DTYPE)
+    bins = np.zeros((m, max(nb, 1)), dtype=_lib.RADIAL_BIN_DTYPE)
+    st = _lib.nb_halo_stats()
+    check(call(handle, C.byref(p), heads.ctypes.data, bins.ctypes.data, C.byref(st)))
+    stats = HaloStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.centers), int(st.tested), int(st.items),
+                      tuple(int(c) for c in st.cells))
+    return HaloProfiles(edges.copy(), bins["count"].copy(), bins["mass"].copy(), bins["m_r"].copy(),
+                        bins["m_ur"].copy(), bins["m_ur2"].copy(), bins["m_u2"].copy(), bins["ang"].copy(),
+                        heads["inside_count"].copy(), heads["inside_mass"].copy(), heads["center"].copy(),
+                        heads["velocity"].copy(), heads["flags"].copy(), stats)
+
+
+def _group_profiles(halo_profiles, groups, center, kw):
+    """rows, HaloProfiles: the profiles about the usable rows of a FofGroups / BoundGroups catalogue."""
+    if center == "com":
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c, v = groups.com, groups.velocity
+        rows = np.nonzero(np.isfinite(c).all(axis=1) & np.isfinite(v).all(axis=1))[0]
+        return rows, halo_profiles(c[rows], velocities=v[rows], **kw)
+    if center == "most_bound":
+        if "most_bound" not in (groups.rows.dtype.names or ()):
+            raise ValueError('group_profiles: center="most_bound" needs a BoundGroups')
+        mb = groups.rows["most_bound"]
+        rows = np.nonzero(mb != _lib.NB_FOF_NONE)[0]
+        return rows, halo_profiles(bodies=mb[rows], **kw)
+    raise ValueError('group_profiles: center is "com" or "most_bound"')
+
+
 SMOOTH_K = _lib.NB_SMOOTH_K
 SMOOTH_PLANES = ("wm", "wm_ua", "wm_ub", "wm_w", "wm_w2", "wm_u2")
 
@@ -1245,6 +1397,23 @@ class Simulator:
         return _knn_density(_lib.lib().nb_sim_knn, self._h, int(self.sim_params().particle_num), k, density,
                             neighbours)
 
+    def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
+                      rmax=None, log: bool = True) -> HaloProfiles:
+        """The spherical radial profile of the current state about many centres at once (nb_sim_halo_profiles):
+        centers (m, 3) points, or bodies (m,) body indices whose positions (and, without velocities, velocities)
+        are the centres; edges shared by all centres, or rmin, rmax, nbins and log for radial_edges().  A centre
+        tests only the bodies of the grid cells its sphere of radius edges[-1] reaches.  The body indices are
+        those of read_particles() now: a TreeSim reorders its bodies at every step."""
+        return _halo_profiles(_lib.lib().nb_sim_halo_profiles, self._h, centers, bodies, velocities, edges, nbins,
+                              rmin, rmax, log)
+
+    def group_profiles(self, groups, *, center: str = "com", **kw):
+        """(rows, HaloProfiles): halo_profiles about the groups of a FofGroups or BoundGroups of the same
+        state -- center="com": their centres of mass and mean velocities, the rows where those are finite;
+        "most_bound": a BoundGroups' most bound bodies, the rows that have one.  rows: the catalogue rows
+        the profiles belong to, in order.  kw: edges / nbins / rmin / rmax / log of halo_profiles."""
+        return _group_profiles(self.halo_profiles, groups, center, kw)
+
     def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                      depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
                      s_min=None, s_max=None) -> SmoothedMap:
@@ -1460,6 +1629,16 @@ class OfflineHeadless:
         """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""
         return _knn_density(_lib.lib().nb_runner_knn, self._h, int(self.sim_params().particle_num), k, density,
                             neighbours)
+
+    def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
+                      rmax=None, log: bool = True) -> HaloProfiles:
+        """nb_runner_halo_profiles: Simulator.halo_profiles of the runner's simulator (one device only)."""
+        return _halo_profiles(_lib.lib().nb_runner_halo_profiles, self._h, centers, bodies, velocities, edges, nbins,
+                              rmin, rmax, log)
+
+    def group_profiles(self, groups, *, center: str = "com", **kw):
+        """Simulator.group_profiles of the runner's simulator (one device only)."""
+        return _group_profiles(self.halo_profiles, groups, center, kw)
 
     def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                      depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,

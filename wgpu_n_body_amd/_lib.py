@@ -162,6 +162,22 @@ class nb_knn_stats(C.Structure):
                 ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_halo_params(C.Structure):
+    _fields_ = [("nbins", C.c_uint32), ("flags", C.c_uint32), ("m", C.c_uint64), ("edges", C.POINTER(C.c_double)),
+                ("centers", C.POINTER(C.c_double)), ("bodies", C.POINTER(C.c_uint32)),
+                ("velocities", C.POINTER(C.c_double))]
+
+
+class nb_halo_head(C.Structure):
+    _fields_ = [("inside_count", C.c_uint32), ("flags", C.c_uint32), ("inside_mass", C.c_double),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3)]
+
+
+class nb_halo_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("centers", C.c_uint64),
+                ("tested", C.c_uint64), ("items", C.c_uint64), ("cells", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
 class nb_smooth_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -194,6 +210,10 @@ BOUND_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("bound_count"
 FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
 FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
 
+# nb_halo_head[] as a numpy record array
+HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
+                            ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -210,6 +230,8 @@ assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
 assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
+assert C.sizeof(nb_halo_params) == 48 and C.sizeof(nb_halo_stats) == 64
+assert C.sizeof(nb_halo_head) == 64 == HALO_HEAD_DTYPE.itemsize
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
@@ -229,6 +251,9 @@ NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
 NB_BOUND_MAX_ITER = 64
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_HALO_MAX_BINS, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS = 64, 1 << 20, 1 << 22
+NB_HALO_MAX_CELLS_PER_AXIS, NB_HALO_CHUNK, NB_HALO_EXTRA_ITEMS = 1024, 4096, 1 << 16
+NB_HALO_CENTER_NONFINITE = 1
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
 NB_SMOOTH_MAX_ENTRIES = 1 << 28
@@ -251,6 +276,7 @@ ABI_SYMBOLS = [
     "nb_sim_fof", "nb_runner_fof",
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
+    "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
@@ -331,6 +357,10 @@ def lib() -> C.CDLL:
     L.nb_runner_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
     L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
+    L.nb_sim_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
+    L.nb_runner_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
+    L.nb_halo_enclosed.argtypes = [vp, vp, C.c_uint32, P(C.c_double)]
+    L.nb_halo_overdensity.argtypes = [vp, vp, P(C.c_double), C.c_uint32, C.c_double, P(C.c_double), P(C.c_double)]
     L.nb_sim_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
     L.nb_runner_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
     L.nb_smooth_centres.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]

@@ -40,6 +40,8 @@ SOURCES = [
     ("nb_knn.hip", ["-ffp-contract=off"]),
     # the weight rule is specified operation by operation: no FMA contraction
     ("nb_smooth.hip", ["-ffp-contract=off"]),
+    # the per-centre rule is nb_radial.hip's and the grid is specified operation by operation
+    ("nb_halo.hip", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

@@ -15,6 +15,8 @@
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
 //            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
 //            [--knn K [--knn-k 6]]
+//            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
+//             [--halo-rho RHO]]
 //
 // --devices: the step sharded over several GPUs of this process (nb_runner_create_multi; both simulators);
 // --let K (with --sim tree --devices): Morton domains + LET exchange, migration every K-th step (0: never);
@@ -79,6 +81,15 @@
 // <peak_density> <peak_index>" (every real %.17g): the density centre and its velocity, the largest density and
 // the body that holds it.  The time it takes is not part of any "Step Duration"; without --knn the output is
 // unchanged.
+//
+// --halo K finds the friends-of-friends groups (as --fof, with --halo-link and --halo-min) of step 0 and of every
+// K-th step and profiles all of them about their centres of mass in their own frames in one call
+// (nb_runner_halo_profiles): --halo-bins log bins (default 32) from RMIN to RMAX.  One line "halo <step> <groups>
+// <tested> <items>" (<groups>: those with a finite centre of mass, which are profiled), then the T largest groups (--halo-top, default 0) as "halo_group <step> <row> <label> <count>
+// <R> <M> <r_peak> <peak>" (every real %.17g): R and M where the mean enclosed density falls through RHO
+// (nb_halo_overdensity; nan without --halo-rho or without a crossing), and the largest M(< r) / r over the edges
+// with the edge that holds it -- the square of the circular-velocity peak over G.  The time it takes is not part of
+// any "Step Duration"; without --halo the output is unchanged.
 //
 // --frames DIR draws the state on the device (nb_runner_render: the reference's draw pass with its
 // default camera, src/runners/online_renderer.rs:224-367) at step 0 and after every K-th step
@@ -304,6 +315,61 @@ static void print_knn(nbody::OfflineHeadless<Sim> &runner, const KnnOptions &ko)
                 d.stats.peak_index);
 }
 
+struct HaloOptions {
+    int every = 0, top = 0;
+    double link = 0.0, rmin = 0.0, rmax = 0.0, rho = 0.0;
+    uint32_t min_members = 20, bins = 32;
+    bool have_range = false;
+};
+
+template <class Sim>
+static void print_halo(nbody::OfflineHeadless<Sim> &runner, const HaloOptions &ho) {
+    const nbody::FofGroups g = runner.fof_groups(ho.link, ho.min_members, false);
+    // the rows with a finite centre of mass and velocity (a group of massless bodies has none), as
+    // Simulator.group_profiles takes them; profile_of[row]: the row's profile, or -1
+    std::vector<double> centers, velocities;
+    std::vector<long> profile_of(g.groups.size(), -1);
+    for (size_t i = 0; i < g.groups.size(); ++i) {
+        const nbody::FofGroup &r = g.groups[i];
+        double c[3], v[3];
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) {
+            c[a] = r.mx[a] / r.mass;
+            v[a] = r.mv[a] / r.mass;
+            ok = ok && std::isfinite(c[a]) && std::isfinite(v[a]);
+        }
+        if (!ok) continue;
+        profile_of[i] = (long)(centers.size() / 3);
+        centers.insert(centers.end(), c, c + 3);
+        velocities.insert(velocities.end(), v, v + 3);
+    }
+    const nbody::HaloProfiles h =
+        runner.halo_profiles(nbody::radial_edges(ho.rmin, ho.rmax, ho.bins, true), centers, velocities);
+    const unsigned long long step = (unsigned long long)h.stats.step_num;
+    std::printf("halo %llu %llu %llu %llu\n", step, (unsigned long long)h.stats.centers,
+                (unsigned long long)h.stats.tested, (unsigned long long)h.stats.items);
+    const std::vector<uint32_t> order = g.by_size();
+    for (size_t k = 0; k < order.size() && k < (size_t)ho.top; ++k) {
+        const uint32_t row = order[k];
+        const double nan = std::nan("");
+        if (profile_of[row] < 0) {
+            std::printf("halo_group %llu %u %u %u nan nan nan nan\n", step, row, g.groups[row].label, g.groups[row].count);
+            continue;
+        }
+        const size_t pr = (size_t)profile_of[row];
+        const std::array<double, 2> od = ho.rho > 0.0 ? h.overdensity(pr, ho.rho) : std::array<double, 2>{nan, nan};
+        const std::vector<double> enclosed = h.enclosed(pr);
+        double peak = 0.0, r_peak = nan;
+        for (size_t e = 0; e < enclosed.size(); ++e)
+            if (h.edges[e] > 0.0 && enclosed[e] / h.edges[e] > peak) {
+                peak = enclosed[e] / h.edges[e];
+                r_peak = h.edges[e];
+            }
+        std::printf("halo_group %llu %u %u %u %.17g %.17g %.17g %.17g\n", step, row, g.groups[row].label,
+                    g.groups[row].count, od[0], od[1], r_peak, peak);
+    }
+}
+
 struct FrameOptions {
     std::string dir;
     int every = 1;
@@ -342,7 +408,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
-               const KnnOptions &knn, const BoundOptions &bound) {
+               const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -355,6 +421,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (fof.every > 0) print_fof(runner, fof);
     if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
+    if (halo.every > 0) print_halo(runner, halo);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -370,6 +437,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
         if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
+        if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -398,6 +466,7 @@ int main(int argc, char **argv) {
     FofOptions fof;
     KnnOptions knn;
     BoundOptions bound;
+    HaloOptions halo;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -566,6 +635,19 @@ int main(int argc, char **argv) {
         else if (k == "--smap-max") smaps.max_pixels = std::atof(v.c_str());
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--halo") halo.every = std::atoi(v.c_str());
+        else if (k == "--halo-link") halo.link = std::atof(v.c_str());
+        else if (k == "--halo-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &halo.rmin, &halo.rmax) != 2) {
+                std::fprintf(stderr, "--halo-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            halo.have_range = true;
+        }
+        else if (k == "--halo-bins") halo.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--halo-min") halo.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--halo-top") halo.top = std::atoi(v.c_str());
+        else if (k == "--halo-rho") halo.rho = std::atof(v.c_str());
         else if (k == "--devices") {
             for (size_t a = 0; a <= v.size();) {
                 const size_t b = std::min(v.find(',', a), v.size());
@@ -611,15 +693,19 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--bound needs --bound-link B > 0\n");
         return 2;
     }
+    if (halo.every > 0 && (!(halo.link > 0.0) || !halo.have_range)) {
+        std::fprintf(stderr, "--halo needs --halo-link B > 0 and --halo-range RMIN,RMAX\n");
+        return 2;
+    }
     const nbody::InitFn fn = init == "disc" ? nbody::inits::disc_init(seed)
                            : init == "spherical" ? nbody::inits::spherical_init(seed)
                                                  : nbody::inits::uniform_init(seed);
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -651,6 +651,47 @@ static int knn_check_params(const nb_knn_params *p) {
     return NB_OK;
 }
 
+// nb_sim_halo_profiles: everything that can be refused without a device (a body index needs n: sim_halo_profiles)
+static int halo_check_params(const nb_halo_params *p) {
+    if (!p || !p->edges) {
+        set_error("halo_profiles: null %s", !p ? "params" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_HALO_MAX_BINS) {
+        set_error("halo_profiles: nbins must be 1..%u (got %u)", NB_HALO_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags) {
+        set_error("halo_profiles: unknown flag bits 0x%x", p->flags);
+        return NB_ERR_INVALID;
+    }
+    if (p->m > NB_HALO_MAX_CENTERS || p->m * p->nbins > NB_HALO_MAX_ROWS) {
+        set_error("halo_profiles: %llu centres of %u bins are more than one call takes (%u centres, %u rows)",
+                  (unsigned long long)p->m, p->nbins, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("halo_profiles: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (p->m == 0) return NB_OK;
+    if (!p->centers == !p->bodies) {
+        set_error("halo_profiles: exactly one of centers and bodies must be given (%s)",
+                  p->centers ? "got both" : "got neither");
+        return NB_ERR_INVALID;
+    }
+    for (uint64_t j = 0; j < 3 * p->m; ++j)
+        if ((p->centers && !std::isfinite(p->centers[j])) || (p->velocities && !std::isfinite(p->velocities[j]))) {
+            set_error("halo_profiles: centre %llu has a non-finite %s", (unsigned long long)(j / 3),
+                      p->centers && !std::isfinite(p->centers[j]) ? "position" : "velocity");
+            return NB_ERR_INVALID;
+        }
+    return NB_OK;
+}
+
 // nb_map_edges / nb_sim_map: the cell size of `cells` cells in [lo, hi), refused unless the edges
 // lo + i * size (i < cells), hi come out strictly ascending
 static int map_cell_size(const char *what, double lo, double hi, uint32_t cells, double *size) {
@@ -1196,6 +1237,55 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
     NB_SIM_PASS(sim, sim_knn, *params, r2, kth, mass_in, density, stats)
 }
 
+int nb_sim_halo_profiles(nb_sim *sim, const nb_halo_params *params, nb_halo_head *heads, nb_radial_bin *bins,
+                         nb_halo_stats *stats) {
+    if (int rc = halo_check_params(params)) return rc;
+    NB_SIM_PASS(sim, sim_halo_profiles, *params, heads, bins, stats)
+}
+
+int nb_halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out) {
+    if (!head || !bins || !out) {
+        set_error("halo_enclosed: null argument");
+        return NB_ERR_INVALID;
+    }
+    if (nbins < 1 || nbins > NB_HALO_MAX_BINS) {
+        set_error("halo_enclosed: nbins must be 1..%u (got %u)", NB_HALO_MAX_BINS, nbins);
+        return NB_ERR_INVALID;
+    }
+    out[0] = head->inside_mass;
+    for (uint32_t k = 0; k < nbins; ++k) out[k + 1] = out[k] + bins[k].mass;
+    return NB_OK;
+}
+
+int nb_halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, const double *edges, uint32_t nbins,
+                        double rho, double *r, double *mass) {
+    if (!edges || !r || !mass) {
+        set_error("halo_overdensity: null argument");
+        return NB_ERR_INVALID;
+    }
+    double enclosed[NB_HALO_MAX_BINS + 1];
+    if (int rc = nb_halo_enclosed(head, bins, nbins, enclosed)) return rc;
+    if (!std::isfinite(rho) || !(rho > 0.0)) {
+        set_error("halo_overdensity: rho must be finite and > 0 (got %g)", rho);
+        return NB_ERR_INVALID;
+    }
+    *r = *mass = std::nan("");
+    for (uint32_t k = 1; k <= nbins; ++k) {
+        const double e0 = edges[k - 1], e1 = edges[k];
+        if (!(e0 > 0.0)) continue;
+        const double rho0 = enclosed[k - 1] / (NB_KNN_SPHERE * ((e0 * e0) * e0));
+        const double rho1 = enclosed[k] / (NB_KNN_SPHERE * ((e1 * e1) * e1));
+        if (rho0 >= rho && rho > rho1) {
+            const double t = (std::log(rho0) - std::log(rho)) / (std::log(rho0) - std::log(rho1));
+            const double x = std::exp(std::log(e0) + t * (std::log(e1) - std::log(e0)));
+            *r = x;
+            *mass = rho * NB_KNN_SPHERE * ((x * x) * x);
+            break;
+        }
+    }
+    return NB_OK;
+}
+
 int nb_sim_smooth_map(nb_sim *sim, const nb_smooth_params *params, const double *s, uint32_t *counts, double *planes,
                       nb_smooth_stats *stats) {
     NB_GUARD({
@@ -1501,6 +1591,14 @@ int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, ui
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "knn")) return rc;
     return nb_sim_knn(runner->sim, params, r2, kth, mass_in, density, stats);
+}
+
+int nb_runner_halo_profiles(nb_runner *runner, const nb_halo_params *params, nb_halo_head *heads,
+                            nb_radial_bin *bins, nb_halo_stats *stats) {
+    if (int rc = halo_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "halo_profiles")) return rc;
+    return nb_sim_halo_profiles(runner->sim, params, heads, bins, stats);
 }
 
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -166,6 +166,11 @@ int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint
 // nb_fof.hip: nb_sim_fof behind the handle (arguments already checked by fof_check_params, nb_abi.cpp)
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
             size_t group_capacity, nb_fof_stats *stats);
+// nb_halo.hip: nb_sim_halo_profiles behind the handle (arguments already checked by halo_check_params, nb_abi.cpp,
+// but for the body indices, which need n)
+int sim_halo_profiles(SimBase &sim, const nb_halo_params &params, nb_halo_head *heads, nb_radial_bin *bins,
+                      nb_halo_stats *stats);
+
 // nb_bound.hip: nb_sim_bound behind the handle (arguments already checked by bound_check_params, nb_abi.cpp)
 int sim_bound(SimBase &sim, const nb_bound_params &params, uint32_t *group_of, uint32_t *bound_of, double *energy,
               nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);

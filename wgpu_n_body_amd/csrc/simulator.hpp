@@ -44,6 +44,8 @@ using FofStats = nb_fof_stats;
 using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound set
 using BoundStats = nb_bound_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
+using HaloHead = nb_halo_head;            // 64 B: what lies inside edges[0], the centre and velocity used, flags
+using HaloStats = nb_halo_stats;
 using SmoothParams = nb_smooth_params;    // a map's parameters and the bounds of the smoothing lengths
 using SmoothStats = nb_smooth_stats;
 using Camera = nb_camera;               // `Camera`, runners/online_renderer.rs:12-20
@@ -340,6 +342,54 @@ KnnDensity knn_density(int (*call)(H *, const nb_knn_params *, double *, uint32_
 }
 }  // namespace detail
 
+// The spherical radial profiles of a state about many centres (nb_sim_halo_profiles; no reference counterpart):
+// heads[c] and bins[c * nbins + k] for centre c and bin k, the edges shared by all centres
+struct HaloProfiles {
+    std::vector<double> edges;  // nbins + 1
+    std::vector<HaloHead> heads;
+    std::vector<RadialBin> bins;
+    HaloStats stats{};
+    uint32_t nbins() const { return (uint32_t)edges.size() - 1; }
+    size_t centers() const { return heads.size(); }
+    const RadialBin *row(size_t c) const { return bins.data() + c * nbins(); }
+    // nb_halo_enclosed: the mass inside every edge
+    std::vector<double> enclosed(size_t c) const {
+        std::vector<double> out(edges.size());
+        check(nb_halo_enclosed(&heads[c], row(c), nbins(), out.data()));
+        return out;
+    }
+    // nb_halo_overdensity: {r, mass} where the mean enclosed density first falls through rho (NaN: nowhere)
+    std::array<double, 2> overdensity(size_t c, double rho) const {
+        std::array<double, 2> o{};
+        check(nb_halo_overdensity(&heads[c], row(c), edges.data(), nbins(), rho, &o[0], &o[1]));
+        return o;
+    }
+};
+
+namespace detail {
+template <class H>
+HaloProfiles halo_profiles(int (*call)(H *, const nb_halo_params *, nb_halo_head *, nb_radial_bin *, nb_halo_stats *),
+                           H *h, const std::vector<double> &edges, const std::vector<double> *centers,
+                           const std::vector<uint32_t> *bodies, const std::vector<double> &velocities) {
+    HaloProfiles o;
+    o.edges = edges;
+    nb_halo_params p{};
+    p.nbins = edges.empty() ? 0u : (uint32_t)(edges.size() - 1);
+    p.edges = edges.data();
+    p.m = centers ? centers->size() / 3 : bodies->size();
+    if (centers) p.centers = centers->data();
+    if (bodies) p.bodies = bodies->data();
+    if (!velocities.empty()) {
+        if (velocities.size() != 3 * p.m) throw Error(NB_ERR_INVALID, "halo_profiles: one velocity per centre");
+        p.velocities = velocities.data();
+    }
+    o.heads.resize(p.m);
+    o.bins.resize(p.m * p.nbins);
+    check(call(h, &p, o.heads.data(), o.bins.data(), &o.stats));
+    return o;
+}
+}  // namespace detail
+
 // A smoothed map (no reference counterpart): width * height counts (the bodies that reach a pixel), row 0 the
 // smallest b, the planes (1, or 6 with NB_SMOOTH_VELOCITY: wm, wm_ua, wm_ub, wm_w, wm_w2, wm_u2; plane 0 is the
 // surface density) plane-major, the smoothing lengths that were passed and what the call measured
@@ -506,6 +556,15 @@ class Simulator {
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
     }
+    // the profiles about points (centers: x y z per centre) or about bodies; velocities: empty, or three per centre
+    HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
+                               const std::vector<double> &velocities = {}) {
+        return detail::halo_profiles(nb_sim_halo_profiles, h_, edges, &centers, nullptr, velocities);
+    }
+    HaloProfiles halo_profiles_of_bodies(const std::vector<double> &edges, const std::vector<uint32_t> &bodies,
+                                         const std::vector<double> &velocities = {}) {
+        return detail::halo_profiles(nb_sim_halo_profiles, h_, edges, nullptr, &bodies, velocities);
+    }
     // the smoothed map of the current state: s[i] the smoothing length of body i in the order of read_particles() now
     SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {
         return detail::smoothed_map(nb_sim_smooth_map, h_, sim_params().particle_num, p, std::move(s));
@@ -660,6 +719,14 @@ class OfflineHeadless {
         SimParams sp{};
         check(nb_runner_sim_params(r_, &sp));
         return detail::knn_density(nb_runner_knn, r_, sp.particle_num, k, density, neighbours);
+    }
+    HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
+                               const std::vector<double> &velocities = {}) {  // one device only
+        return detail::halo_profiles(nb_runner_halo_profiles, r_, edges, &centers, nullptr, velocities);
+    }
+    HaloProfiles halo_profiles_of_bodies(const std::vector<double> &edges, const std::vector<uint32_t> &bodies,
+                                         const std::vector<double> &velocities = {}) {  // one device only
+        return detail::halo_profiles(nb_runner_halo_profiles, r_, edges, nullptr, &bodies, velocities);
     }
     SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {  // one device only
         SimParams sp{};
