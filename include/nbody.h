@@ -916,6 +916,123 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
                double *density, nb_knn_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Density-peak groups -- which bodies belong to which density peak (HOP,     */
+/* Eisenstein & Hut 1998; no reference counterpart)                           */
+/* ------------------------------------------------------------------------- */
+/* Every body hops to the densest of its nearest neighbours until it reaches a
+ * body that is its own densest neighbour, a peak; the bodies that end at one peak
+ * are a group.  Pairs of neighbours in different groups give the boundaries
+ * between groups, from which nb_hop_regroup merges groups across high saddles.
+ * The rule, which DESIGN.md 6m states in full: binary64 from the binary32 state,
+ * one rounding per operation, no contraction; indices are those of
+ * nb_sim_read_particles at that moment:
+ *   counted    the predicate of nb_sim_knn; c is the number of counted bodies.
+ *              With K = max(k_density, k_hop, k_merge) a state with c <= K is
+ *              short: every label is NB_HOP_NONE, there are no groups and no
+ *              boundaries, short_of_k = c (0 otherwise)
+ *   density    density[i] is that of nb_sim_knn with k = k_density, bit for bit;
+ *              its ordering key rho'_i is density[i], or -inf where that is NaN.
+ *              Body a is denser than b iff rho'_a > rho'_b, or they are equal and
+ *              a < b: a strict total order; +inf is allowed (coincident bodies)
+ *   inside     a counted body with rho'_i >= density_min (-inf: no cut).  Every
+ *              other body has label NB_HOP_NONE, is one of `outside` when it is
+ *              counted, and takes no part in what follows
+ *   hop        next[i] is the densest body among i itself and the first k_hop
+ *              bodies of i's neighbour order, the (d2, j) order of nb_sim_knn.  A
+ *              denser neighbour of an inside body is itself inside
+ *   label      following next from i ends at a body p with next[p] = p, a peak:
+ *              every hop goes to a strictly denser body.  labels[i] = p
+ *   catalogue  the groups with count >= min_members in ascending label order:
+ *              nb_fof_group rows with the nine sums and the summation order of
+ *              nb_sim_fof, and peak_density[row] = density[label]; group_of[i] is
+ *              body i's row or NB_HOP_NONE
+ *   boundaries a body pair is taken for every inside body i and every j among the
+ *              first k_merge bodies of i's order where j is inside and labels[i] !=
+ *              labels[j].  It belongs to the label pair (a, b) = (min, max) and its
+ *              value is 0.5 * (rho'_i + rho'_j).  The table holds one row per label
+ *              pair that occurs, in ascending (a, b): `pairs` the number of ordered
+ *              body pairs taken, `density` the maximum of their values.  Labels, not
+ *              rows: groups below min_members have boundaries too
+ * All integers, labels, boundary densities and peak densities are exact and
+ * bit-identical between calls; the sums are within 1e-10 of their sum of |term| of
+ * binary64, as in nb_sim_fof.  No float atomics: the boundary maximum is an integer
+ * maximum of the order-preserving encoding of the value.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.  The search obeys
+ * "knn_span_cells" and "knn_block_queries", the catalogue "fof_chunk_len"; none
+ * changes a bit of the result. */
+#define NB_HOP_NONE 0xFFFFFFFFu
+
+typedef struct nb_hop_params {
+    uint32_t k_density;   /* 2 .. NB_KNN_MAX_K: the k of the density */
+    uint32_t k_hop;       /* 1 .. NB_KNN_MAX_K: neighbours a body may hop to */
+    uint32_t k_merge;     /* 1 .. NB_KNN_MAX_K: neighbours that make boundary pairs */
+    uint32_t min_members; /* >= 1: the smallest group the catalogue holds */
+    double density_min;   /* not NaN; -inf: no cut */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved32;  /* 0 */
+    uint64_t reserved;    /* 0 */
+} nb_hop_params;
+
+typedef struct nb_hop_boundary {
+    uint32_t a, b;        /* the two labels, a < b */
+    uint32_t pairs;       /* ordered body pairs taken */
+    uint32_t reserved;    /* 0 */
+    double density;       /* the largest 0.5 * (rho'_i + rho'_j) among them */
+} nb_hop_boundary;
+
+typedef struct nb_hop_stats {
+    uint64_t step_num, n, nonfinite, counted;
+    uint64_t outside;        /* counted bodies below density_min */
+    uint64_t short_of_k;     /* c when c <= max(k_density, k_hop, k_merge), else 0 */
+    uint64_t peaks;          /* all groups, whatever their size */
+    uint64_t groups;         /* the catalogued ones, even when group_capacity is smaller */
+    uint64_t grouped_bodies; /* bodies of catalogued groups */
+    uint64_t boundaries;     /* label pairs, even when boundary_capacity is smaller */
+    uint64_t boundary_pairs; /* ordered body pairs taken */
+    uint32_t largest_count, largest_label; /* as nb_fof_stats' */
+} nb_hop_stats;
+
+/* The density-peak groups of a simulator's current state.  labels, group_of and density: n values each;
+ * groups and peak_density: room for group_capacity rows, of which the first min(stats->groups,
+ * group_capacity) are written; boundaries: room for boundary_capacity rows, of which the first
+ * min(stats->boundaries, boundary_capacity) are written.  Every output pointer may be null: what is not
+ * asked for is not copied (without `groups` and `peak_density` there is no catalogue, without `boundaries`
+ * the table is still counted); a call with none of them synchronises and measures nothing.  The outputs
+ * are written only by a call that succeeds.  NB_ERR_INVALID for a null handle or params, a k outside its
+ * range, min_members == 0, a NaN density_min, unknown flags or a reserved field != 0 -- all checked
+ * before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1) and for
+ * n * k_merge >= 2^31. */
+int nb_sim_hop(nb_sim *sim, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of, double *density,
+               nb_fof_group *groups, double *peak_density, size_t group_capacity, nb_hop_boundary *boundaries,
+               size_t boundary_capacity, nb_hop_stats *stats);
+
+/* Merges the groups of nb_sim_hop across their boundaries on the host (no device call):
+ *   1. a row is viable iff its peak_density >= params->peak;
+ *   2. boundaries whose two labels are not both rows are skipped; the rest are processed in descending
+ *      density, ties in ascending (a, b), with a union-find over rows;
+ *   3. the sets of a and b are joined unless both sets are viable and density < params->saddle; a set is
+ *      viable if any of its rows is;
+ *   4. a set's representative is its densest peak (peak_density, then the smaller label);
+ *   5. merged_of_row[r] (m values) is the representative's label if the set is viable, else NB_HOP_NONE;
+ *   6. the merged catalogue holds one row per viable set in ascending label: count and the nine sums are
+ *      those of the member rows added in ascending row order from 0, peak_density the representative's.
+ *      The first min(*out_count, out_capacity) rows are written; *out_count is their total.
+ * merged_of_row, out_rows and out_peak may be null.  NB_ERR_INVALID for null params or out_count, null rows
+ * or peak_density with m > 0, null bnd with b > 0, NaN thresholds or saddle > peak, unknown flags, rows
+ * not in strictly ascending label order, or boundaries not in strictly ascending (a, b). */
+typedef struct nb_hop_regroup_params {
+    double saddle, peak; /* saddle <= peak, neither NaN */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved;   /* 0 */
+} nb_hop_regroup_params;
+
+int nb_hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t m, const nb_hop_boundary *bnd,
+                   size_t b, const nb_hop_regroup_params *params, uint32_t *merged_of_row, nb_fof_group *out_rows,
+                   double *out_peak, size_t out_capacity, size_t *out_count);
+
+/* ------------------------------------------------------------------------- */
 /* Halo profiles -- the spherical radial profile about many centres in one    */
 /* call (no reference counterpart)                                            */
 /* ------------------------------------------------------------------------- */
@@ -1306,6 +1423,12 @@ int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labe
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_bound(nb_runner *runner, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of,
                     double *energy, nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
+/* nb_sim_hop of the runner's simulator (no reference counterpart).
+ * NB_ERR_UNSUPPORTED for a several-GPU runner. */
+int nb_runner_hop(nb_runner *runner, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of,
+                  double *density, nb_fof_group *groups, double *peak_density, size_t group_capacity,
+                  nb_hop_boundary *boundaries, size_t boundary_capacity, nb_hop_stats *stats);
+
 /* nb_sim_knn of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,

@@ -22,6 +22,7 @@ constructing a simulator raises NBodyError(NB_ERR_NO_DEVICE) when no HIP device 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
@@ -39,6 +40,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
+           "HopGroups", "HopStats", "HOP_NONE",
            "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
@@ -535,6 +537,127 @@ def _fof_groups(call, handle, n, link, min_members, labels) -> FofGroups:
     return FofGroups(lab, gof, rows[:stats.groups], float(link), mm, stats)
 
 
+HOP_NONE = _lib.NB_HOP_NONE
+
+
+@dataclass(frozen=True)
+class HopStats:
+    """nb_hop_stats (include/nbody.h "Density-peak groups")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    counted: int
+    outside: int          # counted bodies below density_min
+    short_of_k: int
+    peaks: int            # all groups, whatever their size
+    groups: int           # the catalogued ones
+    grouped_bodies: int
+    boundaries: int       # label pairs
+    boundary_pairs: int   # ordered body pairs taken
+    largest_count: int
+    largest_label: int
+
+
+@dataclass(frozen=True)
+class HopGroups:
+    """nb_sim_hop's partition, catalogue and boundary table (include/nbody.h "Density-peak groups"; no
+    reference counterpart): every body hops to the densest of its k_hop nearest neighbours until it reaches a
+    density peak, whose body index is the group's label.  labels and group_of: (n,) uint32, HOP_NONE for a body
+    of no group / of no catalogued group (labels None when not asked for); density: (n,) float64, knn_density's
+    at k_density, or None.  rows: FofGroups' catalogue records in ascending label order, peak_density one per
+    row.  boundaries: _lib.HOP_BOUNDARY_DTYPE records in ascending (a, b), one per pair of labels with
+    neighbouring bodies -- `pairs` body pairs, `density` the largest mean density of a pair -- or None.
+    regroup(saddle, peak) merges the groups across boundaries denser than `saddle` and drops the sets with no
+    peak of at least `peak`."""
+    labels: Optional[np.ndarray]
+    group_of: np.ndarray
+    density: Optional[np.ndarray]
+    rows: np.ndarray
+    peak_density: np.ndarray
+    boundaries: Optional[np.ndarray]
+    k: tuple              # (k_density, k_hop, k_merge)
+    min_members: int
+    density_min: float
+    stats: HopStats
+
+    _per_mass = FofGroups._per_mass
+    label = FofGroups.label
+    count = FofGroups.count
+    mass = FofGroups.mass
+    com = FofGroups.com
+    velocity = FofGroups.velocity
+    rms_radius = FofGroups.rms_radius
+    sigma = FofGroups.sigma
+    by_size = FofGroups.by_size
+
+    def regroup(self, saddle: float, peak: float) -> "HopGroups":
+        """nb_hop_regroup on this catalogue and boundary table: a HopGroups of the merged rows, labels and
+        group_of mapped through the merge (HOP_NONE for a body of a set that is not viable), no boundaries."""
+        if self.boundaries is None:
+            raise ValueError("regroup: this HopGroups was made with boundaries=False")
+        m = len(self.rows)
+        rows = np.ascontiguousarray(self.rows)
+        pk = np.ascontiguousarray(self.peak_density, dtype=np.float64)
+        bnd = np.ascontiguousarray(self.boundaries)
+        rp = _lib.nb_hop_regroup_params()
+        rp.saddle, rp.peak, rp.flags, rp.reserved = float(saddle), float(peak), 0, 0
+        merged = np.empty(m, dtype=np.uint32)
+        out_rows = np.zeros(m, dtype=_lib.FOF_GROUP_DTYPE)
+        out_peak = np.zeros(m, dtype=np.float64)
+        cnt = C.c_size_t(0)
+        check(_lib.lib().nb_hop_regroup(rows.ctypes.data, pk.ctypes.data, m, bnd.ctypes.data, len(bnd), C.byref(rp),
+                                        merged.ctypes.data, out_rows.ctypes.data, out_peak.ctypes.data, m,
+                                        C.byref(cnt)))
+        out_rows, out_peak = out_rows[:cnt.value], out_peak[:cnt.value]
+        # body -> raw row -> merged label -> merged row
+        raw = self.group_of
+        has = raw != HOP_NONE
+        lab = np.full(raw.shape, HOP_NONE, dtype=np.uint32)
+        lab[has] = merged[raw[has]]
+        gof = np.full(raw.shape, HOP_NONE, dtype=np.uint32)
+        ok = lab != HOP_NONE
+        gof[ok] = np.searchsorted(out_rows["label"], lab[ok]).astype(np.uint32)
+        big = int(np.lexsort((out_rows["label"], -out_rows["count"].astype(np.int64)))[0]) if len(out_rows) else -1
+        stats = dataclasses.replace(
+            self.stats, groups=len(out_rows), grouped_bodies=int(out_rows["count"].sum(dtype=np.uint64)),
+            boundaries=0, boundary_pairs=0, largest_count=int(out_rows["count"][big]) if big >= 0 else 0,
+            largest_label=int(out_rows["label"][big]) if big >= 0 else HOP_NONE)
+        return HopGroups(lab if self.labels is not None else None, gof, self.density, out_rows, out_peak, None,
+                         self.k, self.min_members, self.density_min, stats)
+
+
+def _hop_groups(call, handle, n, k_density, k_hop, k_merge, min_members, density_min, labels, density,
+                boundaries) -> HopGroups:
+    p = _lib.nb_hop_params()
+    u32 = lambda v: int(v) if 0 <= int(v) <= 0xFFFFFFFF else 0  # (the call refuses 0 itself)
+    p.k_density, p.k_hop, p.k_merge, p.min_members = u32(k_density), u32(k_hop), u32(k_merge), u32(min_members)
+    p.density_min = -np.inf if density_min is None else float(density_min)
+    p.flags, p.reserved32, p.reserved = 0, 0, 0
+    lab = np.empty(n, dtype=np.uint32) if labels else None
+    gof = np.empty(n, dtype=np.uint32)
+    den = np.empty(n, dtype=np.float64) if density else None
+    st = _lib.nb_hop_stats()
+    cap = n // 4 + 1
+    bcap = 4 * cap if boundaries else 0
+    for attempt in range(2):
+        rows = np.zeros(cap, dtype=_lib.FOF_GROUP_DTYPE)
+        peak = np.zeros(cap, dtype=np.float64)
+        bnd = np.zeros(bcap, dtype=_lib.HOP_BOUNDARY_DTYPE) if boundaries else None
+        check(call(handle, C.byref(p), lab.ctypes.data if labels else None, gof.ctypes.data,
+                   den.ctypes.data if density else None, rows.ctypes.data, peak.ctypes.data, cap,
+                   bnd.ctypes.data if boundaries else None, bcap, C.byref(st)))
+        if int(st.groups) <= cap and (not boundaries or int(st.boundaries) <= bcap):
+            break
+        cap = max(cap, int(st.groups))  # once more, with the sizes the stats report
+        bcap = max(bcap, int(st.boundaries)) if boundaries else 0
+    stats = HopStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.counted), int(st.outside),
+                     int(st.short_of_k), int(st.peaks), int(st.groups), int(st.grouped_bodies), int(st.boundaries),
+                     int(st.boundary_pairs), int(st.largest_count), int(st.largest_label))
+    return HopGroups(lab, gof, den, rows[:stats.groups], peak[:stats.groups],
+                     bnd[:stats.boundaries] if boundaries else None, (int(k_density), int(k_hop), int(k_merge)),
+                     int(min_members), float(p.density_min), stats)
+
+
 BOUND_CONVERGED, BOUND_DISSOLVED = _lib.NB_BOUND_CONVERGED, _lib.NB_BOUND_DISSOLVED
 BOUND_UNCONVERGED, BOUND_SKIPPED = _lib.NB_BOUND_UNCONVERGED, _lib.NB_BOUND_SKIPPED
 
@@ -872,7 +995,7 @@ def _halo_profiles(call, handle, centers, bodies, velocities, edges, nbins, rmin
 
 
 def _group_profiles(halo_profiles, groups, center, kw):
-    """rows, HaloProfiles: the profiles about the usable rows of a FofGroups / BoundGroups catalogue."""
+    """rows, HaloProfiles: the profiles about the usable rows of a FofGroups / BoundGroups / HopGroups catalogue."""
     if center == "com":
         with np.errstate(invalid="ignore", divide="ignore"):
             c, v = groups.com, groups.velocity
@@ -884,7 +1007,12 @@ def _group_profiles(halo_profiles, groups, center, kw):
         mb = groups.rows["most_bound"]
         rows = np.nonzero(mb != _lib.NB_FOF_NONE)[0]
         return rows, halo_profiles(bodies=mb[rows], **kw)
-    raise ValueError('group_profiles: center is "com" or "most_bound"')
+    if center == "peak":
+        if not isinstance(groups, HopGroups):
+            raise ValueError('group_profiles: center="peak" needs a HopGroups')
+        rows = np.arange(len(groups.rows))
+        return rows, halo_profiles(bodies=groups.rows["label"], **kw)
+    raise ValueError('group_profiles: center is "com", "most_bound" or "peak"')
 
 
 SMOOTH_K = _lib.NB_SMOOTH_K
@@ -1389,6 +1517,17 @@ class Simulator:
         return _bound_groups(_lib.lib().nb_sim_bound, self._h, int(self.sim_params().particle_num), link,
                              min_members, min_bound, max_iter, max_group, per_body)
 
+    def hop_groups(self, *, k_density: int = 64, k_hop: int = 16, k_merge: int = 4, min_members: int = 1,
+                   density_min=None, labels: bool = True, density: bool = False, boundaries: bool = True) -> HopGroups:
+        """The density-peak groups of the current state (nb_sim_hop): knn_density(k_density) orders the bodies,
+        every body hops to the densest of its k_hop nearest neighbours until it reaches a peak, and pairs
+        among the k_merge nearest neighbours that end at different peaks give the boundaries .regroup() merges
+        across.  density_min leaves bodies below it out.  The body indices are those of read_particles() now: a
+        TreeSim reorders its bodies at every step.  labels=False and density=False leave the per-body arrays
+        on the device, boundaries=False the boundary table."""
+        return _hop_groups(_lib.lib().nb_sim_hop, self._h, int(self.sim_params().particle_num), k_density, k_hop,
+                           k_merge, min_members, density_min, labels, density, boundaries)
+
     def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
         """The k-th nearest neighbour of every body of the current state, the mass inside it and the density
         from them (nb_sim_knn), with the density-weighted sums: .center is the density centre of Casertano &
@@ -1410,7 +1549,8 @@ class Simulator:
     def group_profiles(self, groups, *, center: str = "com", **kw):
         """(rows, HaloProfiles): halo_profiles about the groups of a FofGroups or BoundGroups of the same
         state -- center="com": their centres of mass and mean velocities, the rows where those are finite;
-        "most_bound": a BoundGroups' most bound bodies, the rows that have one.  rows: the catalogue rows
+        "most_bound": a BoundGroups' most bound bodies, the rows that have one; "peak": a HopGroups' labels, the
+        bodies at the density peaks.  rows: the catalogue rows
         the profiles belong to, in order.  kw: edges / nbins / rmin / rmax / log of halo_profiles."""
         return _group_profiles(self.halo_profiles, groups, center, kw)
 
@@ -1624,6 +1764,12 @@ class OfflineHeadless:
         """nb_runner_bound: Simulator.bound_groups of the runner's simulator (one device only)."""
         return _bound_groups(_lib.lib().nb_runner_bound, self._h, int(self.sim_params().particle_num), link,
                              min_members, min_bound, max_iter, max_group, per_body)
+
+    def hop_groups(self, *, k_density: int = 64, k_hop: int = 16, k_merge: int = 4, min_members: int = 1,
+                   density_min=None, labels: bool = True, density: bool = False, boundaries: bool = True) -> HopGroups:
+        """nb_runner_hop: Simulator.hop_groups of the runner's simulator (one device only)."""
+        return _hop_groups(_lib.lib().nb_runner_hop, self._h, int(self.sim_params().particle_num), k_density, k_hop,
+                           k_merge, min_members, density_min, labels, density, boundaries)
 
     def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
         """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""

@@ -162,6 +162,28 @@ class nb_knn_stats(C.Structure):
                 ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_hop_params(C.Structure):
+    _fields_ = [("k_density", C.c_uint32), ("k_hop", C.c_uint32), ("k_merge", C.c_uint32),
+                ("min_members", C.c_uint32), ("density_min", C.c_double), ("flags", C.c_uint32),
+                ("reserved32", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_hop_boundary(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("pairs", C.c_uint32), ("reserved", C.c_uint32),
+                ("density", C.c_double)]
+
+
+class nb_hop_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("counted", C.c_uint64),
+                ("outside", C.c_uint64), ("short_of_k", C.c_uint64), ("peaks", C.c_uint64), ("groups", C.c_uint64),
+                ("grouped_bodies", C.c_uint64), ("boundaries", C.c_uint64), ("boundary_pairs", C.c_uint64),
+                ("largest_count", C.c_uint32), ("largest_label", C.c_uint32)]
+
+
+class nb_hop_regroup_params(C.Structure):
+    _fields_ = [("saddle", C.c_double), ("peak", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class nb_halo_params(C.Structure):
     _fields_ = [("nbins", C.c_uint32), ("flags", C.c_uint32), ("m", C.c_uint64), ("edges", C.POINTER(C.c_double)),
                 ("centers", C.POINTER(C.c_double)), ("bodies", C.POINTER(C.c_uint32)),
@@ -200,6 +222,9 @@ class nb_smooth_stats(C.Structure):
 FOF_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
                             ("mv", "<f8", (3,)), ("mr2", "<f8"), ("mv2", "<f8")])
 
+# nb_hop_boundary[] as a numpy record array
+HOP_BOUNDARY_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("pairs", "<u4"), ("reserved", "<u4"), ("density", "<f8")])
+
 # nb_bound_group[] as a numpy record array
 BOUND_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("bound_count", "<u4"), ("iterations", "<u4"),
                               ("status", "<u4"), ("most_bound", "<u4"), ("mass", "<f8"), ("mx", "<f8", (3,)),
@@ -230,6 +255,8 @@ assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
 assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
+assert C.sizeof(nb_hop_params) == 40 and C.sizeof(nb_hop_stats) == 96 and C.sizeof(nb_hop_regroup_params) == 24
+assert C.sizeof(nb_hop_boundary) == 24 == HOP_BOUNDARY_DTYPE.itemsize
 assert C.sizeof(nb_halo_params) == 48 and C.sizeof(nb_halo_stats) == 64
 assert C.sizeof(nb_halo_head) == 64 == HALO_HEAD_DTYPE.itemsize
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
@@ -251,6 +278,7 @@ NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
 NB_BOUND_MAX_ITER = 64
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_HOP_NONE = 0xFFFFFFFF
 NB_HALO_MAX_BINS, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS = 64, 1 << 20, 1 << 22
 NB_HALO_MAX_CELLS_PER_AXIS, NB_HALO_CHUNK, NB_HALO_EXTRA_ITEMS = 1024, 4096, 1 << 16
 NB_HALO_CENTER_NONFINITE = 1
@@ -276,6 +304,7 @@ ABI_SYMBOLS = [
     "nb_sim_fof", "nb_runner_fof",
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
+    "nb_sim_hop", "nb_runner_hop", "nb_hop_regroup",
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
@@ -357,6 +386,9 @@ def lib() -> C.CDLL:
     L.nb_runner_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
     L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
     L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
+    for name in ("nb_sim_hop", "nb_runner_hop"):
+        getattr(L, name).argtypes = [vp, P(nb_hop_params), vp, vp, vp, vp, vp, sz, vp, sz, P(nb_hop_stats)]
+    L.nb_hop_regroup.argtypes = [vp, vp, sz, vp, sz, P(nb_hop_regroup_params), vp, vp, vp, sz, P(sz)]
     L.nb_sim_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
     L.nb_runner_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
     L.nb_halo_enclosed.argtypes = [vp, vp, C.c_uint32, P(C.c_double)]

@@ -15,6 +15,7 @@
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
 //            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
 //            [--knn K [--knn-k 6]]
+//            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
 //             [--halo-rho RHO]]
 //
@@ -82,6 +83,13 @@
 // the body that holds it.  The time it takes is not part of any "Step Duration"; without --knn the output is
 // unchanged.
 //
+// --hop K finds the density-peak groups (nb_runner_hop; --hop-k DENS,HOP,MERGE, default 64,16,4; --hop-min M, default
+// 1; --hop-density-min D, default none) of step 0 and of every K-th step.  One line "hop <step> <peaks> <groups>
+// <grouped_bodies> <largest_count> <boundaries> <boundary_pairs>", then the T largest rows (--hop-top, default 0) as
+// "hop_group <step> <row> <label> <count> <mass> <x> <y> <z> <peak_density>" (%.9e).  With --hop-saddle S --hop-peak P
+// the groups are then merged (nb_hop_regroup): "hop_merged <step> <groups> <grouped_bodies> <largest_count>" and the T
+// largest merged rows as "hop_merged_group ..." in the columns of hop_group.  The time they take is not part of any
+// "Step Duration"; without --hop the output is unchanged.
 // --halo K finds the friends-of-friends groups (as --fof, with --halo-link and --halo-min) of step 0 and of every
 // K-th step and profiles all of them about their centres of mass in their own frames in one call
 // (nb_runner_halo_profiles): --halo-bins log bins (default 32) from RMIN to RMAX.  One line "halo <step> <groups>
@@ -315,6 +323,38 @@ static void print_knn(nbody::OfflineHeadless<Sim> &runner, const KnnOptions &ko)
                 d.stats.peak_index);
 }
 
+struct HopOptions {
+    int every = 0, top = 0;
+    nbody::HopParams params;
+    bool regroup = false;
+    double saddle = 0.0, peak = 0.0;
+};
+
+static void print_hop_rows(const char *tag, const nbody::HopGroups &g, int top) {
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    const std::vector<uint32_t> order = g.by_size();
+    for (size_t k = 0; k < order.size() && k < (size_t)top; ++k) {
+        const nbody::FofGroup &r = g.groups[order[k]];
+        std::printf("%s %llu %u %u %u %.9e %.9e %.9e %.9e %.9e\n", tag, step, order[k], r.label, r.count, r.mass,
+                    r.mx[0] / r.mass, r.mx[1] / r.mass, r.mx[2] / r.mass, g.peak_density[order[k]]);
+    }
+}
+
+template <class Sim>
+static void print_hop(nbody::OfflineHeadless<Sim> &runner, const HopOptions &ho) {
+    const nbody::HopGroups g = runner.hop_groups(ho.params, false, false, true);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("hop %llu %llu %llu %llu %u %llu %llu\n", step, (unsigned long long)g.stats.peaks,
+                (unsigned long long)g.stats.groups, (unsigned long long)g.stats.grouped_bodies, g.stats.largest_count,
+                (unsigned long long)g.stats.boundaries, (unsigned long long)g.stats.boundary_pairs);
+    print_hop_rows("hop_group", g, ho.top);
+    if (!ho.regroup) return;
+    const nbody::HopGroups m = g.regroup(ho.saddle, ho.peak);
+    std::printf("hop_merged %llu %llu %llu %u\n", step, (unsigned long long)m.stats.groups,
+                (unsigned long long)m.stats.grouped_bodies, m.stats.largest_count);
+    print_hop_rows("hop_merged_group", m, ho.top);
+}
+
 struct HaloOptions {
     int every = 0, top = 0;
     double link = 0.0, rmin = 0.0, rmax = 0.0, rho = 0.0;
@@ -408,7 +448,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
-               const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo) {
+               const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -421,6 +461,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (fof.every > 0) print_fof(runner, fof);
     if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
+    if (hop.every > 0) print_hop(runner, hop);
     if (halo.every > 0) print_halo(runner, halo);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
@@ -437,6 +478,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
         if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
+        if (hop.every > 0 && (i + 1) % hop.every == 0) print_hop(runner, hop);
         if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
@@ -467,6 +509,8 @@ int main(int argc, char **argv) {
     KnnOptions knn;
     BoundOptions bound;
     HaloOptions halo;
+    HopOptions hop;
+    bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -633,6 +677,25 @@ int main(int argc, char **argv) {
         }
         else if (k == "--smap-k") smaps.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--smap-max") smaps.max_pixels = std::atof(v.c_str());
+        else if (k == "--hop") hop.every = std::atoi(v.c_str());
+        else if (k == "--hop-k") {
+            unsigned a = 0, b = 0, c = 0;
+            if (std::sscanf(v.c_str(), "%u,%u,%u", &a, &b, &c) != 3) {
+                std::fprintf(stderr, "--hop-k needs DENS,HOP,MERGE\n");
+                return 2;
+            }
+            hop.params.k_density = a;
+            hop.params.k_hop = b;
+            hop.params.k_merge = c;
+        } else if (k == "--hop-min") hop.params.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--hop-density-min") hop.params.density_min = std::atof(v.c_str());
+        else if (k == "--hop-saddle") {
+            hop.saddle = std::atof(v.c_str());
+            hop_saddle = true;
+        } else if (k == "--hop-peak") {
+            hop.peak = std::atof(v.c_str());
+            hop_peak = true;
+        } else if (k == "--hop-top") hop.top = std::atoi(v.c_str());
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--halo") halo.every = std::atoi(v.c_str());
@@ -685,6 +748,11 @@ int main(int argc, char **argv) {
         mp.s_min = 2.0 * pixel;
         mp.s_max = smaps.max_pixels * pixel;
     }
+    if (hop_saddle != hop_peak) {
+        std::fprintf(stderr, "--hop-saddle and --hop-peak go together\n");
+        return 2;
+    }
+    hop.regroup = hop_saddle;
     if (fof.every > 0 && !(fof.link > 0.0)) {
         std::fprintf(stderr, "--fof needs --fof-link B > 0\n");
         return 2;
@@ -703,9 +771,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -4,6 +4,7 @@
 // Host side only; the kernels live in nb_naive.hip / nb_tree.hip (nb_tree_*.hpp).  Everything the
 // reference does through wgpu (buffers, bind groups, command encoders, queue.submit,
 // device.poll) maps to hipMalloc'd SoA buffers, a ping-pong index and one hipStream_t.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -651,6 +652,158 @@ static int knn_check_params(const nb_knn_params *p) {
     return NB_OK;
 }
 
+// nb_sim_hop: everything that can be refused without a device
+static int hop_check_params(const nb_hop_params *p) {
+    if (!p) {
+        set_error("hop: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->k_density < 2 || p->k_density > NB_KNN_MAX_K) {
+        set_error("hop: k_density must be 2..%u (got %u)", NB_KNN_MAX_K, p->k_density);
+        return NB_ERR_INVALID;
+    }
+    if (p->k_hop < 1 || p->k_hop > NB_KNN_MAX_K || p->k_merge < 1 || p->k_merge > NB_KNN_MAX_K) {
+        set_error("hop: k_hop and k_merge must be 1..%u (got %u, %u)", NB_KNN_MAX_K, p->k_hop, p->k_merge);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("hop: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (std::isnan(p->density_min)) {
+        set_error("hop: density_min must not be NaN (-inf: no cut)");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved32 || p->reserved) {
+        set_error("hop: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_hop_regroup behind the ABI boundary (include/nbody.h: the rule, step by step)
+// the ordering key of a density, and the "denser" order of include/nbody.h
+static double hop_rho_key(double d) { return std::isnan(d) ? -INFINITY : d; }
+static bool hop_denser(double ra, uint32_t a, double rb, uint32_t b) { return ra > rb || (ra == rb && a < b); }
+
+static int hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t m, const nb_hop_boundary *bnd,
+                       size_t b, const nb_hop_regroup_params *params, uint32_t *merged_of_row, nb_fof_group *out_rows,
+                       double *out_peak, size_t out_capacity, size_t *out_count) {
+    {
+        if (!params || !out_count || (m && (!rows || !peak_density)) || (b && !bnd)) {
+            set_error("hop_regroup: null argument");
+            return NB_ERR_INVALID;
+        }
+        if (std::isnan(params->saddle) || std::isnan(params->peak) || params->saddle > params->peak) {
+            set_error("hop_regroup: saddle and peak must not be NaN, with saddle <= peak (got %g, %g)", params->saddle,
+                      params->peak);
+            return NB_ERR_INVALID;
+        }
+        if (params->flags || params->reserved) {
+            set_error("hop_regroup: unknown flag bits 0x%x or reserved != 0", params->flags);
+            return NB_ERR_INVALID;
+        }
+        for (size_t r = 1; r < m; ++r)
+            if (!(rows[r - 1].label < rows[r].label)) {
+                set_error("hop_regroup: rows must be in strictly ascending label order (row %zu)", r);
+                return NB_ERR_INVALID;
+            }
+        for (size_t e = 0; e < b; ++e) {
+            const bool ordered = e == 0 || bnd[e - 1].a < bnd[e].a || (bnd[e - 1].a == bnd[e].a && bnd[e - 1].b < bnd[e].b);
+            if (!ordered || !(bnd[e].a < bnd[e].b)) {
+                set_error("hop_regroup: boundaries must be in strictly ascending (a, b) with a < b (boundary %zu)", e);
+                return NB_ERR_INVALID;
+            }
+        }
+        // the row of a label: a binary search in the ascending labels
+        auto row_of = [&](uint32_t label) -> size_t {
+            size_t lo = 0, hi = m;
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (rows[mid].label < label) lo = mid + 1;
+                else hi = mid;
+            }
+            return lo < m && rows[lo].label == label ? lo : m;
+        };
+        struct Edge {
+            double density;
+            size_t ra, rb, at;
+        };
+        std::vector<Edge> edges;
+        for (size_t e = 0; e < b; ++e) {
+            const size_t ra = row_of(bnd[e].a), rb = row_of(bnd[e].b);
+            if (ra < m && rb < m) edges.push_back({bnd[e].density, ra, rb, e});
+        }
+        // descending density (a NaN as -inf, like a peak's), ties in ascending (a, b) -- the table's own order
+        std::stable_sort(edges.begin(), edges.end(), [](const Edge &x, const Edge &y) {
+            return hop_rho_key(x.density) > hop_rho_key(y.density);
+        });
+        std::vector<size_t> parent(m);
+        std::vector<char> viable(m);  // of a root: its set's
+        for (size_t r = 0; r < m; ++r) {
+            parent[r] = r;
+            viable[r] = hop_rho_key(peak_density[r]) >= params->peak;
+        }
+        auto find = [&](size_t x) {
+            while (parent[x] != x) {
+                parent[x] = parent[parent[x]];
+                x = parent[x];
+            }
+            return x;
+        };
+        for (const Edge &e : edges) {
+            const size_t x = find(e.ra), y = find(e.rb);
+            if (x == y) continue;
+            if (viable[x] && viable[y] && e.density < params->saddle) continue;
+            parent[y] = x;
+            viable[x] = viable[x] || viable[y];
+        }
+        // the representative of every set: its densest peak
+        std::vector<size_t> rep(m);
+        for (size_t r = 0; r < m; ++r) rep[r] = m;
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (rep[x] == m || hop_denser(hop_rho_key(peak_density[r]), rows[r].label, hop_rho_key(peak_density[rep[x]]),
+                                          rows[rep[x]].label))
+                rep[x] = r;
+        }
+        // the viable sets in ascending representative label: a set is listed at its representative's row
+        std::vector<size_t> out_of(m, m);
+        size_t count = 0;
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (viable[x] && rep[x] == r) out_of[r] = count++;
+        }
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (merged_of_row) merged_of_row[r] = viable[x] ? rows[rep[x]].label : NB_HOP_NONE;
+            if (!viable[x] || out_of[rep[x]] >= out_capacity) continue;
+            const size_t o = out_of[rep[x]];
+            if (out_peak && rep[x] == r) out_peak[o] = peak_density[r];
+        }
+        if (out_rows) {
+            const size_t listed = std::min(count, out_capacity);
+            for (size_t o = 0; o < listed; ++o) out_rows[o] = nb_fof_group{};
+            for (size_t r = 0; r < m; ++r) {  // the member rows in ascending row order
+                const size_t x = find(r);
+                if (!viable[x] || out_of[rep[x]] >= out_capacity) continue;
+                nb_fof_group &g = out_rows[out_of[rep[x]]];
+                g.label = rows[rep[x]].label;
+                g.count += rows[r].count;
+                g.mass += rows[r].mass;
+                for (int a = 0; a < 3; ++a) {
+                    g.mx[a] += rows[r].mx[a];
+                    g.mv[a] += rows[r].mv[a];
+                }
+                g.mr2 += rows[r].mr2;
+                g.mv2 += rows[r].mv2;
+            }
+        }
+        *out_count = count;
+        return NB_OK;
+    }
+}
+
 // nb_sim_halo_profiles: everything that can be refused without a device (a body index needs n: sim_halo_profiles)
 static int halo_check_params(const nb_halo_params *p) {
     if (!p || !p->edges) {
@@ -1237,6 +1390,23 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
     NB_SIM_PASS(sim, sim_knn, *params, r2, kth, mass_in, density, stats)
 }
 
+int nb_sim_hop(nb_sim *sim, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of, double *density,
+               nb_fof_group *groups, double *peak_density, size_t group_capacity, nb_hop_boundary *boundaries,
+               size_t boundary_capacity, nb_hop_stats *stats) {
+    if (int rc = hop_check_params(params)) return rc;
+    NB_SIM_PASS(sim, sim_hop, *params, labels, group_of, density, groups, peak_density, group_capacity, boundaries,
+                boundary_capacity, stats)
+}
+
+int nb_hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t m, const nb_hop_boundary *bnd,
+                   size_t b, const nb_hop_regroup_params *params, uint32_t *merged_of_row, nb_fof_group *out_rows,
+                   double *out_peak, size_t out_capacity, size_t *out_count) {
+    NB_GUARD({
+        return hop_regroup(rows, peak_density, m, bnd, b, params, merged_of_row, out_rows, out_peak, out_capacity,
+                           out_count);
+    })
+}
+
 int nb_sim_halo_profiles(nb_sim *sim, const nb_halo_params *params, nb_halo_head *heads, nb_radial_bin *bins,
                          nb_halo_stats *stats) {
     if (int rc = halo_check_params(params)) return rc;
@@ -1575,6 +1745,16 @@ int nb_runner_fof(nb_runner *runner, const nb_fof_params *params, uint32_t *labe
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "fof")) return rc;
     return nb_sim_fof(runner->sim, params, labels, group_of, groups, group_capacity, stats);
+}
+
+int nb_runner_hop(nb_runner *runner, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of,
+                  double *density, nb_fof_group *groups, double *peak_density, size_t group_capacity,
+                  nb_hop_boundary *boundaries, size_t boundary_capacity, nb_hop_stats *stats) {
+    if (int rc = hop_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "hop")) return rc;
+    return nb_sim_hop(runner->sim, params, labels, group_of, density, groups, peak_density, group_capacity, boundaries,
+                      boundary_capacity, stats);
 }
 
 int nb_runner_bound(nb_runner *runner, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of,

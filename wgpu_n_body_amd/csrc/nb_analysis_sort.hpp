@@ -1,5 +1,5 @@
 // nb_analysis_sort.hpp -- what the analysis passes that sort their bodies by a spatial key share (nb_map.hip,
-// nb_fof.hip, nb_knn.hip; DESIGN.md 6g "The sort", "The bounds"):
+// nb_fof.hip, nb_knn.hip, nb_hop.hip; DESIGN.md 6g "The sort", "The bounds"):
 //   the sort    -- a stable LSD radix sort of (key, index), 8 bits a pass, on 32- or 64-bit keys: its shape
 //                  (chunks, histogram), its two sides, its three kernels and the loop that enqueues them;
 //   the bounds  -- the per-axis minimum and maximum of the counted bodies and their number: the slab kernel and

@@ -589,6 +589,78 @@ int fof_refused(const nb_fof_params &params) {
     return NB_ERR_INVALID;
 }
 
+int fof_catalogue_reserve(FofWork &w, uint32_t n, uint32_t rows_cap) {
+    const SortShape shape = sort_shape(n);
+    const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
+    const size_t run_slots = (size_t)n / kWave + rows_cap + 1;
+    if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return fof_reserve(b, count); })) return rc;
+    if (int rc = fof_reserve(w.flags, n)) return rc;
+    if (int rc = fof_reserve(w.excl, n)) return rc;
+    if (int rc = fof_reserve(w.block_tot, (size_t)scan_blocks + 1)) return rc;
+    if (int rc = fof_reserve(w.labels, n)) return rc;
+    if (int rc = fof_reserve(w.count, n)) return rc;
+    if (int rc = fof_reserve(w.row_of, n)) return rc;
+    if (int rc = fof_reserve(w.group_of, n)) return rc;
+    if (rows_cap > 0) {
+        if (int rc = fof_reserve(w.row_start, (size_t)rows_cap + 1)) return rc;
+        if (int rc = fof_reserve(w.runs, run_slots * kTerms)) return rc;
+        if (int rc = fof_reserve(w.rows, rows_cap)) return rc;
+    }
+    return NB_OK;
+}
+
+int fof_catalogue_enqueue(SimBase &sim, FofWork &w, const uint32_t *parent, uint32_t min_members, uint32_t rows_cap,
+                          bool want_group_of, bool sums) {
+    const uint32_t n = sim.n;
+    const uint32_t len = (uint32_t)sim.fof_chunk_len;
+    const unsigned long long sum_items = (unsigned long long)n / len + rows_cap + 1;
+    const uint32_t blocks = (n + kThreads - 1) / kThreads;
+    const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
+    const SortShape shape = sort_shape(n);
+    const float4 *posm = nullptr, *vel = nullptr;
+    sim.diag_state(&posm, &vel);
+    FofInfo *info = w.info;
+    const auto &keys = w.sort.keys;  // both sides go to the kernels: the plan says where the sorted arrays are
+    const auto &idx = w.sort.idx;
+    // labels, sizes, rows
+    NB_HIP_TRY(hipMemsetAsync(w.count, 0, sizeof(uint32_t) * n, sim.stream));
+    hipLaunchKernelGGL(fof_label_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, parent, n, w.labels,
+                       w.count);
+    NB_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fof_roots_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.count, n,
+                       min_members, w.flags);
+    NB_HIP_TRY(hipGetLastError());
+    if (int rc = enqueue_scan(sim, w, scan_blocks, &info->groups)) return rc;
+    hipLaunchKernelGGL(fof_rows_plan_kernel, dim3(1), dim3(1), 0, sim.stream, info, rows_cap);
+    NB_HIP_TRY(hipGetLastError());
+    nb_fof_group *rows = rows_cap > 0 ? (nb_fof_group *)w.rows : nullptr;
+    hipLaunchKernelGGL(fof_rows_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.flags, w.excl,
+                       w.block_tot, w.count, n, w.row_of, rows);
+    NB_HIP_TRY(hipGetLastError());
+    if (want_group_of || rows_cap > 0) {
+        hipLaunchKernelGGL(fof_group_of_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.row_of,
+                           n, w.group_of, rows_cap > 0 ? (unsigned long long *)keys[0] : nullptr);
+        NB_HIP_TRY(hipGetLastError());
+    }
+    if (rows_cap > 0) {  // the catalogue's sums
+        if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, (bits_of(rows_cap) + 7) / 8, 0, &info->passes[1]))
+            return rc;
+        hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0],
+                           keys[1], n, w.row_start);
+        NB_HIP_TRY(hipGetLastError());
+        if (sums) {
+            hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm,
+                               vel, idx[0], idx[1], w.row_start, len, w.runs);
+            NB_HIP_TRY(hipGetLastError());
+            const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
+            hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info,
+                               w.row_start, w.runs, rows);
+            NB_HIP_TRY(hipGetLastError());
+        }
+    }
+    return NB_OK;
+}
+
 int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t rows_cap, bool want_group_of,
                 bool sums) {
     const uint32_t n = sim.n;
@@ -596,7 +668,6 @@ int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t 
     const double h = fof_cell_side(params.link);
     const uint32_t len = (uint32_t)sim.fof_chunk_len, use_boxes = (uint32_t)sim.fof_cell_boxes;
     const unsigned long long union_items = (unsigned long long)n / len + n + 1;
-    const unsigned long long sum_items = (unsigned long long)n / len + rows_cap + 1;
     if (union_items > 0x7fffffffull) {
         set_error("fof: %u bodies are more than one call takes", n);
         return NB_ERR_UNSUPPORTED;
@@ -605,26 +676,13 @@ int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t 
         const uint32_t blocks = (n + kThreads - 1) / kThreads;
         const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
         const SortShape shape = sort_shape(n);
-        const size_t run_slots = (size_t)n / kWave + rows_cap + 1;
-        if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return fof_reserve(b, count); })) return rc;
+        if (int rc = fof_catalogue_reserve(w, n, rows_cap)) return rc;
         if (int rc = fof_reserve(w.slabs, (size_t)kBoundFields * blocks)) return rc;
-        if (int rc = fof_reserve(w.flags, n)) return rc;
-        if (int rc = fof_reserve(w.excl, n)) return rc;
-        if (int rc = fof_reserve(w.block_tot, (size_t)scan_blocks + 1)) return rc;
         if (int rc = fof_reserve(w.cell_key, n)) return rc;
         if (int rc = fof_reserve(w.cell_start, (size_t)n + 1)) return rc;
         if (int rc = fof_reserve(w.boxes, (size_t)6 * n)) return rc;
         if (int rc = fof_reserve(w.spos, n)) return rc;
         if (int rc = fof_reserve(w.parent, n)) return rc;
-        if (int rc = fof_reserve(w.labels, n)) return rc;
-        if (int rc = fof_reserve(w.count, n)) return rc;
-        if (int rc = fof_reserve(w.row_of, n)) return rc;
-        if (int rc = fof_reserve(w.group_of, n)) return rc;
-        if (rows_cap > 0) {
-            if (int rc = fof_reserve(w.row_start, (size_t)rows_cap + 1)) return rc;
-            if (int rc = fof_reserve(w.runs, run_slots * kTerms)) return rc;
-            if (int rc = fof_reserve(w.rows, rows_cap)) return rc;
-        }
 
         const float4 *posm = nullptr, *vel = nullptr;
         sim.diag_state(&posm, &vel);
@@ -654,42 +712,8 @@ int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t 
         hipLaunchKernelGGL(fof_union_kernel, dim3((uint32_t)union_items), dim3(kWave), 0, sim.stream, info, w.cell_key,
                            w.cell_start, w.boxes, idx[0], idx[1], w.spos, w.parent, len, b2, use_boxes);
         NB_HIP_TRY(hipGetLastError());
-        // labels, sizes, rows
-        NB_HIP_TRY(hipMemsetAsync(w.count, 0, sizeof(uint32_t) * n, sim.stream));
-        hipLaunchKernelGGL(fof_label_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.parent, n, w.labels,
-                           w.count);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_roots_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.count, n,
-                           params.min_members, w.flags);
-        NB_HIP_TRY(hipGetLastError());
-        if (int rc = enqueue_scan(sim, w, scan_blocks, &info->groups)) return rc;
-        hipLaunchKernelGGL(fof_rows_plan_kernel, dim3(1), dim3(1), 0, sim.stream, info, rows_cap);
-        NB_HIP_TRY(hipGetLastError());
-        nb_fof_group *rows = rows_cap > 0 ? (nb_fof_group *)w.rows : nullptr;
-        hipLaunchKernelGGL(fof_rows_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.flags, w.excl,
-                           w.block_tot, w.count, n, w.row_of, rows);
-        NB_HIP_TRY(hipGetLastError());
-        if (want_group_of || rows_cap > 0) {
-            hipLaunchKernelGGL(fof_group_of_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, w.labels, w.row_of,
-                               n, w.group_of, rows_cap > 0 ? (unsigned long long *)keys[0] : nullptr);
-            NB_HIP_TRY(hipGetLastError());
-        }
-        if (rows_cap > 0) {  // the catalogue's sums
-            if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, (bits_of(rows_cap) + 7) / 8, 0, &info->passes[1]))
-                return rc;
-            hipLaunchKernelGGL(fof_row_start_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0],
-                               keys[1], n, w.row_start);
-            NB_HIP_TRY(hipGetLastError());
-            if (sums) {
-                hipLaunchKernelGGL(fof_sum_kernel, dim3((uint32_t)sum_items), dim3(kWave), 0, sim.stream, info, posm,
-                                   vel, idx[0], idx[1], w.row_start, len, w.runs);
-                NB_HIP_TRY(hipGetLastError());
-                const uint32_t combine_blocks = (uint32_t)(((size_t)rows_cap * kRowLanes + kThreads - 1) / kThreads);
-                hipLaunchKernelGGL(fof_combine_kernel, dim3(combine_blocks), dim3(kThreads), 0, sim.stream, info,
-                                   w.row_start, w.runs, rows);
-                NB_HIP_TRY(hipGetLastError());
-            }
-        }
+        if (int rc = fof_catalogue_enqueue(sim, w, w.parent, params.min_members, rows_cap, want_group_of, sums))
+            return rc;
     }
     return NB_OK;
 }

@@ -1,6 +1,7 @@
 // nb_fof.hpp -- what the passes that start from the friends-of-friends groups share (nb_fof.hip: nb_sim_fof itself;
-// nb_bound.hip: nb_sim_bound): the plan and the integer results of the group finder on the device, its workspace,
-// the part of it that only enqueues, and the work-item table over lists of unequal length.
+// nb_bound.hip: nb_sim_bound), and what every group finder shares (nb_hop.hip: nb_sim_hop): the plan and the integer
+// results of the group finder on the device, its workspace, the parts of it that only enqueue, and the work-item table
+// over lists of unequal length.
 #pragma once
 
 #include <algorithm>
@@ -59,6 +60,14 @@ inline uint32_t fof_rows_cap(uint32_t n, size_t group_capacity, uint32_t min_mem
 int fof_work(SimBase &sim, FofWork **out);
 int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t rows_cap, bool want_group_of,
                 bool sums);
+// The part of the pass from "labels, sizes, rows" onwards, which every group finder shares (nb_hop.hip calls it with
+// its own forest): parent[i] is NB_FOF_NONE for a body of no group, else a body of i's group nearer its root, the
+// root pointing at itself.  It resolves w.labels, sizes the groups and makes the catalogue exactly as described
+// above; w.info must hold status 0 and zeroed integer results, and fof_catalogue_reserve(w, n, rows_cap) must have
+// succeeded before anything of the call was enqueued.
+int fof_catalogue_reserve(FofWork &w, uint32_t n, uint32_t rows_cap);
+int fof_catalogue_enqueue(SimBase &sim, FofWork &w, const uint32_t *parent, uint32_t min_members, uint32_t rows_cap,
+                          bool want_group_of, bool sums);
 // the error of a refused plan (info->status), reported after the call's synchronisation
 int fof_refused(const nb_fof_params &params);
 

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -177,6 +177,10 @@ int sim_bound(SimBase &sim, const nb_bound_params &params, uint32_t *group_of, u
 // nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);
+// nb_hop.hip: nb_sim_hop behind the handle (arguments already checked by hop_check_params, nb_abi.cpp)
+int sim_hop(SimBase &sim, const nb_hop_params &params, uint32_t *labels, uint32_t *group_of, double *density,
+            nb_fof_group *groups, double *peak_density, size_t group_capacity, nb_hop_boundary *boundaries,
+            size_t boundary_capacity, nb_hop_stats *stats);
 // nb_smooth.hip: nb_sim_smooth_map behind the handle (arguments already checked by smooth_check_params,
 // nb_abi.cpp, which also forms the frame, the pixel sizes and the pixel centres)
 struct SmoothPlan {

@@ -43,6 +43,8 @@ using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sum
 using FofStats = nb_fof_stats;
 using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound set
 using BoundStats = nb_bound_stats;
+using HopBoundary = nb_hop_boundary;      // 24 B: two labels, their body pairs and the largest pair density
+using HopStats = nb_hop_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
 using HaloHead = nb_halo_head;            // 64 B: what lies inside edges[0], the centre and velocity used, flags
 using HaloStats = nb_halo_stats;
@@ -302,6 +304,104 @@ BoundGroups bound_groups(int (*call)(H *, const nb_bound_params *, uint32_t *, u
 }
 }  // namespace detail
 
+// The density-peak groups of a state (nb_sim_hop; no reference counterpart): per body the label (the body at its
+// density peak) and the catalogue row (NB_HOP_NONE: none), the catalogue in ascending label order with one peak
+// density per row, and the boundaries between labels in ascending (a, b).  A vector that was not asked for is empty
+struct HopParams {
+    uint32_t k_density = 64, k_hop = 16, k_merge = 4, min_members = 1;
+    double density_min = -std::numeric_limits<double>::infinity();
+};
+struct HopGroups {
+    std::vector<uint32_t> labels, group_of;
+    std::vector<double> density;
+    std::vector<FofGroup> groups;
+    std::vector<double> peak_density;
+    std::vector<HopBoundary> boundaries;
+    HopStats stats{};
+    // the rows by count, descending, ties by label
+    std::vector<uint32_t> by_size() const {
+        std::vector<uint32_t> o(groups.size());
+        for (size_t i = 0; i < o.size(); ++i) o[i] = (uint32_t)i;
+        std::sort(o.begin(), o.end(), [this](uint32_t a, uint32_t b) {
+            return groups[a].count != groups[b].count ? groups[a].count > groups[b].count : groups[a].label < groups[b].label;
+        });
+        return o;
+    }
+    // nb_hop_regroup: the merged catalogue, labels and group_of mapped through the merge, no boundaries
+    HopGroups regroup(double saddle, double peak) const {
+        HopGroups m;
+        nb_hop_regroup_params rp{};
+        rp.saddle = saddle;
+        rp.peak = peak;
+        std::vector<uint32_t> merged(groups.size());
+        m.groups.resize(groups.size());
+        m.peak_density.resize(groups.size());
+        size_t count = 0;
+        check(nb_hop_regroup(groups.data(), peak_density.data(), groups.size(), boundaries.data(), boundaries.size(), &rp,
+                             merged.data(), m.groups.data(), m.peak_density.data(), groups.size(), &count));
+        m.groups.resize(count);
+        m.peak_density.resize(count);
+        m.density = density;
+        m.stats = stats;
+        m.stats.groups = count;
+        m.stats.grouped_bodies = m.stats.boundaries = m.stats.boundary_pairs = 0;
+        m.stats.largest_count = 0;
+        m.stats.largest_label = NB_HOP_NONE;
+        for (const FofGroup &g : m.groups) {
+            m.stats.grouped_bodies += g.count;
+            if (g.count > m.stats.largest_count) {
+                m.stats.largest_count = g.count;
+                m.stats.largest_label = g.label;
+            }
+        }
+        m.group_of.assign(group_of.size(), NB_HOP_NONE);
+        if (!labels.empty()) m.labels.assign(labels.size(), NB_HOP_NONE);
+        for (size_t i = 0; i < group_of.size(); ++i) {
+            if (group_of[i] == NB_HOP_NONE || merged[group_of[i]] == NB_HOP_NONE) continue;
+            const uint32_t label = merged[group_of[i]];
+            const auto at = std::lower_bound(m.groups.begin(), m.groups.end(), label,
+                                             [](const FofGroup &g, uint32_t l) { return g.label < l; });
+            m.group_of[i] = (uint32_t)(at - m.groups.begin());
+            if (!labels.empty()) m.labels[i] = label;
+        }
+        return m;
+    }
+};
+
+namespace detail {
+template <class H>
+HopGroups hop_groups(int (*call)(H *, const nb_hop_params *, uint32_t *, uint32_t *, double *, nb_fof_group *, double *,
+                                 size_t, nb_hop_boundary *, size_t, nb_hop_stats *),
+                     H *h, size_t n, const HopParams &hp, bool labels, bool density, bool boundaries) {
+    HopGroups g;
+    nb_hop_params p{};
+    p.k_density = hp.k_density;
+    p.k_hop = hp.k_hop;
+    p.k_merge = hp.k_merge;
+    p.min_members = hp.min_members;
+    p.density_min = hp.density_min;
+    if (labels) g.labels.resize(n);
+    g.group_of.resize(n);
+    if (density) g.density.resize(n);
+    size_t cap = n / 4 + 1, bcap = boundaries ? 4 * cap : 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // once more with the sizes the stats report, if they are larger
+        g.groups.assign(cap, FofGroup{});
+        g.peak_density.assign(cap, 0.0);
+        g.boundaries.assign(bcap, HopBoundary{});
+        check(call(h, &p, labels ? g.labels.data() : nullptr, g.group_of.data(), density ? g.density.data() : nullptr,
+                   g.groups.data(), g.peak_density.data(), cap, boundaries ? g.boundaries.data() : nullptr, bcap,
+                   &g.stats));
+        if (g.stats.groups <= cap && (!boundaries || g.stats.boundaries <= bcap)) break;
+        cap = std::max<size_t>(cap, (size_t)g.stats.groups);
+        if (boundaries) bcap = std::max<size_t>(bcap, (size_t)g.stats.boundaries);
+    }
+    g.groups.resize((size_t)g.stats.groups);
+    g.peak_density.resize((size_t)g.stats.groups);
+    g.boundaries.resize(boundaries ? (size_t)g.stats.boundaries : 0);
+    return g;
+}
+}  // namespace detail
+
 // The k-th nearest neighbour of every body of a state, the mass inside it and the density from them (no
 // reference counterpart); a vector that was not asked for is empty
 struct KnnDensity {
@@ -553,6 +653,10 @@ class Simulator {
                                     min_bound ? min_bound : min_members, max_iter, max_group, per_body);
     }
     // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
+    HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
+                         bool boundaries = true) {
+        return detail::hop_groups(nb_sim_hop, h_, sim_params().particle_num, p, labels, density, boundaries);
+    }
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
     }
@@ -714,6 +818,12 @@ class OfflineHeadless {
         check(nb_runner_sim_params(r_, &sp));
         return detail::bound_groups(nb_runner_bound, r_, sp.particle_num, link, min_members,
                                     min_bound ? min_bound : min_members, max_iter, max_group, per_body);
+    }
+    HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
+                         bool boundaries = true) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::hop_groups(nb_runner_hop, r_, sp.particle_num, p, labels, density, boundaries);
     }
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {  // one device only
         SimParams sp{};
