@@ -1159,6 +1159,152 @@ int nb_halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, con
                         double rho, double *r, double *mass);
 
 /* ------------------------------------------------------------------------- */
+/* Group shapes -- axis ratios, principal axes and angular momentum of every  */
+/* row of an assignment of bodies to rows (no reference counterpart)          */
+/* ------------------------------------------------------------------------- */
+/* For each of m rows: the shape tensor of the row's members inside an ellipsoid
+ * that is deformed round by round until its axis ratios are those of the tensor
+ * (Allgood et al. 2006, Zemp et al. 2011), with the mass, the first and second
+ * moments of position and velocity and the angular momentum of the same members.
+ * The rule, which DESIGN.md 6n states in full; binary64 from the binary32 state,
+ * one rounding per operation, no contraction:
+ *   input     group_of[n]: NB_FOF_NONE or a row < m for every body of the state
+ *             nb_sim_read_particles would return; nb_sim_fof's group_of,
+ *             nb_sim_bound's bound_of, nb_sim_hop's group_of (raw or regrouped) or
+ *             any assignment of the caller's.  0 <= m <= max(n, 1).  centers[m][3],
+ *             velocities[m][3]: finite, either may be null; radius[m]: each finite
+ *             and > 0, or +inf; null: all +inf
+ *   members   row r's list L is the bodies with group_of == r that count (the
+ *             predicate of nb_sim_diagnostics) in ascending body index; the others
+ *             with a row are stats->nonfinite_members.  `count` = |L|.  count == 0:
+ *             the row is EMPTY (sums 0, iterations 0, a centre or velocity that was
+ *             not given NaN, lambda, axes, q and s NaN)
+ *   round t   (t = 1, 2, ...) with centre c, frame velocity V, radius R, axes E
+ *             (rows e_1, e_2, e_3) and ratios (q, s); round 1 has E = identity and
+ *             (q, s) = (1, 1).  Per member: d = (double)x - c and u = (double)v - V per
+ *             component; y_k = (e_kx dx + e_ky dy) + e_kz dz; a = (R, R q, R s);
+ *             rho2 = ((y_1 / a_1)^2 + (y_2 / a_2)^2) + (y_3 / a_3)^2; the member is
+ *             selected iff rho2 <= 1 (a NaN is not).  Over the selected members:
+ *             `selected` = their number, and the 22 sums
+ *               mass = sum m;  md = sum m d;  mu = sum m u;
+ *               t  = sum ((w m) d_i) d_j   for ij = xx xy xz yy yz zz
+ *               uu = sum (m u_i) u_j       in the same order
+ *               j  = sum m (d_y u_z - d_z u_y), m (d_z u_x - d_x u_z), m (d_x u_y - d_y u_x)
+ *             w m = m, or with NB_SHAPE_REDUCED w m = (1 / rho2) m, and 0 for rho2 == 0
+ *             (such a member adds nothing to t).  NB_SHAPE_REDUCED needs a finite R
+ *   round 0   only when centers or velocities is null: the sums of round t with
+ *             R = +inf about c = 0 (centers null) and V = 0 (velocities null), so
+ *             that md = sum m x and mu = sum m v over L; then c = md / mass and
+ *             V = mu / mass per component, for the one that was not given
+ *   verdict   (lambda, E') = nb_shape_eigen(t).  The row is DEGENERATE when
+ *             selected < min_members, or unless lambda_3 > 0 and all three are
+ *             finite: q = s = NaN.  Otherwise q' = sqrt(lambda_2 / lambda_1),
+ *             s' = sqrt(lambda_3 / lambda_1).  R = +inf: CONVERGED (after round 1).
+ *             Otherwise delta = max(|q' - q| / q', |s' - s| / s'); t >= 2 and
+ *             delta < tol: CONVERGED; else t == max_iter: UNCONVERGED; else round t + 1
+ *             with (q', s', E').  A finished row reports round t: iterations = t, the
+ *             sums of round t, lambda, axes = E', q = q', s = s'
+ *   the axes  the major axis keeps the length R and the other two shrink: the
+ *             ellipsoid never reaches outside the sphere of radius R the caller
+ *             chose -- the region the caller vouches for (a group's extent, a virial
+ *             radius) -- whereas an ellipsoid of fixed volume or fixed minor axis
+ *             grows past it into bodies that the first round never saw
+ *   sums      position p of a member is its place in L for the whole call; a member
+ *             that is not selected adds +0 (masking, as nb_sim_bound).  Runs of 64
+ *             positions [64 k, 64 k + 64) are reduced by the fixed butterfly of
+ *             nb_sim_fof (v_i + v_(i xor 32), then xor 16, ... 1) and a row's runs
+ *             are added in order from 0.  So a row's outputs are a function of its
+ *             own list, centre, velocity and radius alone -- not of the other rows,
+ *             of its number, of m or of the tuning key -- and two calls return the
+ *             same bits.  No float atomics.  Every sum is within 1e-10 of its sum of
+ *             |term| of the binary64 sum
+ *   selected_of[i] the row of body i when the row is CONVERGED or UNCONVERGED and i
+ *             was selected in its last round, else NB_FOF_NONE
+ * nb_shape_eigen is the cyclic Jacobi diagonalisation of nb_shape.hpp, the same
+ * function on the host and on the device: t = (xx, xy, xz, yy, yz, zz); V = identity;
+ * at most 12 sweeps; a sweep ends the iteration when (|a01| + |a02|) + |a12| == 0,
+ * else visits (p, q) = (0,1), (0,2), (1,2) with r the third index: a_pq == 0:
+ * nothing; g = 100 |a_pq|; |a_pp| + g == |a_pp| and |a_qq| + g == |a_qq|: a_pq <- 0;
+ * otherwise h = a_qq - a_pp, t = a_pq / h when |h| + g == |h|, else
+ * theta = (0.5 h) / a_pq, t = 1 / (|theta| + sqrt(theta theta + 1)), negated for
+ * theta < 0; c = 1 / sqrt(t t + 1), s = t c, tau = s / (1 + c), z = t a_pq;
+ * a_pp <- a_pp - z, a_qq <- a_qq + z, a_pq <- 0, (a_rp, a_rq) <- (a_rp - s (a_rq +
+ * tau a_rp), a_rq + s (a_rp - tau a_rq)) and likewise (v_kp, v_kq) for k = 0, 1, 2.
+ * lambda = the diagonal sorted descending, equal values in index order;
+ * axes[3 k + j] = component j of the eigenvector of lambda[k], negated when its
+ * component of largest magnitude (the first of equals) is negative.
+ * params->step_num must equal the simulator's step number (a TreeSim reorders its
+ * bodies every step, so an assignment is good for the step it was made at);
+ * NB_SHAPE_ANY_STEP switches the check off.
+ * The call is ordered after the enqueued steps on the simulator's stream, enqueues
+ * all max_iter rounds up front (the blocks of a finished row return at once), ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.
+ * "shape_chunk_len" (nb_sim_set_tuning, 64..65536, a multiple of 64; default 1024):
+ * the positions of a row's list one work item takes.  Speed and testing only: it
+ * changes no bit of the result. */
+#define NB_SHAPE_REDUCED 1u /* nb_shape_params.flags */
+#define NB_SHAPE_CONVERGED 1u
+#define NB_SHAPE_UNCONVERGED 2u
+#define NB_SHAPE_DEGENERATE 4u
+#define NB_SHAPE_EMPTY 8u
+#define NB_SHAPE_MAX_ITER 64u
+#define NB_SHAPE_ANY_STEP 0xFFFFFFFFFFFFFFFFull /* nb_shape_params.step_num: UINT64_MAX */
+
+typedef struct nb_shape_params {
+    uint32_t flags;       /* 0 or NB_SHAPE_REDUCED */
+    uint32_t min_members; /* >= 1: a row with fewer selected members is degenerate */
+    uint32_t max_iter;    /* 1 .. NB_SHAPE_MAX_ITER */
+    uint32_t reserved32;  /* 0 */
+    double tol;           /* finite and > 0 */
+    uint64_t step_num;    /* the simulator's step number, or NB_SHAPE_ANY_STEP */
+    uint64_t reserved;    /* 0 */
+} nb_shape_params;
+
+typedef struct nb_shape_group { /* 360 bytes */
+    uint32_t count, selected;   /* |L|; members selected in the last round */
+    uint32_t iterations, status; /* rounds that ran; one of NB_SHAPE_CONVERGED .. NB_SHAPE_EMPTY */
+    double radius;               /* R */
+    double center[3], velocity[3]; /* the values used */
+    double mass, md[3], mu[3], t[6], uu[6], j[3]; /* the 22 sums of the last round */
+    double lambda[3], axes[9];   /* descending; axes[3 k + j] = component j of axis k */
+    double q, s;                 /* b/a and c/a */
+} nb_shape_group;
+
+typedef struct nb_shape_stats {
+    uint64_t step_num, n;
+    uint64_t rows;              /* m */
+    uint64_t members;           /* counted bodies with a row */
+    uint64_t nonfinite_members; /* bodies with a row that do not count */
+    uint64_t converged, unconverged, degenerate, empty; /* rows by status */
+    uint32_t rounds_max;        /* the largest `iterations` */
+    uint32_t reserved;
+} nb_shape_stats;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_shape_params) == 40 && sizeof(nb_shape_group) == 360 && sizeof(nb_shape_stats) == 80,
+              "nb_shape_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_shape_params) == 40 && sizeof(nb_shape_group) == 360 && sizeof(nb_shape_stats) == 80,
+               "nb_shape_* layouts");
+#endif
+
+/* group_of: n values (may be null for n == 0); rows_out: m rows; selected_of: n values.  Every output
+ * pointer may be null: what is not asked for is not copied.  The outputs are written only by a call
+ * that succeeds.  NB_ERR_INVALID for a null handle or params, a null group_of with n > 0,
+ * m > max(n, 1), a non-finite centre or velocity, a radius that is neither finite and > 0 nor +inf,
+ * NB_SHAPE_REDUCED with an infinite (or null) radius, min_members == 0, max_iter outside
+ * 1..NB_SHAPE_MAX_ITER, a tol that is not finite and > 0, unknown flags or a reserved field != 0, a
+ * step_num that is neither the simulator's nor NB_SHAPE_ANY_STEP -- all checked before any device
+ * call -- and, after the call's one synchronisation, for a value of group_of that is neither
+ * NB_FOF_NONE nor < m; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_sim_group_shapes(nb_sim *sim, const nb_shape_params *params, const uint32_t *group_of, size_t m,
+                        const double *centers, const double *velocities, const double *radius,
+                        nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats);
+/* Host only: the eigen-solver of the rule above.  NB_ERR_INVALID for a null pointer. */
+int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]);
+
+/* ------------------------------------------------------------------------- */
 /* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
 /* kernel of its own radius (no reference counterpart: the image of the       */
 /* density estimate, where nb_sim_map gives shot noise)                       */
@@ -1437,6 +1583,11 @@ int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, ui
  * runner. */
 int nb_runner_halo_profiles(nb_runner *runner, const nb_halo_params *params, nb_halo_head *heads,
                             nb_radial_bin *bins, nb_halo_stats *stats);
+/* nb_sim_group_shapes of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_runner_group_shapes(nb_runner *runner, const nb_shape_params *params, const uint32_t *group_of, size_t m,
+                           const double *centers, const double *velocities, const double *radius,
+                           nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

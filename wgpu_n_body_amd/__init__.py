@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import math
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
@@ -1015,6 +1016,214 @@ def _group_profiles(halo_profiles, groups, center, kw):
     raise ValueError('group_profiles: center is "com", "most_bound" or "peak"')
 
 
+SHAPE_CONVERGED, SHAPE_UNCONVERGED = _lib.NB_SHAPE_CONVERGED, _lib.NB_SHAPE_UNCONVERGED
+SHAPE_DEGENERATE, SHAPE_EMPTY = _lib.NB_SHAPE_DEGENERATE, _lib.NB_SHAPE_EMPTY
+
+
+@dataclass(frozen=True)
+class ShapeStats:
+    """nb_shape_stats (include/nbody.h "Group shapes")."""
+    step_num: int
+    n: int
+    rows: int
+    members: int            # counted bodies with a row
+    nonfinite_members: int
+    converged: int
+    unconverged: int
+    degenerate: int
+    empty: int
+    rounds_max: int
+
+
+@dataclass(frozen=True)
+class GroupShapes:
+    """nb_sim_group_shapes' rows (include/nbody.h "Group shapes"; no reference counterpart): for every row of an
+    assignment of bodies to rows the shape tensor of the members inside an ellipsoid deformed until its axis ratios
+    are the tensor's, with the mass, the velocity moments and the angular momentum of the same members.  rows:
+    _lib.SHAPE_GROUP_DTYPE records; catalogue_rows: the rows of the catalogue they belong to (group_shapes leaves
+    out the rows without a finite centre; shapes_of: 0 .. m - 1); selected_of: (n,) uint32, the row (of `rows`) of a
+    body selected in the last round of a row with a shape, FOF_NONE otherwise, or None when not asked for."""
+    rows: np.ndarray
+    catalogue_rows: np.ndarray
+    selected_of: Optional[np.ndarray]
+    reduced: bool
+    max_iter: int
+    tol: float
+    min_members: int
+    stats: ShapeStats
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.rows["status"]
+
+    @property
+    def b_over_a(self) -> np.ndarray:
+        """q = sqrt(lambda_2 / lambda_1); NaN for a row without a shape."""
+        return self.rows["q"]
+
+    @property
+    def c_over_a(self) -> np.ndarray:
+        """s = sqrt(lambda_3 / lambda_1)."""
+        return self.rows["s"]
+
+    @property
+    def triaxiality(self) -> np.ndarray:
+        """(1 - q^2) / (1 - s^2): 0 oblate, 1 prolate; NaN for a sphere."""
+        q, s = self.rows["q"], self.rows["s"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (1.0 - q * q) / (1.0 - s * s)
+
+    @property
+    def major_axis(self) -> np.ndarray:
+        """(rows, 3): the unit eigenvector of the largest eigenvalue."""
+        return self.rows["axes"][:, 0:3]
+
+    @property
+    def minor_axis(self) -> np.ndarray:
+        return self.rows["axes"][:, 6:9]
+
+    @property
+    def angular_momentum(self) -> np.ndarray:
+        """(rows, 3): J = sum m (d x u) of the selected members about the centre, in the frame of `velocity`."""
+        return self.rows["j"]
+
+    @property
+    def spin_axis(self) -> np.ndarray:
+        """(rows, 3): J / |J|; NaN for J = 0."""
+        j = self.rows["j"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return j / np.sqrt((j * j).sum(axis=1))[:, None]
+
+    @property
+    def misalignment(self) -> np.ndarray:
+        """The angle between J and the minor axis, 0 .. pi/2 (an axis has no sign)."""
+        with np.errstate(invalid="ignore"):
+            return np.arccos(np.minimum(np.abs((self.spin_axis * self.minor_axis).sum(axis=1)), 1.0))
+
+    @property
+    def sigma_tensor(self) -> np.ndarray:
+        """(rows, 3, 3): the mass-weighted velocity dispersion tensor of the selected members about their mean."""
+        r = self.rows
+        with np.errstate(invalid="ignore", divide="ignore"):
+            uu = r["uu"] / r["mass"][:, None]
+            mean = r["mu"] / r["mass"][:, None]
+        out = np.empty((len(r), 3, 3))
+        for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+            out[:, i, j] = out[:, j, i] = uu[:, k] - mean[:, i] * mean[:, j]
+        return out
+
+    def spin_bullock(self, G: float) -> np.ndarray:
+        """|J| / (sqrt(2) M R sqrt(G M / R)) (Bullock et al. 2001) of the selected members, for a finite R."""
+        r = self.rows
+        j = np.sqrt((r["j"] * r["j"]).sum(axis=1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lam = j / (math.sqrt(2.0) * r["mass"] * r["radius"] * np.sqrt(G * r["mass"] / r["radius"]))
+        return np.where(np.isfinite(r["radius"]), lam, np.nan)
+
+
+def _shape_radius(radius, m, rms):
+    """None, or the (m,) radii of a call: a number for all rows, one per row, or ("rms", k) for k rms[r]."""
+    if radius is None:
+        return None
+    if isinstance(radius, tuple) and len(radius) == 2 and radius[0] == "rms":
+        if rms is None:
+            raise ValueError('group_shapes: radius=("rms", k) needs a catalogue with an rms radius')
+        return np.ascontiguousarray(float(radius[1]) * np.asarray(rms, dtype=np.float64))
+    r = np.asarray(radius, dtype=np.float64)
+    if r.ndim == 0:
+        return np.full(m, float(r))
+    if r.shape != (m,):
+        raise ValueError(f"group_shapes: {m} rows need {m} radii, or one for all")
+    return np.ascontiguousarray(r)
+
+
+def _group_shapes(call, handle, n, group_of, m, centers, velocities, radius, reduced, max_iter, tol, min_members,
+                  per_body, step_num, catalogue_rows) -> GroupShapes:
+    for name, v in (("min_members", min_members), ("max_iter", max_iter), ("m", m)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:  # (the call itself refuses the zeros that mean nothing)
+            raise ValueError(f"group_shapes: {name} = {v} is not a 32-bit count")
+    m = int(m)
+    gof = np.ascontiguousarray(group_of, dtype=np.uint32).reshape(-1)
+    if gof.shape[0] != n:
+        raise ValueError(f"group_shapes: group_of has {gof.shape[0]} values for {n} bodies")
+    p = _lib.nb_shape_params()
+    p.flags, p.reserved32, p.reserved = (_lib.NB_SHAPE_REDUCED if reduced else 0), 0, 0
+    p.min_members, p.max_iter, p.tol = int(min_members), int(max_iter), float(tol)
+    p.step_num = _lib.NB_SHAPE_ANY_STEP if step_num is None else int(step_num)
+
+    def vec(a, width, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, width) if width > 1 else _shape_radius(a, m, None)
+        if a.shape[0] != m:
+            raise ValueError(f"group_shapes: {m} rows need {m} {what}")
+        return a
+    centers, velocities, radius = vec(centers, 3, "centers"), vec(velocities, 3, "velocities"), vec(radius, 1, "radii")
+    rows = np.zeros(m, dtype=_lib.SHAPE_GROUP_DTYPE)
+    sel = np.empty(n, dtype=np.uint32) if per_body else None
+    st = _lib.nb_shape_stats()
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    check(call(handle, C.byref(p), ptr(gof), m, ptr(centers), ptr(velocities), ptr(radius), rows.ctypes.data, ptr(sel),
+               C.byref(st)))
+    stats = ShapeStats(int(st.step_num), int(st.n), int(st.rows), int(st.members), int(st.nonfinite_members),
+                       int(st.converged), int(st.unconverged), int(st.degenerate), int(st.empty), int(st.rounds_max))
+    return GroupShapes(rows, np.asarray(catalogue_rows), sel, bool(reduced), int(max_iter), float(tol),
+                       int(min_members), stats)
+
+
+def _catalogue_rms(groups):
+    """The catalogue's mass-weighted rms radius about com (FofGroups.rms_radius), for every kind of catalogue."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = groups.com
+        return np.sqrt(np.maximum(groups._per_mass(groups.rows["mr2"]) - (c * c).sum(axis=1), 0.0))
+
+
+def _shapes_of_groups(shapes_of, read_particles, groups, members, center, radius, check_step, kw) -> GroupShapes:
+    """group_shapes: the assignment, the centres (as _group_profiles resolves them) and the radii from a catalogue."""
+    if members == "group":
+        assign = groups.group_of
+    elif members == "bound":
+        assign = getattr(groups, "bound_of", None)
+        if assign is None:
+            raise ValueError('group_shapes: members="bound" needs a BoundGroups made with per_body=True')
+    else:
+        raise ValueError('group_shapes: members is "group" or "bound"')
+    total = len(groups.rows)
+    if center == "com":
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c, v = groups.com, groups.velocity
+        rows = np.nonzero(np.isfinite(c).all(axis=1) & np.isfinite(v).all(axis=1))[0]
+        c, v = c[rows], v[rows]
+    elif center in ("most_bound", "peak"):
+        if center == "most_bound":
+            if "most_bound" not in (groups.rows.dtype.names or ()):
+                raise ValueError('group_shapes: center="most_bound" needs a BoundGroups')
+            body = groups.rows["most_bound"]
+            rows = np.nonzero(body != _lib.NB_FOF_NONE)[0]
+        else:
+            if not isinstance(groups, HopGroups):
+                raise ValueError('group_shapes: center="peak" needs a HopGroups')
+            body = groups.rows["label"]
+            rows = np.arange(total)
+        parts = read_particles()  # the body's widened position and velocity, as a body centre of halo_profiles
+        at = body[rows].astype(np.int64)
+        c = parts["position"][at].astype(np.float64)
+        v = parts["velocity"][at].astype(np.float64)
+        ok = np.isfinite(c).all(axis=1) & np.isfinite(v).all(axis=1)
+        rows, c, v = rows[ok], c[ok], v[ok]
+    else:
+        raise ValueError('group_shapes: center is "com", "most_bound" or "peak"')
+    rad = _shape_radius(radius, total, _catalogue_rms(groups) if isinstance(radius, tuple) else None)
+    # the usable rows renumbered 0 .. len(rows) - 1; a body of another row has no row
+    renumber = np.full(total + 1, _lib.NB_FOF_NONE, dtype=np.uint32)
+    renumber[rows] = np.arange(len(rows), dtype=np.uint32)
+    assign = np.asarray(assign, dtype=np.uint32)
+    mapped = renumber[np.minimum(assign, total)]  # (FOF_NONE -> the spare entry)
+    step = groups.stats.step_num if check_step else None
+    return shapes_of(mapped, len(rows), centers=c, velocities=v, radius=None if rad is None else rad[rows],
+                     step_num=step, catalogue_rows=rows, **kw)
+
+
 SMOOTH_K = _lib.NB_SMOOTH_K
 SMOOTH_PLANES = ("wm", "wm_ua", "wm_ub", "wm_w", "wm_w2", "wm_u2")
 
@@ -1554,6 +1763,31 @@ class Simulator:
         the profiles belong to, in order.  kw: edges / nbins / rmin / rmax / log of halo_profiles."""
         return _group_profiles(self.halo_profiles, groups, center, kw)
 
+    def shapes_of(self, group_of, m: int, *, centers=None, velocities=None, radius=None, reduced: bool = False,
+                  max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                  step_num=None, catalogue_rows=None) -> GroupShapes:
+        """The shapes of the m rows of a raw assignment (nb_sim_group_shapes): group_of (n,) uint32, FOF_NONE or a
+        row < m for every body of read_particles() now.  centers, velocities: (m, 3) or None for the members' own
+        centre of mass and mean velocity, formed on the device; radius: None (no cut: one round), a number or (m,);
+        reduced: weight the tensor by 1 / rho^2 (needs a radius).  step_num: the step the assignment was made at, to
+        have a stale one refused (a TreeSim reorders its bodies every step); None: not checked."""
+        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
+        return _group_shapes(_lib.lib().nb_sim_group_shapes, self._h, int(self.sim_params().particle_num), group_of, m,
+                             centers, velocities, radius, reduced, max_iter, tol, min_members, per_body, step_num, rows)
+
+    def group_shapes(self, groups, *, members: str = "group", center: str = "com", radius=None, reduced: bool = False,
+                     max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                     check_step: bool = True) -> GroupShapes:
+        """The shapes of the groups of a FofGroups, BoundGroups or HopGroups (raw or regrouped) of the same state:
+        axis ratios, principal axes, angular momentum and velocity moments of every group inside an ellipsoid
+        deformed to its own shape.  members: "group" (group_of) or "bound" (a BoundGroups' bound_of); center: as
+        group_profiles -- "com", "most_bound" or "peak" -- and the rows without a finite centre are left out
+        (GroupShapes.catalogue_rows names the ones that stay).  radius: None, a number, one per catalogue row, or
+        ("rms", k) for k times the catalogue's rms radius.  check_step: refuse a catalogue made at another step."""
+        kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
+        return _shapes_of_groups(self.shapes_of, self.dest_particle_slice, groups, members, center, radius, check_step,
+                                 kw)
+
     def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                      depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
                      s_min=None, s_max=None) -> SmoothedMap:
@@ -1785,6 +2019,22 @@ class OfflineHeadless:
     def group_profiles(self, groups, *, center: str = "com", **kw):
         """Simulator.group_profiles of the runner's simulator (one device only)."""
         return _group_profiles(self.halo_profiles, groups, center, kw)
+
+    def shapes_of(self, group_of, m: int, *, centers=None, velocities=None, radius=None, reduced: bool = False,
+                  max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                  step_num=None, catalogue_rows=None) -> GroupShapes:
+        """nb_runner_group_shapes: Simulator.shapes_of of the runner's simulator (one device only)."""
+        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
+        return _group_shapes(_lib.lib().nb_runner_group_shapes, self._h, int(self.sim_params().particle_num), group_of,
+                             m, centers, velocities, radius, reduced, max_iter, tol, min_members, per_body, step_num,
+                             rows)
+
+    def group_shapes(self, groups, *, members: str = "group", center: str = "com", radius=None, reduced: bool = False,
+                     max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                     check_step: bool = True) -> GroupShapes:
+        """Simulator.group_shapes of the runner's simulator (one device only)."""
+        kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
+        return _shapes_of_groups(self.shapes_of, self.read_particles, groups, members, center, radius, check_step, kw)
 
     def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                      depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,

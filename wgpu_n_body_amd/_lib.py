@@ -200,6 +200,26 @@ class nb_halo_stats(C.Structure):
                 ("tested", C.c_uint64), ("items", C.c_uint64), ("cells", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
+class nb_shape_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("min_members", C.c_uint32), ("max_iter", C.c_uint32),
+                ("reserved32", C.c_uint32), ("tol", C.c_double), ("step_num", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class nb_shape_group(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("selected", C.c_uint32), ("iterations", C.c_uint32), ("status", C.c_uint32),
+                ("radius", C.c_double), ("center", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("mass", C.c_double), ("md", C.c_double * 3), ("mu", C.c_double * 3), ("t", C.c_double * 6),
+                ("uu", C.c_double * 6), ("j", C.c_double * 3), ("lambda", C.c_double * 3), ("axes", C.c_double * 9),
+                ("q", C.c_double), ("s", C.c_double)]
+
+
+class nb_shape_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("rows", C.c_uint64), ("members", C.c_uint64),
+                ("nonfinite_members", C.c_uint64), ("converged", C.c_uint64), ("unconverged", C.c_uint64),
+                ("degenerate", C.c_uint64), ("empty", C.c_uint64), ("rounds_max", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class nb_smooth_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -239,6 +259,13 @@ FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"
 HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
                             ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
 
+# nb_shape_group[] as a numpy record array
+SHAPE_GROUP_DTYPE = np.dtype([("count", "<u4"), ("selected", "<u4"), ("iterations", "<u4"), ("status", "<u4"),
+                              ("radius", "<f8"), ("center", "<f8", (3,)), ("velocity", "<f8", (3,)), ("mass", "<f8"),
+                              ("md", "<f8", (3,)), ("mu", "<f8", (3,)), ("t", "<f8", (6,)), ("uu", "<f8", (6,)),
+                              ("j", "<f8", (3,)), ("lambda", "<f8", (3,)), ("axes", "<f8", (9,)), ("q", "<f8"),
+                              ("s", "<f8")])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -259,6 +286,8 @@ assert C.sizeof(nb_hop_params) == 40 and C.sizeof(nb_hop_stats) == 96 and C.size
 assert C.sizeof(nb_hop_boundary) == 24 == HOP_BOUNDARY_DTYPE.itemsize
 assert C.sizeof(nb_halo_params) == 48 and C.sizeof(nb_halo_stats) == 64
 assert C.sizeof(nb_halo_head) == 64 == HALO_HEAD_DTYPE.itemsize
+assert C.sizeof(nb_shape_params) == 40 and C.sizeof(nb_shape_stats) == 80
+assert C.sizeof(nb_shape_group) == 360 == SHAPE_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
@@ -282,6 +311,9 @@ NB_HOP_NONE = 0xFFFFFFFF
 NB_HALO_MAX_BINS, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS = 64, 1 << 20, 1 << 22
 NB_HALO_MAX_CELLS_PER_AXIS, NB_HALO_CHUNK, NB_HALO_EXTRA_ITEMS = 1024, 4096, 1 << 16
 NB_HALO_CENTER_NONFINITE = 1
+NB_SHAPE_REDUCED = 1
+NB_SHAPE_CONVERGED, NB_SHAPE_UNCONVERGED, NB_SHAPE_DEGENERATE, NB_SHAPE_EMPTY = 1, 2, 4, 8
+NB_SHAPE_MAX_ITER, NB_SHAPE_ANY_STEP = 64, 0xFFFFFFFFFFFFFFFF
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
 NB_SMOOTH_MAX_ENTRIES = 1 << 28
@@ -306,6 +338,7 @@ ABI_SYMBOLS = [
     "nb_sim_knn", "nb_runner_knn",
     "nb_sim_hop", "nb_runner_hop", "nb_hop_regroup",
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
+    "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
@@ -391,6 +424,9 @@ def lib() -> C.CDLL:
     L.nb_hop_regroup.argtypes = [vp, vp, sz, vp, sz, P(nb_hop_regroup_params), vp, vp, vp, sz, P(sz)]
     L.nb_sim_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
     L.nb_runner_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
+    L.nb_sim_group_shapes.argtypes = [vp, P(nb_shape_params), vp, sz, vp, vp, vp, vp, vp, P(nb_shape_stats)]
+    L.nb_runner_group_shapes.argtypes = [vp, P(nb_shape_params), vp, sz, vp, vp, vp, vp, vp, P(nb_shape_stats)]
+    L.nb_shape_eigen.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_halo_enclosed.argtypes = [vp, vp, C.c_uint32, P(C.c_double)]
     L.nb_halo_overdensity.argtypes = [vp, vp, P(C.c_double), C.c_uint32, C.c_double, P(C.c_double), P(C.c_double)]
     L.nb_sim_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]

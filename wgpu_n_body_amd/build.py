@@ -45,6 +45,9 @@ SOURCES = [
     ("nb_smooth.hip", ["-ffp-contract=off"]),
     # the per-centre rule is nb_radial.hip's and the grid is specified operation by operation
     ("nb_halo.hip", ["-ffp-contract=off"]),
+    # the selection, the 22 terms and the eigen-solver are specified operation by operation: no FMA
+    # contraction, on the host side of the unit (nb_shape_eigen) as on the device side
+    ("nb_shape.hip", ["-ffp-contract=off"]),
     ("nb_abi.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction

@@ -14,6 +14,8 @@
 //             [--smap-center com|X,Y,Z] [--smap-depth LO,HI] [--smap-k 32] [--smap-max PIXELS]]
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
 //            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
+//            [--shapes K --shapes-link B [--shapes-min M] [--shapes-radius KRMS] [--shapes-reduced 0|1]
+//             [--shapes-iter I] [--shapes-top T]]
 //            [--knn K [--knn-k 6]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
@@ -76,6 +78,15 @@
 // <row> <label> <count> <bound_count> <iterations> <status> <mass> <x> <y> <z> <kinetic> <potential>" (%.9e: the
 // bound mass, its centre of mass and its energies).  The time they take is not part of any "Step Duration";
 // without --bound the output is unchanged.
+//
+// --shapes K finds the friends-of-friends groups (as --fof, with --shapes-link and --shapes-min, default 20) of step 0
+// and of every K-th step and measures the shape of all of them in one call (nb_runner_group_shapes) about their centres
+// of mass in their own frames: inside KRMS times every group's rms radius (--shapes-radius; default 0: no cut, one
+// round), the tensor weighted by 1 / rho^2 with --shapes-reduced 1, at most I rounds (--shapes-iter, default 32).  One
+// line "shapes <step> <groups> <converged> <unconverged> <degenerate> <empty> <rounds_max>", then the T largest groups
+// (--shapes-top, default 0) as "shape_group <step> <row> <count> <selected> <q> <s> <T> <|J|> <status>" (every real
+// %.17g; T the triaxiality).  The time it takes is not part of any "Step Duration"; without --shapes the output is
+// unchanged.
 //
 // --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
 // every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
@@ -308,6 +319,32 @@ static void print_bound(nbody::OfflineHeadless<Sim> &runner, const BoundOptions 
     }
 }
 
+struct ShapesOptions {
+    int every = 0, top = 0;
+    double link = 0.0, k_rms = 0.0;
+    uint32_t min_members = 20, max_iter = 32;
+    bool reduced = false;
+};
+
+template <class Sim>
+static void print_shapes(nbody::OfflineHeadless<Sim> &runner, const ShapesOptions &so) {
+    const nbody::FofGroups f = runner.fof_groups(so.link, so.min_members, false);
+    nbody::ShapeOptions o;
+    o.reduced = so.reduced;
+    o.max_iter = so.max_iter;
+    const nbody::GroupShapes g = runner.group_shapes(f, so.k_rms, o);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("shapes %llu %llu %llu %llu %llu %llu %u\n", step, (unsigned long long)g.stats.rows,
+                (unsigned long long)g.stats.converged, (unsigned long long)g.stats.unconverged,
+                (unsigned long long)g.stats.degenerate, (unsigned long long)g.stats.empty, g.stats.rounds_max);
+    const std::vector<uint32_t> order = f.by_size();
+    for (size_t k = 0; k < order.size() && k < (size_t)so.top; ++k) {
+        const nbody::ShapeGroup &r = g.rows[order[k]];
+        std::printf("shape_group %llu %u %u %u %.17g %.17g %.17g %.17g %u\n", step, order[k], r.count, r.selected, r.q,
+                    r.s, g.triaxiality(order[k]), g.j_norm(order[k]), r.status);
+    }
+}
+
 struct KnnOptions {
     int every = 0;
     uint32_t k = 6;
@@ -448,7 +485,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int steps, int device, const std::vector<int> &devices, const std::string &dump, int let,
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
-               const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop) {
+               const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
+               const ShapesOptions &shapes) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -463,6 +501,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (knn.every > 0) print_knn(runner, knn);
     if (hop.every > 0) print_hop(runner, hop);
     if (halo.every > 0) print_halo(runner, halo);
+    if (shapes.every > 0) print_shapes(runner, shapes);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -480,6 +519,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
         if (hop.every > 0 && (i + 1) % hop.every == 0) print_hop(runner, hop);
         if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
+        if (shapes.every > 0 && (i + 1) % shapes.every == 0) print_shapes(runner, shapes);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -510,6 +550,7 @@ int main(int argc, char **argv) {
     BoundOptions bound;
     HaloOptions halo;
     HopOptions hop;
+    ShapesOptions shapes;
     bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -635,6 +676,13 @@ int main(int argc, char **argv) {
         else if (k == "--bound-iter") bound.max_iter = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--bound-max-group") bound.max_group = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--bound-top") bound.top = std::atoi(v.c_str());
+        else if (k == "--shapes") shapes.every = std::atoi(v.c_str());
+        else if (k == "--shapes-link") shapes.link = std::atof(v.c_str());
+        else if (k == "--shapes-min") shapes.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--shapes-radius") shapes.k_rms = std::atof(v.c_str());
+        else if (k == "--shapes-reduced") shapes.reduced = std::atoi(v.c_str()) != 0;
+        else if (k == "--shapes-iter") shapes.max_iter = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--shapes-top") shapes.top = std::atoi(v.c_str());
         else if (k == "--smaps") smaps.dir = v;
         else if (k == "--smap-every") smaps.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--smap-size") {
@@ -761,6 +809,14 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--bound needs --bound-link B > 0\n");
         return 2;
     }
+    if (shapes.every > 0 && !(shapes.link > 0.0)) {
+        std::fprintf(stderr, "--shapes needs --shapes-link B > 0\n");
+        return 2;
+    }
+    if (shapes.every > 0 && shapes.reduced && !(shapes.k_rms > 0.0)) {
+        std::fprintf(stderr, "--shapes-reduced 1 needs --shapes-radius KRMS > 0\n");
+        return 2;
+    }
     if (halo.every > 0 && (!(halo.link > 0.0) || !halo.have_range)) {
         std::fprintf(stderr, "--halo needs --halo-link B > 0 and --halo-range RMIN,RMAX\n");
         return 2;
@@ -771,9 +827,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -635,6 +635,74 @@ static int bound_check_e(const nb_sim *sim) {
     return NB_OK;
 }
 
+// nb_sim_group_shapes: everything that can be refused without a device -- the parameters alone, then (a handle in
+// hand) what needs the simulator's n and step number
+static int shape_check_params(const nb_shape_params *p) {
+    if (!p) {
+        set_error("group_shapes: null params");
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~NB_SHAPE_REDUCED) || p->reserved32 || p->reserved) {
+        set_error("group_shapes: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("group_shapes: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->max_iter < 1 || p->max_iter > NB_SHAPE_MAX_ITER) {
+        set_error("group_shapes: max_iter must be 1..%u (got %u)", NB_SHAPE_MAX_ITER, p->max_iter);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->tol) || !(p->tol > 0.0)) {
+        set_error("group_shapes: tol must be finite and > 0 (got %g)", p->tol);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+static int shape_check_args(const nb_sim *sim, const nb_shape_params *p, const uint32_t *group_of, size_t m,
+                            const double *centers, const double *velocities, const double *radius) {
+    if (!sim || !sim->impl) {
+        set_error("null simulator");
+        return NB_ERR_INVALID;
+    }
+    const SimBase &s = *sim->impl;
+    if (s.n > 0 && !group_of) {
+        set_error("group_shapes: null group_of");
+        return NB_ERR_INVALID;
+    }
+    if (m > std::max<size_t>(s.n, 1)) {
+        set_error("group_shapes: %zu rows are more than %u bodies can fill", m, s.n);
+        return NB_ERR_INVALID;
+    }
+    for (size_t k = 0; k < 3 * m; ++k)
+        if ((centers && !std::isfinite(centers[k])) || (velocities && !std::isfinite(velocities[k]))) {
+            set_error("group_shapes: the centre or the velocity of row %zu is not finite", k / 3);
+            return NB_ERR_INVALID;
+        }
+    const bool reduced = (p->flags & NB_SHAPE_REDUCED) != 0;
+    if (reduced && !radius && m > 0) {
+        set_error("group_shapes: NB_SHAPE_REDUCED needs a finite radius for every row (radius is null)");
+        return NB_ERR_INVALID;
+    }
+    for (size_t r = 0; radius && r < m; ++r) {
+        if (!(radius[r] > 0.0)) {  // (a NaN too)
+            set_error("group_shapes: radius[%zu] = %g is neither finite and > 0 nor +inf", r, radius[r]);
+            return NB_ERR_INVALID;
+        }
+        if (reduced && std::isinf(radius[r])) {
+            set_error("group_shapes: NB_SHAPE_REDUCED needs a finite radius (radius[%zu] is +inf)", r);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (p->step_num != NB_SHAPE_ANY_STEP && p->step_num != s.step_num) {
+        set_error("group_shapes: the assignment was made at step %llu, the simulator is at step %llu",
+                  (unsigned long long)p->step_num, (unsigned long long)s.step_num);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_sim_knn: everything that can be refused without a device
 static int knn_check_params(const nb_knn_params *p) {
     if (!p) {
@@ -1203,6 +1271,18 @@ int nb_sim_set_tuning(nb_sim *sim, const char *key, int value) {
         sim->impl->bound_chunk_len = value;
         return NB_OK;
     }
+    if (!std::strcmp(key, "shape_chunk_len")) {  // the group shapes', whichever simulator holds the state
+        if (!sim || !sim->impl) {
+            set_error("null simulator");
+            return NB_ERR_INVALID;
+        }
+        if (value < 64 || value > 65536 || value % 64) {
+            set_error("shape_chunk_len: a multiple of 64 in 64..65536, not %d", value);
+            return NB_ERR_INVALID;
+        }
+        sim->impl->shape_chunk_len = value;
+        return NB_OK;
+    }
     if (!std::strcmp(key, "bound_tile")) {
         if (!sim || !sim->impl) {
             set_error("null simulator");
@@ -1411,6 +1491,23 @@ int nb_sim_halo_profiles(nb_sim *sim, const nb_halo_params *params, nb_halo_head
                          nb_halo_stats *stats) {
     if (int rc = halo_check_params(params)) return rc;
     NB_SIM_PASS(sim, sim_halo_profiles, *params, heads, bins, stats)
+}
+
+int nb_sim_group_shapes(nb_sim *sim, const nb_shape_params *params, const uint32_t *group_of, size_t m,
+                        const double *centers, const double *velocities, const double *radius,
+                        nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats) {
+    if (int rc = shape_check_params(params)) return rc;
+    if (int rc = shape_check_args(sim, params, group_of, m, centers, velocities, radius)) return rc;
+    NB_SIM_PASS(sim, sim_group_shapes, *params, group_of, m, centers, velocities, radius, rows_out, selected_of, stats)
+}
+
+int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]) {
+    if (!t || !lambda || !axes) {
+        set_error("shape_eigen: null argument");
+        return NB_ERR_INVALID;
+    }
+    shape_eigen_host(t, lambda, axes);
+    return NB_OK;
 }
 
 int nb_halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out) {
@@ -1779,6 +1876,16 @@ int nb_runner_halo_profiles(nb_runner *runner, const nb_halo_params *params, nb_
     if (int rc = check_runner(runner)) return rc;
     if (int rc = refuse_group(runner, "halo_profiles")) return rc;
     return nb_sim_halo_profiles(runner->sim, params, heads, bins, stats);
+}
+
+int nb_runner_group_shapes(nb_runner *runner, const nb_shape_params *params, const uint32_t *group_of, size_t m,
+                           const double *centers, const double *velocities, const double *radius,
+                           nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats) {
+    if (int rc = shape_check_params(params)) return rc;
+    if (int rc = check_runner(runner)) return rc;
+    if (int rc = refuse_group(runner, "group_shapes")) return rc;
+    return nb_sim_group_shapes(runner->sim, params, group_of, m, centers, velocities, radius, rows_out, selected_of,
+                               stats);
 }
 
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -130,6 +130,7 @@ class SimBase {
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
     int bound_chunk_len = 1024;  // "bound_chunk_len": j positions of a group per work item of nb_sim_bound's pair pass
     int bound_tile = 0;          // "bound_tile": members per i-tile of that pass, 64 or 256; 0 chooses by the group's size
+    int shape_chunk_len = 1024;  // "shape_chunk_len": positions of a row's list per work item of nb_sim_group_shapes
     int knn_span_cells = 3;      // "knn_span_cells": octree cells per axis the search of nb_sim_knn opens around a body
     int knn_block_queries = 4;   // "knn_block_queries": bodies (a wave each) per block of that search
 };
@@ -174,6 +175,13 @@ int sim_halo_profiles(SimBase &sim, const nb_halo_params &params, nb_halo_head *
 // nb_bound.hip: nb_sim_bound behind the handle (arguments already checked by bound_check_params, nb_abi.cpp)
 int sim_bound(SimBase &sim, const nb_bound_params &params, uint32_t *group_of, uint32_t *bound_of, double *energy,
               nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
+// nb_shape.hip: nb_sim_group_shapes behind the handle (arguments already checked by shape_check_args, nb_abi.cpp,
+// but for the values of group_of, which are checked on the device), and nb_shape_eigen's body, which lives in the
+// unit built without contraction
+int sim_group_shapes(SimBase &sim, const nb_shape_params &params, const uint32_t *group_of, size_t m,
+                     const double *centers, const double *velocities, const double *radius, nb_shape_group *rows,
+                     uint32_t *selected_of, nb_shape_stats *stats);
+void shape_eigen_host(const double t[6], double lambda[3], double axes[9]);
 // nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);

@@ -43,6 +43,8 @@ using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sum
 using FofStats = nb_fof_stats;
 using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound set
 using BoundStats = nb_bound_stats;
+using ShapeGroup = nb_shape_group;        // 360 B: a row's sums, eigenvalues, axes and axis ratios
+using ShapeStats = nb_shape_stats;
 using HopBoundary = nb_hop_boundary;      // 24 B: two labels, their body pairs and the largest pair density
 using HopStats = nb_hop_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
@@ -301,6 +303,75 @@ BoundGroups bound_groups(int (*call)(H *, const nb_bound_params *, uint32_t *, u
                g.groups.data(), cap, &g.stats));
     g.groups.resize((size_t)g.stats.groups);
     return g;
+}
+}  // namespace detail
+
+// The shapes of the rows of an assignment of bodies to rows (nb_sim_group_shapes; no reference counterpart): one
+// row per row of the assignment; selected_of is empty when not asked for
+struct ShapeOptions {
+    bool reduced = false;       // weight the tensor by 1 / rho^2 (needs finite radii)
+    uint32_t max_iter = 32, min_members = 10;
+    double tol = 1e-3;
+    bool per_body = false;      // selected_of
+    uint64_t step_num = NB_SHAPE_ANY_STEP;  // the step the assignment was made at, or no check
+};
+struct GroupShapes {
+    std::vector<ShapeGroup> rows;
+    std::vector<uint32_t> selected_of;
+    ShapeStats stats{};
+    // (1 - q^2) / (1 - s^2) of row r: 0 oblate, 1 prolate
+    double triaxiality(size_t r) const { return (1.0 - rows[r].q * rows[r].q) / (1.0 - rows[r].s * rows[r].s); }
+    double j_norm(size_t r) const {
+        const double *j = rows[r].j;
+        return std::sqrt(j[0] * j[0] + j[1] * j[1] + j[2] * j[2]);
+    }
+};
+
+namespace detail {
+// centers, velocities: empty (the members' own, formed on the device) or three per row; radius: empty (+inf) or one per row
+template <class H>
+GroupShapes group_shapes(int (*call)(H *, const nb_shape_params *, const uint32_t *, size_t, const double *, const double *,
+                                     const double *, nb_shape_group *, uint32_t *, nb_shape_stats *),
+                         H *h, size_t n, const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o,
+                         const std::vector<double> &centers, const std::vector<double> &velocities,
+                         const std::vector<double> &radius) {
+    if (group_of.size() != n) throw std::invalid_argument("group_shapes: one group_of value per body");
+    if ((!centers.empty() && centers.size() != 3 * m) || (!velocities.empty() && velocities.size() != 3 * m) ||
+        (!radius.empty() && radius.size() != m))
+        throw std::invalid_argument("group_shapes: centers, velocities and radius are per row, or empty");
+    GroupShapes g;
+    nb_shape_params p{};
+    p.flags = o.reduced ? NB_SHAPE_REDUCED : 0u;
+    p.min_members = o.min_members;
+    p.max_iter = o.max_iter;
+    p.tol = o.tol;
+    p.step_num = o.step_num;
+    g.rows.resize(m);
+    if (o.per_body) g.selected_of.resize(n);
+    check(call(h, &p, group_of.data(), m, centers.empty() ? nullptr : centers.data(),
+               velocities.empty() ? nullptr : velocities.data(), radius.empty() ? nullptr : radius.data(), g.rows.data(),
+               o.per_body ? g.selected_of.data() : nullptr, &g.stats));
+    return g;
+}
+// ... of a friends-of-friends catalogue about its centres of mass and mean velocities, out to k_rms times every
+// group's rms radius (k_rms <= 0: no cut)
+template <class H, class Call>
+GroupShapes fof_shapes(Call call, H *h, size_t n, const FofGroups &f, double k_rms, ShapeOptions o) {
+    const size_t m = f.groups.size();
+    std::vector<double> c(3 * m), v(3 * m), radius;
+    if (k_rms > 0.0) radius.resize(m);
+    for (size_t r = 0; r < m; ++r) {
+        const FofGroup &g = f.groups[r];
+        double c2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            c[3 * r + a] = g.mx[a] / g.mass;
+            v[3 * r + a] = g.mv[a] / g.mass;
+            c2 += c[3 * r + a] * c[3 * r + a];
+        }
+        if (k_rms > 0.0) radius[r] = k_rms * std::sqrt(std::max(g.mr2 / g.mass - c2, 0.0));
+    }
+    o.step_num = f.stats.step_num;
+    return group_shapes(call, h, n, f.group_of, m, o, c, v, radius);
 }
 }  // namespace detail
 
@@ -652,6 +723,16 @@ class Simulator {
         return detail::bound_groups(nb_sim_bound, h_, sim_params().particle_num, link, min_members,
                                     min_bound ? min_bound : min_members, max_iter, max_group, per_body);
     }
+    // the shapes of the rows of an assignment: group_of of read_particles() now, NB_FOF_NONE or a row < m
+    GroupShapes group_shapes(const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o = ShapeOptions{},
+                             const std::vector<double> &centers = {}, const std::vector<double> &velocities = {},
+                             const std::vector<double> &radius = {}) {
+        return detail::group_shapes(nb_sim_group_shapes, h_, sim_params().particle_num, group_of, m, o, centers,
+                                    velocities, radius);
+    }
+    GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
+        return detail::fof_shapes(nb_sim_group_shapes, h_, sim_params().particle_num, f, k_rms, o);
+    }
     // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
     HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
                          bool boundaries = true) {
@@ -824,6 +905,19 @@ class OfflineHeadless {
         SimParams sp{};
         check(nb_runner_sim_params(r_, &sp));
         return detail::hop_groups(nb_runner_hop, r_, sp.particle_num, p, labels, density, boundaries);
+    }
+    GroupShapes group_shapes(const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o = ShapeOptions{},
+                             const std::vector<double> &centers = {}, const std::vector<double> &velocities = {},
+                             const std::vector<double> &radius = {}) {  // one device only
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::group_shapes(nb_runner_group_shapes, r_, sp.particle_num, group_of, m, o, centers, velocities,
+                                    radius);
+    }
+    GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
+        SimParams sp{};
+        check(nb_runner_sim_params(r_, &sp));
+        return detail::fof_shapes(nb_runner_group_shapes, r_, sp.particle_num, f, k_rms, o);
     }
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {  // one device only
         SimParams sp{};
