@@ -139,6 +139,32 @@ def test_init_fn_exceptions_do_not_cross_the_abi(nb):
         nb.NaiveSim.new(nb.SimParams(particle_num=4), None, short)
 
 
+PASS_METHODS = ["diagnostics", "radial_profile", "field", "circular_velocity", "projected_map", "fof_groups",
+                "bound_groups", "hop_groups", "knn_density", "halo_profiles", "group_profiles", "shapes_of",
+                "group_shapes", "smoothed_map", "render"]
+# nb_sim_* entry points that are not analysis passes: the runner has its own protocol for them, or none
+NOT_PASSES = {"create", "create_from_particles", "encode", "encode_phase", "let_set_imports", "let_set_import_stride",
+              "let_set_owners", "let_set_arrivals", "cleanup", "wait", "sim_params", "read_particles",
+              "write_particles", "read_tree", "exchange_region", "exchange_count", "exchange_region_i", "step_num",
+              "encode_n_timed", "set_tuning", "debug_buffer", "destroy"}
+
+
+def test_a_pass_is_stated_once_for_simulator_and_runner(nb):
+    """Every analysis pass is one Python method shared by Simulator and OfflineHeadless, and one set of argument
+    types shared by nb_sim_<pass> and nb_runner_<pass>."""
+    from wgpu_n_body_amd import _lib
+    L = _lib.lib()
+    for m in PASS_METHODS:
+        assert getattr(nb.Simulator, m) is getattr(nb.OfflineHeadless, m), m
+    passes = [s[len("nb_sim_"):] for s in _lib.ABI_SYMBOLS if s.startswith("nb_sim_")]
+    passes = [p for p in passes if p not in NOT_PASSES]
+    assert len(passes) == 12, passes
+    for p in passes:
+        assert "nb_runner_" + p in _lib.ABI_SYMBOLS, p
+        a, b = getattr(L, "nb_sim_" + p).argtypes, getattr(L, "nb_runner_" + p).argtypes
+        assert a is not None and list(a) == list(b), p
+
+
 def test_product_does_not_import_the_oracle():
     """The oracle is test infrastructure: nothing under wgpu_n_body_amd/ may reference it."""
     pkg = os.path.join(ROOT, "wgpu_n_body_amd")

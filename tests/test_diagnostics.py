@@ -66,7 +66,12 @@ def test_bad_arguments_are_invalid_without_a_device(nb):
     assert b"unknown flag" in L.nb_last_error()
     assert L.nb_sim_diagnostics(None, 0x80000001, C.byref(d)) == _lib.NB_ERR_INVALID
     assert L.nb_runner_diagnostics(None, 1, C.byref(d)) == _lib.NB_ERR_INVALID
+    assert L.nb_last_error() == b"null runner"
+    # the arguments are looked at before the handle, as in every other pass
     assert L.nb_runner_diagnostics(None, 8, C.byref(d)) == _lib.NB_ERR_INVALID
+    assert L.nb_last_error() == b"diagnostics: unknown flag bits 0x8"
+    assert L.nb_runner_diagnostics(None, 3, None) == _lib.NB_ERR_INVALID
+    assert L.nb_last_error() == b"diagnostics: out is null"
     # nothing was written
     assert bytes(d) == bytes(C.sizeof(d))
 

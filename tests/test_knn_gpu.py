@@ -447,6 +447,26 @@ def test_center_density_is_the_explicit_call(gpu):
     sim.destroy()
 
 
+def test_center_density_on_a_runner_is_its_simulators(gpu):
+    """radial_profile and projected_map are one method for Simulator and OfflineHeadless: center="density" on a
+    one-device runner returns what the runner's simulator returns, field for field and bit for bit."""
+    nb = gpu
+    runner = nb.OfflineHeadless(nb.TreeSim, nb.SimParams(particle_num=2048), nb.AddParams.TreeSimParams(0.75),
+                                lambda sp: nb.inits.spherical_init(sp, seed=1), device_id=0)
+    for _ in range(2):
+        runner.step()
+    kw = dict(rmin=1e-3, rmax=10.0, nbins=24)
+    _same_result(runner.radial_profile(center="density", **kw), runner.sim.radial_profile(center="density", **kw))
+    kw = dict(extent=(-0.5, 0.5, -0.5, 0.5), axis=(0.0, 0.0, 1.0))
+    a = runner.projected_map(48, 40, center="density", **kw)
+    _same_result(a, runner.sim.projected_map(48, 40, center="density", **kw))
+    d = runner.knn_density(6, neighbours=False)
+    assert np.array_equal(a.center, d.center)
+    with pytest.raises(ValueError):
+        runner.projected_map(8, 8, center="density", velocity=(0.0, 0.0, 0.0), extent=(-1, 1, -1, 1))
+    runner.destroy()
+
+
 def test_the_density_centre_ignores_escapers(gpu):
     """What the feature exists for.  A 4,096-body `spherical` state, then the same with 40 bodies moved 57 length
     units out: the density centre of the disturbed state stays within 0.25 r_core of the undisturbed one, where

@@ -1558,10 +1558,182 @@ def _init_trampoline(init_fn: InitFn, sim_params: SimParams):
     return _lib.NB_INIT_FN(trampoline), err
 
 
-class Simulator:
+class _Passes:
+    """The analysis passes of the current state, once for Simulator (nb_sim_*) and OfflineHeadless (nb_runner_*: the
+    same pass on the runner's simulator).  The two differ in the ABI prefix and in read_particles()."""
+
+    _ABI: str
+
+    def _pass(self, name: str):
+        return getattr(_lib.lib(), self._ABI + name)
+
+    def diagnostics(self, potential: bool = False) -> Diagnostics:
+        """Energy, momentum and angular momentum of the current state (nb_sim_diagnostics); with
+        potential=True also the exact O(N^2) pair potential.  A several-GPU runner refuses."""
+        d = _lib.nb_diagnostics()
+        check(self._pass("diagnostics")(self._h, _diag_flags(potential), C.byref(d)))
+        return Diagnostics._from_c(d)
+
+    def radial_profile(self, edges=None, *, nbins: int = 64, rmin=None, rmax=None, log: bool = True,
+                       cylindrical: bool = False, axis=(0.0, 1.0, 0.0), center="com",
+                       velocity=(0.0, 0.0, 0.0)) -> RadialProfile:
+        """Per-shell mass and velocity moments of the current state (nb_sim_radial_profile).  edges: the
+        nbins + 1 radii, or rmin, rmax, nbins and log for radial_edges().  cylindrical: bin by distance
+        from `axis` through the centre (a disc's annuli) instead of from the centre.  center: "com" (the
+        centre of mass and its velocity P/M, as diagnostics() returns them) or three coordinates, then
+        with `velocity` as the centre's velocity; "density": the density centre and its velocity of
+        knn_density(6), passed on as explicit values.  A several-GPU runner refuses."""
+        if isinstance(center, str) and center == "density":
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
+        return _radial_profile(self._pass("radial_profile"), self._h, edges, nbins, rmin, rmax, log,
+                               cylindrical, axis, center, velocity)
+
+    def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
+        """The exact acceleration and potential of the current state at `points` ((M, 3), float32), summed
+        over all bodies on the device (nb_sim_field).  A body at a point itself adds nothing and is counted
+        in `.coincident`, so the field at a body's position is the field of the others.
+        A several-GPU runner refuses."""
+        return _field(self._pass("field"), self._h, points, accel, potential)
+
+    def circular_velocity(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16,
+                          potential: bool = False) -> RingMeans:
+        """The rotation curve from the force: field() on n_phi points of each ring of field_rings(), then
+        the ring means (nb_field_ring_means): v_c = sqrt(max(0, -R a_R)).  A several-GPU runner refuses."""
+        return _circular_velocity(self._pass("field"), self._h, radii, axis, center, n_phi, potential)
+
+    def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                      depth=None, velocities: bool = True) -> ProjectedMap:
+        """Per-cell count, mass and velocity moments of the current state on a width x height grid seen
+        along `axis` (nb_sim_map).  extent: (x0, x1, y0, y1), the window [x0, x1) x [y0, y1) in the plane
+        coordinates of map_frame(axis) about the centre.  center: "com" (the centre of mass and its
+        velocity P/M, as diagnostics() returns them) or three coordinates, then with `velocity` (default:
+        at rest); "density": the density centre and its velocity of knn_density(6), passed on as explicit
+        values.  depth: (lo, hi) keeps the bodies with lo <= h < hi along the line of sight.
+        velocities=False returns the counts and the mass alone.  A several-GPU runner refuses."""
+        if isinstance(center, str) and center == "density":
+            if velocity is not None:
+                raise ValueError('center="density" brings its own velocity')
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
+        return _projected_map(self._pass("map"), self._h, width, height, extent, axis, center, velocity, depth,
+                              velocities)
+
+    def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
+        """The friends-of-friends groups of the current state (nb_sim_fof): bodies within `link` of each
+        other are friends, a group is a connected component; the catalogue holds the groups of at least
+        min_members bodies.  The body indices are those of read_particles() now: a TreeSim reorders its
+        bodies at every step.  labels=False leaves the per-body labels on the device.  A several-GPU runner refuses."""
+        return _fof_groups(self._pass("fof"), self._h, int(self.sim_params().particle_num), link, min_members,
+                           labels)
+
+    def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
+                     max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:
+        """The friends-of-friends groups of the current state (as fof_groups(link, min_members=...)), each
+        unbound on the device (nb_sim_bound): round by round the members with positive energy in the group's
+        own frame leave, until nobody does, fewer than min_bound (default min_members) are left, or max_iter
+        rounds have run.  A group of more than max_group members (0: no limit) is skipped: a round costs
+        count^2 pair terms.  per_body=False leaves bound_of and energy on the device.  A several-GPU runner refuses."""
+        return _bound_groups(self._pass("bound"), self._h, int(self.sim_params().particle_num), link,
+                             min_members, min_bound, max_iter, max_group, per_body)
+
+    def hop_groups(self, *, k_density: int = 64, k_hop: int = 16, k_merge: int = 4, min_members: int = 1,
+                   density_min=None, labels: bool = True, density: bool = False, boundaries: bool = True) -> HopGroups:
+        """The density-peak groups of the current state (nb_sim_hop): knn_density(k_density) orders the bodies,
+        every body hops to the densest of its k_hop nearest neighbours until it reaches a peak, and pairs
+        among the k_merge nearest neighbours that end at different peaks give the boundaries .regroup() merges
+        across.  density_min leaves bodies below it out.  The body indices are those of read_particles() now: a
+        TreeSim reorders its bodies at every step.  labels=False and density=False leave the per-body arrays
+        on the device, boundaries=False the boundary table.  A several-GPU runner refuses."""
+        return _hop_groups(self._pass("hop"), self._h, int(self.sim_params().particle_num), k_density, k_hop,
+                           k_merge, min_members, density_min, labels, density, boundaries)
+
+    def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
+        """The k-th nearest neighbour of every body of the current state, the mass inside it and the density
+        from them (nb_sim_knn), with the density-weighted sums: .center is the density centre of Casertano &
+        Hut (1985).  The body indices are those of read_particles() now: a TreeSim reorders its bodies at
+        every step.  density=False leaves mass_in and density on the device, neighbours=False r2 and kth.
+        A several-GPU runner refuses."""
+        return _knn_density(self._pass("knn"), self._h, int(self.sim_params().particle_num), k, density,
+                            neighbours)
+
+    def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
+                      rmax=None, log: bool = True) -> HaloProfiles:
+        """The spherical radial profile of the current state about many centres at once (nb_sim_halo_profiles):
+        centers (m, 3) points, or bodies (m,) body indices whose positions (and, without velocities, velocities)
+        are the centres; edges shared by all centres, or rmin, rmax, nbins and log for radial_edges().  A centre
+        tests only the bodies of the grid cells its sphere of radius edges[-1] reaches.  The body indices are
+        those of read_particles() now: a TreeSim reorders its bodies at every step.  A several-GPU runner refuses."""
+        return _halo_profiles(self._pass("halo_profiles"), self._h, centers, bodies, velocities, edges, nbins,
+                              rmin, rmax, log)
+
+    def group_profiles(self, groups, *, center: str = "com", **kw):
+        """(rows, HaloProfiles): halo_profiles about the groups of a FofGroups or BoundGroups of the same
+        state -- center="com": their centres of mass and mean velocities, the rows where those are finite;
+        "most_bound": a BoundGroups' most bound bodies, the rows that have one; "peak": a HopGroups' labels, the
+        bodies at the density peaks.  rows: the catalogue rows
+        the profiles belong to, in order.  kw: edges / nbins / rmin / rmax / log of halo_profiles.
+        A several-GPU runner refuses."""
+        return _group_profiles(self.halo_profiles, groups, center, kw)
+
+    def shapes_of(self, group_of, m: int, *, centers=None, velocities=None, radius=None, reduced: bool = False,
+                  max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                  step_num=None, catalogue_rows=None) -> GroupShapes:
+        """The shapes of the m rows of a raw assignment (nb_sim_group_shapes): group_of (n,) uint32, FOF_NONE or a
+        row < m for every body of read_particles() now.  centers, velocities: (m, 3) or None for the members' own
+        centre of mass and mean velocity, formed on the device; radius: None (no cut: one round), a number or (m,);
+        reduced: weight the tensor by 1 / rho^2 (needs a radius).  step_num: the step the assignment was made at, to
+        have a stale one refused (a TreeSim reorders its bodies every step); None: not checked.
+        A several-GPU runner refuses."""
+        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
+        return _group_shapes(self._pass("group_shapes"), self._h, int(self.sim_params().particle_num), group_of, m,
+                             centers, velocities, radius, reduced, max_iter, tol, min_members, per_body, step_num, rows)
+
+    def group_shapes(self, groups, *, members: str = "group", center: str = "com", radius=None, reduced: bool = False,
+                     max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
+                     check_step: bool = True) -> GroupShapes:
+        """The shapes of the groups of a FofGroups, BoundGroups or HopGroups (raw or regrouped) of the same state:
+        axis ratios, principal axes, angular momentum and velocity moments of every group inside an ellipsoid
+        deformed to its own shape.  members: "group" (group_of) or "bound" (a BoundGroups' bound_of); center: as
+        group_profiles -- "com", "most_bound" or "peak" -- and the rows without a finite centre are left out
+        (GroupShapes.catalogue_rows names the ones that stay).  radius: None, a number, one per catalogue row, or
+        ("rms", k) for k times the catalogue's rms radius.  check_step: refuse a catalogue made at another step.
+        A several-GPU runner refuses."""
+        kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
+        return _shapes_of_groups(self.shapes_of, self.read_particles, groups, members, center, radius, check_step,
+                                 kw)
+
+    def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
+                     depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
+                     s_min=None, s_max=None) -> SmoothedMap:
+        """The smoothed image of the current state on a width x height grid seen along `axis`
+        (nb_sim_smooth_map): every body spread over the pixels whose centre lies within its smoothing length.
+        extent, axis, center, velocity, depth, velocities: as projected_map (center="density" is not offered).
+        smoothing: "knn" (scale times the distance to the k-th neighbour, from knn_density(k) on the same
+        state), an array of n lengths in the order of read_particles() now, or one length for all.  s_min,
+        s_max: the lengths are raised and lowered to these; default 2 and 64 times the larger side of a pixel.
+        A several-GPU runner refuses."""
+        n = int(self.sim_params().particle_num)
+        s = _smoothing_lengths(self, smoothing, k, scale)
+        return _smoothed_map(self._pass("smooth_map"), self._h, n, s, width, height, extent, axis, center,
+                             velocity, depth, velocities, s_min, s_max)
+
+    def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
+               counts: bool = False, **params):
+        """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
+        online_renderer.rs:331-367): a Frame, the (H, W, 4) uint8 image with .stats; with counts=True
+        (frame, counts), counts the (H, W) uint32 coverage image.  camera: a Camera (default: the
+        reference's); view_proj: 16 floats, column-major, instead; params: half_size, clear, alpha,
+        srgb of RenderParams.  A several-GPU runner refuses."""
+        return _render(self._pass("render"), self._h, _render_params(width, height, camera, view_proj, params),
+                       counts)
+
+
+class Simulator(_Passes):
     """`trait Simulator` (sims/mod.rs:73-90) over an nb_sim handle."""
 
     KIND = NB_NAIVE_SIM_PARAMS
+    _ABI = "nb_sim_"
 
     def __init__(self, handle: int, borrowed: bool = False):
         self._h = C.c_void_p(handle)
@@ -1657,161 +1829,6 @@ class Simulator:
 
     read_particles = dest_particle_slice
 
-    def diagnostics(self, potential: bool = False) -> Diagnostics:
-        """Energy, momentum and angular momentum of the current state (nb_sim_diagnostics); with
-        potential=True also the exact O(N^2) pair potential."""
-        d = _lib.nb_diagnostics()
-        check(_lib.lib().nb_sim_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
-        return Diagnostics._from_c(d)
-
-    def radial_profile(self, edges=None, *, nbins: int = 64, rmin=None, rmax=None, log: bool = True,
-                       cylindrical: bool = False, axis=(0.0, 1.0, 0.0), center="com",
-                       velocity=(0.0, 0.0, 0.0)) -> RadialProfile:
-        """Per-shell mass and velocity moments of the current state (nb_sim_radial_profile).  edges: the
-        nbins + 1 radii, or rmin, rmax, nbins and log for radial_edges().  cylindrical: bin by distance
-        from `axis` through the centre (a disc's annuli) instead of from the centre.  center: "com" (the
-        centre of mass and its velocity P/M, as diagnostics() returns them) or three coordinates, then
-        with `velocity` as the centre's velocity; "density": the density centre and its velocity of
-        knn_density(6), passed on as explicit values."""
-        if isinstance(center, str) and center == "density":
-            d = self.knn_density(6, neighbours=False)
-            center, velocity = d.center, d.center_velocity
-        return _radial_profile(_lib.lib().nb_sim_radial_profile, self._h, edges, nbins, rmin, rmax, log,
-                               cylindrical, axis, center, velocity)
-
-    def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
-        """The exact acceleration and potential of the current state at `points` ((M, 3), float32), summed
-        over all bodies on the device (nb_sim_field).  A body at a point itself adds nothing and is counted
-        in `.coincident`, so the field at a body's position is the field of the others."""
-        return _field(_lib.lib().nb_sim_field, self._h, points, accel, potential)
-
-    def circular_velocity(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16,
-                          potential: bool = False) -> RingMeans:
-        """The rotation curve from the force: field() on n_phi points of each ring of field_rings(), then
-        the ring means (nb_field_ring_means): v_c = sqrt(max(0, -R a_R))."""
-        return _circular_velocity(_lib.lib().nb_sim_field, self._h, radii, axis, center, n_phi, potential)
-
-    def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
-                      depth=None, velocities: bool = True) -> ProjectedMap:
-        """Per-cell count, mass and velocity moments of the current state on a width x height grid seen
-        along `axis` (nb_sim_map).  extent: (x0, x1, y0, y1), the window [x0, x1) x [y0, y1) in the plane
-        coordinates of map_frame(axis) about the centre.  center: "com" (the centre of mass and its
-        velocity P/M, as diagnostics() returns them) or three coordinates, then with `velocity` (default:
-        at rest); "density": the density centre and its velocity of knn_density(6), passed on as explicit
-        values.  depth: (lo, hi) keeps the bodies with lo <= h < hi along the line of sight.
-        velocities=False returns the counts and the mass alone."""
-        if isinstance(center, str) and center == "density":
-            if velocity is not None:
-                raise ValueError('center="density" brings its own velocity')
-            d = self.knn_density(6, neighbours=False)
-            center, velocity = d.center, d.center_velocity
-        return _projected_map(_lib.lib().nb_sim_map, self._h, width, height, extent, axis, center, velocity, depth,
-                              velocities)
-
-    def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
-        """The friends-of-friends groups of the current state (nb_sim_fof): bodies within `link` of each
-        other are friends, a group is a connected component; the catalogue holds the groups of at least
-        min_members bodies.  The body indices are those of read_particles() now: a TreeSim reorders its
-        bodies at every step.  labels=False leaves the per-body labels on the device."""
-        return _fof_groups(_lib.lib().nb_sim_fof, self._h, int(self.sim_params().particle_num), link, min_members,
-                           labels)
-
-    def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
-                     max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:
-        """The friends-of-friends groups of the current state (as fof_groups(link, min_members=...)), each
-        unbound on the device (nb_sim_bound): round by round the members with positive energy in the group's
-        own frame leave, until nobody does, fewer than min_bound (default min_members) are left, or max_iter
-        rounds have run.  A group of more than max_group members (0: no limit) is skipped: a round costs
-        count^2 pair terms.  per_body=False leaves bound_of and energy on the device."""
-        return _bound_groups(_lib.lib().nb_sim_bound, self._h, int(self.sim_params().particle_num), link,
-                             min_members, min_bound, max_iter, max_group, per_body)
-
-    def hop_groups(self, *, k_density: int = 64, k_hop: int = 16, k_merge: int = 4, min_members: int = 1,
-                   density_min=None, labels: bool = True, density: bool = False, boundaries: bool = True) -> HopGroups:
-        """The density-peak groups of the current state (nb_sim_hop): knn_density(k_density) orders the bodies,
-        every body hops to the densest of its k_hop nearest neighbours until it reaches a peak, and pairs
-        among the k_merge nearest neighbours that end at different peaks give the boundaries .regroup() merges
-        across.  density_min leaves bodies below it out.  The body indices are those of read_particles() now: a
-        TreeSim reorders its bodies at every step.  labels=False and density=False leave the per-body arrays
-        on the device, boundaries=False the boundary table."""
-        return _hop_groups(_lib.lib().nb_sim_hop, self._h, int(self.sim_params().particle_num), k_density, k_hop,
-                           k_merge, min_members, density_min, labels, density, boundaries)
-
-    def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
-        """The k-th nearest neighbour of every body of the current state, the mass inside it and the density
-        from them (nb_sim_knn), with the density-weighted sums: .center is the density centre of Casertano &
-        Hut (1985).  The body indices are those of read_particles() now: a TreeSim reorders its bodies at
-        every step.  density=False leaves mass_in and density on the device, neighbours=False r2 and kth."""
-        return _knn_density(_lib.lib().nb_sim_knn, self._h, int(self.sim_params().particle_num), k, density,
-                            neighbours)
-
-    def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
-                      rmax=None, log: bool = True) -> HaloProfiles:
-        """The spherical radial profile of the current state about many centres at once (nb_sim_halo_profiles):
-        centers (m, 3) points, or bodies (m,) body indices whose positions (and, without velocities, velocities)
-        are the centres; edges shared by all centres, or rmin, rmax, nbins and log for radial_edges().  A centre
-        tests only the bodies of the grid cells its sphere of radius edges[-1] reaches.  The body indices are
-        those of read_particles() now: a TreeSim reorders its bodies at every step."""
-        return _halo_profiles(_lib.lib().nb_sim_halo_profiles, self._h, centers, bodies, velocities, edges, nbins,
-                              rmin, rmax, log)
-
-    def group_profiles(self, groups, *, center: str = "com", **kw):
-        """(rows, HaloProfiles): halo_profiles about the groups of a FofGroups or BoundGroups of the same
-        state -- center="com": their centres of mass and mean velocities, the rows where those are finite;
-        "most_bound": a BoundGroups' most bound bodies, the rows that have one; "peak": a HopGroups' labels, the
-        bodies at the density peaks.  rows: the catalogue rows
-        the profiles belong to, in order.  kw: edges / nbins / rmin / rmax / log of halo_profiles."""
-        return _group_profiles(self.halo_profiles, groups, center, kw)
-
-    def shapes_of(self, group_of, m: int, *, centers=None, velocities=None, radius=None, reduced: bool = False,
-                  max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
-                  step_num=None, catalogue_rows=None) -> GroupShapes:
-        """The shapes of the m rows of a raw assignment (nb_sim_group_shapes): group_of (n,) uint32, FOF_NONE or a
-        row < m for every body of read_particles() now.  centers, velocities: (m, 3) or None for the members' own
-        centre of mass and mean velocity, formed on the device; radius: None (no cut: one round), a number or (m,);
-        reduced: weight the tensor by 1 / rho^2 (needs a radius).  step_num: the step the assignment was made at, to
-        have a stale one refused (a TreeSim reorders its bodies every step); None: not checked."""
-        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
-        return _group_shapes(_lib.lib().nb_sim_group_shapes, self._h, int(self.sim_params().particle_num), group_of, m,
-                             centers, velocities, radius, reduced, max_iter, tol, min_members, per_body, step_num, rows)
-
-    def group_shapes(self, groups, *, members: str = "group", center: str = "com", radius=None, reduced: bool = False,
-                     max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
-                     check_step: bool = True) -> GroupShapes:
-        """The shapes of the groups of a FofGroups, BoundGroups or HopGroups (raw or regrouped) of the same state:
-        axis ratios, principal axes, angular momentum and velocity moments of every group inside an ellipsoid
-        deformed to its own shape.  members: "group" (group_of) or "bound" (a BoundGroups' bound_of); center: as
-        group_profiles -- "com", "most_bound" or "peak" -- and the rows without a finite centre are left out
-        (GroupShapes.catalogue_rows names the ones that stay).  radius: None, a number, one per catalogue row, or
-        ("rms", k) for k times the catalogue's rms radius.  check_step: refuse a catalogue made at another step."""
-        kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
-        return _shapes_of_groups(self.shapes_of, self.dest_particle_slice, groups, members, center, radius, check_step,
-                                 kw)
-
-    def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
-                     depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
-                     s_min=None, s_max=None) -> SmoothedMap:
-        """The smoothed image of the current state on a width x height grid seen along `axis`
-        (nb_sim_smooth_map): every body spread over the pixels whose centre lies within its smoothing length.
-        extent, axis, center, velocity, depth, velocities: as projected_map (center="density" is not offered).
-        smoothing: "knn" (scale times the distance to the k-th neighbour, from knn_density(k) on the same
-        state), an array of n lengths in the order of read_particles() now, or one length for all.  s_min,
-        s_max: the lengths are raised and lowered to these; default 2 and 64 times the larger side of a pixel."""
-        n = int(self.sim_params().particle_num)
-        s = _smoothing_lengths(self, smoothing, k, scale)
-        return _smoothed_map(_lib.lib().nb_sim_smooth_map, self._h, n, s, width, height, extent, axis, center,
-                             velocity, depth, velocities, s_min, s_max)
-
-    def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
-               counts: bool = False, **params):
-        """The current state drawn on the device (nb_sim_render; OnlineRenderer::render,
-        online_renderer.rs:331-367): a Frame, the (H, W, 4) uint8 image with .stats; with counts=True
-        (frame, counts), counts the (H, W) uint32 coverage image.  camera: a Camera (default: the
-        reference's); view_proj: 16 floats, column-major, instead; params: half_size, clear, alpha,
-        srgb of RenderParams."""
-        return _render(_lib.lib().nb_sim_render, self._h, _render_params(width, height, camera, view_proj, params),
-                       counts)
-
     def write_particles(self, particles) -> None:
         arr = as_particles(particles)
         check(_lib.lib().nb_sim_write_particles(self._h, arr.ctypes.data, arr.shape[0]))
@@ -1888,11 +1905,13 @@ class TreeSim(Simulator):
     KIND = NB_TREE_SIM_PARAMS
 
 
-class OfflineHeadless:
+class OfflineHeadless(_Passes):
     """`OfflineHeadless<T: Simulator>` (runners/offline_headless.rs:4-45) over nb_runner.
 
     OfflineHeadless(NaiveSim, sim_params, add_params, init_fn) ~
     OfflineHeadless::<NaiveSim>::new(sim_params, add_params, init_fn)."""
+
+    _ABI = "nb_runner_"
 
     def __init__(self, sim_type, sim_params: SimParams, add_params: Optional[AddParams],
                  init_fn: InitFn, device_id: int = -1, device_ids: Optional[Sequence[int]] = None,
@@ -1959,97 +1978,6 @@ class OfflineHeadless:
         out = np.zeros(n, dtype=PARTICLE_DTYPE)
         check(_lib.lib().nb_runner_read_particles(self._h, out.ctypes.data, n))
         return out
-
-    def diagnostics(self, potential: bool = False) -> Diagnostics:
-        """nb_runner_diagnostics: Simulator.diagnostics of the runner's simulator (one device only)."""
-        d = _lib.nb_diagnostics()
-        check(_lib.lib().nb_runner_diagnostics(self._h, _diag_flags(potential), C.byref(d)))
-        return Diagnostics._from_c(d)
-
-    def radial_profile(self, edges=None, *, nbins: int = 64, rmin=None, rmax=None, log: bool = True,
-                       cylindrical: bool = False, axis=(0.0, 1.0, 0.0), center="com",
-                       velocity=(0.0, 0.0, 0.0)) -> RadialProfile:
-        """nb_runner_radial_profile: Simulator.radial_profile of the runner's simulator (one device only)."""
-        return _radial_profile(_lib.lib().nb_runner_radial_profile, self._h, edges, nbins, rmin, rmax, log,
-                               cylindrical, axis, center, velocity)
-
-    def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
-        """nb_runner_field: Simulator.field of the runner's simulator (one device only)."""
-        return _field(_lib.lib().nb_runner_field, self._h, points, accel, potential)
-
-    def circular_velocity(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), n_phi: int = 16,
-                          potential: bool = False) -> RingMeans:
-        """Simulator.circular_velocity of the runner's simulator (one device only)."""
-        return _circular_velocity(_lib.lib().nb_runner_field, self._h, radii, axis, center, n_phi, potential)
-
-    def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
-                      depth=None, velocities: bool = True) -> ProjectedMap:
-        """nb_runner_map: Simulator.projected_map of the runner's simulator (one device only)."""
-        return _projected_map(_lib.lib().nb_runner_map, self._h, width, height, extent, axis, center, velocity, depth,
-                              velocities)
-
-    def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
-        """nb_runner_fof: Simulator.fof_groups of the runner's simulator (one device only)."""
-        return _fof_groups(_lib.lib().nb_runner_fof, self._h, int(self.sim_params().particle_num), link, min_members,
-                           labels)
-
-    def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
-                     max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:
-        """nb_runner_bound: Simulator.bound_groups of the runner's simulator (one device only)."""
-        return _bound_groups(_lib.lib().nb_runner_bound, self._h, int(self.sim_params().particle_num), link,
-                             min_members, min_bound, max_iter, max_group, per_body)
-
-    def hop_groups(self, *, k_density: int = 64, k_hop: int = 16, k_merge: int = 4, min_members: int = 1,
-                   density_min=None, labels: bool = True, density: bool = False, boundaries: bool = True) -> HopGroups:
-        """nb_runner_hop: Simulator.hop_groups of the runner's simulator (one device only)."""
-        return _hop_groups(_lib.lib().nb_runner_hop, self._h, int(self.sim_params().particle_num), k_density, k_hop,
-                           k_merge, min_members, density_min, labels, density, boundaries)
-
-    def knn_density(self, k: int = 6, *, density: bool = True, neighbours: bool = True) -> KnnDensity:
-        """nb_runner_knn: Simulator.knn_density of the runner's simulator (one device only)."""
-        return _knn_density(_lib.lib().nb_runner_knn, self._h, int(self.sim_params().particle_num), k, density,
-                            neighbours)
-
-    def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
-                      rmax=None, log: bool = True) -> HaloProfiles:
-        """nb_runner_halo_profiles: Simulator.halo_profiles of the runner's simulator (one device only)."""
-        return _halo_profiles(_lib.lib().nb_runner_halo_profiles, self._h, centers, bodies, velocities, edges, nbins,
-                              rmin, rmax, log)
-
-    def group_profiles(self, groups, *, center: str = "com", **kw):
-        """Simulator.group_profiles of the runner's simulator (one device only)."""
-        return _group_profiles(self.halo_profiles, groups, center, kw)
-
-    def shapes_of(self, group_of, m: int, *, centers=None, velocities=None, radius=None, reduced: bool = False,
-                  max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
-                  step_num=None, catalogue_rows=None) -> GroupShapes:
-        """nb_runner_group_shapes: Simulator.shapes_of of the runner's simulator (one device only)."""
-        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
-        return _group_shapes(_lib.lib().nb_runner_group_shapes, self._h, int(self.sim_params().particle_num), group_of,
-                             m, centers, velocities, radius, reduced, max_iter, tol, min_members, per_body, step_num,
-                             rows)
-
-    def group_shapes(self, groups, *, members: str = "group", center: str = "com", radius=None, reduced: bool = False,
-                     max_iter: int = 32, tol: float = 1e-3, min_members: int = 10, per_body: bool = False,
-                     check_step: bool = True) -> GroupShapes:
-        """Simulator.group_shapes of the runner's simulator (one device only)."""
-        kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
-        return _shapes_of_groups(self.shapes_of, self.read_particles, groups, members, center, radius, check_step, kw)
-
-    def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
-                     depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,
-                     s_min=None, s_max=None) -> SmoothedMap:
-        """nb_runner_smooth_map: Simulator.smoothed_map of the runner's simulator (one device only)."""
-        n = int(self.sim_params().particle_num)
-        s = _smoothing_lengths(self, smoothing, k, scale)
-        return _smoothed_map(_lib.lib().nb_runner_smooth_map, self._h, n, s, width, height, extent, axis, center,
-                             velocity, depth, velocities, s_min, s_max)
-
-    def render(self, width: int, height: int, camera: Optional[Camera] = None, view_proj=None,
-               counts: bool = False, **params):
-        """nb_runner_render: Simulator.render of the runner's simulator (one device only)."""
-        return _render(_lib.lib().nb_runner_render, self._h, _render_params(width, height, camera, view_proj, params),
-                       counts)
 
     def sim_params(self) -> SimParams:
         sp = _lib.nb_sim_params()

@@ -400,44 +400,41 @@ def lib() -> C.CDLL:
     L.nb_sim_encode_n_timed.argtypes = [vp, C.c_int, P(C.c_float), P(C.c_float)]
     L.nb_sim_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]
     L.nb_sim_debug_buffer.argtypes = [vp, C.c_char_p, vp, sz, P(sz)]
-    L.nb_sim_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
-    L.nb_sim_radial_profile.argtypes = [vp, P(nb_radial_params), P(nb_radial_profile), vp]
+    # the analysis passes: the arguments after the handle, the same for nb_sim_X and nb_runner_X
+    passes = {
+        "diagnostics": [C.c_uint32, P(nb_diagnostics)],
+        "radial_profile": [P(nb_radial_params), P(nb_radial_profile), vp],
+        "field": [vp, sz, C.c_uint32, vp, P(nb_field_stats)],
+        "map": [P(nb_map_params), vp, vp, P(nb_map_stats)],
+        "fof": [P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)],
+        "bound": [P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)],
+        "knn": [P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)],
+        "hop": [P(nb_hop_params), vp, vp, vp, vp, vp, sz, vp, sz, P(nb_hop_stats)],
+        "halo_profiles": [P(nb_halo_params), vp, vp, P(nb_halo_stats)],
+        "group_shapes": [P(nb_shape_params), vp, sz, vp, vp, vp, vp, vp, P(nb_shape_stats)],
+        "smooth_map": [P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)],
+        "render": [P(nb_render_params), vp, vp, P(nb_render_stats)],
+    }
+    for name, args in passes.items():
+        for prefix in ("nb_sim_", "nb_runner_"):
+            getattr(L, prefix + name).argtypes = [vp] + args
     for name in ("nb_radial_edges_log", "nb_radial_edges_linear"):
         getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_radial_lagrangian.argtypes = [P(nb_radial_profile), vp, P(C.c_double), P(C.c_double), C.c_uint32,
                                        P(C.c_double)]
-    L.nb_sim_field.argtypes = [vp, vp, sz, C.c_uint32, vp, P(nb_field_stats)]
-    L.nb_runner_field.argtypes = [vp, vp, sz, C.c_uint32, vp, P(nb_field_stats)]
     L.nb_field_rings.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp]
     L.nb_field_ring_means.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp, vp,
                                       vp]
-    L.nb_sim_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
-    L.nb_runner_map.argtypes = [vp, P(nb_map_params), vp, vp, P(nb_map_stats)]
-    L.nb_sim_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
-    L.nb_runner_fof.argtypes = [vp, P(nb_fof_params), vp, vp, vp, sz, P(nb_fof_stats)]
-    L.nb_sim_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
-    L.nb_runner_bound.argtypes = [vp, P(nb_bound_params), vp, vp, vp, vp, sz, P(nb_bound_stats)]
-    L.nb_sim_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
-    L.nb_runner_knn.argtypes = [vp, P(nb_knn_params), vp, vp, vp, vp, P(nb_knn_stats)]
-    for name in ("nb_sim_hop", "nb_runner_hop"):
-        getattr(L, name).argtypes = [vp, P(nb_hop_params), vp, vp, vp, vp, vp, sz, vp, sz, P(nb_hop_stats)]
     L.nb_hop_regroup.argtypes = [vp, vp, sz, vp, sz, P(nb_hop_regroup_params), vp, vp, vp, sz, P(sz)]
-    L.nb_sim_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
-    L.nb_runner_halo_profiles.argtypes = [vp, P(nb_halo_params), vp, vp, P(nb_halo_stats)]
-    L.nb_sim_group_shapes.argtypes = [vp, P(nb_shape_params), vp, sz, vp, vp, vp, vp, vp, P(nb_shape_stats)]
-    L.nb_runner_group_shapes.argtypes = [vp, P(nb_shape_params), vp, sz, vp, vp, vp, vp, vp, P(nb_shape_stats)]
     L.nb_shape_eigen.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_halo_enclosed.argtypes = [vp, vp, C.c_uint32, P(C.c_double)]
     L.nb_halo_overdensity.argtypes = [vp, vp, P(C.c_double), C.c_uint32, C.c_double, P(C.c_double), P(C.c_double)]
-    L.nb_sim_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
-    L.nb_runner_smooth_map.argtypes = [vp, P(nb_smooth_params), vp, vp, vp, P(nb_smooth_stats)]
     L.nb_smooth_centres.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_map_frame.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_map_edges.argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_camera_default.argtypes = [P(nb_camera), C.c_uint32, C.c_uint32]
     L.nb_camera_view_proj.argtypes = [P(nb_camera), P(C.c_float)]
     L.nb_render_params_default.argtypes = [P(nb_render_params), C.c_uint32, C.c_uint32]
-    L.nb_sim_render.argtypes = [vp, P(nb_render_params), vp, vp, P(nb_render_stats)]
     L.nb_naive_variant_count.restype = C.c_int
     L.nb_naive_variant_name.argtypes = [C.c_int]
     L.nb_naive_variant_name.restype = C.c_char_p
@@ -452,9 +449,6 @@ def lib() -> C.CDLL:
     L.nb_runner_set_profiling.argtypes = [vp, C.c_int]
     L.nb_runner_rank_times.argtypes = [vp, P(C.c_float), P(C.c_float), C.c_int]
     L.nb_runner_sim_params.argtypes = [vp, P(nb_sim_params)]
-    L.nb_runner_diagnostics.argtypes = [vp, C.c_uint32, P(nb_diagnostics)]
-    L.nb_runner_radial_profile.argtypes = [vp, P(nb_radial_params), P(nb_radial_profile), vp]
-    L.nb_runner_render.argtypes = [vp, P(nb_render_params), vp, vp, P(nb_render_stats)]
     L.nb_runner_sim.argtypes = [vp]
     L.nb_runner_sim.restype = vp
     L.nb_runner_destroy.argtypes = [vp]

@@ -48,7 +48,10 @@ SOURCES = [
     # the selection, the 22 terms and the eigen-solver are specified operation by operation: no FMA
     # contraction, on the host side of the unit (nb_shape_eigen) as on the device side
     ("nb_shape.hip", ["-ffp-contract=off"]),
+    # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
+    ("nb_simbase.cpp", []),
+    ("nb_passes.cpp", []),
     ("nb_group.cpp", []),
     # the inits are specified bit-exactly (DESIGN.md "RNG"): no FMA contraction
     ("nb_inits.cpp", ["-ffp-contract=off"]),

@@ -1,4 +1,4 @@
-// nb_common.hpp -- internal declarations shared by the host side (nb_abi.cpp) and the
+// nb_common.hpp -- internal declarations shared by the host side (nb_abi.cpp, nb_simbase.cpp, nb_passes.cpp) and the
 // HIP translation units.  Not part of the C ABI (include/nbody.h is).
 #pragma once
 

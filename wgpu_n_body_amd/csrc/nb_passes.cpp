@@ -1,0 +1,784 @@
+// nb_passes.cpp -- everything an analysis pass does without a device: the refusal rules of every pass (the
+// *_check_params and *_check_args that run before the simulator is looked at, and the two checks that read the
+// simulator's parameters), the frames, edges and grids the passes and the host-only entry points share, and the
+// bodies of the host-only entry points of include/nbody.h.  No HIP call is made here; the functions are declared
+// in nb_sim.hpp next to the sim_X they guard.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "nb_common.hpp"
+#include "nb_sim.hpp"
+
+namespace nb {
+
+// The frame nb_field_rings and the maps share (include/nbody.h): n the unit axis, e1 the coordinate axis
+// of the smallest |n_k| made orthogonal to n, e2 = n x e1.
+bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(axis[a])) return false;
+    // (an axis whose length over- or underflows has no finite unit vector either)
+    const double len = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) return false;
+    for (int a = 0; a < 3; ++a) n[a] = axis[a] / len;
+    int s = 0;  // the coordinate axis of the smallest |n_k|, the lowest index on ties
+    for (int a = 1; a < 3; ++a)
+        if (std::fabs(n[a]) < std::fabs(n[s])) s = a;
+    double el = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        e1[a] = (a == s ? 1.0 : 0.0) - n[s] * n[a];
+        el += e1[a] * e1[a];
+    }
+    el = std::sqrt(el);  // >= sqrt(2/3): |n_s| <= 1/sqrt(3)
+    for (int a = 0; a < 3; ++a) e1[a] /= el;
+    e2[0] = n[1] * e1[2] - n[2] * e1[1];
+    e2[1] = n[2] * e1[0] - n[0] * e1[2];
+    e2[2] = n[0] * e1[1] - n[1] * e1[0];
+    return true;
+}
+
+// nb_sim_radial_profile: everything that can be refused without a device
+int radial_check_params(const nb_radial_params *p, const nb_radial_profile *out, const nb_radial_bin *bins) {
+    if (!p || !out || !bins || !p->edges) {
+        set_error("radial_profile: null %s", !p ? "params" : !out ? "out" : !bins ? "bins" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_RADIAL_MAX_BINS) {
+        set_error("radial_profile: nbins must be 1..%u (got %u)", NB_RADIAL_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & ~(NB_RADIAL_CYLINDRICAL | NB_RADIAL_CENTER_COM)) {
+        set_error("radial_profile: unknown flag bits 0x%x", p->flags & ~(NB_RADIAL_CYLINDRICAL | NB_RADIAL_CENTER_COM));
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("radial_profile: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (!(p->flags & NB_RADIAL_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("radial_profile: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    const double *a = p->axis;
+    if (!std::isfinite(a[0]) || !std::isfinite(a[1]) || !std::isfinite(a[2])) {
+        set_error("radial_profile: axis must be finite");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & NB_RADIAL_CYLINDRICAL) {
+        // (an axis whose length over- or underflows has no finite unit vector either)
+        const double len = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+        if (!(len > 0.0) || !std::isfinite(len)) {
+            set_error("radial_profile: a cylindrical profile needs a non-zero axis");
+            return NB_ERR_INVALID;
+        }
+    }
+    return NB_OK;
+}
+
+int radial_edges(const char *what, bool log, double rmin, double rmax, uint32_t nbins, double *edges) {
+    if (!edges) {
+        set_error("%s: edges is null", what);
+        return NB_ERR_INVALID;
+    }
+    if (nbins < 1 || nbins > NB_RADIAL_MAX_BINS) {
+        set_error("%s: nbins must be 1..%u (got %u)", what, NB_RADIAL_MAX_BINS, nbins);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(rmin) || !std::isfinite(rmax) || !(rmax > rmin) || !(log ? rmin > 0.0 : rmin >= 0.0)) {
+        set_error("%s: needs finite %s rmin < rmax (got %g, %g)", what, log ? "0 <" : "0 <=", rmin, rmax);
+        return NB_ERR_INVALID;
+    }
+    double prev = rmin;
+    for (uint32_t k = 1; k < nbins; ++k) {  // checked before anything is written
+        const double t = (double)k / (double)nbins;
+        const double e = log ? rmin * std::pow(rmax / rmin, t) : rmin + (rmax - rmin) * t;
+        if (!(e > prev) || !(e < rmax)) {
+            set_error("%s: %u bins between %g and %g are not strictly ascending in fp64", what, nbins, rmin, rmax);
+            return NB_ERR_INVALID;
+        }
+        prev = e;
+    }
+    edges[0] = rmin;
+    for (uint32_t k = 1; k < nbins; ++k) {
+        const double t = (double)k / (double)nbins;
+        edges[k] = log ? rmin * std::pow(rmax / rmin, t) : rmin + (rmax - rmin) * t;
+    }
+    edges[nbins] = rmax;
+    return NB_OK;
+}
+
+// nb_sim_field: everything about the arguments that can be refused without a device
+int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out) {
+    if (m > 0 && (!points || !out)) {
+        set_error("field: null %s", !points ? "points" : "out");
+        return NB_ERR_INVALID;
+    }
+    if (!flags || (flags & ~(NB_FIELD_ACCEL | NB_FIELD_POTENTIAL))) {
+        set_error("field: flags must be NB_FIELD_ACCEL, NB_FIELD_POTENTIAL or both (got 0x%x)", flags);
+        return NB_ERR_INVALID;
+    }
+    if (m > NB_FIELD_MAX_POINTS) {
+        set_error("field: at most %u points (got %zu)", NB_FIELD_MAX_POINTS, m);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_field_rings / nb_field_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
+static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
+                      uint32_t n_phi, double n[3], double e1[3], double e2[3]) {
+    if (!center || !axis || (k && !radii)) {
+        set_error("%s: null %s", what, !center ? "center" : !axis ? "axis" : "radii");
+        return NB_ERR_INVALID;
+    }
+    if (n_phi == 0) {
+        set_error("%s: n_phi must be at least 1", what);
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(center[a]) || !std::isfinite(axis[a])) {
+            set_error("%s: center and axis must be finite", what);
+            return NB_ERR_INVALID;
+        }
+    double fn[3], f1[3], f2[3];  // (nothing is written on a refusal)
+    if (!axis_frame(axis, fn, f1, f2)) {
+        set_error("%s: needs a non-zero axis", what);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i)
+        if (!std::isfinite(radii[i]) || radii[i] < 0.0) {
+            set_error("%s: radii must be finite and >= 0 (radii[%u] = %g)", what, i, radii[i]);
+            return NB_ERR_INVALID;
+        }
+    for (int a = 0; a < 3; ++a) {
+        n[a] = fn[a];
+        e1[a] = f1[a];
+        e2[a] = f2[a];
+    }
+    return NB_OK;
+}
+
+// nb_sim_fof: everything that can be refused without a device
+int fof_check_params(const nb_fof_params *p) {
+    if (!p) {
+        set_error("fof: null params");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->link) || !(p->link > 0.0)) {
+        set_error("fof: link must be finite and > 0 (got %g)", p->link);
+        return NB_ERR_INVALID;
+    }
+    const double b2 = p->link * p->link;  // what the rule compares with
+    if (!(b2 > 0.0) || !std::isfinite(b2)) {
+        set_error("fof: link %g squared is not a positive finite double", p->link);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("fof: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved) {
+        set_error("fof: unknown flag bits 0x%x or reserved %llu != 0", p->flags, (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_sim_bound: everything that can be refused without a device (the softening is the simulator's: bound_check_e)
+int bound_check_params(const nb_bound_params *p) {
+    if (!p) {
+        set_error("bound: null params");
+        return NB_ERR_INVALID;
+    }
+    nb_fof_params fp{};
+    fp.link = p->link;
+    fp.min_members = p->min_members;
+    if (int rc = fof_check_params(&fp)) return rc;
+    if (p->max_iter < 1 || p->max_iter > NB_BOUND_MAX_ITER) {
+        set_error("bound: max_iter must be 1..%u (got %u)", NB_BOUND_MAX_ITER, p->max_iter);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_bound < 1) {
+        set_error("bound: min_bound must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved32 || p->reserved) {
+        set_error("bound: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+int bound_check_e(const SimBase &s) {
+    if (!(s.params.e >= 0.f)) {
+        set_error("bound: the pair potential needs e >= 0 (e = %g)", (double)s.params.e);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_sim_group_shapes: everything that can be refused without a device -- the parameters alone, then (a handle in
+// hand) what needs the simulator's n and step number
+int shape_check_params(const nb_shape_params *p) {
+    if (!p) {
+        set_error("group_shapes: null params");
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~NB_SHAPE_REDUCED) || p->reserved32 || p->reserved) {
+        set_error("group_shapes: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("group_shapes: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->max_iter < 1 || p->max_iter > NB_SHAPE_MAX_ITER) {
+        set_error("group_shapes: max_iter must be 1..%u (got %u)", NB_SHAPE_MAX_ITER, p->max_iter);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->tol) || !(p->tol > 0.0)) {
+        set_error("group_shapes: tol must be finite and > 0 (got %g)", p->tol);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+int shape_check_args(const SimBase &s, const nb_shape_params *p, const uint32_t *group_of, size_t m,
+                     const double *centers, const double *velocities, const double *radius) {
+    if (s.n > 0 && !group_of) {
+        set_error("group_shapes: null group_of");
+        return NB_ERR_INVALID;
+    }
+    if (m > std::max<size_t>(s.n, 1)) {
+        set_error("group_shapes: %zu rows are more than %u bodies can fill", m, s.n);
+        return NB_ERR_INVALID;
+    }
+    for (size_t k = 0; k < 3 * m; ++k)
+        if ((centers && !std::isfinite(centers[k])) || (velocities && !std::isfinite(velocities[k]))) {
+            set_error("group_shapes: the centre or the velocity of row %zu is not finite", k / 3);
+            return NB_ERR_INVALID;
+        }
+    const bool reduced = (p->flags & NB_SHAPE_REDUCED) != 0;
+    if (reduced && !radius && m > 0) {
+        set_error("group_shapes: NB_SHAPE_REDUCED needs a finite radius for every row (radius is null)");
+        return NB_ERR_INVALID;
+    }
+    for (size_t r = 0; radius && r < m; ++r) {
+        if (!(radius[r] > 0.0)) {  // (a NaN too)
+            set_error("group_shapes: radius[%zu] = %g is neither finite and > 0 nor +inf", r, radius[r]);
+            return NB_ERR_INVALID;
+        }
+        if (reduced && std::isinf(radius[r])) {
+            set_error("group_shapes: NB_SHAPE_REDUCED needs a finite radius (radius[%zu] is +inf)", r);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (p->step_num != NB_SHAPE_ANY_STEP && p->step_num != s.step_num) {
+        set_error("group_shapes: the assignment was made at step %llu, the simulator is at step %llu",
+                  (unsigned long long)p->step_num, (unsigned long long)s.step_num);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_sim_knn: everything that can be refused without a device
+int knn_check_params(const nb_knn_params *p) {
+    if (!p) {
+        set_error("knn: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->k < 1 || p->k > NB_KNN_MAX_K) {
+        set_error("knn: k must be 1..%u (got %u)", NB_KNN_MAX_K, p->k);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved) {
+        set_error("knn: unknown flag bits 0x%x or reserved %llu != 0", p->flags, (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_sim_hop: everything that can be refused without a device
+int hop_check_params(const nb_hop_params *p) {
+    if (!p) {
+        set_error("hop: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->k_density < 2 || p->k_density > NB_KNN_MAX_K) {
+        set_error("hop: k_density must be 2..%u (got %u)", NB_KNN_MAX_K, p->k_density);
+        return NB_ERR_INVALID;
+    }
+    if (p->k_hop < 1 || p->k_hop > NB_KNN_MAX_K || p->k_merge < 1 || p->k_merge > NB_KNN_MAX_K) {
+        set_error("hop: k_hop and k_merge must be 1..%u (got %u, %u)", NB_KNN_MAX_K, p->k_hop, p->k_merge);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("hop: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (std::isnan(p->density_min)) {
+        set_error("hop: density_min must not be NaN (-inf: no cut)");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved32 || p->reserved) {
+        set_error("hop: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_hop_regroup behind the ABI boundary (include/nbody.h: the rule, step by step)
+// the ordering key of a density, and the "denser" order of include/nbody.h
+static double hop_rho_key(double d) { return std::isnan(d) ? -INFINITY : d; }
+static bool hop_denser(double ra, uint32_t a, double rb, uint32_t b) { return ra > rb || (ra == rb && a < b); }
+
+int hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t m, const nb_hop_boundary *bnd,
+                size_t b, const nb_hop_regroup_params *params, uint32_t *merged_of_row, nb_fof_group *out_rows,
+                double *out_peak, size_t out_capacity, size_t *out_count) {
+    {
+        if (!params || !out_count || (m && (!rows || !peak_density)) || (b && !bnd)) {
+            set_error("hop_regroup: null argument");
+            return NB_ERR_INVALID;
+        }
+        if (std::isnan(params->saddle) || std::isnan(params->peak) || params->saddle > params->peak) {
+            set_error("hop_regroup: saddle and peak must not be NaN, with saddle <= peak (got %g, %g)", params->saddle,
+                      params->peak);
+            return NB_ERR_INVALID;
+        }
+        if (params->flags || params->reserved) {
+            set_error("hop_regroup: unknown flag bits 0x%x or reserved != 0", params->flags);
+            return NB_ERR_INVALID;
+        }
+        for (size_t r = 1; r < m; ++r)
+            if (!(rows[r - 1].label < rows[r].label)) {
+                set_error("hop_regroup: rows must be in strictly ascending label order (row %zu)", r);
+                return NB_ERR_INVALID;
+            }
+        for (size_t e = 0; e < b; ++e) {
+            const bool ordered = e == 0 || bnd[e - 1].a < bnd[e].a || (bnd[e - 1].a == bnd[e].a && bnd[e - 1].b < bnd[e].b);
+            if (!ordered || !(bnd[e].a < bnd[e].b)) {
+                set_error("hop_regroup: boundaries must be in strictly ascending (a, b) with a < b (boundary %zu)", e);
+                return NB_ERR_INVALID;
+            }
+        }
+        // the row of a label: a binary search in the ascending labels
+        auto row_of = [&](uint32_t label) -> size_t {
+            size_t lo = 0, hi = m;
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (rows[mid].label < label) lo = mid + 1;
+                else hi = mid;
+            }
+            return lo < m && rows[lo].label == label ? lo : m;
+        };
+        struct Edge {
+            double density;
+            size_t ra, rb, at;
+        };
+        std::vector<Edge> edges;
+        for (size_t e = 0; e < b; ++e) {
+            const size_t ra = row_of(bnd[e].a), rb = row_of(bnd[e].b);
+            if (ra < m && rb < m) edges.push_back({bnd[e].density, ra, rb, e});
+        }
+        // descending density (a NaN as -inf, like a peak's), ties in ascending (a, b) -- the table's own order
+        std::stable_sort(edges.begin(), edges.end(), [](const Edge &x, const Edge &y) {
+            return hop_rho_key(x.density) > hop_rho_key(y.density);
+        });
+        std::vector<size_t> parent(m);
+        std::vector<char> viable(m);  // of a root: its set's
+        for (size_t r = 0; r < m; ++r) {
+            parent[r] = r;
+            viable[r] = hop_rho_key(peak_density[r]) >= params->peak;
+        }
+        auto find = [&](size_t x) {
+            while (parent[x] != x) {
+                parent[x] = parent[parent[x]];
+                x = parent[x];
+            }
+            return x;
+        };
+        for (const Edge &e : edges) {
+            const size_t x = find(e.ra), y = find(e.rb);
+            if (x == y) continue;
+            if (viable[x] && viable[y] && e.density < params->saddle) continue;
+            parent[y] = x;
+            viable[x] = viable[x] || viable[y];
+        }
+        // the representative of every set: its densest peak
+        std::vector<size_t> rep(m);
+        for (size_t r = 0; r < m; ++r) rep[r] = m;
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (rep[x] == m || hop_denser(hop_rho_key(peak_density[r]), rows[r].label, hop_rho_key(peak_density[rep[x]]),
+                                          rows[rep[x]].label))
+                rep[x] = r;
+        }
+        // the viable sets in ascending representative label: a set is listed at its representative's row
+        std::vector<size_t> out_of(m, m);
+        size_t count = 0;
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (viable[x] && rep[x] == r) out_of[r] = count++;
+        }
+        for (size_t r = 0; r < m; ++r) {
+            const size_t x = find(r);
+            if (merged_of_row) merged_of_row[r] = viable[x] ? rows[rep[x]].label : NB_HOP_NONE;
+            if (!viable[x] || out_of[rep[x]] >= out_capacity) continue;
+            const size_t o = out_of[rep[x]];
+            if (out_peak && rep[x] == r) out_peak[o] = peak_density[r];
+        }
+        if (out_rows) {
+            const size_t listed = std::min(count, out_capacity);
+            for (size_t o = 0; o < listed; ++o) out_rows[o] = nb_fof_group{};
+            for (size_t r = 0; r < m; ++r) {  // the member rows in ascending row order
+                const size_t x = find(r);
+                if (!viable[x] || out_of[rep[x]] >= out_capacity) continue;
+                nb_fof_group &g = out_rows[out_of[rep[x]]];
+                g.label = rows[rep[x]].label;
+                g.count += rows[r].count;
+                g.mass += rows[r].mass;
+                for (int a = 0; a < 3; ++a) {
+                    g.mx[a] += rows[r].mx[a];
+                    g.mv[a] += rows[r].mv[a];
+                }
+                g.mr2 += rows[r].mr2;
+                g.mv2 += rows[r].mv2;
+            }
+        }
+        *out_count = count;
+        return NB_OK;
+    }
+}
+
+// nb_sim_halo_profiles: everything that can be refused without a device (a body index needs n: sim_halo_profiles)
+int halo_check_params(const nb_halo_params *p) {
+    if (!p || !p->edges) {
+        set_error("halo_profiles: null %s", !p ? "params" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_HALO_MAX_BINS) {
+        set_error("halo_profiles: nbins must be 1..%u (got %u)", NB_HALO_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags) {
+        set_error("halo_profiles: unknown flag bits 0x%x", p->flags);
+        return NB_ERR_INVALID;
+    }
+    if (p->m > NB_HALO_MAX_CENTERS || p->m * p->nbins > NB_HALO_MAX_ROWS) {
+        set_error("halo_profiles: %llu centres of %u bins are more than one call takes (%u centres, %u rows)",
+                  (unsigned long long)p->m, p->nbins, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("halo_profiles: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (p->m == 0) return NB_OK;
+    if (!p->centers == !p->bodies) {
+        set_error("halo_profiles: exactly one of centers and bodies must be given (%s)",
+                  p->centers ? "got both" : "got neither");
+        return NB_ERR_INVALID;
+    }
+    for (uint64_t j = 0; j < 3 * p->m; ++j)
+        if ((p->centers && !std::isfinite(p->centers[j])) || (p->velocities && !std::isfinite(p->velocities[j]))) {
+            set_error("halo_profiles: centre %llu has a non-finite %s", (unsigned long long)(j / 3),
+                      p->centers && !std::isfinite(p->centers[j]) ? "position" : "velocity");
+            return NB_ERR_INVALID;
+        }
+    return NB_OK;
+}
+
+// nb_map_edges / nb_sim_map: the cell size of `cells` cells in [lo, hi), refused unless the edges
+// lo + i * size (i < cells), hi come out strictly ascending
+static int map_cell_size(const char *what, double lo, double hi, uint32_t cells, double *size) {
+    if (cells < 1 || cells > NB_MAP_MAX_SIDE) {
+        set_error("%s: a side must be 1..%u cells (got %u)", what, NB_MAP_MAX_SIDE, cells);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) {
+        set_error("%s: a window needs finite lo < hi (got %g, %g)", what, lo, hi);
+        return NB_ERR_INVALID;
+    }
+    const double d = (hi - lo) / (double)cells;
+    double prev = lo;
+    for (uint32_t i = 1; i <= cells; ++i) {
+        const double e = i < cells ? lo + (double)i * d : hi;
+        if (!(e > prev) || !std::isfinite(e)) {
+            set_error("%s: %u cells between %g and %g are not strictly ascending in fp64", what, cells, lo, hi);
+            return NB_ERR_INVALID;
+        }
+        prev = e;
+    }
+    *size = d;
+    return NB_OK;
+}
+
+// nb_sim_map: everything that can be refused without a device; the frame and the cell sizes on the way
+int map_check_params(const nb_map_params *p, MapPlan *plan) {
+    if (!p) {
+        set_error("map: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->width < 1 || p->width > NB_MAP_MAX_SIDE || p->height < 1 || p->height > NB_MAP_MAX_SIDE) {
+        set_error("map: a side must be 1..%u cells (got %u x %u)", NB_MAP_MAX_SIDE, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)p->width * p->height > NB_MAP_MAX_CELLS) {
+        set_error("map: at most %u cells (got %u x %u)", NB_MAP_MAX_CELLS, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~(NB_MAP_CENTER_COM | NB_MAP_VELOCITY)) || p->reserved) {
+        set_error("map: unknown flag bits 0x%x or reserved %u != 0", p->flags & ~(NB_MAP_CENTER_COM | NB_MAP_VELOCITY),
+                  p->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (!axis_frame(p->axis, plan->n, plan->e1, plan->e2)) {
+        set_error("map: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    if (!(p->flags & NB_MAP_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("map: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    if (int rc = map_cell_size("map: x_range", p->x_range[0], p->x_range[1], p->width, &plan->dx)) return rc;
+    if (int rc = map_cell_size("map: y_range", p->y_range[0], p->y_range[1], p->height, &plan->dy)) return rc;
+    // (either bound may be infinite; a NaN fails the comparison)
+    if (!(p->depth_range[1] > p->depth_range[0])) {
+        set_error("map: depth_range needs lo < hi without NaN (got %g, %g)", p->depth_range[0], p->depth_range[1]);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_smooth_centres / nb_sim_smooth_map: the `cells` pixel centres of a window, from the edges of nb_map_edges
+static void smooth_centres(double lo, double hi, uint32_t cells, double size, double *out) {
+    double prev = lo;  // xe[i]
+    for (uint32_t i = 0; i < cells; ++i) {
+        const double next = i + 1 < cells ? lo + (double)(i + 1) * size : hi;
+        out[i] = 0.5 * (prev + next);
+        prev = next;
+    }
+}
+
+// nb_sim_smooth_map: everything that can be refused without a device, in the words of the pass; the frame, the
+// pixel sizes and the pixel centres on the way.  The fields the two share are checked by map_check_params.
+int smooth_check_params(const nb_smooth_params *p, SmoothPlan *plan) {
+    if (!p) {
+        set_error("smooth_map: null params");
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~(NB_SMOOTH_CENTER_COM | NB_SMOOTH_VELOCITY)) || p->reserved) {
+        set_error("smooth_map: unknown flag bits 0x%x or reserved %u != 0",
+                  p->flags & ~(NB_SMOOTH_CENTER_COM | NB_SMOOTH_VELOCITY), p->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->s_min) || !std::isfinite(p->s_max) || !(p->s_min > 0.0) || !(p->s_max >= p->s_min)) {
+        set_error("smooth_map: needs finite 0 < s_min <= s_max (got %g, %g)", p->s_min, p->s_max);
+        return NB_ERR_INVALID;
+    }
+    static_assert(NB_SMOOTH_CENTER_COM == NB_MAP_CENTER_COM && NB_SMOOTH_VELOCITY == NB_MAP_VELOCITY, "shared flag bits");
+    nb_map_params m{};
+    m.width = p->width;
+    m.height = p->height;
+    m.flags = p->flags;
+    for (int k = 0; k < 3; ++k) {
+        m.center[k] = p->center[k];
+        m.velocity[k] = p->velocity[k];
+        m.axis[k] = p->axis[k];
+    }
+    for (int k = 0; k < 2; ++k) {
+        m.x_range[k] = p->x_range[k];
+        m.y_range[k] = p->y_range[k];
+        m.depth_range[k] = p->depth_range[k];
+    }
+    if (int rc = map_check_params(&m, &plan->frame)) {
+        const std::string why = nb_last_error();  // "map: ..."
+        set_error("smooth_%s", why.c_str());
+        return rc;
+    }
+    plan->xc.resize(p->width);
+    plan->yc.resize(p->height);
+    smooth_centres(p->x_range[0], p->x_range[1], p->width, plan->frame.dx, plan->xc.data());
+    smooth_centres(p->y_range[0], p->y_range[1], p->height, plan->frame.dy, plan->yc.data());
+    return NB_OK;
+}
+
+// ---- the host-only entry points of include/nbody.h behind the ABI boundary (nb_X is X here) ----
+int radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, const double *edges,
+                      const double *fractions, uint32_t k, double *radii) {
+    if (!p || !bins || !edges || (k && (!fractions || !radii))) {
+        set_error("radial_lagrangian: null argument");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_RADIAL_MAX_BINS) {
+        set_error("radial_lagrangian: profile with %u bins", p->nbins);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        const double f = fractions[i], target = f * p->mass;
+        radii[i] = std::nan("");
+        if (!(f > 0.0 && f < 1.0) || !(target >= p->inside_mass)) continue;  // ... or the crossing lies in `inside`
+        double cum = p->inside_mass;
+        for (uint32_t b = 0; b < p->nbins; ++b) {
+            const double m = bins[b].mass, next = cum + m;
+            if (target <= next) {  // linear in r inside the bin that crosses
+                radii[i] = m > 0.0 ? edges[b] + (target - cum) / m * (edges[b + 1] - edges[b]) : edges[b];
+                break;
+            }
+            cum = next;
+        }
+    }
+    return NB_OK;
+}
+
+int field_rings(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                float *points) {
+    double n[3], e1[3], e2[3];
+    if (int rc = ring_basis("field_rings", center, axis, radii, k, n_phi, n, e1, e2)) return rc;
+    if (k && !points) {
+        set_error("field_rings: null points");
+        return NB_ERR_INVALID;
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (uint32_t i = 0; i < k; ++i)
+        for (uint32_t q = 0; q < n_phi; ++q) {
+            const double phi = two_pi * (double)q / (double)n_phi, c = std::cos(phi), s = std::sin(phi);
+            float *p = points + 3 * ((size_t)i * n_phi + q);
+            for (int a = 0; a < 3; ++a) p[a] = (float)(center[a] + radii[i] * (c * e1[a] + s * e2[a]));
+        }
+    return NB_OK;
+}
+
+int field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
+                     uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out) {
+    double n[3], e1[3], e2[3];
+    if (int rc = ring_basis("field_ring_means", center, axis, radii, k, n_phi, n, e1, e2)) return rc;
+    if (k && (!points || !samples || !out)) {
+        set_error("field_ring_means: null %s", !points ? "points" : !samples ? "samples" : "out");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        double a_r = 0.0, a_n = 0.0, pot = 0.0;
+        for (uint32_t q = 0; q < n_phi; ++q) {
+            const size_t j = (size_t)i * n_phi + q;
+            const nb_field_sample &f = samples[j];
+            double d[3], h = 0.0;  // the fp32 point actually used, from the centre; its height along n
+            for (int a = 0; a < 3; ++a) {
+                d[a] = (double)points[3 * j + a] - center[a];
+                h += d[a] * n[a];
+            }
+            double len = 0.0, dot = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                d[a] -= h * n[a];
+                len += d[a] * d[a];
+                dot += f.acc[a] * d[a];
+            }
+            len = std::sqrt(len);
+            if (len > 0.0) a_r += dot / len;
+            a_n += f.acc[0] * n[0] + f.acc[1] * n[1] + f.acc[2] * n[2];
+            pot += f.potential;
+        }
+        nb_field_ring r{};
+        r.a_R = a_r / (double)n_phi;
+        r.a_n = a_n / (double)n_phi;
+        r.potential = pot / (double)n_phi;
+        r.v_c = std::sqrt(std::fmax(0.0, -radii[i] * r.a_R));
+        out[i] = r;
+    }
+    return NB_OK;
+}
+
+int halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out) {
+    if (!head || !bins || !out) {
+        set_error("halo_enclosed: null argument");
+        return NB_ERR_INVALID;
+    }
+    if (nbins < 1 || nbins > NB_HALO_MAX_BINS) {
+        set_error("halo_enclosed: nbins must be 1..%u (got %u)", NB_HALO_MAX_BINS, nbins);
+        return NB_ERR_INVALID;
+    }
+    out[0] = head->inside_mass;
+    for (uint32_t k = 0; k < nbins; ++k) out[k + 1] = out[k] + bins[k].mass;
+    return NB_OK;
+}
+
+int halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, const double *edges, uint32_t nbins,
+                     double rho, double *r, double *mass) {
+    if (!edges || !r || !mass) {
+        set_error("halo_overdensity: null argument");
+        return NB_ERR_INVALID;
+    }
+    double enclosed[NB_HALO_MAX_BINS + 1];
+    if (int rc = halo_enclosed(head, bins, nbins, enclosed)) return rc;
+    if (!std::isfinite(rho) || !(rho > 0.0)) {
+        set_error("halo_overdensity: rho must be finite and > 0 (got %g)", rho);
+        return NB_ERR_INVALID;
+    }
+    *r = *mass = std::nan("");
+    for (uint32_t k = 1; k <= nbins; ++k) {
+        const double e0 = edges[k - 1], e1 = edges[k];
+        if (!(e0 > 0.0)) continue;
+        const double rho0 = enclosed[k - 1] / (NB_KNN_SPHERE * ((e0 * e0) * e0));
+        const double rho1 = enclosed[k] / (NB_KNN_SPHERE * ((e1 * e1) * e1));
+        if (rho0 >= rho && rho > rho1) {
+            const double t = (std::log(rho0) - std::log(rho)) / (std::log(rho0) - std::log(rho1));
+            const double x = std::exp(std::log(e0) + t * (std::log(e1) - std::log(e0)));
+            *r = x;
+            *mass = rho * NB_KNN_SPHERE * ((x * x) * x);
+            break;
+        }
+    }
+    return NB_OK;
+}
+
+int smooth_centres(double lo, double hi, uint32_t cells, double *out) {
+    if (!out) {
+        set_error("smooth_centres: out is null");
+        return NB_ERR_INVALID;
+    }
+    double d = 0.0;
+    if (int rc = map_cell_size("smooth_centres", lo, hi, cells, &d)) return rc;
+    smooth_centres(lo, hi, cells, d, out);
+    return NB_OK;
+}
+
+int map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]) {
+    if (!axis || !n_hat || !e1 || !e2) {
+        set_error("map_frame: null argument");
+        return NB_ERR_INVALID;
+    }
+    double n[3], f1[3], f2[3];
+    if (!axis_frame(axis, n, f1, f2)) {
+        set_error("map_frame: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 3; ++a) {
+        n_hat[a] = n[a];
+        e1[a] = f1[a];
+        e2[a] = f2[a];
+    }
+    return NB_OK;
+}
+
+int map_edges(double lo, double hi, uint32_t cells, double *edges) {
+    if (!edges) {
+        set_error("map_edges: edges is null");
+        return NB_ERR_INVALID;
+    }
+    double d = 0.0;
+    if (int rc = map_cell_size("map_edges", lo, hi, cells, &d)) return rc;
+    for (uint32_t i = 0; i < cells; ++i) edges[i] = lo + (double)i * d;
+    edges[cells] = hi;
+    return NB_OK;
+}
+
+}  // namespace nb

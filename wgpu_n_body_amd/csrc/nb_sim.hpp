@@ -144,62 +144,94 @@ int sim_diagnostics(SimBase &sim, uint32_t flags, nb_diagnostics *out);
 constexpr int kDiagResMass = 0, kDiagResMX = 1, kDiagResMV = 4, kDiagResBad = 12;
 int diag_enqueue_moments(SimBase &sim, const double **res_dev);
 
-// nb_render.hip: nb_sim_render behind the handle (arguments already checked by render_check_params,
-// nb_camera.cpp) and the "render_design" tuning key
+// Every pass below is stated as its refusal rules and the call behind the handle.  The rules that need no device
+// live in nb_passes.cpp (the renderer's in nb_camera.cpp, next to the camera they share) and run before the
+// simulator is looked at; sim_X takes arguments they have passed.
+
+// nb_render.hip: nb_sim_render behind the handle and the "render_design" tuning key
 int render_check_params(const nb_render_params *params);
 int sim_render(SimBase &sim, const nb_render_params &params, uint8_t *rgba, uint32_t *counts, nb_render_stats *stats);
 int sim_render_set_design(SimBase &sim, int design);
 
-// nb_radial.hip: nb_sim_radial_profile behind the handle (arguments already checked, nb_abi.cpp)
+// nb_radial.hip: nb_sim_radial_profile behind the handle; radial_edges: nb_radial_edges_log / _linear behind the
+// ABI boundary (`what` names the entry point in a refusal)
+int radial_check_params(const nb_radial_params *p, const nb_radial_profile *out, const nb_radial_bin *bins);
 int sim_radial_profile(SimBase &sim, const nb_radial_params &params, nb_radial_profile *out, nb_radial_bin *bins);
+int radial_edges(const char *what, bool log, double rmin, double rmax, uint32_t nbins, double *edges);
 
-// nb_field.hip: nb_sim_field behind the handle (arguments already checked, nb_abi.cpp)
+// nb_field.hip: nb_sim_field behind the handle
+int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out);
 int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out, nb_field_stats *stats);
 
-// nb_map.hip: nb_sim_map behind the handle (arguments already checked by map_check_params, nb_abi.cpp, which
-// also forms the frame and the cell sizes)
+// nb_map.hip: nb_sim_map behind the handle; map_check_params also forms the frame and the cell sizes
 struct MapPlan {
     double n[3], e1[3], e2[3];  // axis_frame of the caller's axis
     double dx, dy;              // (hi - lo) / W, (hi - lo) / H
 };
+int map_check_params(const nb_map_params *p, MapPlan *plan);
 int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
             nb_map_stats *stats);
-// nb_fof.hip: nb_sim_fof behind the handle (arguments already checked by fof_check_params, nb_abi.cpp)
+// nb_fof.hip: nb_sim_fof behind the handle
+int fof_check_params(const nb_fof_params *p);
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
             size_t group_capacity, nb_fof_stats *stats);
-// nb_halo.hip: nb_sim_halo_profiles behind the handle (arguments already checked by halo_check_params, nb_abi.cpp,
-// but for the body indices, which need n)
+// nb_halo.hip: nb_sim_halo_profiles behind the handle (the body indices need n: they are checked there)
+int halo_check_params(const nb_halo_params *p);
 int sim_halo_profiles(SimBase &sim, const nb_halo_params &params, nb_halo_head *heads, nb_radial_bin *bins,
                       nb_halo_stats *stats);
 
-// nb_bound.hip: nb_sim_bound behind the handle (arguments already checked by bound_check_params, nb_abi.cpp)
+// nb_bound.hip: nb_sim_bound behind the handle; the softening is the simulator's (bound_check_e)
+int bound_check_params(const nb_bound_params *p);
+int bound_check_e(const SimBase &sim);
 int sim_bound(SimBase &sim, const nb_bound_params &params, uint32_t *group_of, uint32_t *bound_of, double *energy,
               nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats);
-// nb_shape.hip: nb_sim_group_shapes behind the handle (arguments already checked by shape_check_args, nb_abi.cpp,
-// but for the values of group_of, which are checked on the device), and nb_shape_eigen's body, which lives in the
+// nb_shape.hip: nb_sim_group_shapes behind the handle -- the parameters alone, then what needs the simulator's n and
+// step number (the values of group_of are checked on the device) -- and nb_shape_eigen's body, which lives in the
 // unit built without contraction
+int shape_check_params(const nb_shape_params *p);
+int shape_check_args(const SimBase &sim, const nb_shape_params *p, const uint32_t *group_of, size_t m,
+                     const double *centers, const double *velocities, const double *radius);
 int sim_group_shapes(SimBase &sim, const nb_shape_params &params, const uint32_t *group_of, size_t m,
                      const double *centers, const double *velocities, const double *radius, nb_shape_group *rows,
                      uint32_t *selected_of, nb_shape_stats *stats);
 void shape_eigen_host(const double t[6], double lambda[3], double axes[9]);
-// nb_knn.hip: nb_sim_knn behind the handle (arguments already checked by knn_check_params, nb_abi.cpp)
+// nb_knn.hip: nb_sim_knn behind the handle
+int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);
-// nb_hop.hip: nb_sim_hop behind the handle (arguments already checked by hop_check_params, nb_abi.cpp)
+// nb_hop.hip: nb_sim_hop behind the handle
+int hop_check_params(const nb_hop_params *p);
 int sim_hop(SimBase &sim, const nb_hop_params &params, uint32_t *labels, uint32_t *group_of, double *density,
             nb_fof_group *groups, double *peak_density, size_t group_capacity, nb_hop_boundary *boundaries,
             size_t boundary_capacity, nb_hop_stats *stats);
-// nb_smooth.hip: nb_sim_smooth_map behind the handle (arguments already checked by smooth_check_params,
-// nb_abi.cpp, which also forms the frame, the pixel sizes and the pixel centres)
+// nb_smooth.hip: nb_sim_smooth_map behind the handle; smooth_check_params also forms the frame, the pixel sizes and
+// the pixel centres
 struct SmoothPlan {
     MapPlan frame;
     std::vector<double> xc, yc;  // nb_smooth_centres of the two windows
 };
+int smooth_check_params(const nb_smooth_params *p, SmoothPlan *plan);
 int sim_smooth_map(SimBase &sim, const nb_smooth_params &params, const SmoothPlan &plan, const double *s,
                    uint32_t *counts, double *planes, nb_smooth_stats *stats);
-// nb_abi.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
+// nb_passes.cpp: the unit axis n and the basis e1, e2 = n x e1 that nb_field_rings and the maps share (the
 // rule of include/nbody.h); false for an axis without a finite, non-zero length
 bool axis_frame(const double axis[3], double n[3], double e1[3], double e2[3]);
+// nb_passes.cpp: the host-only entry points of include/nbody.h behind the ABI boundary (nb_X is X here)
+int radial_lagrangian(const nb_radial_profile *p, const nb_radial_bin *bins, const double *edges,
+                      const double *fractions, uint32_t k, double *radii);
+int field_rings(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                float *points);
+int field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                     const float *points, const nb_field_sample *samples, nb_field_ring *out);
+int halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out);
+int halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, const double *edges, uint32_t nbins,
+                     double rho, double *r, double *mass);
+int hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t m, const nb_hop_boundary *bnd, size_t b,
+                const nb_hop_regroup_params *params, uint32_t *merged_of_row, nb_fof_group *out_rows,
+                double *out_peak, size_t out_capacity, size_t *out_count);
+int map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[3]);
+int map_edges(double lo, double hi, uint32_t cells, double *edges);
+int smooth_centres(double lo, double hi, uint32_t cells, double *out);
 
 class NaiveSim final : public SimBase {
    public:
@@ -244,7 +276,11 @@ class NaiveSim final : public SimBase {
 // Implemented in nb_tree.hip; returns nullptr when the tree path is not built.
 SimBase *make_tree_sim();
 
-// nb_abi.cpp: construct a simulator object (what nb_sim_create does behind the handle)
+// nb_simbase.cpp: construct a simulator object (what nb_sim_create does behind the handle); add_params == NULL
+// stands for the all-pairs simulator; the shard layout of nb_shard_bodies_per_rank / nb_shard_padded_bodies
+nb_add_params add_params_or_default(const nb_add_params *ap);
+size_t shard_bodies_per_rank(size_t particle_num, int world);
+size_t shard_padded_bodies(size_t particle_num, int world);
 int make_sim_impl(std::unique_ptr<SimBase> &out, const nb_sim_params *sp, const nb_add_params *ap,
                   const nb_placement *pl, const nb_particle *particles, size_t count);
 

@@ -666,14 +666,150 @@ struct InitThunk {
         }
     }
 };
+
+// the entry points of the analysis passes per handle type: nb_sim_X, and nb_runner_X -- the same pass on the
+// runner's simulator, refused by a several-GPU runner
+template <class H>
+struct PassAbi;
+template <>
+struct PassAbi<nb_sim> {
+    static constexpr auto sim_params = nb_sim_sim_params;
+    static constexpr auto diagnostics = nb_sim_diagnostics;
+    static constexpr auto radial_profile = nb_sim_radial_profile;
+    static constexpr auto field = nb_sim_field;
+    static constexpr auto map = nb_sim_map;
+    static constexpr auto fof = nb_sim_fof;
+    static constexpr auto bound = nb_sim_bound;
+    static constexpr auto knn = nb_sim_knn;
+    static constexpr auto hop = nb_sim_hop;
+    static constexpr auto halo_profiles = nb_sim_halo_profiles;
+    static constexpr auto group_shapes = nb_sim_group_shapes;
+    static constexpr auto smooth_map = nb_sim_smooth_map;
+    static constexpr auto render = nb_sim_render;
+};
+template <>
+struct PassAbi<nb_runner> {
+    static constexpr auto sim_params = nb_runner_sim_params;
+    static constexpr auto diagnostics = nb_runner_diagnostics;
+    static constexpr auto radial_profile = nb_runner_radial_profile;
+    static constexpr auto field = nb_runner_field;
+    static constexpr auto map = nb_runner_map;
+    static constexpr auto fof = nb_runner_fof;
+    static constexpr auto bound = nb_runner_bound;
+    static constexpr auto knn = nb_runner_knn;
+    static constexpr auto hop = nb_runner_hop;
+    static constexpr auto halo_profiles = nb_runner_halo_profiles;
+    static constexpr auto group_shapes = nb_runner_group_shapes;
+    static constexpr auto smooth_map = nb_runner_smooth_map;
+    static constexpr auto render = nb_runner_render;
+};
 }  // namespace detail
 
+// The analysis passes of the current state (no reference counterpart), once for Simulator and OfflineHeadless<T>;
+// on a runner each is the pass of the runner's simulator, for one device only
+template <class H>
+class Passes {
+    using Abi = detail::PassAbi<H>;
+
+   public:
+    // energy, momentum, angular momentum of the current state; potential: the O(N^2) pair potential too
+    Diagnostics diagnostics(bool potential = false) {
+        Diagnostics d{};
+        check(Abi::diagnostics(h_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
+        return d;
+    }
+    // per-shell mass and velocity moments of the current state between `edges`; p: flags
+    // (NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
+    RadialProfile radial_profile(const std::vector<double> &edges, const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
+        return detail::radial_profile(Abi::radial_profile, h_, edges, p);
+    }
+    // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
+    ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(Abi::map, h_, p); }
+    // the friends-of-friends groups of the current state: bodies within `link` are friends
+    FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
+        return detail::fof_groups(Abi::fof, h_, n_bodies(), link, min_members, labels);
+    }
+    // those groups unbound: min_bound 0 stands for min_members, max_group 0 for no limit
+    BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
+                             uint32_t max_group = 262144, bool per_body = true) {
+        return detail::bound_groups(Abi::bound, h_, n_bodies(), link, min_members,
+                                    min_bound ? min_bound : min_members, max_iter, max_group, per_body);
+    }
+    // the shapes of the rows of an assignment: group_of of read_particles() now, NB_FOF_NONE or a row < m
+    GroupShapes group_shapes(const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o = ShapeOptions{},
+                             const std::vector<double> &centers = {}, const std::vector<double> &velocities = {},
+                             const std::vector<double> &radius = {}) {
+        return detail::group_shapes(Abi::group_shapes, h_, n_bodies(), group_of, m, o, centers,
+                                    velocities, radius);
+    }
+    GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
+        return detail::fof_shapes(Abi::group_shapes, h_, n_bodies(), f, k_rms, o);
+    }
+    // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
+    HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
+                         bool boundaries = true) {
+        return detail::hop_groups(Abi::hop, h_, n_bodies(), p, labels, density, boundaries);
+    }
+    KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
+        return detail::knn_density(Abi::knn, h_, n_bodies(), k, density, neighbours);
+    }
+    // the profiles about points (centers: x y z per centre) or about bodies; velocities: empty, or three per centre
+    HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
+                               const std::vector<double> &velocities = {}) {
+        return detail::halo_profiles(Abi::halo_profiles, h_, edges, &centers, nullptr, velocities);
+    }
+    HaloProfiles halo_profiles_of_bodies(const std::vector<double> &edges, const std::vector<uint32_t> &bodies,
+                                         const std::vector<double> &velocities = {}) {
+        return detail::halo_profiles(Abi::halo_profiles, h_, edges, nullptr, &bodies, velocities);
+    }
+    // the smoothed map of the current state: s[i] the smoothing length of body i in the order of read_particles() now
+    SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {
+        return detail::smoothed_map(Abi::smooth_map, h_, n_bodies(), p, std::move(s));
+    }
+    // ... with scale times the distance to the k-th neighbour (knn_density(k) on the same state)
+    SmoothedMap smoothed_map_knn(const SmoothParams &p, uint32_t k = 32, double scale = 1.0) {
+        return smoothed_map(p, detail::knn_lengths(knn_density(k, false, true), scale));
+    }
+    Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
+        return detail::field(Abi::field, h_, points, flags);
+    }
+    // the rotation curve from the force on n_phi points of each ring: v_c = sqrt(max(0, -R a_R))
+    RingMeans circular_velocity(const std::vector<double> &radii, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
+                                const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
+                                bool potential = false) {
+        return detail::circular_velocity(Abi::field, h_, radii, axis, center, n_phi, potential);
+    }
+    // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
+    Frame render(const RenderParams &p, bool counts = false) {
+        Frame f;
+        f.width = p.width;
+        f.height = p.height;
+        f.rgba.resize((size_t)p.width * p.height * 4);
+        if (counts) f.counts.resize((size_t)p.width * p.height);
+        check(Abi::render(h_, &p, f.rgba.data(), counts ? f.counts.data() : nullptr, &f.stats));
+        return f;
+    }
+
+   protected:
+    Passes() = default;
+    ~Passes() = default;
+    size_t n_bodies() const {
+        SimParams p{};
+        check(Abi::sim_params(h_, &p));
+        return p.particle_num;
+    }
+    H *h_ = nullptr;
+};
+
 // trait Simulator, sims/mod.rs:73-90
-class Simulator {
+class Simulator : public Passes<nb_sim> {
    public:
     Simulator(const Simulator &) = delete;
     Simulator &operator=(const Simulator &) = delete;
-    Simulator(Simulator &&o) noexcept : h_(o.h_), owned_(o.owned_) { o.h_ = nullptr; }
+    Simulator(Simulator &&o) noexcept : owned_(o.owned_) {
+        h_ = o.h_;
+        o.h_ = nullptr;
+    }
     virtual ~Simulator() {
         if (h_ && owned_) nb_sim_destroy(h_);
     }
@@ -700,87 +836,10 @@ class Simulator {
         check(nb_sim_step_num(h_, &v));
         return v;
     }
-    // energy, momentum, angular momentum of the current state; potential: the O(N^2) pair potential too
-    Diagnostics diagnostics(bool potential = false) {
-        Diagnostics d{};
-        check(nb_sim_diagnostics(h_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
-        return d;
-    }
-    // per-shell mass and velocity moments of the current state between `edges`; p: flags
-    // (NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
-    RadialProfile radial_profile(const std::vector<double> &edges, const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
-        return detail::radial_profile(nb_sim_radial_profile, h_, edges, p);
-    }
-    // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
-    ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(nb_sim_map, h_, p); }
-    // the friends-of-friends groups of the current state: bodies within `link` are friends
-    FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
-        return detail::fof_groups(nb_sim_fof, h_, sim_params().particle_num, link, min_members, labels);
-    }
-    // those groups unbound: min_bound 0 stands for min_members, max_group 0 for no limit
-    BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
-                             uint32_t max_group = 262144, bool per_body = true) {
-        return detail::bound_groups(nb_sim_bound, h_, sim_params().particle_num, link, min_members,
-                                    min_bound ? min_bound : min_members, max_iter, max_group, per_body);
-    }
-    // the shapes of the rows of an assignment: group_of of read_particles() now, NB_FOF_NONE or a row < m
-    GroupShapes group_shapes(const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o = ShapeOptions{},
-                             const std::vector<double> &centers = {}, const std::vector<double> &velocities = {},
-                             const std::vector<double> &radius = {}) {
-        return detail::group_shapes(nb_sim_group_shapes, h_, sim_params().particle_num, group_of, m, o, centers,
-                                    velocities, radius);
-    }
-    GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
-        return detail::fof_shapes(nb_sim_group_shapes, h_, sim_params().particle_num, f, k_rms, o);
-    }
-    // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
-    HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
-                         bool boundaries = true) {
-        return detail::hop_groups(nb_sim_hop, h_, sim_params().particle_num, p, labels, density, boundaries);
-    }
-    KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
-        return detail::knn_density(nb_sim_knn, h_, sim_params().particle_num, k, density, neighbours);
-    }
-    // the profiles about points (centers: x y z per centre) or about bodies; velocities: empty, or three per centre
-    HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
-                               const std::vector<double> &velocities = {}) {
-        return detail::halo_profiles(nb_sim_halo_profiles, h_, edges, &centers, nullptr, velocities);
-    }
-    HaloProfiles halo_profiles_of_bodies(const std::vector<double> &edges, const std::vector<uint32_t> &bodies,
-                                         const std::vector<double> &velocities = {}) {
-        return detail::halo_profiles(nb_sim_halo_profiles, h_, edges, nullptr, &bodies, velocities);
-    }
-    // the smoothed map of the current state: s[i] the smoothing length of body i in the order of read_particles() now
-    SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {
-        return detail::smoothed_map(nb_sim_smooth_map, h_, sim_params().particle_num, p, std::move(s));
-    }
-    // ... with scale times the distance to the k-th neighbour (knn_density(k) on the same state)
-    SmoothedMap smoothed_map_knn(const SmoothParams &p, uint32_t k = 32, double scale = 1.0) {
-        return smoothed_map(p, detail::knn_lengths(knn_density(k, false, true), scale));
-    }
-    Field field(const std::vector<float> &points, uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
-        return detail::field(nb_sim_field, h_, points, flags);
-    }
-    // the rotation curve from the force on n_phi points of each ring: v_c = sqrt(max(0, -R a_R))
-    RingMeans circular_velocity(const std::vector<double> &radii, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
-                                const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
-                                bool potential = false) {
-        return detail::circular_velocity(nb_sim_field, h_, radii, axis, center, n_phi, potential);
-    }
-    // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
-    Frame render(const RenderParams &p, bool counts = false) {
-        Frame f;
-        f.width = p.width;
-        f.height = p.height;
-        f.rgba.resize((size_t)p.width * p.height * 4);
-        if (counts) f.counts.resize((size_t)p.width * p.height);
-        check(nb_sim_render(h_, &p, f.rgba.data(), counts ? f.counts.data() : nullptr, &f.stats));
-        return f;
-    }
     nb_sim *handle() { return h_; }
 
    protected:
-    Simulator(nb_sim *h, bool owned) : h_(h), owned_(owned) {}
+    Simulator(nb_sim *h, bool owned) : owned_(owned) { h_ = h; }
     static nb_sim *create(const SimParams &sp, nb_add_params ap, const InitFn &init,
                           const nb_placement *pl) {
         detail::InitThunk thunk{&init, {}};
@@ -793,7 +852,6 @@ class Simulator {
         check(rc);
         return h;
     }
-    nb_sim *h_;
     bool owned_;
     template <class T>
     friend class OfflineHeadless;
@@ -832,15 +890,15 @@ class TreeSim : public Simulator {  // sims/tree.rs
 
 // OfflineHeadless<T: Simulator>, runners/offline_headless.rs:4-45
 template <class T>
-class OfflineHeadless {
+class OfflineHeadless : public Passes<nb_runner> {
    public:
     OfflineHeadless(const SimParams &sp, const AddParams &ap, const InitFn &init, int device_id = -1) {
         detail::InitThunk thunk{&init, {}};
         nb_add_params c = ap.c;
         if (c.kind != T::kKind) c = nb_add_params{T::kKind, 0.f};
-        int rc = nb_runner_create(&r_, &sp, &c, &detail::InitThunk::call, &thunk, device_id);
+        int rc = nb_runner_create(&h_, &sp, &c, &detail::InitThunk::call, &thunk, device_id);
         if (!thunk.error.empty()) {
-            if (rc == NB_OK) nb_runner_destroy(r_);
+            if (rc == NB_OK) nb_runner_destroy(h_);
             throw Error(NB_ERR_INVALID, thunk.error);
         }
         check(rc);
@@ -854,120 +912,36 @@ class OfflineHeadless {
         nb_add_params c = ap.c;
         if (c.kind != T::kKind) c = nb_add_params{T::kKind, 0.f};
         int rc = let_migrate_every >= 0
-                     ? nb_runner_create_multi_let(&r_, &sp, &c, &detail::InitThunk::call, &thunk, device_ids.data(),
+                     ? nb_runner_create_multi_let(&h_, &sp, &c, &detail::InitThunk::call, &thunk, device_ids.data(),
                                                   (int)device_ids.size(), let_migrate_every)
-                     : nb_runner_create_multi(&r_, &sp, &c, &detail::InitThunk::call, &thunk, device_ids.data(),
+                     : nb_runner_create_multi(&h_, &sp, &c, &detail::InitThunk::call, &thunk, device_ids.data(),
                                               (int)device_ids.size());
         if (!thunk.error.empty()) {
-            if (rc == NB_OK) nb_runner_destroy(r_);
+            if (rc == NB_OK) nb_runner_destroy(h_);
             throw Error(NB_ERR_INVALID, thunk.error);
         }
         check(rc);
     }
     OfflineHeadless(const OfflineHeadless &) = delete;
     ~OfflineHeadless() {
-        if (r_) nb_runner_destroy(r_);
+        if (h_) nb_runner_destroy(h_);
     }
-    void step() { check(nb_runner_step(r_)); }  // encode -> submit -> cleanup -> poll(Wait)
-    void step_n(int n) { check(nb_runner_step_n(r_, n)); }
-    T sim() { return T(nb_runner_sim(r_)); }  // borrowed view of the runner's simulator (one device)
+    void step() { check(nb_runner_step(h_)); }  // encode -> submit -> cleanup -> poll(Wait)
+    void step_n(int n) { check(nb_runner_step_n(h_, n)); }
+    T sim() { return T(nb_runner_sim(h_)); }  // borrowed view of the runner's simulator (one device)
     uint64_t step_num() const {
         uint64_t v = 0;
-        check(nb_runner_step_num(r_, &v));
+        check(nb_runner_step_num(h_, &v));
         return v;
-    }
-    Diagnostics diagnostics(bool potential = false) {  // one device only
-        Diagnostics d{};
-        check(nb_runner_diagnostics(r_, NB_DIAG_MOMENTS | (potential ? NB_DIAG_POTENTIAL : 0u), &d));
-        return d;
-    }
-    RadialProfile radial_profile(const std::vector<double> &edges,  // one device only
-                                 const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
-        return detail::radial_profile(nb_runner_radial_profile, r_, edges, p);
-    }
-    ProjectedMap projected_map(const MapParams &p) {  // one device only
-        return detail::projected_map(nb_runner_map, r_, p);
-    }
-    FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::fof_groups(nb_runner_fof, r_, sp.particle_num, link, min_members, labels);
-    }
-    BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
-                             uint32_t max_group = 262144, bool per_body = true) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::bound_groups(nb_runner_bound, r_, sp.particle_num, link, min_members,
-                                    min_bound ? min_bound : min_members, max_iter, max_group, per_body);
-    }
-    HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
-                         bool boundaries = true) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::hop_groups(nb_runner_hop, r_, sp.particle_num, p, labels, density, boundaries);
-    }
-    GroupShapes group_shapes(const std::vector<uint32_t> &group_of, size_t m, const ShapeOptions &o = ShapeOptions{},
-                             const std::vector<double> &centers = {}, const std::vector<double> &velocities = {},
-                             const std::vector<double> &radius = {}) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::group_shapes(nb_runner_group_shapes, r_, sp.particle_num, group_of, m, o, centers, velocities,
-                                    radius);
-    }
-    GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::fof_shapes(nb_runner_group_shapes, r_, sp.particle_num, f, k_rms, o);
-    }
-    KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::knn_density(nb_runner_knn, r_, sp.particle_num, k, density, neighbours);
-    }
-    HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
-                               const std::vector<double> &velocities = {}) {  // one device only
-        return detail::halo_profiles(nb_runner_halo_profiles, r_, edges, &centers, nullptr, velocities);
-    }
-    HaloProfiles halo_profiles_of_bodies(const std::vector<double> &edges, const std::vector<uint32_t> &bodies,
-                                         const std::vector<double> &velocities = {}) {  // one device only
-        return detail::halo_profiles(nb_runner_halo_profiles, r_, edges, nullptr, &bodies, velocities);
-    }
-    SmoothedMap smoothed_map(const SmoothParams &p, std::vector<double> s) {  // one device only
-        SimParams sp{};
-        check(nb_runner_sim_params(r_, &sp));
-        return detail::smoothed_map(nb_runner_smooth_map, r_, sp.particle_num, p, std::move(s));
-    }
-    SmoothedMap smoothed_map_knn(const SmoothParams &p, uint32_t k = 32, double scale = 1.0) {  // one device only
-        return smoothed_map(p, detail::knn_lengths(knn_density(k, false, true), scale));
-    }
-    Field field(const std::vector<float> &points,  // one device only
-                uint32_t flags = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL) {
-        return detail::field(nb_runner_field, r_, points, flags);
-    }
-    RingMeans circular_velocity(const std::vector<double> &radii, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
-                                const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
-                                bool potential = false) {  // one device only
-        return detail::circular_velocity(nb_runner_field, r_, radii, axis, center, n_phi, potential);
-    }
-    Frame render(const RenderParams &p, bool counts = false) {  // one device only
-        Frame f;
-        f.width = p.width;
-        f.height = p.height;
-        f.rgba.resize((size_t)p.width * p.height * 4);
-        if (counts) f.counts.resize((size_t)p.width * p.height);
-        check(nb_runner_render(r_, &p, f.rgba.data(), counts ? f.counts.data() : nullptr, &f.stats));
-        return f;
     }
     std::vector<Particle> read_particles() {
         SimParams p{};
-        check(nb_runner_sim_params(r_, &p));
+        check(nb_runner_sim_params(h_, &p));
         std::vector<Particle> out(p.particle_num);
-        check(nb_runner_read_particles(r_, out.data(), out.size()));
+        check(nb_runner_read_particles(h_, out.data(), out.size()));
         return out;
     }
 
-   private:
-    nb_runner *r_ = nullptr;
 };
 
 }  // namespace nbody
