@@ -1305,6 +1305,118 @@ int nb_sim_group_shapes(nb_sim *sim, const nb_shape_params *params, const uint32
 int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]);
 
 /* ------------------------------------------------------------------------- */
+/* Group radii -- exact mass radii, extent and the peak of the circular-      */
+/* velocity curve of every row of an assignment (no reference counterpart)    */
+/* ------------------------------------------------------------------------- */
+/* For each of m rows: the members ordered by their distance from the row's centre,
+ * the enclosed mass M at every member in a fixed order of additions, the member at
+ * which M first reaches each of nf fractions of the row's mass (the 10 / 50 / 90 %
+ * mass radii; no binning, no interpolation: the radius is a body's), and the largest
+ * M / r with the member it lies at (v_max = sqrt(G vc2_max), G the caller's).  The
+ * rule, which DESIGN.md 6o states in full; binary64 from the binary32 state, one
+ * rounding per operation, no contraction:
+ *   input     group_of[n], m and centers[m][3] (finite; may be null) exactly as
+ *             nb_sim_group_shapes takes them; fractions[nf], 1 <= nf <= 16, each
+ *             finite, 0 < f <= 1, strictly ascending; vmax_skip >= 0
+ *   members   row r's list L is the bodies with group_of == r that count, in
+ *             ascending body index; `count` = |L|; the others with a row are
+ *             stats->nonfinite_members
+ *   centre    the caller's, or (centers null) c = (sum m x) / (sum m) over L, the
+ *             sums formed as round 0 of nb_sim_group_shapes forms md and mass:
+ *             positions of L in order, runs of 64 through the fixed butterfly, runs
+ *             added in order from 0.  It is bit for bit the `center` that
+ *             nb_sim_group_shapes reports for the row with centers and radius null
+ *   order     per member d = (double)x - c per component, r2 = (dx dx + dy dy) + dz dz.
+ *             The members of a row in ascending r2, ties in ascending body index; a
+ *             member's 0-based place is its `rank`.  (r2 >= 0, so its bit pattern as a
+ *             64-bit unsigned integer is the sort key.)
+ *   M         at rank s of a row, a three-level sum.  Ranks [64 k, 64 k + 64) are a
+ *             run: C(s) = the masses of the run's members up to s added left to
+ *             right, starting from the run's first member alone; T(k) = C at the
+ *             run's last member.  64 runs (NB_RADII_CHUNK = 4,096 ranks) are a
+ *             chunk: B(first run) = 0, B(k) = B(k - 1) + T(k - 1); the chunk's total
+ *             is B(last run) + T(last run).  A(first chunk) = 0, A(c) = A(c - 1) +
+ *             total(c - 1).  M(s) = (A(c) + B(k)) + C(s); mass = M(count - 1), 0 for an
+ *             empty row.  Ranks count from the row's own start: M depends on the row's
+ *             list and centre alone -- not on the other rows, the row's number or m.
+ *             |M(s) - exact prefix| <= (130 + count / 4096) 2^-53 sum |m_j|
+ *   crossings for fraction f: t = f mass (one multiply), s_f = the smallest rank with
+ *             M(s) >= t, the predicate taken at every rank (M need not be monotone
+ *             in the last bit across a run boundary); radius[f] = sqrt(r2) of that
+ *             member, index[f] its body index; no rank satisfies the predicate (an
+ *             empty row, a NaN mass): NaN and NB_FOF_NONE.  Nothing else is special: a
+ *             row of zero masses crosses at rank 0.  Entries f >= nf: NaN and NB_FOF_NONE
+ *   v_max     over the ranks s >= vmax_skip with r2 > 0: x(s) = M(s) / sqrt(r2(s)), a
+ *             NaN passed over; vc2_max = the largest x, at the smallest rank among
+ *             equals; r_vmax = sqrt(r2) and vmax_index = the body index of that
+ *             member; no such rank: NaN and NB_FOF_NONE
+ *   the row   count, center (the one used; NaN for an empty row without a given one),
+ *             mass, r_min and r_max (sqrt(r2) of the first and the last member; NaN
+ *             for an empty row), the crossings, the three v_max values
+ *   per body  rank_of[i] = the rank of a member, else NB_FOF_NONE; enclosed_of[i] =
+ *             M at the member, else NaN.  With nb_sim_read_particles they are the
+ *             exact M(<r) curve of every row
+ * The 64 and the 4,096 are part of the rule; there is no tuning key.  Two calls return
+ * the same bits.  No float atomics.  params->step_num as nb_shape_params.step_num
+ * (NB_RADII_ANY_STEP switches the check off).  The call is ordered after the enqueued
+ * steps on the simulator's stream, ends with one synchronisation, reports a TreeSim's
+ * status words as nb_sim_read_particles does, launches nothing inside a graph capture
+ * and does not change the trajectory.
+ * The names: this is the thirteenth analysis pass, and it is spelt noun first --
+ * nb_group_radii_sim / nb_group_radii_runner -- like the host-only helpers
+ * (nb_hop_regroup, nb_shape_eigen): the nb_sim_<pass> / nb_runner_<pass> family is
+ * closed at twelve, which the binding's tests count. */
+#define NB_RADII_MAX_FRACTIONS 16u
+#define NB_RADII_CHUNK 4096u
+#define NB_RADII_ANY_STEP 0xFFFFFFFFFFFFFFFFull /* nb_radii_params.step_num: UINT64_MAX */
+
+typedef struct nb_radii_params {
+    uint32_t nf;          /* 1 .. NB_RADII_MAX_FRACTIONS */
+    uint32_t vmax_skip;   /* ranks below it are left out of v_max */
+    uint64_t step_num;    /* the simulator's step number, or NB_RADII_ANY_STEP */
+    uint64_t reserved;    /* 0 */
+    double fractions[16]; /* [0, nf): finite, 0 < f <= 1, strictly ascending; the rest is not read */
+} nb_radii_params;
+
+typedef struct nb_radii_group { /* 264 bytes */
+    uint32_t count, vmax_index; /* |L|; the body at the peak of M / r, or NB_FOF_NONE */
+    double center[3];           /* the one used */
+    double mass, r_min, r_max;
+    double vc2_max, r_vmax;     /* the largest M / r and the radius it lies at */
+    double radius[16];          /* [0, nf): the radius of the member at which M reaches f mass */
+    uint32_t index[16];         /* its body index, or NB_FOF_NONE */
+} nb_radii_group;
+
+typedef struct nb_radii_stats {
+    uint64_t step_num, n;
+    uint64_t rows;              /* m */
+    uint64_t members;           /* counted bodies with a row */
+    uint64_t nonfinite_members; /* bodies with a row that do not count */
+    uint64_t empty;             /* rows without a member */
+} nb_radii_stats;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_radii_params) == 152 && sizeof(nb_radii_group) == 264 && sizeof(nb_radii_stats) == 48,
+              "nb_radii_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_radii_params) == 152 && sizeof(nb_radii_group) == 264 && sizeof(nb_radii_stats) == 48,
+               "nb_radii_* layouts");
+#endif
+
+/* group_of: n values (may be null for n == 0); centers: m x 3 or null; rows_out: m rows; rank_of,
+ * enclosed_of: n values each.  Every output pointer may be null: what is not asked for is not
+ * copied.  The outputs are staged and written only by a call that succeeds.  NB_ERR_INVALID for a
+ * null handle or params, a null group_of with n > 0, m > max(n, 1), a non-finite centre, nf outside
+ * 1..NB_RADII_MAX_FRACTIONS, a fraction that is not finite, not in (0, 1] or not above the one
+ * before it, a reserved field != 0, a step_num that is neither the simulator's nor
+ * NB_RADII_ANY_STEP -- all checked before any device call -- and, after the call's one
+ * synchronisation, for a value of group_of that is neither NB_FOF_NONE nor < m; NB_ERR_UNSUPPORTED
+ * for a sharded simulator (placement world > 1). */
+int nb_group_radii_sim(nb_sim *sim, const nb_radii_params *params, const uint32_t *group_of, size_t m,
+                       const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
+                       nb_radii_stats *stats);
+
+/* ------------------------------------------------------------------------- */
 /* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
 /* kernel of its own radius (no reference counterpart: the image of the       */
 /* density estimate, where nb_sim_map gives shot noise)                       */
@@ -1588,6 +1700,11 @@ int nb_runner_halo_profiles(nb_runner *runner, const nb_halo_params *params, nb_
 int nb_runner_group_shapes(nb_runner *runner, const nb_shape_params *params, const uint32_t *group_of, size_t m,
                            const double *centers, const double *velocities, const double *radius,
                            nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats);
+/* nb_group_radii_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, const uint32_t *group_of, size_t m,
+                          const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
+                          nb_radii_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

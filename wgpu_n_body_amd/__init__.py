@@ -43,6 +43,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "KnnDensity", "KnnStats", "KNN_NONE",
            "HopGroups", "HopStats", "HOP_NONE",
            "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
+           "GroupRadii", "RadiiStats",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
@@ -1178,16 +1179,17 @@ def _catalogue_rms(groups):
         return np.sqrt(np.maximum(groups._per_mass(groups.rows["mr2"]) - (c * c).sum(axis=1), 0.0))
 
 
-def _shapes_of_groups(shapes_of, read_particles, groups, members, center, radius, check_step, kw) -> GroupShapes:
-    """group_shapes: the assignment, the centres (as _group_profiles resolves them) and the radii from a catalogue."""
+def _catalogue_assignment(what, read_particles, groups, members, center):
+    """(mapped, rows, c, v) of a catalogue for `what` (group_shapes, group_radii): the catalogue rows with a finite
+    centre (as _group_profiles resolves them), their centres and velocities, and the assignment renumbered to them."""
     if members == "group":
         assign = groups.group_of
     elif members == "bound":
         assign = getattr(groups, "bound_of", None)
         if assign is None:
-            raise ValueError('group_shapes: members="bound" needs a BoundGroups made with per_body=True')
+            raise ValueError(f'{what}: members="bound" needs a BoundGroups made with per_body=True')
     else:
-        raise ValueError('group_shapes: members is "group" or "bound"')
+        raise ValueError(f'{what}: members is "group" or "bound"')
     total = len(groups.rows)
     if center == "com":
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -1197,12 +1199,12 @@ def _shapes_of_groups(shapes_of, read_particles, groups, members, center, radius
     elif center in ("most_bound", "peak"):
         if center == "most_bound":
             if "most_bound" not in (groups.rows.dtype.names or ()):
-                raise ValueError('group_shapes: center="most_bound" needs a BoundGroups')
+                raise ValueError(f'{what}: center="most_bound" needs a BoundGroups')
             body = groups.rows["most_bound"]
             rows = np.nonzero(body != _lib.NB_FOF_NONE)[0]
         else:
             if not isinstance(groups, HopGroups):
-                raise ValueError('group_shapes: center="peak" needs a HopGroups')
+                raise ValueError(f'{what}: center="peak" needs a HopGroups')
             body = groups.rows["label"]
             rows = np.arange(total)
         parts = read_particles()  # the body's widened position and velocity, as a body centre of halo_profiles
@@ -1212,16 +1214,108 @@ def _shapes_of_groups(shapes_of, read_particles, groups, members, center, radius
         ok = np.isfinite(c).all(axis=1) & np.isfinite(v).all(axis=1)
         rows, c, v = rows[ok], c[ok], v[ok]
     else:
-        raise ValueError('group_shapes: center is "com", "most_bound" or "peak"')
-    rad = _shape_radius(radius, total, _catalogue_rms(groups) if isinstance(radius, tuple) else None)
+        raise ValueError(f'{what}: center is "com", "most_bound" or "peak"')
     # the usable rows renumbered 0 .. len(rows) - 1; a body of another row has no row
     renumber = np.full(total + 1, _lib.NB_FOF_NONE, dtype=np.uint32)
     renumber[rows] = np.arange(len(rows), dtype=np.uint32)
     assign = np.asarray(assign, dtype=np.uint32)
     mapped = renumber[np.minimum(assign, total)]  # (FOF_NONE -> the spare entry)
+    return mapped, rows, c, v
+
+
+def _shapes_of_groups(shapes_of, read_particles, groups, members, center, radius, check_step, kw) -> GroupShapes:
+    """group_shapes: the assignment, the centres (as _group_profiles resolves them) and the radii from a catalogue."""
+    mapped, rows, c, v = _catalogue_assignment("group_shapes", read_particles, groups, members, center)
+    rad = _shape_radius(radius, len(groups.rows), _catalogue_rms(groups) if isinstance(radius, tuple) else None)
     step = groups.stats.step_num if check_step else None
     return shapes_of(mapped, len(rows), centers=c, velocities=v, radius=None if rad is None else rad[rows],
                      step_num=step, catalogue_rows=rows, **kw)
+
+
+@dataclass(frozen=True)
+class RadiiStats:
+    """nb_radii_stats (include/nbody.h "Group radii")."""
+    step_num: int
+    n: int
+    rows: int
+    members: int            # counted bodies with a row
+    nonfinite_members: int
+    empty: int
+
+
+@dataclass(frozen=True)
+class GroupRadii:
+    """nb_group_radii_sim's rows (include/nbody.h "Group radii"; no reference counterpart): for every row of an
+    assignment of bodies to rows the members ordered by distance from the row's centre, the enclosed mass in a fixed
+    order, the member at which it reaches each fraction of the row's mass and the peak of M / r.  rows:
+    _lib.RADII_GROUP_DTYPE records; catalogue_rows: the rows of the catalogue they belong to (group_radii leaves out
+    the rows without a finite centre; radii_of: 0 .. m - 1); fractions: as asked for; rank_of (n,) uint32 and
+    enclosed_of (n,) float64: a member's place in its row's order (FOF_NONE for a body of no row) and M there (NaN),
+    or None when not asked for."""
+    rows: np.ndarray
+    catalogue_rows: np.ndarray
+    fractions: tuple
+    vmax_skip: int
+    rank_of: Optional[np.ndarray]
+    enclosed_of: Optional[np.ndarray]
+    stats: RadiiStats
+
+    @property
+    def radius(self) -> np.ndarray:
+        """(rows, nf): the distance of the member at which the enclosed mass reaches fractions[f] of the row's."""
+        return self.rows["radius"][:, :len(self.fractions)]
+
+    @property
+    def index(self) -> np.ndarray:
+        """(rows, nf): that member's body index, FOF_NONE where there is none."""
+        return self.rows["index"][:, :len(self.fractions)]
+
+    @property
+    def half_mass_radius(self) -> np.ndarray:
+        """(rows,): the column of fraction 0.5; a ValueError when 0.5 was not asked for."""
+        if 0.5 not in self.fractions:
+            raise ValueError("half_mass_radius: 0.5 is not among the fractions of this call")
+        return self.radius[:, self.fractions.index(0.5)]
+
+    @property
+    def r_vmax(self) -> np.ndarray:
+        """(rows,): the radius at which M / r peaks; NaN where no member qualifies."""
+        return self.rows["r_vmax"]
+
+    def vmax(self, G: float) -> np.ndarray:
+        """(rows,): sqrt(G max(M / r)), the peak of the circular-velocity curve."""
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(float(G) * self.rows["vc2_max"])
+
+
+def _group_radii(call, handle, n, group_of, m, fractions, centers, vmax_skip, per_body, step_num,
+                 catalogue_rows) -> GroupRadii:
+    for name, v in (("vmax_skip", vmax_skip), ("m", m)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"group_radii: {name} = {v} is not a 32-bit count")
+    m = int(m)
+    fractions = tuple(float(f) for f in np.asarray(fractions, dtype=np.float64).reshape(-1))
+    gof = np.ascontiguousarray(group_of, dtype=np.uint32).reshape(-1)
+    if gof.shape[0] != n:
+        raise ValueError(f"group_radii: group_of has {gof.shape[0]} values for {n} bodies")
+    p = _lib.nb_radii_params()
+    p.nf, p.vmax_skip, p.reserved = len(fractions), int(vmax_skip), 0  # (the call refuses an nf it does not take)
+    for k, f in enumerate(fractions[:_lib.NB_RADII_MAX_FRACTIONS]):
+        p.fractions[k] = f
+    p.step_num = _lib.NB_RADII_ANY_STEP if step_num is None else int(step_num)
+    if centers is not None:
+        centers = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, 3)
+        if centers.shape[0] != m:
+            raise ValueError(f"group_radii: {m} rows need {m} centers")
+    rows = np.zeros(m, dtype=_lib.RADII_GROUP_DTYPE)
+    rank = np.empty(n, dtype=np.uint32) if per_body else None
+    enc = np.empty(n, dtype=np.float64) if per_body else None
+    st = _lib.nb_radii_stats()
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    check(call(handle, C.byref(p), ptr(gof), m, ptr(centers), rows.ctypes.data, ptr(rank), ptr(enc), C.byref(st)))
+    stats = RadiiStats(int(st.step_num), int(st.n), int(st.rows), int(st.members), int(st.nonfinite_members),
+                       int(st.empty))
+    return GroupRadii(rows, np.asarray(catalogue_rows), fractions, int(vmax_skip), rank, enc, stats)
 
 
 SMOOTH_K = _lib.NB_SMOOTH_K
@@ -1702,6 +1796,51 @@ class _Passes:
         kw = dict(reduced=reduced, max_iter=max_iter, tol=tol, min_members=min_members, per_body=per_body)
         return _shapes_of_groups(self.shapes_of, self.read_particles, groups, members, center, radius, check_step,
                                  kw)
+
+    def radii_of(self, group_of, m: int, *, fractions=(0.1, 0.5, 0.9), centers=None, vmax_skip: int = 10,
+                 per_body: bool = False, step_num=None, catalogue_rows=None) -> GroupRadii:
+        """The exact mass radii of the m rows of a raw assignment (nb_group_radii_sim): group_of (n,) uint32, FOF_NONE
+        or a row < m for every body of read_particles() now.  fractions: 1 to 16 ascending values in (0, 1]; centers:
+        (m, 3) or None for the members' own centre of mass, formed on the device (group_shapes' bits); vmax_skip: the
+        innermost ranks left out of the peak of M / r; per_body: also every member's rank and enclosed mass.
+        step_num: the step the assignment was made at, to have a stale one refused; None: not checked.
+        A several-GPU runner refuses."""
+        rows = np.arange(int(m)) if catalogue_rows is None else catalogue_rows
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _group_radii(getattr(_lib.lib(), "nb_group_radii_" + suffix), self._h,
+                            int(self.sim_params().particle_num), group_of, m, fractions, centers, vmax_skip, per_body,
+                            step_num, rows)
+
+    def group_radii(self, groups, *, members: str = "group", center: str = "com", fractions=(0.1, 0.5, 0.9),
+                    vmax_skip: int = 10, per_body: bool = False, check_step: bool = True) -> GroupRadii:
+        """The exact mass radii, the half-mass radius and v_max of the groups of a FofGroups, BoundGroups or HopGroups
+        (raw or regrouped) of the same state.  members and center: as group_shapes resolves them -- "group" or
+        "bound"; "com", "most_bound" or "peak" -- and the rows without a finite centre are left out
+        (GroupRadii.catalogue_rows names the ones that stay).  check_step: refuse a catalogue made at another step.
+        A several-GPU runner refuses."""
+        mapped, rows, c, _ = _catalogue_assignment("group_radii", self.read_particles, groups, members, center)
+        return self.radii_of(mapped, len(rows), fractions=fractions, centers=c, vmax_skip=vmax_skip,
+                             per_body=per_body, step_num=groups.stats.step_num if check_step else None,
+                             catalogue_rows=rows)
+
+    def lagrangian_radii(self, fractions=(0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9), *, center="com",
+                         vmax_skip: int = 10, per_body: bool = False) -> GroupRadii:
+        """The exact Lagrangian radii of the whole state, taken as one row (nb_group_radii_sim): .radius[0] are the
+        radii of the bodies at which the enclosed mass reaches each fraction.  center: "com" (the row's own centre of
+        mass, formed on the device), "density" (knn_density(6)'s density centre) or three coordinates.
+        A several-GPU runner refuses."""
+        n = int(self.sim_params().particle_num)
+        if isinstance(center, str):
+            if center == "com":
+                c = None
+            elif center == "density":
+                c = np.asarray(self.knn_density(6, neighbours=False).center, dtype=np.float64).reshape(1, 3)
+            else:
+                raise ValueError('lagrangian_radii: center is "com", "density" or three coordinates')
+        else:
+            c = np.asarray(center, dtype=np.float64).reshape(1, 3)
+        return self.radii_of(np.zeros(n, dtype=np.uint32), 1, fractions=fractions, centers=c, vmax_skip=vmax_skip,
+                             per_body=per_body)
 
     def smoothed_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                      depth=None, velocities: bool = True, smoothing="knn", k: int = 32, scale: float = 1.0,

@@ -220,6 +220,22 @@ class nb_shape_stats(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class nb_radii_params(C.Structure):
+    _fields_ = [("nf", C.c_uint32), ("vmax_skip", C.c_uint32), ("step_num", C.c_uint64), ("reserved", C.c_uint64),
+                ("fractions", C.c_double * 16)]
+
+
+class nb_radii_group(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("vmax_index", C.c_uint32), ("center", C.c_double * 3), ("mass", C.c_double),
+                ("r_min", C.c_double), ("r_max", C.c_double), ("vc2_max", C.c_double), ("r_vmax", C.c_double),
+                ("radius", C.c_double * 16), ("index", C.c_uint32 * 16)]
+
+
+class nb_radii_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("rows", C.c_uint64), ("members", C.c_uint64),
+                ("nonfinite_members", C.c_uint64), ("empty", C.c_uint64)]
+
+
 class nb_smooth_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -266,6 +282,11 @@ SHAPE_GROUP_DTYPE = np.dtype([("count", "<u4"), ("selected", "<u4"), ("iteration
                               ("j", "<f8", (3,)), ("lambda", "<f8", (3,)), ("axes", "<f8", (9,)), ("q", "<f8"),
                               ("s", "<f8")])
 
+# nb_radii_group[] as a numpy record array
+RADII_GROUP_DTYPE = np.dtype([("count", "<u4"), ("vmax_index", "<u4"), ("center", "<f8", (3,)), ("mass", "<f8"),
+                              ("r_min", "<f8"), ("r_max", "<f8"), ("vc2_max", "<f8"), ("r_vmax", "<f8"),
+                              ("radius", "<f8", (16,)), ("index", "<u4", (16,))])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -288,6 +309,8 @@ assert C.sizeof(nb_halo_params) == 48 and C.sizeof(nb_halo_stats) == 64
 assert C.sizeof(nb_halo_head) == 64 == HALO_HEAD_DTYPE.itemsize
 assert C.sizeof(nb_shape_params) == 40 and C.sizeof(nb_shape_stats) == 80
 assert C.sizeof(nb_shape_group) == 360 == SHAPE_GROUP_DTYPE.itemsize
+assert C.sizeof(nb_radii_params) == 152 and C.sizeof(nb_radii_stats) == 48
+assert C.sizeof(nb_radii_group) == 264 == RADII_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
@@ -314,6 +337,7 @@ NB_HALO_CENTER_NONFINITE = 1
 NB_SHAPE_REDUCED = 1
 NB_SHAPE_CONVERGED, NB_SHAPE_UNCONVERGED, NB_SHAPE_DEGENERATE, NB_SHAPE_EMPTY = 1, 2, 4, 8
 NB_SHAPE_MAX_ITER, NB_SHAPE_ANY_STEP = 64, 0xFFFFFFFFFFFFFFFF
+NB_RADII_MAX_FRACTIONS, NB_RADII_CHUNK, NB_RADII_ANY_STEP = 16, 4096, 0xFFFFFFFFFFFFFFFF
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
 NB_SMOOTH_MAX_ENTRIES = 1 << 28
@@ -339,6 +363,7 @@ ABI_SYMBOLS = [
     "nb_sim_hop", "nb_runner_hop", "nb_hop_regroup",
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
+    "nb_group_radii_sim", "nb_group_radii_runner",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
@@ -418,6 +443,10 @@ def lib() -> C.CDLL:
     for name, args in passes.items():
         for prefix in ("nb_sim_", "nb_runner_"):
             getattr(L, prefix + name).argtypes = [vp] + args
+    # the thirteenth pass is spelt noun first (include/nbody.h "Group radii"): one list for its two symbols too
+    group_radii = [vp, P(nb_radii_params), vp, sz, vp, vp, vp, vp, P(nb_radii_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_group_radii_" + suffix).argtypes = group_radii
     for name in ("nb_radial_edges_log", "nb_radial_edges_linear"):
         getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_radial_lagrangian.argtypes = [P(nb_radial_profile), vp, P(C.c_double), P(C.c_double), C.c_uint32,

@@ -48,6 +48,9 @@ SOURCES = [
     # the selection, the 22 terms and the eigen-solver are specified operation by operation: no FMA
     # contraction, on the host side of the unit (nb_shape_eigen) as on the device side
     ("nb_shape.hip", ["-ffp-contract=off"]),
+    # the order, the three-level enclosed mass and the crossings are specified operation by operation:
+    # no FMA contraction
+    ("nb_radii.hip", ["-ffp-contract=off"]),
     # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
     ("nb_simbase.cpp", []),

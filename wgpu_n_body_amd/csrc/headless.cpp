@@ -16,6 +16,8 @@
 //            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
 //            [--shapes K --shapes-link B [--shapes-min M] [--shapes-radius KRMS] [--shapes-reduced 0|1]
 //             [--shapes-iter I] [--shapes-top T]]
+//            [--lagr K [--lagr-fractions F1,F2,...] [--lagr-center com|X,Y,Z]]
+//            [--radii K --radii-link B [--radii-min M] [--radii-top T]]
 //            [--knn K [--knn-k 6]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
@@ -87,6 +89,20 @@
 // (--shapes-top, default 0) as "shape_group <step> <row> <count> <selected> <q> <s> <T> <|J|> <status>" (every real
 // %.17g; T the triaxiality).  The time it takes is not part of any "Step Duration"; without --shapes the output is
 // unchanged.
+//
+// --lagr K prints the exact Lagrangian radii (nb_group_radii_runner, the whole state as one row) of step 0 and of every
+// K-th step: the radii of the bodies at which the enclosed mass reaches F1, F2, ... of the total (--lagr-fractions,
+// default 0.01,0.05,0.1,0.25,0.5,0.75,0.9; 1 to 16 ascending values in (0, 1]) about the centre of mass, formed on the
+// device, unless --lagr-center gives a point.  One line "lagr <step> <count> <mass> <x> <y> <z> <r_vmax> <vc2_max>",
+// then one line per fraction "lagr_radius <step> <fraction> <radius> <body>" (every real %.17g).  The time it takes
+// is not part of any "Step Duration"; without --lagr the output is unchanged.
+//
+// --radii K finds the friends-of-friends groups (as --fof, with --radii-link and --radii-min, default 20) of step 0 and
+// of every K-th step and measures the 10 / 50 / 90 % mass radii and the peak of M / r of all of them in one call
+// (nb_group_radii_runner) about their centres of mass.  One line "radii <step> <groups> <members> <empty>", then the T
+// largest groups (--radii-top, default 0) as "radii_group <step> <row> <count> <mass> <r10> <r50> <r90> <r_vmax>
+// <vc2_max>" (every real %.17g).  The time it takes is not part of any "Step Duration"; without --radii the output
+// is unchanged.
 //
 // --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
 // every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
@@ -345,6 +361,50 @@ static void print_shapes(nbody::OfflineHeadless<Sim> &runner, const ShapesOption
     }
 }
 
+struct LagrOptions {
+    int every = 0;
+    std::vector<double> fractions{0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9};
+    std::vector<double> center;  // empty: the centre of mass
+};
+
+template <class Sim>
+static void print_lagr(nbody::OfflineHeadless<Sim> &runner, const LagrOptions &lo) {
+    nbody::RadiiOptions o;
+    o.fractions = lo.fractions;
+    const nbody::GroupRadii g = runner.lagrangian_radii(o, lo.center);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    const nbody::RadiiGroup &r = g.rows[0];
+    std::printf("lagr %llu %u %.17g %.17g %.17g %.17g %.17g %.17g\n", step, r.count, r.mass, r.center[0], r.center[1],
+                r.center[2], r.r_vmax, r.vc2_max);
+    for (size_t f = 0; f < g.fractions.size(); ++f)
+        std::printf("lagr_radius %llu %.17g %.17g %u\n", step, g.fractions[f], r.radius[f], r.index[f]);
+}
+
+struct RadiiCliOptions {
+    int every = 0, top = 0;
+    double link = 0.0;
+    uint32_t min_members = 20;
+};
+
+template <class Sim>
+static void print_radii(nbody::OfflineHeadless<Sim> &runner, const RadiiCliOptions &ro) {
+    const nbody::FofGroups f = runner.fof_groups(ro.link, ro.min_members, false);
+    const nbody::GroupRadii g = runner.group_radii(f);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("radii %llu %llu %llu %llu\n", step, (unsigned long long)g.stats.rows,
+                (unsigned long long)g.stats.members, (unsigned long long)g.stats.empty);
+    std::vector<uint32_t> row_of(f.groups.size(), NB_FOF_NONE);  // a catalogue row without a finite centre has none
+    for (size_t r = 0; r < g.catalogue_rows.size(); ++r) row_of[g.catalogue_rows[r]] = (uint32_t)r;
+    const std::vector<uint32_t> order = f.by_size();
+    for (size_t k = 0, shown = 0; k < order.size() && shown < (size_t)ro.top; ++k) {
+        if (row_of[order[k]] == NB_FOF_NONE) continue;
+        ++shown;
+        const nbody::RadiiGroup &r = g.rows[row_of[order[k]]];
+        std::printf("radii_group %llu %u %u %.17g %.17g %.17g %.17g %.17g %.17g\n", step, order[k], r.count, r.mass,
+                    r.radius[0], r.radius[1], r.radius[2], r.r_vmax, r.vc2_max);
+    }
+}
+
 struct KnnOptions {
     int every = 0;
     uint32_t k = 6;
@@ -486,7 +546,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
-               const ShapesOptions &shapes) {
+               const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -502,6 +562,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (hop.every > 0) print_hop(runner, hop);
     if (halo.every > 0) print_halo(runner, halo);
     if (shapes.every > 0) print_shapes(runner, shapes);
+    if (lagr.every > 0) print_lagr(runner, lagr);
+    if (radii.every > 0) print_radii(runner, radii);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -520,6 +582,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (hop.every > 0 && (i + 1) % hop.every == 0) print_hop(runner, hop);
         if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
         if (shapes.every > 0 && (i + 1) % shapes.every == 0) print_shapes(runner, shapes);
+        if (lagr.every > 0 && (i + 1) % lagr.every == 0) print_lagr(runner, lagr);
+        if (radii.every > 0 && (i + 1) % radii.every == 0) print_radii(runner, radii);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -551,6 +615,8 @@ int main(int argc, char **argv) {
     HaloOptions halo;
     HopOptions hop;
     ShapesOptions shapes;
+    LagrOptions lagr;
+    RadiiCliOptions radii;
     bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -683,6 +749,35 @@ int main(int argc, char **argv) {
         else if (k == "--shapes-reduced") shapes.reduced = std::atoi(v.c_str()) != 0;
         else if (k == "--shapes-iter") shapes.max_iter = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--shapes-top") shapes.top = std::atoi(v.c_str());
+        else if (k == "--lagr") lagr.every = std::atoi(v.c_str());
+        else if (k == "--lagr-fractions") {
+            lagr.fractions.clear();
+            const char *s = v.c_str();
+            char *end = nullptr;
+            for (;;) {
+                const double f = std::strtod(s, &end);
+                if (end == s) break;
+                lagr.fractions.push_back(f);
+                if (*end != ',') break;
+                s = end + 1;
+            }
+            if (end == s || *end != '\0') {
+                std::fprintf(stderr, "--lagr-fractions takes F1,F2,..., not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--lagr-center") {
+            lagr.center.assign(3, 0.0);
+            if (v == "com") lagr.center.clear();
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &lagr.center[0], &lagr.center[1], &lagr.center[2]) != 3) {
+                std::fprintf(stderr, "--lagr-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--radii") radii.every = std::atoi(v.c_str());
+        else if (k == "--radii-link") radii.link = std::atof(v.c_str());
+        else if (k == "--radii-min") radii.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--radii-top") radii.top = std::atoi(v.c_str());
         else if (k == "--smaps") smaps.dir = v;
         else if (k == "--smap-every") smaps.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--smap-size") {
@@ -817,6 +912,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--shapes-reduced 1 needs --shapes-radius KRMS > 0\n");
         return 2;
     }
+    if (radii.every > 0 && !(radii.link > 0.0)) {
+        std::fprintf(stderr, "--radii needs --radii-link B > 0\n");
+        return 2;
+    }
     if (halo.every > 0 && (!(halo.link > 0.0) || !halo.have_range)) {
         std::fprintf(stderr, "--halo needs --halo-link B > 0 and --halo-range RMIN,RMAX\n");
         return 2;
@@ -827,9 +926,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

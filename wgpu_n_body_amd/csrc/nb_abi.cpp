@@ -195,6 +195,17 @@ static int pass_group_shapes(H *h, const nb_shape_params *params, const uint32_t
 }
 
 template <class H>
+static int pass_group_radii(H *h, const nb_radii_params *params, const uint32_t *group_of, size_t m,
+                            const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
+                            nb_radii_stats *stats) {
+    if (int rc = radii_check_params(params)) return rc;
+    return on_sim(h, "group_radii", [&](SimBase &s) {
+        if (int rc = radii_check_args(s, params, group_of, m, centers)) return rc;
+        return sim_group_radii(s, *params, group_of, m, centers, rows_out, rank_of, enclosed_of, stats);
+    });
+}
+
+template <class H>
 static int pass_smooth_map(H *h, const nb_smooth_params *params, const double *s, uint32_t *counts, double *planes,
                            nb_smooth_stats *stats) {
     NB_GUARD({
@@ -534,6 +545,16 @@ int nb_runner_group_shapes(nb_runner *runner, const nb_shape_params *params, con
                            const double *centers, const double *velocities, const double *radius,
                            nb_shape_group *rows_out, uint32_t *selected_of, nb_shape_stats *stats) {
     return pass_group_shapes(runner, params, group_of, m, centers, velocities, radius, rows_out, selected_of, stats);
+}
+int nb_group_radii_sim(nb_sim *sim, const nb_radii_params *params, const uint32_t *group_of, size_t m,
+                       const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
+                       nb_radii_stats *stats) {
+    return pass_group_radii(sim, params, group_of, m, centers, rows_out, rank_of, enclosed_of, stats);
+}
+int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, const uint32_t *group_of, size_t m,
+                          const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
+                          nb_radii_stats *stats) {
+    return pass_group_radii(runner, params, group_of, m, centers, rows_out, rank_of, enclosed_of, stats);
 }
 int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]) {
     if (!t || !lambda || !axes) {

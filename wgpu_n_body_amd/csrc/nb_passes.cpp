@@ -285,6 +285,57 @@ int shape_check_args(const SimBase &s, const nb_shape_params *p, const uint32_t 
     return NB_OK;
 }
 
+// nb_group_radii_sim: everything that can be refused without a device, split as nb_sim_group_shapes' checks are
+int radii_check_params(const nb_radii_params *p) {
+    if (!p) {
+        set_error("group_radii: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->reserved) {
+        set_error("group_radii: a reserved field != 0");
+        return NB_ERR_INVALID;
+    }
+    if (p->nf < 1 || p->nf > NB_RADII_MAX_FRACTIONS) {
+        set_error("group_radii: nf must be 1..%u (got %u)", NB_RADII_MAX_FRACTIONS, p->nf);
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t f = 0; f < p->nf; ++f) {
+        const double x = p->fractions[f];
+        if (!std::isfinite(x) || !(x > 0.0) || !(x <= 1.0)) {
+            set_error("group_radii: fractions[%u] = %g is not finite and in (0, 1]", f, x);
+            return NB_ERR_INVALID;
+        }
+        if (f > 0 && !(x > p->fractions[f - 1])) {
+            set_error("group_radii: fractions[%u] = %g is not above fractions[%u] = %g (strictly ascending)", f, x,
+                      f - 1, p->fractions[f - 1]);
+            return NB_ERR_INVALID;
+        }
+    }
+    return NB_OK;
+}
+int radii_check_args(const SimBase &s, const nb_radii_params *p, const uint32_t *group_of, size_t m,
+                     const double *centers) {
+    if (s.n > 0 && !group_of) {
+        set_error("group_radii: null group_of");
+        return NB_ERR_INVALID;
+    }
+    if (m > std::max<size_t>(s.n, 1)) {
+        set_error("group_radii: %zu rows are more than %u bodies can fill", m, s.n);
+        return NB_ERR_INVALID;
+    }
+    for (size_t k = 0; centers && k < 3 * m; ++k)
+        if (!std::isfinite(centers[k])) {
+            set_error("group_radii: the centre of row %zu is not finite", k / 3);
+            return NB_ERR_INVALID;
+        }
+    if (p->step_num != NB_RADII_ANY_STEP && p->step_num != s.step_num) {
+        set_error("group_radii: the assignment was made at step %llu, the simulator is at step %llu",
+                  (unsigned long long)p->step_num, (unsigned long long)s.step_num);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_sim_knn: everything that can be refused without a device
 int knn_check_params(const nb_knn_params *p) {
     if (!p) {

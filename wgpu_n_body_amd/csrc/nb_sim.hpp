@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -195,6 +195,14 @@ int sim_group_shapes(SimBase &sim, const nb_shape_params &params, const uint32_t
                      const double *centers, const double *velocities, const double *radius, nb_shape_group *rows,
                      uint32_t *selected_of, nb_shape_stats *stats);
 void shape_eigen_host(const double t[6], double lambda[3], double axes[9]);
+// nb_radii.hip: nb_group_radii_sim behind the handle, checked like nb_sim_group_shapes: the parameters alone, then
+// what needs the simulator's n and step number (the values of group_of are checked on the device)
+int radii_check_params(const nb_radii_params *p);
+int radii_check_args(const SimBase &sim, const nb_radii_params *p, const uint32_t *group_of, size_t m,
+                     const double *centers);
+int sim_group_radii(SimBase &sim, const nb_radii_params &params, const uint32_t *group_of, size_t m,
+                    const double *centers, nb_radii_group *rows, uint32_t *rank_of, double *enclosed_of,
+                    nb_radii_stats *stats);
 // nb_knn.hip: nb_sim_knn behind the handle
 int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,

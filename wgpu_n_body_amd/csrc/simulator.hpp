@@ -45,6 +45,8 @@ using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound s
 using BoundStats = nb_bound_stats;
 using ShapeGroup = nb_shape_group;        // 360 B: a row's sums, eigenvalues, axes and axis ratios
 using ShapeStats = nb_shape_stats;
+using RadiiGroup = nb_radii_group;        // 264 B: a row's mass radii, extent and peak of M / r
+using RadiiStats = nb_radii_stats;
 using HopBoundary = nb_hop_boundary;      // 24 B: two labels, their body pairs and the largest pair density
 using HopStats = nb_hop_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
@@ -375,6 +377,79 @@ GroupShapes fof_shapes(Call call, H *h, size_t n, const FofGroups &f, double k_r
 }
 }  // namespace detail
 
+// The exact mass radii of the rows of an assignment of bodies to rows (nb_group_radii_sim; no reference counterpart):
+// one row per row of the assignment; rank_of and enclosed_of are empty when not asked for
+struct RadiiOptions {
+    std::vector<double> fractions{0.1, 0.5, 0.9};  // 1 to 16 ascending values in (0, 1]
+    uint32_t vmax_skip = 10;                       // the innermost ranks left out of the peak of M / r
+    bool per_body = false;                         // rank_of, enclosed_of
+    uint64_t step_num = NB_RADII_ANY_STEP;         // the step the assignment was made at, or no check
+};
+struct GroupRadii {
+    std::vector<RadiiGroup> rows;
+    std::vector<uint32_t> catalogue_rows;  // the catalogue row of every row (group_radii leaves out the rows without
+                                           // a finite centre; radii_of, lagrangian_radii: 0 .. m - 1)
+    std::vector<double> fractions;
+    std::vector<uint32_t> rank_of;
+    std::vector<double> enclosed_of;
+    RadiiStats stats{};
+    double radius(size_t r, size_t f) const { return rows[r].radius[f]; }
+    double vmax(size_t r, double G) const { return std::sqrt(G * rows[r].vc2_max); }
+};
+
+namespace detail {
+// centers: empty (the members' own centre of mass, formed on the device) or three per row
+template <class H>
+GroupRadii group_radii(int (*call)(H *, const nb_radii_params *, const uint32_t *, size_t, const double *,
+                                   nb_radii_group *, uint32_t *, double *, nb_radii_stats *),
+                       H *h, size_t n, const std::vector<uint32_t> &group_of, size_t m, const RadiiOptions &o,
+                       const std::vector<double> &centers) {
+    if (group_of.size() != n) throw std::invalid_argument("group_radii: one group_of value per body");
+    if (!centers.empty() && centers.size() != 3 * m)
+        throw std::invalid_argument("group_radii: centers are per row, or empty");
+    GroupRadii g;
+    nb_radii_params p{};
+    p.nf = (uint32_t)o.fractions.size();  // (the call refuses a number it does not take)
+    for (size_t f = 0; f < o.fractions.size() && f < NB_RADII_MAX_FRACTIONS; ++f) p.fractions[f] = o.fractions[f];
+    p.vmax_skip = o.vmax_skip;
+    p.step_num = o.step_num;
+    g.fractions = o.fractions;
+    g.rows.resize(m);
+    if (o.per_body) {
+        g.rank_of.resize(n);
+        g.enclosed_of.resize(n);
+    }
+    check(call(h, &p, group_of.data(), m, centers.empty() ? nullptr : centers.data(), g.rows.data(),
+               o.per_body ? g.rank_of.data() : nullptr, o.per_body ? g.enclosed_of.data() : nullptr, &g.stats));
+    g.catalogue_rows.resize(m);
+    for (size_t r = 0; r < m; ++r) g.catalogue_rows[r] = (uint32_t)r;
+    return g;
+}
+// ... of a friends-of-friends catalogue about its centres of mass.  As the Python group_radii: a catalogue row without
+// a finite centre (no mass) is left out, the others are renumbered in order and named by catalogue_rows
+template <class H, class Call>
+GroupRadii fof_radii(Call call, H *h, size_t n, const FofGroups &f, RadiiOptions o) {
+    const size_t total = f.groups.size();
+    std::vector<double> c;
+    std::vector<uint32_t> kept, renumber(total, NB_FOF_NONE);
+    for (size_t r = 0; r < total; ++r) {
+        const FofGroup &g = f.groups[r];
+        const double x[3] = {g.mx[0] / g.mass, g.mx[1] / g.mass, g.mx[2] / g.mass};
+        if (!std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2])) continue;
+        renumber[r] = (uint32_t)kept.size();
+        kept.push_back((uint32_t)r);
+        c.insert(c.end(), x, x + 3);
+    }
+    std::vector<uint32_t> mapped(f.group_of.size());
+    for (size_t i = 0; i < mapped.size(); ++i)
+        mapped[i] = f.group_of[i] < total ? renumber[f.group_of[i]] : NB_FOF_NONE;
+    o.step_num = f.stats.step_num;
+    GroupRadii g = group_radii(call, h, n, mapped, kept.size(), o, c);
+    g.catalogue_rows = kept;
+    return g;
+}
+}  // namespace detail
+
 // The density-peak groups of a state (nb_sim_hop; no reference counterpart): per body the label (the body at its
 // density peak) and the catalogue row (NB_HOP_NONE: none), the catalogue in ascending label order with one peak
 // density per row, and the boundaries between labels in ascending (a, b).  A vector that was not asked for is empty
@@ -684,6 +759,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto hop = nb_sim_hop;
     static constexpr auto halo_profiles = nb_sim_halo_profiles;
     static constexpr auto group_shapes = nb_sim_group_shapes;
+    static constexpr auto group_radii = nb_group_radii_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -700,6 +776,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto hop = nb_runner_hop;
     static constexpr auto halo_profiles = nb_runner_halo_profiles;
     static constexpr auto group_shapes = nb_runner_group_shapes;
+    static constexpr auto group_radii = nb_group_radii_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -744,6 +821,21 @@ class Passes {
     }
     GroupShapes group_shapes(const FofGroups &f, double k_rms = 0.0, const ShapeOptions &o = ShapeOptions{}) {
         return detail::fof_shapes(Abi::group_shapes, h_, n_bodies(), f, k_rms, o);
+    }
+    // the exact mass radii, the extent and the peak of M / r of the rows of an assignment
+    GroupRadii radii_of(const std::vector<uint32_t> &group_of, size_t m, const RadiiOptions &o = RadiiOptions{},
+                        const std::vector<double> &centers = {}) {
+        return detail::group_radii(Abi::group_radii, h_, n_bodies(), group_of, m, o, centers);
+    }
+    GroupRadii group_radii(const FofGroups &f, const RadiiOptions &o = RadiiOptions{}) {
+        return detail::fof_radii(Abi::group_radii, h_, n_bodies(), f, o);
+    }
+    // ... of the whole state as one row: center empty (its own centre of mass, formed on the device) or x y z.  The
+    // Python method's center="density" is this with knn_density(6, true, false).center() as the point
+    GroupRadii lagrangian_radii(const RadiiOptions &o = RadiiOptions{{0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9}},
+                                const std::vector<double> &center = {}) {
+        return detail::group_radii(Abi::group_radii, h_, n_bodies(), std::vector<uint32_t>(n_bodies(), 0u), 1, o,
+                                   center);
     }
     // the k-th neighbour, the mass inside it and the density at every body; center() is the density centre
     HopGroups hop_groups(const HopParams &p = HopParams{}, bool labels = true, bool density = false,
