@@ -1417,6 +1417,133 @@ int nb_group_radii_sim(nb_sim *sim, const nb_radii_params *params, const uint32_
                        nb_radii_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Disc modes -- azimuthal Fourier sums per annulus: bar strength, phases,    */
+/* pattern speeds, bending modes, thickness (no reference counterpart)        */
+/* ------------------------------------------------------------------------- */
+/* Per annulus about an axis through a centre: sum m e^(i m phi) for m = 0 .. mmax and
+ * three weighted variants (by dphi/dt, by the height above the plane, and their
+ * combinations), from which nb_disc_modes_derive forms the amplitude A_m / A_0, the
+ * phase, the single-snapshot pattern speed (Dehnen, Semczuk & Schoenrich 2023: dphi/dt
+ * of every body is known, so no second output is needed) and the bending mode.  The
+ * rule, which DESIGN.md 6p states in full; binary64 from the binary32 state, one
+ * rounding per operation, no contraction, in this order:
+ *   input     nbins in 1..NB_MODES_MAX_BINS and nbins + 1 edges, checked exactly as
+ *             nb_sim_radial_profile checks its edges; mmax in 0..NB_MODES_MAX_M; a
+ *             centre c and a frame velocity v_c, or NB_MODES_CENTER_COM: the fp64 `com`
+ *             and `momentum / mass` of nb_sim_diagnostics bit for bit, formed on the
+ *             device; an axis
+ *   frame     n, e1, e2 exactly as nb_map_frame(axis) returns them: phi = 0 is the
+ *             direction nb_field_rings starts its rings from, (a, b) are a map's axes
+ *   per body  that counts (position, velocity and mass finite; the others are
+ *             `nonfinite`):
+ *               d = (double)x - c, u = (double)v - v_c         per component
+ *               h  = (dx nx + dy ny) + dz nz                   the height above the plane
+ *               p  = d - h n,  r2 = (px px + py py) + pz pz    nb_sim_radial_profile's
+ *                                                              cylindrical rule
+ *               bin: the k with edges[k]^2 <= r2 < edges[k + 1]^2 (the squares formed
+ *                    once on the host); r2 < edges[0]^2: inside; r2 >= edges[nbins]^2:
+ *                    outside; a NaN r2 (a NaN centre) is below every edge
+ *               a  = (px e1x + py e1y) + pz e1z,  b likewise with e2
+ *               ua = (ux e1x + uy e1y) + uz e1z,  ub likewise with e2
+ *               R  = sqrt(r2), c_1 = a / R, s_1 = b / R, w = (a ub - b ua) / r2
+ *               r2 == 0: c_1 = s_1 = 0 and w = 0 (the body counts in m = 0 only)
+ *               c_0 = 1, s_0 = 0; c_m = c_(m-1) c_1 - s_(m-1) s_1,
+ *                                 s_m = s_(m-1) c_1 + c_(m-1) s_1      m = 1 .. mmax
+ *               with mu = (double)mass, per m the six terms
+ *                 C = mu c_m, S = mu s_m, DC = (mu w) c_m, DS = (mu w) s_m,
+ *                 ZC = (mu h) c_m, ZS = (mu h) s_m
+ *               and once mu R and (mu h) h
+ *             cos m phi and sin m phi come from the recurrence: every term is a chain
+ *             of correctly rounded +, -, x, / and sqrt
+ *   lists     a bin's list is its members in ascending body index; inside and outside
+ *             are lists too (only their count and their sum of mu are reported).  A
+ *             member's place is its 0-based position in its list
+ *   sums      every field of a list in three fixed levels: the places [64 k, 64 k + 64)
+ *             are a run, summed by the xor butterfly over offsets 32, 16, 8, 4, 2, 1 (x_i
+ *             + x_(i xor o) on every place, an absent place holding +0); the up to 64
+ *             runs of a chunk of NB_MODES_CHUNK = 4,096 places are added left to right
+ *             starting from +0; the chunks of the list are added left to right starting
+ *             from +0.  A bin's bits depend on its own members, the centre and the frame
+ *             alone: not on the other bins, on nbins or on the call
+ *   mass      inside_mass + the bins' C_0 in order + outside_mass, added in that order
+ *             starting from inside_mass
+ * modes[(k (mmax + 1) + m) 6 + f] is field f of mode m of bin k, f in the order C, S,
+ * DC, DS, ZC, ZS (NB_MODES_C ..).  At m = 0: C = sum mu, DC = sum mu w, ZC = sum mu h and
+ * the three sine sums are sums of zeros.  Two calls return the same bits.  No float
+ * atomics.  The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as nb_sim_read_particles
+ * does, launches nothing inside a graph capture and does not change the trajectory.
+ * This is the fourteenth analysis pass, spelt noun first as nb_group_radii_sim is. */
+#define NB_MODES_MAX_BINS 256u
+#define NB_MODES_MAX_M 8u
+#define NB_MODES_FIELDS 6u
+#define NB_MODES_CHUNK 4096u
+#define NB_MODES_CENTER_COM 1u /* centre = com, frame velocity = P/M of the measured state (as NB_RADIAL_CENTER_COM) */
+enum { NB_MODES_C = 0, NB_MODES_S, NB_MODES_DC, NB_MODES_DS, NB_MODES_ZC, NB_MODES_ZS };
+
+typedef struct nb_modes_params {
+    uint32_t nbins, mmax; /* 1..NB_MODES_MAX_BINS, 0..NB_MODES_MAX_M */
+    uint32_t flags;       /* NB_MODES_CENTER_COM */
+    uint32_t reserved;    /* 0 */
+    double center[3];     /* ignored with NB_MODES_CENTER_COM */
+    double velocity[3];   /* ignored with NB_MODES_CENTER_COM */
+    double axis[3];       /* finite, non-zero; need not be a unit vector */
+    const double *edges;  /* nbins + 1 cylindrical radii: finite, >= 0, strictly ascending */
+} nb_modes_params;
+
+typedef struct nb_modes_head { /* 200 bytes */
+    uint64_t step_num, n, nonfinite;
+    uint64_t inside_count, outside_count;
+    double inside_mass, outside_mass;
+    double mass;                      /* inside + the bins in order + outside */
+    double center[3], velocity[3];    /* the ones used */
+    double axis[3], e1[3], e2[3];     /* nb_map_frame of the caller's axis */
+    uint32_t nbins, mmax, flags, reserved;
+} nb_modes_head;
+
+typedef struct nb_modes_bin { /* 24 bytes */
+    uint64_t count;
+    double m_r;  /* sum mu R */
+    double m_h2; /* sum (mu h) h */
+} nb_modes_bin;
+
+typedef struct nb_modes_derived { /* 40 bytes: one mode m >= 1 of one bin */
+    double amplitude;      /* hypot(C, S) / C_0 */
+    double phase;          /* atan2(S, C) / m, in (-pi/m, pi/m] */
+    double pattern_speed;  /* (C DC + S DS) / (C C + S S) */
+    double bend_amplitude; /* hypot(ZC, ZS) / C_0 */
+    double bend_phase;     /* atan2(ZS, ZC) / m */
+} nb_modes_derived;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_modes_params) == 96 && sizeof(nb_modes_head) == 200 && sizeof(nb_modes_bin) == 24 &&
+                  sizeof(nb_modes_derived) == 40,
+              "nb_modes_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_modes_params) == 96 && sizeof(nb_modes_head) == 200 && sizeof(nb_modes_bin) == 24 &&
+                   sizeof(nb_modes_derived) == 40,
+               "nb_modes_* layouts");
+#endif
+
+/* out: the head; bins: nbins records; modes: nbins (mmax + 1) 6 doubles.  NB_ERR_INVALID for a null
+ * handle or pointer, nbins outside 1..NB_MODES_MAX_BINS, mmax above NB_MODES_MAX_M, unknown flag bits, a
+ * reserved field != 0, non-finite, negative or not strictly ascending edges, a non-finite centre or
+ * velocity (without NB_MODES_CENTER_COM), an axis without a finite non-zero length -- all checked before
+ * any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1).  n == 0 is answered
+ * on the host: zero sums, the explicit centre or NaN for the centre of no mass. */
+int nb_disc_modes_sim(nb_sim *sim, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
+                      double *modes);
+/* Host only, a pure function of its arguments: mode m (1 <= m <= mmax) of every bin of `modes` as
+ * nb_disc_modes_sim filled it, out[nbins].  With C_0 = modes[k][0][NB_MODES_C]: amplitude = hypot(C, S) / C_0,
+ * phase = atan2(S, C) / m, pattern_speed = (C DC + S DS) / (C C + S S) (from dC/dt = -m DS, dS/dt = m DC: the
+ * rate at which the phase of the bodies now in the annulus turns; the flux through the annulus' edges is
+ * not in it), bend_amplitude = hypot(ZC, ZS) / C_0, bend_phase = atan2(ZS, ZC) / m.  Every
+ * field of a bin is NaN where C_0 is 0 or NaN; phase and pattern_speed are NaN where C C + S S == 0, bend_phase
+ * where ZC ZC + ZS ZS == 0.  NB_ERR_INVALID for a null pointer, nbins or mmax out of range, m outside
+ * 1..mmax. */
+int nb_disc_modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out);
+
+/* ------------------------------------------------------------------------- */
 /* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
 /* kernel of its own radius (no reference counterpart: the image of the       */
 /* density estimate, where nb_sim_map gives shot noise)                       */
@@ -1705,6 +1832,10 @@ int nb_runner_group_shapes(nb_runner *runner, const nb_shape_params *params, con
 int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, const uint32_t *group_of, size_t m,
                           const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
                           nb_radii_stats *stats);
+/* nb_disc_modes_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
+                         double *modes);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

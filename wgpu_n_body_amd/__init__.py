@@ -44,6 +44,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "HopGroups", "HopStats", "HOP_NONE",
            "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
            "GroupRadii", "RadiiStats",
+           "DiscModes", "MODES_FIELDS",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
@@ -259,6 +260,149 @@ def _radial_profile(call, handle, edges, nbins, rmin, rmax, log, cylindrical, ax
     bins = np.zeros(max(int(p.nbins), 1), dtype=_lib.RADIAL_BIN_DTYPE)
     check(call(handle, C.byref(p), C.byref(out), bins.ctypes.data))
     return RadialProfile._from_c(out, bins, edges)
+
+
+MODES_FIELDS = ("C", "S", "DC", "DS", "ZC", "ZS")
+
+
+def _wrap_phase(x, m):
+    """x wrapped into (-pi/m, pi/m]."""
+    period = 2.0 * np.pi / m
+    return x - period * np.ceil(x / period - 0.5)
+
+
+@dataclass(frozen=True)
+class DiscModes:
+    """nb_modes_head + nb_modes_bin[nbins] + modes[nbins][mmax + 1][6] (include/nbody.h "Disc modes"; no reference
+    counterpart): per annulus of the state read_particles would return, about `axis` through `center`, the sums
+    over the members of mu e^(i m phi) (C, S), of the same weighted by dphi/dt (DC, DS) and by the height above the
+    plane (ZC, ZS), summed on the device in a fixed order.  phi = 0 is along e1 (map_frame(axis)).  modes:
+    (nbins, mmax + 1, 6) float64 in the order MODES_FIELDS; count: uint64; m_r: sum mu R; m_h2: sum mu h^2."""
+    step_num: int
+    n: int
+    nonfinite: int
+    inside_count: int
+    outside_count: int
+    inside_mass: float
+    outside_mass: float
+    mass: float
+    center: np.ndarray
+    velocity: np.ndarray
+    axis: np.ndarray
+    e1: np.ndarray
+    e2: np.ndarray
+    flags: int
+    mmax: int
+    dt: float              # the simulator's time step (pattern_speed_between)
+    edges: np.ndarray      # nbins + 1
+    count: np.ndarray
+    m_r: np.ndarray
+    m_h2: np.ndarray
+    modes: np.ndarray
+
+    @property
+    def nbins(self) -> int:
+        return self.edges.shape[0] - 1
+
+    @property
+    def bin_mass(self) -> np.ndarray:
+        """C_0: the mass of every annulus."""
+        return self.modes[:, 0, 0]
+
+    def derived(self, m: int) -> np.ndarray:
+        """nb_disc_modes_derive: _lib.MODES_DERIVED_DTYPE records of mode m (1 <= m <= mmax), one per bin."""
+        out = np.zeros(self.nbins, dtype=_lib.MODES_DERIVED_DTYPE)
+        modes = np.ascontiguousarray(self.modes, dtype=np.float64)
+        check(_lib.lib().nb_disc_modes_derive(modes.ctypes.data, self.nbins, self.mmax, int(m), out.ctypes.data))
+        return out
+
+    def amplitude(self, m: int) -> np.ndarray:
+        """A_m / A_0 = hypot(C_m, S_m) / C_0 per bin (NaN in a bin without mass)."""
+        return self.derived(m)["amplitude"]
+
+    def phase(self, m: int) -> np.ndarray:
+        """atan2(S_m, C_m) / m per bin, in (-pi/m, pi/m]: the azimuth of the mode's maximum from e1."""
+        return self.derived(m)["phase"]
+
+    def pattern_speed(self, m: int) -> np.ndarray:
+        """The single-snapshot pattern speed (C DC + S DS) / (C^2 + S^2) per bin: the rate at which the phase of the
+        bodies now in the annulus turns (the flux through the annulus' edges is not in it)."""
+        return self.derived(m)["pattern_speed"]
+
+    def bending(self, m: int):
+        """(amplitude, phase) of the bending mode m: hypot(ZC_m, ZS_m) / C_0 and atan2(ZS_m, ZC_m) / m per bin."""
+        d = self.derived(m)
+        return d["bend_amplitude"], d["bend_phase"]
+
+    def bar_strength(self):
+        """(A_2, bin): the largest A_2 / A_0 over the bins with mass and the bin it occurs in ((nan, -1): none)."""
+        a = self.amplitude(2)
+        ok = np.isfinite(a) & (self.bin_mass != 0.0)
+        if not ok.any():
+            return float("nan"), -1
+        k = int(np.argmax(np.where(ok, a, -np.inf)))
+        return float(a[k]), k
+
+    def warp_tilt(self) -> np.ndarray:
+        """2 hypot(ZC_1, ZS_1) / sum mu R per bin: the tilt (rise over run) of the annulus' plane."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return 2.0 * np.hypot(self.modes[:, 1, 4], self.modes[:, 1, 5]) / self.m_r
+
+    def thickness(self) -> np.ndarray:
+        """sqrt(sum mu h^2 / C_0 - (ZC_0 / C_0)^2) per bin: the rms height about the mean height."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = self.modes[:, 0, 4] / self.bin_mass
+            return np.sqrt(np.maximum(self.m_h2 / self.bin_mass - mean * mean, 0.0))
+
+    def total(self, m: int) -> np.ndarray:
+        """The six sums of mode m over all bins, the bins added in order."""
+        out = np.zeros(6)
+        for k in range(self.nbins):
+            out = out + self.modes[k, m]
+        return out
+
+    def pattern_speed_between(self, other: "DiscModes", m: int, time=None) -> np.ndarray:
+        """The pattern speed of mode m from two measurements: (other.phase(m) - self.phase(m)) wrapped into
+        (-pi/m, pi/m], over `time` (default: the steps between the two times dt)."""
+        if time is None:
+            time = (other.step_num - self.step_num) * self.dt
+        return _wrap_phase(other.phase(m) - self.phase(m), int(m)) / time
+
+
+def _disc_modes(call, handle, dt, edges, nbins, rmin, rmax, log, mmax, axis, center, velocity) -> DiscModes:
+    if edges is None:
+        if rmin is None or rmax is None:
+            raise ValueError("disc_modes needs edges, or rmin and rmax")
+        edges = radial_edges(rmin, rmax, nbins, log)
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if not 0 <= int(mmax) <= 0xFFFFFFFF:
+        raise ValueError(f"disc_modes: mmax = {mmax} is not a 32-bit count")
+    p = _lib.nb_modes_params()
+    p.nbins, p.mmax, p.flags, p.reserved = max(edges.shape[0] - 1, 0), int(mmax), 0, 0
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com", "density" or three coordinates')
+        if velocity is not None:
+            raise ValueError('center="com" brings its own velocity')
+        p.flags |= _lib.NB_MODES_CENTER_COM
+    else:
+        velocity = (0.0, 0.0, 0.0) if velocity is None else velocity
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    p.edges = edges.ctypes.data_as(C.POINTER(C.c_double))
+    out = _lib.nb_modes_head()
+    nb_, mm = max(int(p.nbins), 1), min(int(p.mmax), _lib.NB_MODES_MAX_M)  # (the call refuses what it does not take)
+    bins = np.zeros(nb_, dtype=_lib.MODES_BIN_DTYPE)
+    modes = np.zeros((nb_, mm + 1, _lib.NB_MODES_FIELDS), dtype=np.float64)
+    check(call(handle, C.byref(p), C.byref(out), bins.ctypes.data, modes.ctypes.data))
+    vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+    return DiscModes(int(out.step_num), int(out.n), int(out.nonfinite), int(out.inside_count),
+                     int(out.outside_count), float(out.inside_mass), float(out.outside_mass), float(out.mass),
+                     vec(out.center), vec(out.velocity), vec(out.axis), vec(out.e1), vec(out.e2), int(out.flags),
+                     int(out.mmax), float(dt), edges.copy(), bins["count"].copy(), bins["m_r"].copy(),
+                     bins["m_h2"].copy(), modes)
 
 
 @dataclass(frozen=True)
@@ -1682,6 +1826,23 @@ class _Passes:
             center, velocity = d.center, d.center_velocity
         return _radial_profile(self._pass("radial_profile"), self._h, edges, nbins, rmin, rmax, log,
                                cylindrical, axis, center, velocity)
+
+    def disc_modes(self, edges=None, *, nbins: int = 32, rmin=None, rmax=None, log: bool = False, mmax: int = 4,
+                   axis=(0.0, 1.0, 0.0), center="com", velocity=None) -> DiscModes:
+        """The azimuthal Fourier sums of the current state per annulus about `axis` (nb_disc_modes_sim): bar strength,
+        phases, pattern speeds, bending modes and thickness are methods of the DiscModes it returns.  edges: the
+        nbins + 1 cylindrical radii, or rmin, rmax, nbins and log for radial_edges().  mmax: the highest mode, 0 to 8.
+        center: "com" (the centre of mass and its velocity P/M, as diagnostics() returns them), three coordinates,
+        then with `velocity` as the frame's velocity (default: at rest), or "density": the density centre and its
+        velocity of knn_density(6), passed on as explicit values.  A several-GPU runner refuses."""
+        if isinstance(center, str) and center == "density":
+            if velocity is not None:
+                raise ValueError('center="density" brings its own velocity')
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _disc_modes(getattr(_lib.lib(), "nb_disc_modes_" + suffix), self._h, self.sim_params().dt, edges,
+                           nbins, rmin, rmax, log, mmax, axis, center, velocity)
 
     def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
         """The exact acceleration and potential of the current state at `points` ((M, 3), float32), summed

@@ -236,6 +236,21 @@ class nb_radii_stats(C.Structure):
                 ("nonfinite_members", C.c_uint64), ("empty", C.c_uint64)]
 
 
+class nb_modes_params(C.Structure):
+    _fields_ = [("nbins", C.c_uint32), ("mmax", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("edges", C.POINTER(C.c_double))]
+
+
+class nb_modes_head(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("inside_count", C.c_uint64), ("outside_count", C.c_uint64), ("inside_mass", C.c_double),
+                ("outside_mass", C.c_double), ("mass", C.c_double), ("center", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("axis", C.c_double * 3), ("e1", C.c_double * 3),
+                ("e2", C.c_double * 3), ("nbins", C.c_uint32), ("mmax", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class nb_smooth_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -287,6 +302,11 @@ RADII_GROUP_DTYPE = np.dtype([("count", "<u4"), ("vmax_index", "<u4"), ("center"
                               ("r_min", "<f8"), ("r_max", "<f8"), ("vc2_max", "<f8"), ("r_vmax", "<f8"),
                               ("radius", "<f8", (16,)), ("index", "<u4", (16,))])
 
+# nb_modes_bin[] and nb_modes_derived[] as numpy record arrays
+MODES_BIN_DTYPE = np.dtype([("count", "<u8"), ("m_r", "<f8"), ("m_h2", "<f8")])
+MODES_DERIVED_DTYPE = np.dtype([("amplitude", "<f8"), ("phase", "<f8"), ("pattern_speed", "<f8"),
+                                ("bend_amplitude", "<f8"), ("bend_phase", "<f8")])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -311,6 +331,8 @@ assert C.sizeof(nb_shape_params) == 40 and C.sizeof(nb_shape_stats) == 80
 assert C.sizeof(nb_shape_group) == 360 == SHAPE_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_radii_params) == 152 and C.sizeof(nb_radii_stats) == 48
 assert C.sizeof(nb_radii_group) == 264 == RADII_GROUP_DTYPE.itemsize
+assert C.sizeof(nb_modes_params) == 96 and C.sizeof(nb_modes_head) == 200
+assert MODES_BIN_DTYPE.itemsize == 24 and MODES_DERIVED_DTYPE.itemsize == 40
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
@@ -338,6 +360,7 @@ NB_SHAPE_REDUCED = 1
 NB_SHAPE_CONVERGED, NB_SHAPE_UNCONVERGED, NB_SHAPE_DEGENERATE, NB_SHAPE_EMPTY = 1, 2, 4, 8
 NB_SHAPE_MAX_ITER, NB_SHAPE_ANY_STEP = 64, 0xFFFFFFFFFFFFFFFF
 NB_RADII_MAX_FRACTIONS, NB_RADII_CHUNK, NB_RADII_ANY_STEP = 16, 4096, 0xFFFFFFFFFFFFFFFF
+NB_MODES_MAX_BINS, NB_MODES_MAX_M, NB_MODES_FIELDS, NB_MODES_CHUNK, NB_MODES_CENTER_COM = 256, 8, 6, 4096, 1
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
 NB_SMOOTH_MAX_ENTRIES = 1 << 28
@@ -364,6 +387,7 @@ ABI_SYMBOLS = [
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
     "nb_group_radii_sim", "nb_group_radii_runner",
+    "nb_disc_modes_sim", "nb_disc_modes_runner", "nb_disc_modes_derive",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
@@ -447,6 +471,11 @@ def lib() -> C.CDLL:
     group_radii = [vp, P(nb_radii_params), vp, sz, vp, vp, vp, vp, P(nb_radii_stats)]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_group_radii_" + suffix).argtypes = group_radii
+    # ... and the fourteenth (include/nbody.h "Disc modes")
+    disc_modes = [vp, P(nb_modes_params), P(nb_modes_head), vp, vp]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_disc_modes_" + suffix).argtypes = disc_modes
+    L.nb_disc_modes_derive.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     for name in ("nb_radial_edges_log", "nb_radial_edges_linear"):
         getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]
     L.nb_radial_lagrangian.argtypes = [P(nb_radial_profile), vp, P(C.c_double), P(C.c_double), C.c_uint32,

@@ -51,6 +51,9 @@ SOURCES = [
     # the order, the three-level enclosed mass and the crossings are specified operation by operation:
     # no FMA contraction
     ("nb_radii.hip", ["-ffp-contract=off"]),
+    # the frame, the recurrence and the three-level sums are specified operation by operation: no FMA
+    # contraction
+    ("nb_modes.hip", ["-ffp-contract=off"]),
     # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
     ("nb_simbase.cpp", []),

@@ -18,6 +18,8 @@
 //             [--shapes-iter I] [--shapes-top T]]
 //            [--lagr K [--lagr-fractions F1,F2,...] [--lagr-center com|X,Y,Z]]
 //            [--radii K --radii-link B [--radii-min M] [--radii-top T]]
+//            [--modes K --modes-range RMIN,RMAX [--modes-bins B] [--modes-m M] [--modes-log 0|1]
+//             [--modes-axis X,Y,Z] [--modes-center com|X,Y,Z]]
 //            [--knn K [--knn-k 6]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
@@ -103,6 +105,14 @@
 // largest groups (--radii-top, default 0) as "radii_group <step> <row> <count> <mass> <r10> <r50> <r90> <r_vmax>
 // <vc2_max>" (every real %.17g).  The time it takes is not part of any "Step Duration"; without --radii the output
 // is unchanged.
+//
+// --modes K measures the azimuthal Fourier sums (nb_disc_modes_runner) of step 0 and of every K-th step in B annuli
+// (--modes-bins, default 32; --modes-log 1: of constant ratio) between RMIN and RMAX about --modes-axis (default
+// 0,1,0) through the centre of mass, unless --modes-center gives a point, up to mode M (--modes-m, default 4, at
+// least 2).  One line "modes <step> <A2> <radius> <phase> <pattern_speed> <tilt>" (every real %.17g): the largest
+// A_2 / A_0 over the annuli with mass, that annulus' mass-weighted mean radius, the phase and the single-snapshot
+// pattern speed of its m = 2 mode, and the largest warp tilt of any annulus (NaN where there is none).  The time it
+// takes is not part of any "Step Duration"; without --modes the output is unchanged.
 //
 // --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
 // every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
@@ -405,6 +415,42 @@ static void print_radii(nbody::OfflineHeadless<Sim> &runner, const RadiiCliOptio
     }
 }
 
+struct ModesOptions {
+    int every = 0;
+    bool have_range = false, log = false;
+    double rmin = 0.0, rmax = 0.0;
+    uint32_t bins = 32, mmax = 4;
+    double axis[3] = {0.0, 1.0, 0.0};
+    std::vector<double> center;  // empty: the centre of mass
+};
+
+template <class Sim>
+static void print_modes(nbody::OfflineHeadless<Sim> &runner, const ModesOptions &mo) {
+    nbody::ModesParams p{};
+    p.mmax = mo.mmax;
+    p.flags = mo.center.empty() ? NB_MODES_CENTER_COM : 0u;
+    for (int a = 0; a < 3; ++a) {
+        p.axis[a] = mo.axis[a];
+        p.center[a] = mo.center.empty() ? 0.0 : mo.center[a];
+    }
+    const nbody::DiscModes d = runner.disc_modes(nbody::radial_edges(mo.rmin, mo.rmax, mo.bins, mo.log), p);
+    const nbody::BarStrength bar = d.bar_strength();
+    const double nan = std::nan("");
+    double radius = nan, phase = nan, omega = nan, tilt = nan;
+    if (bar.bin >= 0) {
+        const nbody::ModesDerived m2 = d.derived(2)[bar.bin];
+        radius = d.bins[bar.bin].m_r / d.field(bar.bin, 0, NB_MODES_C);
+        phase = m2.phase;
+        omega = m2.pattern_speed;
+    }
+    for (size_t k = 0; k < d.bins.size(); ++k) {
+        const double t = d.warp_tilt(k);
+        if (std::isfinite(t) && !(t <= tilt)) tilt = t;
+    }
+    std::printf("modes %llu %.17g %.17g %.17g %.17g %.17g\n", (unsigned long long)d.head.step_num, bar.a2, radius,
+                phase, omega, tilt);
+}
+
 struct KnnOptions {
     int every = 0;
     uint32_t k = 6;
@@ -546,7 +592,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                int diag, bool diag_potential, const FrameOptions &frames, const RadialOptions &radial,
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
-               const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii) {
+               const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
+               const ModesOptions &modes) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -564,6 +611,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (shapes.every > 0) print_shapes(runner, shapes);
     if (lagr.every > 0) print_lagr(runner, lagr);
     if (radii.every > 0) print_radii(runner, radii);
+    if (modes.every > 0) print_modes(runner, modes);
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -584,6 +632,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (shapes.every > 0 && (i + 1) % shapes.every == 0) print_shapes(runner, shapes);
         if (lagr.every > 0 && (i + 1) % lagr.every == 0) print_lagr(runner, lagr);
         if (radii.every > 0 && (i + 1) % radii.every == 0) print_radii(runner, radii);
+        if (modes.every > 0 && (i + 1) % modes.every == 0) print_modes(runner, modes);
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -617,6 +666,7 @@ int main(int argc, char **argv) {
     ShapesOptions shapes;
     LagrOptions lagr;
     RadiiCliOptions radii;
+    ModesOptions modes;
     bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -778,6 +828,31 @@ int main(int argc, char **argv) {
         else if (k == "--radii-link") radii.link = std::atof(v.c_str());
         else if (k == "--radii-min") radii.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--radii-top") radii.top = std::atoi(v.c_str());
+        else if (k == "--modes") modes.every = std::atoi(v.c_str());
+        else if (k == "--modes-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &modes.rmin, &modes.rmax) != 2) {
+                std::fprintf(stderr, "--modes-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            modes.have_range = true;
+        }
+        else if (k == "--modes-bins") modes.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--modes-m") modes.mmax = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--modes-log") modes.log = std::atoi(v.c_str()) != 0;
+        else if (k == "--modes-axis") {
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &modes.axis[0], &modes.axis[1], &modes.axis[2]) != 3) {
+                std::fprintf(stderr, "--modes-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--modes-center") {
+            modes.center.assign(3, 0.0);
+            if (v == "com") modes.center.clear();
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &modes.center[0], &modes.center[1], &modes.center[2]) != 3) {
+                std::fprintf(stderr, "--modes-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--smaps") smaps.dir = v;
         else if (k == "--smap-every") smaps.every = std::max(1, std::atoi(v.c_str()));
         else if (k == "--smap-size") {
@@ -912,6 +987,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--shapes-reduced 1 needs --shapes-radius KRMS > 0\n");
         return 2;
     }
+    if (modes.every > 0 && (!modes.have_range || modes.mmax < 2)) {
+        std::fprintf(stderr, "--modes needs --modes-range RMIN,RMAX and --modes-m M >= 2\n");
+        return 2;
+    }
     if (radii.every > 0 && !(radii.link > 0.0)) {
         std::fprintf(stderr, "--radii needs --radii-link B > 0\n");
         return 2;
@@ -926,9 +1005,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -206,6 +206,13 @@ static int pass_group_radii(H *h, const nb_radii_params *params, const uint32_t 
 }
 
 template <class H>
+static int pass_disc_modes(H *h, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
+                           double *modes) {
+    if (int rc = modes_check_params(params, out, bins, modes)) return rc;
+    return on_sim(h, "disc_modes", [&](SimBase &s) { return sim_disc_modes(s, *params, out, bins, modes); });
+}
+
+template <class H>
 static int pass_smooth_map(H *h, const nb_smooth_params *params, const double *s, uint32_t *counts, double *planes,
                            nb_smooth_stats *stats) {
     NB_GUARD({
@@ -555,6 +562,17 @@ int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, cons
                           const double *centers, nb_radii_group *rows_out, uint32_t *rank_of, double *enclosed_of,
                           nb_radii_stats *stats) {
     return pass_group_radii(runner, params, group_of, m, centers, rows_out, rank_of, enclosed_of, stats);
+}
+int nb_disc_modes_sim(nb_sim *sim, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
+                      double *modes) {
+    return pass_disc_modes(sim, params, out, bins, modes);
+}
+int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
+                         double *modes) {
+    return pass_disc_modes(runner, params, out, bins, modes);
+}
+int nb_disc_modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out) {
+    NB_GUARD({ return modes_derive(modes, nbins, mmax, m, out); })
 }
 int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]) {
     if (!t || !lambda || !axes) {

@@ -336,6 +336,83 @@ int radii_check_args(const SimBase &s, const nb_radii_params *p, const uint32_t 
     return NB_OK;
 }
 
+// nb_disc_modes_sim: everything that can be refused without a device; the edges exactly as radial_check_params'
+int modes_check_params(const nb_modes_params *p, const nb_modes_head *out, const nb_modes_bin *bins,
+                       const double *modes) {
+    if (!p || !out || !bins || !modes || !p->edges) {
+        set_error("disc_modes: null %s", !p ? "params" : !out ? "out" : !bins ? "bins" : !modes ? "modes" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_MODES_MAX_BINS) {
+        set_error("disc_modes: nbins must be 1..%u (got %u)", NB_MODES_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->mmax > NB_MODES_MAX_M) {
+        set_error("disc_modes: mmax must be 0..%u (got %u)", NB_MODES_MAX_M, p->mmax);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & ~NB_MODES_CENTER_COM) {
+        set_error("disc_modes: unknown flag bits 0x%x", p->flags & ~NB_MODES_CENTER_COM);
+        return NB_ERR_INVALID;
+    }
+    if (p->reserved) {
+        set_error("disc_modes: a reserved field != 0");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("disc_modes: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (!(p->flags & NB_MODES_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("disc_modes: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    double n[3], e1[3], e2[3];
+    if (!axis_frame(p->axis, n, e1, e2)) {
+        set_error("disc_modes: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_disc_modes_derive
+int modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out) {
+#pragma clang fp contract(off)
+    if (!modes || !out) {
+        set_error("disc_modes_derive: null %s", !modes ? "modes" : "out");
+        return NB_ERR_INVALID;
+    }
+    if (nbins < 1 || nbins > NB_MODES_MAX_BINS || mmax > NB_MODES_MAX_M || m < 1 || m > mmax) {
+        set_error("disc_modes_derive: needs nbins in 1..%u, mmax in 0..%u and 1 <= m <= mmax (got %u, %u, %u)",
+                  NB_MODES_MAX_BINS, NB_MODES_MAX_M, nbins, mmax, m);
+        return NB_ERR_INVALID;
+    }
+    const double nan = std::nan("");
+    for (uint32_t k = 0; k < nbins; ++k) {
+        const double *f0 = modes + (size_t)k * (mmax + 1) * NB_MODES_FIELDS, *f = f0 + (size_t)m * NB_MODES_FIELDS;
+        const double c0 = f0[NB_MODES_C], c = f[NB_MODES_C], s = f[NB_MODES_S];
+        const double zc = f[NB_MODES_ZC], zs = f[NB_MODES_ZS];
+        nb_modes_derived d{nan, nan, nan, nan, nan};
+        if (c0 != 0.0 && c0 == c0) {  // (a NaN C_0: NaN throughout, as without mass)
+            const double p2 = c * c + s * s, z2 = zc * zc + zs * zs;
+            d.amplitude = std::hypot(c, s) / c0;
+            d.bend_amplitude = std::hypot(zc, zs) / c0;
+            if (p2 != 0.0) {
+                d.phase = std::atan2(s, c) / (double)m;
+                d.pattern_speed = (c * f[NB_MODES_DC] + s * f[NB_MODES_DS]) / p2;
+            }
+            if (z2 != 0.0) d.bend_phase = std::atan2(zs, zc) / (double)m;
+        }
+        out[k] = d;
+    }
+    return NB_OK;
+}
+
 // nb_sim_knn: everything that can be refused without a device
 int knn_check_params(const nb_knn_params *p) {
     if (!p) {

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -203,6 +203,11 @@ int radii_check_args(const SimBase &sim, const nb_radii_params *p, const uint32_
 int sim_group_radii(SimBase &sim, const nb_radii_params &params, const uint32_t *group_of, size_t m,
                     const double *centers, nb_radii_group *rows, uint32_t *rank_of, double *enclosed_of,
                     nb_radii_stats *stats);
+// nb_modes.hip: nb_disc_modes_sim behind the handle; modes_derive: nb_disc_modes_derive behind the ABI boundary
+int modes_check_params(const nb_modes_params *p, const nb_modes_head *out, const nb_modes_bin *bins,
+                       const double *modes);
+int sim_disc_modes(SimBase &sim, const nb_modes_params &params, nb_modes_head *out, nb_modes_bin *bins, double *modes);
+int modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out);
 // nb_knn.hip: nb_sim_knn behind the handle
 int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,

@@ -136,6 +136,84 @@ RadialProfile radial_profile(int (*call)(H *, const nb_radial_params *, nb_radia
 }
 }  // namespace detail
 
+// The azimuthal Fourier sums of a disc per annulus (nb_disc_modes_sim; no reference counterpart): the header, the
+// bins, modes[nbins][mmax + 1][6] in the order NB_MODES_C .. NB_MODES_ZS, and the edges they lie between
+using ModesParams = nb_modes_params;      // 96 B
+using ModesBin = nb_modes_bin;            // 24 B: count, sum mu R, sum mu h^2
+using ModesDerived = nb_modes_derived;    // 40 B: amplitude, phase, pattern speed, bending amplitude and phase
+struct BarStrength {
+    double a2;    // the largest A_2 / A_0 over the bins with mass (NaN: none)
+    int bin;      // the bin it occurs in (-1: none)
+};
+struct DiscModes {
+    nb_modes_head head{};
+    std::vector<ModesBin> bins;
+    std::vector<double> modes;
+    std::vector<double> edges;
+    double dt = 0.0;  // the simulator's time step (pattern_speed_between)
+    double field(size_t bin, uint32_t m, uint32_t f) const { return modes[(bin * (head.mmax + 1) + m) * NB_MODES_FIELDS + f]; }
+    // mode m (1 <= m <= mmax) of every bin: nb_disc_modes_derive
+    std::vector<ModesDerived> derived(uint32_t m) const {
+        std::vector<ModesDerived> d(bins.size());
+        check(nb_disc_modes_derive(modes.data(), head.nbins, head.mmax, m, d.data()));
+        return d;
+    }
+    BarStrength bar_strength() const {
+        const std::vector<ModesDerived> d = derived(2);
+        BarStrength b{std::nan(""), -1};
+        for (size_t k = 0; k < d.size(); ++k)
+            if (std::isfinite(d[k].amplitude) && field(k, 0, NB_MODES_C) != 0.0 && (b.bin < 0 || d[k].amplitude > b.a2))
+                b = BarStrength{d[k].amplitude, (int)k};
+        return b;
+    }
+    // 2 hypot(ZC_1, ZS_1) / sum mu R: the tilt of the annulus' plane
+    double warp_tilt(size_t bin) const {
+        return 2.0 * std::hypot(field(bin, 1, NB_MODES_ZC), field(bin, 1, NB_MODES_ZS)) / bins[bin].m_r;
+    }
+    // sqrt(sum mu h^2 / C_0 - (ZC_0 / C_0)^2): the rms height about the mean height
+    double thickness(size_t bin) const {
+        const double c0 = field(bin, 0, NB_MODES_C), mean = field(bin, 0, NB_MODES_ZC) / c0;
+        return std::sqrt(std::max(bins[bin].m_h2 / c0 - mean * mean, 0.0));
+    }
+    // the six sums of mode m over all bins, the bins added in order
+    std::array<double, 6> total(uint32_t m) const {
+        std::array<double, 6> t{};
+        for (size_t k = 0; k < bins.size(); ++k)
+            for (uint32_t f = 0; f < NB_MODES_FIELDS; ++f) t[f] = t[f] + field(k, m, f);
+        return t;
+    }
+    // the pattern speed of mode m per bin from two measurements: the phase difference wrapped into (-pi/m, pi/m]
+    // over `time` (<= 0: the steps between the two times dt)
+    std::vector<double> pattern_speed_between(const DiscModes &other, uint32_t m, double time = 0.0) const {
+        const std::vector<ModesDerived> a = derived(m), b = other.derived(m);
+        if (!(time > 0.0)) time = ((double)other.head.step_num - (double)head.step_num) * dt;
+        const double period = 2.0 * 3.14159265358979323846 / (double)m;
+        std::vector<double> w(a.size());
+        for (size_t k = 0; k < a.size(); ++k) {
+            const double x = b[k].phase - a[k].phase;
+            w[k] = (x - period * std::ceil(x / period - 0.5)) / time;
+        }
+        return w;
+    }
+};
+
+namespace detail {
+// p: mmax, flags (NB_MODES_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
+template <class H>
+DiscModes disc_modes(int (*call)(H *, const nb_modes_params *, nb_modes_head *, nb_modes_bin *, double *), H *h,
+                     double dt, const std::vector<double> &edges, ModesParams p) {
+    DiscModes r;
+    r.edges = edges;
+    r.dt = dt;
+    r.bins.resize(edges.size() > 1 ? edges.size() - 1 : 1);
+    r.modes.resize(r.bins.size() * (std::min<size_t>(p.mmax, NB_MODES_MAX_M) + 1) * NB_MODES_FIELDS);
+    p.nbins = edges.empty() ? 0u : (uint32_t)(edges.size() - 1);
+    p.edges = r.edges.data();
+    check(call(h, &p, &r.head, r.bins.data(), r.modes.data()));
+    return r;
+}
+}  // namespace detail
+
 // The field at a set of points (no reference counterpart): the samples and what the call measured
 struct Field {
     std::vector<FieldSample> samples;
@@ -760,6 +838,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto halo_profiles = nb_sim_halo_profiles;
     static constexpr auto group_shapes = nb_sim_group_shapes;
     static constexpr auto group_radii = nb_group_radii_sim;
+    static constexpr auto disc_modes = nb_disc_modes_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -777,6 +856,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto halo_profiles = nb_runner_halo_profiles;
     static constexpr auto group_shapes = nb_runner_group_shapes;
     static constexpr auto group_radii = nb_group_radii_runner;
+    static constexpr auto disc_modes = nb_disc_modes_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -799,6 +879,13 @@ class Passes {
     // (NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM), centre, velocity and axis (nbins and edges are set here)
     RadialProfile radial_profile(const std::vector<double> &edges, const RadialParams &p = RadialParams{0, NB_RADIAL_CENTER_COM}) {
         return detail::radial_profile(Abi::radial_profile, h_, edges, p);
+    }
+    // the azimuthal Fourier sums per annulus between `edges` about p.axis; p: mmax, flags (NB_MODES_CENTER_COM),
+    // centre, velocity and axis (nbins and edges are set here)
+    DiscModes disc_modes(const std::vector<double> &edges, const ModesParams &p) {
+        SimParams sp{};
+        check(Abi::sim_params(h_, &sp));
+        return detail::disc_modes(Abi::disc_modes, h_, (double)sp.dt, edges, p);
     }
     // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
     ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(Abi::map, h_, p); }
