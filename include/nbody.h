@@ -630,6 +630,139 @@ int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[
 int nb_map_edges(double lo, double hi, uint32_t cells, double *edges);
 
 /* ------------------------------------------------------------------------- */
+/* Phase maps -- 2-D histograms of any two per-body quantities, a third       */
+/* summed per cell (no reference counterpart: velocity distributions)         */
+/* ------------------------------------------------------------------------- */
+/* Bins the state nb_sim_read_particles would return on two per-body quantities
+ * x and y and sums, per cell, the count, the mass and (NB_PHASE_WEIGHT) two
+ * moments of a third quantity q: the r - u_r diagram, the R - u_phi diagram, a
+ * position-velocity diagram, a line-of-sight velocity distribution, the
+ * L_z - E diagram, on the device.  The rule, which DESIGN.md 6q states in full:
+ * everything in binary64 from the binary32 state, one rounding per operation, no
+ * contraction, only + - * / and sqrt, in this order:
+ *   frame     n, e1, e2 exactly as nb_map_frame(axis) returns them
+ *   per body  d = (double)x - c, u = (double)v - v_c, mu = (double)mass
+ *             a, b, h and ua, ub, w exactly as nb_sim_map forms them
+ *             R = sqrt(a a + b b);  r = sqrt((dx dx + dy dy) + dz dz)
+ *             u2 = (ux ux + uy uy) + uz uz;  du = (dx ux + dy uy) + dz uz
+ *             jx = dy uz - dz uy, jy = dz ux - dx uz, jz = dx uy - dy ux
+ *   quantity  NB_PHASE_Q_* (nb_phase_quantity gives the id of a name):
+ *             a, b, h       plane coordinates and height
+ *             R, r          cylindrical and spherical radius
+ *             ua, ub, w     velocity in the frame (w: along the line of sight)
+ *             u_R           (a ua + b ub) / R
+ *             u_phi         (a ub - b ua) / R
+ *             u_r           du / r
+ *             u_t           sqrt(t), t = u2 - u_r u_r, a t < 0 replaced by +0
+ *             speed         sqrt(u2)
+ *             j_z           a ub - b ua
+ *             j             sqrt((jx jx + jy jy) + jz jz)
+ *             e_kin         0.5 u2
+ *             mass          mu
+ *             value         values[i], the caller's n doubles in the order of
+ *                           nb_sim_read_particles now (the potential of nb_sim_field,
+ *                           the density of nb_sim_knn, the energy of nb_sim_bound)
+ *             There is no azimuth: atan2 is not restated bit for bit (nb_disc_modes_sim).
+ *   edges     the caller's x_edges[W + 1] and y_edges[H + 1], strictly ascending, the
+ *             interior ones finite; the first may be -inf and the last +inf
+ *             (nb_map_edges and nb_radial_edges_log build linear and log ones)
+ *   cell      the (i, j) with xe[i] <= x < xe[i+1] and ye[j] <= y < ye[j+1]: decided by
+ *             comparisons against the edges alone
+ *   classes   nonfinite: any non-finite position, velocity or mass component (the
+ *             predicate of nb_sim_diagnostics); left out of everything
+ *             undefined: x, y or (NB_PHASE_WEIGHT) q is not finite -- 0/0 for u_phi at
+ *             R = 0, a NaN in values; such a body is outside
+ *             outside: x or y is in no cell;  binned: every other body
+ *   terms     mu, and with NB_PHASE_WEIGHT mu q and (mu q) q
+ * binned_count + outside_count + nonfinite == n; undefined_count <= outside_count;
+ * sum of counts == binned_count.
+ * When x, y or (NB_PHASE_WEIGHT) q is `value`, step_num must be the simulator's step
+ * number (NB_PHASE_ANY_STEP switches the check off): a TreeSim reorders its bodies
+ * every step, and a stale array is refused as nb_shape_params refuses a stale catalogue.
+ * NB_PHASE_CENTER_COM: c and v_c are the fp64 `com` and `momentum / mass` that
+ * nb_sim_diagnostics returns for the same state, bit for bit (the same moments
+ * pass runs ahead on the stream; no host round trip).
+ * The guarantees are those of nb_sim_map, whose grouping and summing code this pass
+ * runs: no float atomics, two calls on one state return bit-identical counts,
+ * planes and stats, every double is within 1e-10 of its sum of |term| of the
+ * binary64 sum; with x = a, y = b, q = w on the edges of nb_map_edges and equal
+ * segment lengths the counts and the three planes are nb_sim_map's counts, mass,
+ * m_w and m_w2 bit for bit.  The call is ordered after the enqueued steps on the
+ * simulator's stream, ends with one synchronisation, reports a TreeSim's status
+ * words as nb_sim_read_particles does, and does not change the trajectory.
+ * "phase_segment_len" (nb_sim_set_tuning, 256..65536, a multiple of 256; default
+ * 4096; speed and testing only) is this pass's "map_segment_len".
+ * This is the fifteenth analysis pass, spelt noun first as nb_group_radii_sim is. */
+#define NB_PHASE_CENTER_COM 1u /* as NB_MAP_CENTER_COM */
+#define NB_PHASE_WEIGHT 2u     /* add the planes mu q and (mu q) q */
+#define NB_PHASE_ANY_STEP 0xFFFFFFFFFFFFFFFFull /* nb_phase_params.step_num: UINT64_MAX */
+
+enum {
+    NB_PHASE_Q_A = 0,
+    NB_PHASE_Q_B,
+    NB_PHASE_Q_H,
+    NB_PHASE_Q_R_CYL, /* "R" */
+    NB_PHASE_Q_R,     /* "r" */
+    NB_PHASE_Q_UA,
+    NB_PHASE_Q_UB,
+    NB_PHASE_Q_W,
+    NB_PHASE_Q_U_R_CYL, /* "u_R" */
+    NB_PHASE_Q_U_PHI,
+    NB_PHASE_Q_U_R, /* "u_r" */
+    NB_PHASE_Q_U_T,
+    NB_PHASE_Q_SPEED,
+    NB_PHASE_Q_J_Z,
+    NB_PHASE_Q_J,
+    NB_PHASE_Q_E_KIN,
+    NB_PHASE_Q_MASS,
+    NB_PHASE_Q_VALUE,
+    NB_PHASE_Q_COUNT
+};
+
+typedef struct nb_phase_params {
+    uint32_t width, height, flags, reserved; /* sides 1..NB_MAP_MAX_SIDE, at most NB_MAP_MAX_CELLS cells; reserved 0 */
+    uint32_t x, y, q, reserved2;             /* NB_PHASE_Q_*; q is summed only with NB_PHASE_WEIGHT; reserved2 0 */
+    double center[3], velocity[3];           /* ignored with NB_PHASE_CENTER_COM */
+    double axis[3];                          /* the frame's axis; any non-zero finite vector */
+    const double *x_edges, *y_edges;         /* width + 1 and height + 1 edges */
+    const double *values;                    /* n doubles, or NULL when no quantity is `value` */
+    uint64_t step_num;                       /* with `value`: the simulator's step number, or NB_PHASE_ANY_STEP */
+} nb_phase_params;
+
+typedef struct nb_phase_stats {
+    uint64_t step_num, n, nonfinite, binned_count, outside_count, undefined_count;
+    double binned_mass, outside_mass, mass; /* mass: all finite bodies */
+    double center[3], velocity[3];          /* the values used */
+    double n_hat[3], e1[3], e2[3];          /* the frame used */
+    uint32_t width, height, flags, max_count;
+    uint32_t x, y, q, reserved; /* the quantity ids */
+} nb_phase_stats;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_phase_params) == 136 && sizeof(nb_phase_stats) == 224, "nb_phase_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_phase_params) == 136 && sizeof(nb_phase_stats) == 224, "nb_phase_* layouts");
+#endif
+
+/* The phase map of a simulator's current state.  counts: height * width values, row j the cells with y in
+ * [ye[j], ye[j+1]).  planes: P planes of height * width doubles, plane-major: P = 1 `mass`; with
+ * NB_PHASE_WEIGHT P = 3: mass, m_q, m_q2.  counts, planes and stats may each be null: what is not asked for is
+ * not copied, and a call with none of them synchronises and measures nothing.  A simulator without bodies is
+ * answered on the host.  NB_ERR_INVALID for a null handle, params or edge array, a side outside
+ * 1..NB_MAP_MAX_SIDE, more than NB_MAP_MAX_CELLS cells, unknown flag bits, an unknown quantity id, a reserved
+ * field != 0, a zero or non-finite axis, a non-finite centre or velocity without NB_PHASE_CENTER_COM, edges
+ * that are not strictly ascending or have a non-finite interior edge, `value` without values, or a stale
+ * step_num -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement
+ * world > 1).  Launches nothing inside a graph capture of the steps: the call is ordered after them. */
+int nb_phase_map_sim(nb_sim *sim, const nb_phase_params *params, uint32_t *counts, double *planes,
+                     nb_phase_stats *stats);
+/* Host only, no device: the id of the quantity called `name` (the names of the table above, case-sensitive).
+ * NB_ERR_INVALID for a null pointer or a name that is not in the table. */
+int nb_phase_quantity(const char *name, uint32_t *id);
+/* Host only, no device: the name of quantity `id`, or NULL for an id that is not in the table. */
+const char *nb_phase_quantity_name(uint32_t id);
+
+/* ------------------------------------------------------------------------- */
 /* Friends-of-friends groups -- which bodies belong together (no reference    */
 /* counterpart: the clumps of the current state, on the device)               */
 /* ------------------------------------------------------------------------- */
@@ -1836,6 +1969,10 @@ int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, cons
  * runner. */
 int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
                          double *modes);
+/* nb_phase_map_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32_t *counts, double *planes,
+                        nb_phase_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

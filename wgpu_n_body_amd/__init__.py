@@ -38,6 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
+           "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
@@ -587,6 +588,165 @@ def _projected_map(call, handle, width, height, extent, axis, center, velocity, 
                         int(st.n), int(st.nonfinite), int(st.binned_count), int(st.outside_count),
                         float(st.binned_mass), float(st.outside_mass), float(st.mass), vec(st.center),
                         vec(st.velocity), vec(st.n_hat), vec(st.e1), vec(st.e2), int(st.flags), int(st.max_count))
+
+
+def phase_quantity(name: str) -> int:
+    """nb_phase_quantity: the id (NB_PHASE_Q_*) of the per-body quantity called `name`."""
+    out = C.c_uint32()
+    check(_lib.lib().nb_phase_quantity(str(name).encode(), C.byref(out)))
+    return int(out.value)
+
+
+def phase_quantities() -> tuple:
+    """The names of the per-body quantities a phase map bins and sums, in the order of their ids
+    (nb_phase_quantity_name)."""
+    L = _lib.lib()
+    return tuple(L.nb_phase_quantity_name(q).decode() for q in range(_lib.NB_PHASE_Q_COUNT))
+
+
+def phase_edges(lo: float, hi: float, cells: int, log: bool = False) -> np.ndarray:
+    """The cells + 1 edges of one side of a phase map: map_edges() (linear), or edges with a constant ratio from
+    lo > 0 (radial_edges() up to its 256 bins, the same expression lo (hi / lo)^(k / cells) beyond)."""
+    if not log:
+        return map_edges(lo, hi, cells)
+    if int(cells) <= _lib.NB_RADIAL_MAX_BINS:
+        return radial_edges(lo, hi, cells, log=True)
+    lo, hi, cells = float(lo), float(hi), int(cells)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo < hi):
+        raise ValueError("log edges need finite 0 < lo < hi")
+    out = lo * np.power(hi / lo, np.arange(cells + 1, dtype=np.float64) / cells)
+    out[0], out[cells] = lo, hi
+    return out
+
+
+@dataclass(frozen=True)
+class PhaseStats:
+    """nb_phase_stats.  undefined_count: the bodies whose x, y or weight is not finite (they are among the
+    outside_count); binned_count + outside_count + nonfinite == n."""
+    step_num: int
+    n: int
+    nonfinite: int
+    binned_count: int
+    outside_count: int
+    undefined_count: int
+    binned_mass: float
+    outside_mass: float
+    total_mass: float            # nb_phase_stats.mass: all finite bodies
+    center: np.ndarray
+    velocity: np.ndarray
+    n_hat: np.ndarray
+    e1: np.ndarray
+    e2: np.ndarray
+    flags: int
+    max_count: int
+    x: str                       # the names of the three quantities; weight None without one
+    y: str
+    weight: Optional[str]
+
+
+@dataclass(frozen=True)
+class PhaseMap:
+    """nb_phase_map_sim's counts, planes and nb_phase_stats (include/nbody.h "Phase maps"; no reference
+    counterpart): the bodies of the state read_particles would return, binned on two per-body quantities --
+    x along the columns, y along the rows, row 0 the smallest y -- and summed per cell on the device.
+    counts: (H, W) uint32; mass (H, W) float64; m_q and m_q2, the sums of mass times the weight quantity and its
+    square, None unless a weight was asked for."""
+    counts: np.ndarray
+    mass: np.ndarray
+    m_q: Optional[np.ndarray]
+    m_q2: Optional[np.ndarray]
+    x_edges: np.ndarray          # W + 1
+    y_edges: np.ndarray          # H + 1
+    stats: PhaseStats
+
+    def _per_mass(self, plane):
+        if plane is None:
+            raise ValueError("this phase map was taken without a weight")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.mass != 0.0, plane / self.mass, np.nan)
+
+    @property
+    def mean_q(self) -> np.ndarray:
+        """Mass-weighted mean of the weight quantity per cell (NaN in a cell without mass)."""
+        return self._per_mass(self.m_q)
+
+    @property
+    def sigma_q(self) -> np.ndarray:
+        """Mass-weighted dispersion of the weight quantity per cell: sqrt(max(0, m_q2 / mass - mean_q^2))."""
+        mean = self.mean_q
+        return np.sqrt(np.maximum(self._per_mass(self.m_q2) - mean * mean, 0.0))
+
+    @property
+    def density(self) -> np.ndarray:
+        """mass per unit of x times y (NaN in a cell without mass; a cell with an infinite edge has density 0)."""
+        area = np.outer(np.diff(self.y_edges), np.diff(self.x_edges))
+        return np.where(self.mass != 0.0, self.mass / area, np.nan)
+
+    def marginal_x(self) -> np.ndarray:
+        """The mass per column: the distribution of x over the binned bodies."""
+        return self.mass.sum(axis=0)
+
+    def marginal_y(self) -> np.ndarray:
+        """The mass per row: the distribution of y over the binned bodies."""
+        return self.mass.sum(axis=1)
+
+
+def _phase_side(what, edges, rng, cells, log):
+    if edges is not None:
+        if rng is not None:
+            raise ValueError(f"give {what}_edges or {what}_range, not both")
+        return np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if rng is None:
+        raise ValueError(f"a phase map needs {what}_edges or {what}_range")
+    return phase_edges(rng[0], rng[1], cells, log)
+
+
+def _phase_map(call, handle, n, step_now, x, y, x_edges, y_edges, weight, values, axis, center, velocity,
+               check_step) -> PhaseMap:
+    p = _lib.nb_phase_params()
+    names = (str(x), str(y), None if weight is None else str(weight))
+    p.x, p.y = phase_quantity(names[0]), phase_quantity(names[1])
+    p.q = _lib.NB_PHASE_Q_MASS if weight is None else phase_quantity(names[2])
+    p.flags = 0 if weight is None else _lib.NB_PHASE_WEIGHT
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com", "density" or three coordinates')
+        if velocity is not None:
+            raise ValueError('center="com" brings its own velocity')
+        p.flags |= _lib.NB_PHASE_CENTER_COM
+    else:
+        velocity = (0.0, 0.0, 0.0) if velocity is None else velocity
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    if len(x_edges) < 2 or len(y_edges) < 2:
+        raise ValueError("a side of a phase map needs at least two edges")
+    p.width, p.height = len(x_edges) - 1, len(y_edges) - 1
+    dp = C.POINTER(C.c_double)
+    p.x_edges, p.y_edges = x_edges.ctypes.data_as(dp), y_edges.ctypes.data_as(dp)
+    if values is not None:
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if values.shape[0] != n:
+            raise ValueError(f"values needs one entry per body ({n}), not {values.shape[0]}")
+        p.values = values.ctypes.data_as(dp)
+    # values in hand were read off the state as it is now unless the caller says otherwise (check_step: a step number)
+    p.step_num = _lib.NB_PHASE_ANY_STEP if check_step is False else step_now if check_step is True else int(check_step)
+    ok = 1 <= p.width <= _lib.NB_MAP_MAX_SIDE and 1 <= p.height <= _lib.NB_MAP_MAX_SIDE and \
+        p.width * p.height <= _lib.NB_MAP_MAX_CELLS
+    h, w = (p.height, p.width) if ok else (1, 1)  # (the call refuses the sizes itself)
+    nplanes = 1 if weight is None else 3
+    counts = np.empty((h, w), dtype=np.uint32)
+    planes = np.empty((nplanes, h, w), dtype=np.float64)
+    st = _lib.nb_phase_stats()
+    check(call(handle, C.byref(p), counts.ctypes.data, planes.ctypes.data, C.byref(st)))
+    vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+    stats = PhaseStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.binned_count), int(st.outside_count),
+                       int(st.undefined_count), float(st.binned_mass), float(st.outside_mass), float(st.mass),
+                       vec(st.center), vec(st.velocity), vec(st.n_hat), vec(st.e1), vec(st.e2), int(st.flags),
+                       int(st.max_count), *names)
+    rest = [planes[1], planes[2]] if weight is not None else [None, None]
+    return PhaseMap(counts, planes[0], *rest, x_edges, y_edges, stats)
 
 
 FOF_NONE = _lib.NB_FOF_NONE
@@ -1873,6 +2033,38 @@ class _Passes:
             center, velocity = d.center, d.center_velocity
         return _projected_map(self._pass("map"), self._h, width, height, extent, axis, center, velocity, depth,
                               velocities)
+
+    def phase_map(self, x: str, y: str, *, x_edges=None, y_edges=None, x_range=None, y_range=None, bins=(128, 128),
+                  log=(False, False), weight: Optional[str] = None, values=None, axis=(0.0, 1.0, 0.0), center="com",
+                  velocity=None, check_step=True) -> PhaseMap:
+        """The 2-D histogram of the current state on two per-body quantities (nb_phase_map_sim): x and y are names
+        of phase_quantities() -- "a", "b", "h", "R", "r", "ua", "ub", "w", "u_R", "u_phi", "u_r", "u_t", "speed",
+        "j_z", "j", "e_kin", "mass", "value" -- in the frame of map_frame(axis) about the centre.  Per side either
+        the edges (strictly ascending; the first may be -inf, the last +inf) or a range (lo, hi) with bins[side]
+        cells, log[side] for a constant ratio (phase_edges()).  weight: a third quantity whose mass-weighted mean
+        and dispersion per cell the PhaseMap gives.  values: one float64 per body of read_particles() now, the
+        quantity "value" (a potential from field(), a density from knn_density(), an energy from bound_groups()).
+        center: "com" (the centre of mass and its velocity P/M, as diagnostics() returns them), three coordinates,
+        then with `velocity` (default: at rest), or "density": the density centre and its velocity of
+        knn_density(6), passed on as explicit values.  check_step: True takes `values` as made from the state as it
+        is now; a step number names the step they were made at, to have stale ones refused (a TreeSim reorders its
+        bodies every step); False: not checked.  A several-GPU runner refuses."""
+        if isinstance(center, str) and center == "density":
+            if velocity is not None:
+                raise ValueError('center="density" brings its own velocity')
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
+        xe = _phase_side("x", x_edges, x_range, bins[0], log[0])
+        ye = _phase_side("y", y_edges, y_range, bins[1], log[1])
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _phase_map(getattr(_lib.lib(), "nb_phase_map_" + suffix), self._h,
+                          int(self.sim_params().particle_num), int(self.step_num()), x, y, xe, ye, weight, values, axis,
+                          center, velocity, check_step)
+
+    def distribution(self, x: str, edges, **kw) -> PhaseMap:
+        """The 1-D distribution of quantity x over `edges`: a phase map of height 1 with y = "mass" on the edges
+        (-inf, +inf); the other arguments are phase_map's.  counts[0], mass[0] and marginal_x() are the histogram."""
+        return self.phase_map(x, "mass", x_edges=edges, y_edges=(-np.inf, np.inf), **kw)
 
     def fof_groups(self, link: float, *, min_members: int = 20, labels: bool = True) -> FofGroups:
         """The friends-of-friends groups of the current state (nb_sim_fof): bodies within `link` of each

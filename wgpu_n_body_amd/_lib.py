@@ -111,6 +111,24 @@ class nb_map_stats(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_count", C.c_uint32)]
 
 
+class nb_phase_params(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("x", C.c_uint32), ("y", C.c_uint32), ("q", C.c_uint32), ("reserved2", C.c_uint32),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("x_edges", C.POINTER(C.c_double)), ("y_edges", C.POINTER(C.c_double)),
+                ("values", C.POINTER(C.c_double)), ("step_num", C.c_uint64)]
+
+
+class nb_phase_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("binned_count", C.c_uint64), ("outside_count", C.c_uint64), ("undefined_count", C.c_uint64),
+                ("binned_mass", C.c_double), ("outside_mass", C.c_double), ("mass", C.c_double),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3),
+                ("n_hat", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("max_count", C.c_uint32),
+                ("x", C.c_uint32), ("y", C.c_uint32), ("q", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class nb_fof_params(C.Structure):
     _fields_ = [("link", C.c_double), ("min_members", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
@@ -318,6 +336,7 @@ assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
 assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.sizeof(nb_field_stats) == 48
 assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
+assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
 assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
@@ -348,6 +367,8 @@ NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
+NB_PHASE_CENTER_COM, NB_PHASE_WEIGHT, NB_PHASE_ANY_STEP = 1, 2, 0xFFFFFFFFFFFFFFFF
+NB_PHASE_Q_COUNT, NB_PHASE_Q_MASS, NB_PHASE_Q_VALUE = 18, 16, 17
 NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
 NB_BOUND_MAX_ITER = 64
@@ -380,6 +401,7 @@ ABI_SYMBOLS = [
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
+    "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
@@ -475,6 +497,13 @@ def lib() -> C.CDLL:
     disc_modes = [vp, P(nb_modes_params), P(nb_modes_head), vp, vp]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_disc_modes_" + suffix).argtypes = disc_modes
+    # ... and the fifteenth (include/nbody.h "Phase maps")
+    phase_map = [vp, P(nb_phase_params), vp, vp, P(nb_phase_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_phase_map_" + suffix).argtypes = phase_map
+    L.nb_phase_quantity.argtypes = [C.c_char_p, P(C.c_uint32)]
+    L.nb_phase_quantity_name.argtypes = [C.c_uint32]
+    L.nb_phase_quantity_name.restype = C.c_char_p
     L.nb_disc_modes_derive.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     for name in ("nb_radial_edges_log", "nb_radial_edges_linear"):
         getattr(L, name).argtypes = [C.c_double, C.c_double, C.c_uint32, P(C.c_double)]

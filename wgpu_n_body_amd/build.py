@@ -54,6 +54,8 @@ SOURCES = [
     # the frame, the recurrence and the three-level sums are specified operation by operation: no FMA
     # contraction
     ("nb_modes.hip", ["-ffp-contract=off"]),
+    # the quantities and the cell rule are specified operation by operation: no FMA contraction
+    ("nb_phase.hip", ["-ffp-contract=off"]),
     # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
     ("nb_simbase.cpp", []),

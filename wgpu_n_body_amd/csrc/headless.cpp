@@ -18,6 +18,8 @@
 //             [--shapes-iter I] [--shapes-top T]]
 //            [--lagr K [--lagr-fractions F1,F2,...] [--lagr-center com|X,Y,Z]]
 //            [--radii K --radii-link B [--radii-min M] [--radii-top T]]
+//            [--phase DIR [--phase-every K] --phase-x NAME,LO,HI,CELLS[,log] --phase-y NAME,LO,HI,CELLS[,log]
+//             [--phase-weight NAME] [--phase-axis X,Y,Z] [--phase-center com|X,Y,Z]]
 //            [--modes K --modes-range RMIN,RMAX [--modes-bins B] [--modes-m M] [--modes-log 0|1]
 //             [--modes-axis X,Y,Z] [--modes-center com|X,Y,Z]]
 //            [--knn K [--knn-k 6]]
@@ -105,6 +107,15 @@
 // largest groups (--radii-top, default 0) as "radii_group <step> <row> <count> <mass> <r10> <r50> <r90> <r_vmax>
 // <vc2_max>" (every real %.17g).  The time it takes is not part of any "Step Duration"; without --radii the output
 // is unchanged.
+//
+// --phase DIR writes the phase map (nb_phase_map_runner) of step 0 and of every K-th step (--phase-every, default 1)
+// as DIR/phase_<step, 6 digits>.npy: the layout of --maps, shape (1 + P, H, W) -- the counts as doubles, then the
+// mass and, with --phase-weight NAME, the sums of mass times that quantity and its square.  --phase-x and --phase-y
+// name the quantity of the columns and of the rows (include/nbody.h "Phase maps": a, b, h, R, r, ua, ub, w, u_R,
+// u_phi, u_r, u_t, speed, j_z, j, e_kin, mass) with CELLS cells between LO and HI, of constant ratio with ",log",
+// in the frame of --phase-axis (default 0,1,0) about the centre of mass unless --phase-center gives a point (at
+// rest).  One line per map "phase <step> <binned> <outside> <undefined> <nonfinite> <max_count>".  DIR must exist.
+// The time they take is not part of any "Step Duration"; without --phase the output is unchanged.
 //
 // --modes K measures the azimuthal Fourier sums (nb_disc_modes_runner) of step 0 and of every K-th step in B annuli
 // (--modes-bins, default 32; --modes-log 1: of constant ratio) between RMIN and RMAX about --modes-axis (default
@@ -277,6 +288,51 @@ static bool write_map(nbody::OfflineHeadless<Sim> &runner, const MapOptions &mo)
     std::printf("map %llu %llu %llu %llu %u\n", (unsigned long long)m.stats.step_num,
                 (unsigned long long)m.stats.binned_count, (unsigned long long)m.stats.outside_count,
                 (unsigned long long)m.stats.nonfinite, m.stats.max_count);
+    return true;
+}
+
+struct PhaseSide {
+    std::string name;
+    double lo = 0.0, hi = 0.0;
+    uint32_t cells = 0;
+    bool log = false;
+};
+
+struct PhaseOptions {
+    std::string dir, weight;
+    int every = 1;
+    PhaseSide x, y;
+    std::array<double, 3> axis{0.0, 1.0, 0.0};
+    std::vector<double> center;  // empty: the centre of mass
+};
+
+// NAME,LO,HI,CELLS[,log]
+static bool parse_phase_side(const std::string &v, PhaseSide *side) {
+    const size_t comma = v.find(',');
+    if (comma == std::string::npos) return false;
+    side->name = v.substr(0, comma);
+    char tail[8] = "";
+    const int got = std::sscanf(v.c_str() + comma + 1, "%lf,%lf,%u,%7s", &side->lo, &side->hi, &side->cells, tail);
+    if (got < 3 || (got == 4 && std::string(tail) != "log")) return false;
+    side->log = got == 4;
+    return true;
+}
+
+template <class Sim>
+static bool write_phase(nbody::OfflineHeadless<Sim> &runner, const PhaseOptions &po) {
+    nbody::PhaseParams p = nbody::phase_params(po.x.name, po.y.name, po.weight, po.axis);
+    if (!po.center.empty()) {
+        p.flags &= ~NB_PHASE_CENTER_COM;
+        for (int k = 0; k < 3; ++k) p.center[k] = po.center[(size_t)k];
+    }
+    const nbody::PhaseMap m = runner.phase_map(p, nbody::phase_edges(po.x.lo, po.x.hi, po.x.cells, po.x.log),
+                                               nbody::phase_edges(po.y.lo, po.y.hi, po.y.cells, po.y.log));
+    char name[64];
+    std::snprintf(name, sizeof name, "/phase_%06llu.npy", (unsigned long long)m.stats.step_num);
+    if (!write_npy_planes(po.dir + name, m.width, m.height, m.counts, m.planes)) return false;
+    std::printf("phase %llu %llu %llu %llu %llu %u\n", (unsigned long long)m.stats.step_num,
+                (unsigned long long)m.stats.binned_count, (unsigned long long)m.stats.outside_count,
+                (unsigned long long)m.stats.undefined_count, (unsigned long long)m.stats.nonfinite, m.stats.max_count);
     return true;
 }
 
@@ -593,7 +649,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
-               const ModesOptions &modes) {
+               const ModesOptions &modes, const PhaseOptions &phase) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -612,6 +668,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (lagr.every > 0) print_lagr(runner, lagr);
     if (radii.every > 0) print_radii(runner, radii);
     if (modes.every > 0) print_modes(runner, modes);
+    if (!phase.dir.empty() && !write_phase(runner, phase)) return 1;
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -633,6 +690,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (lagr.every > 0 && (i + 1) % lagr.every == 0) print_lagr(runner, lagr);
         if (radii.every > 0 && (i + 1) % radii.every == 0) print_radii(runner, radii);
         if (modes.every > 0 && (i + 1) % modes.every == 0) print_modes(runner, modes);
+        if (!phase.dir.empty() && (i + 1) % phase.every == 0 && !write_phase(runner, phase)) return 1;
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
     std::puts("Finished Running");
@@ -667,6 +725,7 @@ int main(int argc, char **argv) {
     LagrOptions lagr;
     RadiiCliOptions radii;
     ModesOptions modes;
+    PhaseOptions phase;
     bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
@@ -828,6 +887,29 @@ int main(int argc, char **argv) {
         else if (k == "--radii-link") radii.link = std::atof(v.c_str());
         else if (k == "--radii-min") radii.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--radii-top") radii.top = std::atoi(v.c_str());
+        else if (k == "--phase") phase.dir = v;
+        else if (k == "--phase-every") phase.every = std::max(1, std::atoi(v.c_str()));
+        else if (k == "--phase-x" || k == "--phase-y") {
+            if (!parse_phase_side(v, k == "--phase-x" ? &phase.x : &phase.y)) {
+                std::fprintf(stderr, "%s takes NAME,LO,HI,CELLS[,log], not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--phase-weight") phase.weight = v;
+        else if (k == "--phase-axis") {
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &phase.axis[0], &phase.axis[1], &phase.axis[2]) != 3) {
+                std::fprintf(stderr, "--phase-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--phase-center") {
+            phase.center.assign(3, 0.0);
+            if (v == "com") phase.center.clear();
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &phase.center[0], &phase.center[1], &phase.center[2]) != 3) {
+                std::fprintf(stderr, "--phase-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--modes") modes.every = std::atoi(v.c_str());
         else if (k == "--modes-range") {
             if (std::sscanf(v.c_str(), "%lf,%lf", &modes.rmin, &modes.rmax) != 2) {
@@ -987,6 +1069,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--shapes-reduced 1 needs --shapes-radius KRMS > 0\n");
         return 2;
     }
+    if (!phase.dir.empty() && (phase.x.cells == 0 || phase.y.cells == 0)) {
+        std::fprintf(stderr, "--phase needs --phase-x and --phase-y NAME,LO,HI,CELLS[,log]\n");
+        return 2;
+    }
     if (modes.every > 0 && (!modes.have_range || modes.mmax < 2)) {
         std::fprintf(stderr, "--modes needs --modes-range RMIN,RMAX and --modes-m M >= 2\n");
         return 2;
@@ -1005,9 +1091,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -213,6 +213,17 @@ static int pass_disc_modes(H *h, const nb_modes_params *params, nb_modes_head *o
 }
 
 template <class H>
+static int pass_phase_map(H *h, const nb_phase_params *params, uint32_t *counts, double *planes,
+                          nb_phase_stats *stats) {
+    PhasePlan plan{};
+    if (int rc = phase_check_params(params, &plan)) return rc;
+    return on_sim(h, "phase_map", [&](SimBase &s) {
+        if (int rc = phase_check_args(s, params, plan)) return rc;
+        return sim_phase_map(s, *params, plan, counts, planes, stats);
+    });
+}
+
+template <class H>
 static int pass_smooth_map(H *h, const nb_smooth_params *params, const double *s, uint32_t *counts, double *planes,
                            nb_smooth_stats *stats) {
     NB_GUARD({
@@ -246,6 +257,8 @@ static bool multiple_in(int v, int step, int hi) { return v >= step && v <= hi &
 static const TuningKey kTuningKeys[] = {
     {"field_launch_pairs_log2", &SimBase::field_pairs_log2, "16..40", [](int v) { return v >= 16 && v <= 40; }},
     {"map_segment_len", &SimBase::map_segment_len, "a multiple of 256 in 256..65536",
+     [](int v) { return multiple_in(v, 256, 65536); }},
+    {"phase_segment_len", &SimBase::phase_segment_len, "a multiple of 256 in 256..65536",
      [](int v) { return multiple_in(v, 256, 65536); }},
     {"smooth_segment_len", &SimBase::smooth_segment_len, "a multiple of 256 in 256..65536",
      [](int v) { return multiple_in(v, 256, 65536); }},
@@ -478,6 +491,17 @@ int nb_map_frame(const double axis[3], double n_hat[3], double e1[3], double e2[
     return map_frame(axis, n_hat, e1, e2);
 }
 int nb_map_edges(double lo, double hi, uint32_t cells, double *edges) { return map_edges(lo, hi, cells, edges); }
+
+int nb_phase_map_sim(nb_sim *sim, const nb_phase_params *params, uint32_t *counts, double *planes,
+                     nb_phase_stats *stats) {
+    return pass_phase_map(sim, params, counts, planes, stats);
+}
+int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32_t *counts, double *planes,
+                        nb_phase_stats *stats) {
+    return pass_phase_map(runner, params, counts, planes, stats);
+}
+int nb_phase_quantity(const char *name, uint32_t *id) { return phase_quantity(name, id); }
+const char *nb_phase_quantity_name(uint32_t id) { return phase_quantity_name(id); }
 
 int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
                size_t group_capacity, nb_fof_stats *stats) {

@@ -687,6 +687,95 @@ int map_check_params(const nb_map_params *p, MapPlan *plan) {
     return NB_OK;
 }
 
+// nb_phase_quantity / nb_phase_quantity_name: the names of NB_PHASE_Q_*, in the enum's order
+static const char *const kPhaseNames[NB_PHASE_Q_COUNT] = {"a",   "b",     "h",   "R",     "r",   "ua", "ub",    "w",    "u_R",
+                                                          "u_phi", "u_r", "u_t", "speed", "j_z", "j",  "e_kin", "mass", "value"};
+
+int phase_quantity(const char *name, uint32_t *id) {
+    if (!name || !id) {
+        set_error("phase_quantity: null argument");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t q = 0; q < NB_PHASE_Q_COUNT; ++q)
+        if (std::string(name) == kPhaseNames[q]) {
+            *id = q;
+            return NB_OK;
+        }
+    set_error("phase_quantity: no quantity is called '%s'", name);
+    return NB_ERR_INVALID;
+}
+
+const char *phase_quantity_name(uint32_t id) { return id < NB_PHASE_Q_COUNT ? kPhaseNames[id] : nullptr; }
+
+// nb_phase_map_sim: the edges of one side, strictly ascending, the interior ones finite; the first may be -inf
+// and the last +inf
+static int phase_check_edges(const char *what, const double *e, uint32_t cells) {
+    for (uint32_t i = 0; i <= cells; ++i) {
+        const bool outer_ok = (i == 0 && e[i] == -INFINITY) || (i == cells && e[i] == INFINITY);
+        if (!(std::isfinite(e[i]) || outer_ok) || (i > 0 && !(e[i] > e[i - 1]))) {
+            set_error("phase_map: %s must be strictly ascending with finite interior edges (%s[%u] = %g)", what, what, i,
+                      e[i]);
+            return NB_ERR_INVALID;
+        }
+    }
+    return NB_OK;
+}
+
+// nb_phase_map_sim: everything that can be refused without a device; the frame on the way
+int phase_check_params(const nb_phase_params *p, PhasePlan *plan) {
+    if (!p || !p->x_edges || !p->y_edges) {
+        set_error("phase_map: null %s", !p ? "params" : !p->x_edges ? "x_edges" : "y_edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->width < 1 || p->width > NB_MAP_MAX_SIDE || p->height < 1 || p->height > NB_MAP_MAX_SIDE) {
+        set_error("phase_map: a side must be 1..%u cells (got %u x %u)", NB_MAP_MAX_SIDE, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)p->width * p->height > NB_MAP_MAX_CELLS) {
+        set_error("phase_map: at most %u cells (got %u x %u)", NB_MAP_MAX_CELLS, p->width, p->height);
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~(NB_PHASE_CENTER_COM | NB_PHASE_WEIGHT)) || p->reserved || p->reserved2) {
+        set_error("phase_map: unknown flag bits 0x%x or a reserved field != 0",
+                  p->flags & ~(NB_PHASE_CENTER_COM | NB_PHASE_WEIGHT));
+        return NB_ERR_INVALID;
+    }
+    if (p->x >= NB_PHASE_Q_COUNT || p->y >= NB_PHASE_Q_COUNT || p->q >= NB_PHASE_Q_COUNT) {
+        set_error("phase_map: unknown quantity id (x %u, y %u, q %u; ids end at %u)", p->x, p->y, p->q,
+                  NB_PHASE_Q_COUNT - 1);
+        return NB_ERR_INVALID;
+    }
+    if (!axis_frame(p->axis, plan->n, plan->e1, plan->e2)) {
+        set_error("phase_map: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    if (!(p->flags & NB_PHASE_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("phase_map: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    if (int rc = phase_check_edges("x_edges", p->x_edges, p->width)) return rc;
+    if (int rc = phase_check_edges("y_edges", p->y_edges, p->height)) return rc;
+    plan->uses_values = p->x == NB_PHASE_Q_VALUE || p->y == NB_PHASE_Q_VALUE ||
+                        ((p->flags & NB_PHASE_WEIGHT) && p->q == NB_PHASE_Q_VALUE);
+    if (plan->uses_values && !p->values) {
+        set_error("phase_map: the quantity `value` needs params->values");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// ... and what needs the simulator's step number: `values` is in the order of the bodies now
+int phase_check_args(const SimBase &s, const nb_phase_params *p, const PhasePlan &plan) {
+    if (plan.uses_values && p->step_num != NB_PHASE_ANY_STEP && p->step_num != s.step_num) {
+        set_error("phase_map: the values were made at step %llu, the simulator is at step %llu",
+                  (unsigned long long)p->step_num, (unsigned long long)s.step_num);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_smooth_centres / nb_sim_smooth_map: the `cells` pixel centres of a window, from the edges of nb_map_edges
 static void smooth_centres(double lo, double hi, uint32_t cells, double size, double *out) {
     double prev = lo;  // xe[i]

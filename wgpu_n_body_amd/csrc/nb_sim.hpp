@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -125,6 +125,7 @@ class SimBase {
     std::unique_ptr<Workspace> work[kWorkSlots];  // the analysis passes' workspaces (nb_analysis.hpp)
     int field_pairs_log2 = 35;  // "field_launch_pairs_log2": pairs per launch of nb_sim_field, 2^16 .. 2^40
     int map_segment_len = 4096;  // "map_segment_len": bodies of a tile summed by one block of nb_sim_map
+    int phase_segment_len = 4096;  // "phase_segment_len": bodies of a tile summed by one block of nb_phase_map_sim
     int smooth_segment_len = 4096;  // "smooth_segment_len": entries of a tile summed by one block of nb_sim_smooth_map
     int fof_chunk_len = 1024;    // "fof_chunk_len": bodies of a cell or a catalogue row per work item of nb_sim_fof
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
@@ -171,6 +172,19 @@ struct MapPlan {
 int map_check_params(const nb_map_params *p, MapPlan *plan);
 int sim_map(SimBase &sim, const nb_map_params &params, const MapPlan &plan, uint32_t *counts, double *planes,
             nb_map_stats *stats);
+// nb_phase.hip: nb_phase_map_sim behind the handle; phase_check_params also forms the frame, phase_check_args is
+// what needs the simulator's step number; phase_quantity / phase_quantity_name: the table of names behind
+// nb_phase_quantity / nb_phase_quantity_name
+struct PhasePlan {
+    double n[3], e1[3], e2[3];  // axis_frame of the caller's axis
+    bool uses_values;           // x, y or (NB_PHASE_WEIGHT) q is NB_PHASE_Q_VALUE
+};
+int phase_check_params(const nb_phase_params *p, PhasePlan *plan);
+int phase_check_args(const SimBase &sim, const nb_phase_params *p, const PhasePlan &plan);
+int sim_phase_map(SimBase &sim, const nb_phase_params &params, const PhasePlan &plan, uint32_t *counts, double *planes,
+                  nb_phase_stats *stats);
+int phase_quantity(const char *name, uint32_t *id);
+const char *phase_quantity_name(uint32_t id);
 // nb_fof.hip: nb_sim_fof behind the handle
 int fof_check_params(const nb_fof_params *p);
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,

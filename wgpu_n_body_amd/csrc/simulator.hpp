@@ -39,6 +39,8 @@ using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and c
 using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
 using MapParams = nb_map_params;          // grid, window, line of sight and centre of a projected map
 using MapStats = nb_map_stats;
+using PhaseParams = nb_phase_params;      // quantities, flags, centre and axis of a phase map (the edges are set by the call)
+using PhaseStats = nb_phase_stats;
 using FofGroup = nb_fof_group;            // 80 B: label, count and the nine sums of a catalogued group
 using FofStats = nb_fof_stats;
 using BoundGroup = nb_bound_group;        // 128 B: a catalogued group's bound set
@@ -297,6 +299,79 @@ ProjectedMap projected_map(int (*call)(H *, const nb_map_params *, uint32_t *, d
     m.width = ok ? p.width : 1;
     m.height = ok ? p.height : 1;
     m.nplanes = (p.flags & NB_MAP_VELOCITY) ? 6 : 1;
+    m.counts.resize((size_t)m.width * m.height);
+    m.planes.resize((size_t)m.nplanes * m.width * m.height);
+    check(call(h, &p, m.counts.data(), m.planes.data(), &m.stats));
+    return m;
+}
+}  // namespace detail
+
+// A phase map (no reference counterpart): the bodies binned on two per-body quantities, x along the columns and y
+// along the rows, width * height counts, the planes (1, or 3 with NB_PHASE_WEIGHT: mass, m_q, m_q2) plane-major,
+// the edges they lie between and what the call measured
+struct PhaseMap {
+    uint32_t width = 0, height = 0, nplanes = 0;
+    std::vector<uint32_t> counts;
+    std::vector<double> planes;
+    std::vector<double> x_edges, y_edges;
+    PhaseStats stats{};
+    const double *plane(uint32_t k) const { return planes.data() + (size_t)k * width * height; }
+};
+
+// the id of the per-body quantity called `name` (nb_phase_quantity)
+inline uint32_t phase_quantity(const std::string &name) {
+    uint32_t id = 0;
+    check(nb_phase_quantity(name.c_str(), &id));
+    return id;
+}
+
+// the cells + 1 edges of one side: nb_map_edges, or (log) a constant ratio from lo > 0 -- nb_radial_edges_log up to
+// its NB_RADIAL_MAX_BINS bins, the same expression lo (hi / lo)^(k / cells) beyond
+inline std::vector<double> phase_edges(double lo, double hi, uint32_t cells, bool log = false) {
+    std::vector<double> e((size_t)cells + 1);
+    if (!log) {
+        check(nb_map_edges(lo, hi, cells, e.data()));
+    } else if (cells <= NB_RADIAL_MAX_BINS) {
+        check(nb_radial_edges_log(lo, hi, cells, e.data()));
+    } else {
+        if (!(lo > 0.0 && hi > lo && std::isfinite(hi))) throw std::invalid_argument("log edges need finite 0 < lo < hi");
+        for (uint32_t k = 0; k <= cells; ++k) e[k] = lo * std::pow(hi / lo, (double)k / (double)cells);
+        e[0] = lo;
+        e[cells] = hi;
+    }
+    return e;
+}
+
+// The parameters of a phase map of x against y about the centre of mass in the frame of `axis`; weight: the name of
+// the quantity to sum, or empty
+inline PhaseParams phase_params(const std::string &x, const std::string &y, const std::string &weight = "",
+                                const std::array<double, 3> &axis = {0.0, 1.0, 0.0}) {
+    PhaseParams p{};
+    p.x = phase_quantity(x);
+    p.y = phase_quantity(y);
+    p.q = weight.empty() ? (uint32_t)NB_PHASE_Q_MASS : phase_quantity(weight);
+    p.flags = NB_PHASE_CENTER_COM | (weight.empty() ? 0u : NB_PHASE_WEIGHT);
+    for (int k = 0; k < 3; ++k) p.axis[k] = axis[(size_t)k];
+    p.step_num = NB_PHASE_ANY_STEP;
+    return p;
+}
+
+namespace detail {
+template <class H>
+PhaseMap phase_map(int (*call)(H *, const nb_phase_params *, uint32_t *, double *, nb_phase_stats *), H *h,
+                   PhaseParams p, const std::vector<double> &x_edges, const std::vector<double> &y_edges) {
+    PhaseMap m;
+    m.x_edges = x_edges;
+    m.y_edges = y_edges;
+    p.width = x_edges.empty() ? 0 : (uint32_t)(x_edges.size() - 1);
+    p.height = y_edges.empty() ? 0 : (uint32_t)(y_edges.size() - 1);
+    p.x_edges = m.x_edges.data();
+    p.y_edges = m.y_edges.data();
+    const bool ok = p.width >= 1 && p.width <= NB_MAP_MAX_SIDE && p.height >= 1 && p.height <= NB_MAP_MAX_SIDE &&
+                    (uint64_t)p.width * p.height <= NB_MAP_MAX_CELLS;  // (the call refuses the sizes itself)
+    m.width = ok ? p.width : 1;
+    m.height = ok ? p.height : 1;
+    m.nplanes = (p.flags & NB_PHASE_WEIGHT) ? 3 : 1;
     m.counts.resize((size_t)m.width * m.height);
     m.planes.resize((size_t)m.nplanes * m.width * m.height);
     check(call(h, &p, m.counts.data(), m.planes.data(), &m.stats));
@@ -839,6 +914,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto group_shapes = nb_sim_group_shapes;
     static constexpr auto group_radii = nb_group_radii_sim;
     static constexpr auto disc_modes = nb_disc_modes_sim;
+    static constexpr auto phase_map = nb_phase_map_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -857,6 +933,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto group_shapes = nb_runner_group_shapes;
     static constexpr auto group_radii = nb_group_radii_runner;
     static constexpr auto disc_modes = nb_disc_modes_runner;
+    static constexpr auto phase_map = nb_phase_map_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -889,6 +966,11 @@ class Passes {
     }
     // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
     ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(Abi::map, h_, p); }
+    // the bodies of the current state binned on p.x and p.y between the edges, p.q summed with NB_PHASE_WEIGHT;
+    // p: phase_params(); p.values (the quantity "value") must hold one double per body of read_particles() now
+    PhaseMap phase_map(const PhaseParams &p, const std::vector<double> &x_edges, const std::vector<double> &y_edges) {
+        return detail::phase_map(Abi::phase_map, h_, p, x_edges, y_edges);
+    }
     // the friends-of-friends groups of the current state: bodies within `link` are friends
     FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
         return detail::fof_groups(Abi::fof, h_, n_bodies(), link, min_members, labels);
