@@ -550,6 +550,87 @@ int nb_field_ring_means(const double center[3], const double axis[3], const doub
                         uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out);
 
 /* ------------------------------------------------------------------------- */
+/* Tidal tensor probes -- the exact gradient of the field at arbitrary points, */
+/* and a disc's epicyclic and vertical frequencies from it (no reference       */
+/* counterpart)                                                                */
+/* ------------------------------------------------------------------------- */
+/* T_ab = d acc_a / d x_b of the field above, summed pair by pair on the device as
+ * the field is -- differencing nb_sim_field cannot resolve it: the points and the
+ * pair terms are fp32, and a step small enough for a cored law is below the
+ * rounding of the difference.  The rule, which DESIGN.md 6r states in full.  The
+ * bodies, d, r2, r, g, e and `coincident` are those of "Field probes": the sums run
+ * over the bodies nb_sim_diagnostics counts as finite, and a body with r2 == 0 adds
+ * nothing and is counted.  Differentiating acc = g sum_j m_j d / (r^4 + e r) by p:
+ *   w_j  = m_j / (r^4 + e r)                 (the field's own pair weight)
+ *   c_j  = (4 r^3 + e) / (r^2 (r^3 + e))
+ *   S_ab = sum_j w_j c_j d_a d_b             (six sums: xx, yy, zz, xy, xz, yz)
+ *   W    = sum_j w_j
+ *   T_ab = g (S_ab - delta_ab W)             (symmetric by construction)
+ * The trace is g sum_j m_j (r^3 - 2 e) / (r (r^3 + e)^2): not zero, because the
+ * reference's force is m / (r^3 + e).  No psi is involved: any e is accepted (the
+ * error bound below is derived for e >= 0).
+ * Arithmetic, in fp32 per pair, every operation rounded once (no contraction):
+ *   den = fma(e, r, r2 r2), w = rcp(den) m_j            (v_sqrt_f32, v_rcp_f32: 1 ulp)
+ *   r3 = r2 r, c = fma(4, r3, e) rcp(r2 (r3 + e)), wc = w c
+ *   t_a = wc d_a;  S_ab += fma(t_a, d_b, .) with a <= b;  W += w
+ * The range of the form is narrower than the field's.  A body whose r3 is not an
+ * fp32 number (r > 6.9e12) adds 0 to every sum (its w has underflowed already; the
+ * true term is below 2e-51 m_j).  A pair so close that w c exceeds fp32 -- about
+ * r^3 < m_j / (e 3e38), or r < (4 m_j / 3e38)^(1/6) for e = 0 -- gives inf or NaN
+ * in the sample: such a point is, to fp32, on the body, and outside the bound.
+ * Runs of exactly 64 consecutive bodies are summed in fp32; each run is folded into
+ * an fp64 sum; the waves and then the body chunks are added in fp64 in a fixed
+ * order; S_aa - W is formed once, in fp64, after all of that, so a diagonal
+ * element never cancels per pair; the result is multiplied once by (double)g.
+ * Against the same sums in binary64 each of the seven sums is within
+ *   (64 + NB_TIDAL_K) 2^-24 g sum_j |term_j|,    NB_TIDAL_K = 33,
+ * and a diagonal T_aa within the sum of the bounds of S_aa and W.  K counts the
+ * roundings of the pair form above weighted by how often each enters a term, to
+ * first order and for e >= 0 (DESIGN.md 6r derives it).
+ * No float atomics, and the grid and the chunking are functions of (m, n) alone:
+ * two calls return bit-identical samples, and a point's sample does not depend on
+ * its place in the array.  A point with a non-finite coordinate gets NaN (coincident
+ * 0) and is counted in stats.nonfinite_points; n = 0 gives zeros; m = 0 is valid,
+ * only synchronises and measures nothing.  The call is ordered after the enqueued
+ * steps on the simulator's stream, ends with one synchronisation, reports a
+ * TreeSim's status words as nb_sim_read_particles does, and does not change the
+ * trajectory.  The points go in bands as nb_sim_field's do, bounded by the same
+ * "field_launch_pairs_log2" (speed and testing only, identical samples).
+ * A Toomre Q or a Jacobi radius would assume a 1/r^2 force and are not offered. */
+#define NB_TIDAL_K 33u
+
+typedef struct nb_tidal_sample { /* 56 bytes */
+    double tensor[6];    /* xx, yy, zz, xy, xz, yz */
+    uint32_t coincident; /* bodies at the point itself (left out of every sum) */
+    uint32_t reserved;
+} nb_tidal_sample;
+
+typedef nb_field_stats nb_tidal_stats; /* the same fields; flags is 0 */
+
+/* The tidal tensor of a simulator's current state at `points` (3 floats per point) into out[0 .. m).
+ * stats may be null.  NB_ERR_INVALID for a null handle, null points or out with m > 0, or
+ * m > NB_FIELD_MAX_POINTS -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded
+ * simulator (placement world > 1).  Eigenvalues: nb_shape_eigen of (xx, xy, xz, yy, yz, zz). */
+int nb_tidal_sim(nb_sim *sim, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
+typedef struct nb_tidal_ring { /* means over the n_phi samples of one ring, and what follows from them */
+    double t_RR;   /* rhat . T rhat, rhat the unit vector from the axis to the fp32 point actually used */
+    double t_pp;   /* phihat . T phihat, phihat = n cross rhat */
+    double t_nn;   /* n . T n */
+    double t_Rn;   /* rhat . T n */
+    double omega2; /* -a_R / R_i of the field's ring row (NaN for R_i = 0) */
+    double kappa2; /* -t_RR + 3 omega2: R dOmega^2/dR + 4 Omega^2, for any central force law */
+    double nu2;    /* -t_nn */
+} nb_tidal_ring;
+/* Host only, a pure function of its arguments: the ring means of the tidal `samples` taken at the `points`
+ * nb_field_rings wrote for the same center, axis, radii, k and n_phi, in the frame of nb_field_ring_means, and
+ * the squared frequencies with a_R from `rings`, the rows nb_field_ring_means gave for the field at the same
+ * points.  A point on the axis has no rhat and adds 0 to t_RR, t_pp and t_Rn.  Refusals as nb_field_rings, and
+ * null samples, rings or out. */
+int nb_tidal_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
+                        uint32_t n_phi, const float *points, const nb_tidal_sample *samples,
+                        const nb_field_ring *rings, nb_tidal_ring *out);
+
+/* ------------------------------------------------------------------------- */
 /* Projected maps -- per-cell mass and velocity moments on a 2-D grid (no     */
 /* reference counterpart: structure in two dimensions, without symmetry)      */
 /* ------------------------------------------------------------------------- */
@@ -1973,6 +2054,9 @@ int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_mo
  * runner. */
 int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32_t *counts, double *planes,
                         nb_phase_stats *stats);
+/* nb_tidal_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_tidal_runner(nb_runner *runner, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 import math
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
@@ -37,7 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
-           "Field", "RingMeans", "field_rings", "ProjectedMap", "map_frame", "map_edges",
+           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "ProjectedMap", "map_frame", "map_edges",
            "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
@@ -470,6 +471,140 @@ def _circular_velocity(call, handle, radii, axis, center, n_phi, potential) -> R
                                          r.shape[0], int(n_phi), pts.ctypes.data, samples.ctypes.data,
                                          out.ctypes.data))
     return RingMeans(r, out["a_R"].copy(), out["a_n"].copy(), out["potential"].copy(), out["v_c"].copy(), f)
+
+
+@dataclass(frozen=True)
+class TidalField:
+    """nb_tidal_sample[M] + nb_tidal_stats (include/nbody.h "Tidal tensor probes"; no reference counterpart): the
+    exact tidal tensor T_ab = d acc_a / d x_b of the state read_particles would return, at M points."""
+    tensor: np.ndarray       # (M, 3, 3) float64, symmetric
+    coincident: np.ndarray   # (M,) uint32: bodies at the point itself, left out of every sum
+    step_num: int
+    n: int
+    nonfinite: int           # bodies left out, as diagnostics() counts them
+    points: int
+    nonfinite_points: int
+    launches: int
+
+    @property
+    def trace(self) -> np.ndarray:
+        """(M,): the divergence of the acceleration, T_xx + T_yy + T_zz."""
+        return self.tensor[:, 0, 0] + self.tensor[:, 1, 1] + self.tensor[:, 2, 2]
+
+    @functools.cached_property
+    def _eigen_cache(self):
+        """(eigenvalues, eigenvectors), computed once per object: one nb_shape_eigen call per finite sample."""
+        lam = np.full((self.tensor.shape[0], 3), np.nan)
+        axes = np.full((self.tensor.shape[0], 3, 3), np.nan)
+        eig, DP = _lib.lib().nb_shape_eigen, C.POINTER(C.c_double)
+        t6, l3, a9 = (C.c_double * 6)(), (C.c_double * 3)(), (C.c_double * 9)()
+        for i, t in enumerate(self.tensor):
+            if not np.isfinite(t).all():
+                continue
+            t6[:] = [t[0, 0], t[0, 1], t[0, 2], t[1, 1], t[1, 2], t[2, 2]]  # nb_shape_eigen's order
+            check(eig(C.cast(t6, DP), C.cast(l3, DP), C.cast(a9, DP)))
+            lam[i], axes[i] = list(l3), np.array(list(a9)).reshape(3, 3)
+        return lam, axes
+
+    def eigenvalues(self) -> np.ndarray:
+        """(M, 3), descending (nb_shape_eigen); NaN for a point without a finite tensor.  Positive stretches,
+        negative compresses."""
+        return self._eigen_cache[0].copy()
+
+    def eigenvectors(self) -> np.ndarray:
+        """(M, 3, 3): row k of sample i is the unit eigenvector of eigenvalues()[i, k], with nb_shape_eigen's sign."""
+        return self._eigen_cache[1].copy()
+
+    def compressive_axes(self) -> np.ndarray:
+        """(M,) int: the count of negative eigenvalues, 0 to 3 -- the cosmic-web class of the point (-1 where the
+        tensor is not finite)."""
+        lam = self.eigenvalues()
+        return np.where(np.isnan(lam).any(axis=1), -1, (lam < 0).sum(axis=1))
+
+
+@dataclass(frozen=True)
+class DiscFrequencies:
+    """Per ring of field_rings(): the angular, epicyclic and vertical frequencies of a disc from the force and its
+    gradient (nb_field_ring_means, nb_tidal_ring_means).  omega2 = -a_R / R, kappa2 = -T_RR + 3 omega2 (= R dOmega^2/dR
+    + 4 Omega^2, for any central force law), nu2 = -T_nn; omega, kappa and nu are their roots, NaN where the square
+    is negative."""
+    radii: np.ndarray
+    omega2: np.ndarray
+    kappa2: np.ndarray
+    nu2: np.ndarray
+    v_c: np.ndarray
+    t_RR: np.ndarray
+    t_pp: np.ndarray
+    t_nn: np.ndarray
+    t_Rn: np.ndarray
+    rings: "RingMeans"       # the field's ring means behind omega2 and v_c
+    tidal: TidalField        # the tidal samples behind the rest, ring-major
+
+    @staticmethod
+    def _root(x):
+        with np.errstate(invalid="ignore"):
+            return np.where(x >= 0, np.sqrt(np.where(x >= 0, x, 0.0)), np.nan)
+
+    @property
+    def omega(self) -> np.ndarray:
+        return self._root(self.omega2)
+
+    @property
+    def kappa(self) -> np.ndarray:
+        return self._root(self.kappa2)
+
+    @property
+    def nu(self) -> np.ndarray:
+        return self._root(self.nu2)
+
+    def _crossings(self, f, level):
+        d = f - level
+        out = []
+        for i in range(len(d)):
+            if d[i] == 0.0:  # on a ring
+                out.append(self.radii[i])
+            elif i + 1 < len(d) and d[i] * d[i + 1] < 0.0:  # (False with a NaN on either side)
+                out.append(self.radii[i] + d[i] / (d[i] - d[i + 1]) * (self.radii[i + 1] - self.radii[i]))
+        return np.array(out, dtype=np.float64)
+
+    def resonances(self, pattern_speed: float, m: int = 2) -> dict:
+        """The radii where a pattern of speed `pattern_speed` (DiscModes.pattern_speed) and m arms resonates with
+        the disc: "corotation" (Omega = Omega_p), "inner_lindblad" (Omega - kappa / m = Omega_p) and
+        "outer_lindblad" (Omega + kappa / m = Omega_p), each an array (empty where the curve never crosses).
+        Found by linear interpolation between the neighbouring rings where the sign of the difference changes: as
+        fine as the rings, no finer.  Rings where a frequency is NaN are not crossed."""
+        om, ka = self.omega, self.kappa
+        return {"corotation": self._crossings(om, pattern_speed),
+                "inner_lindblad": self._crossings(om - ka / m, pattern_speed),
+                "outer_lindblad": self._crossings(om + ka / m, pattern_speed)}
+
+
+def _tidal_tensor(call, handle, points) -> TidalField:
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(pts.shape[0], dtype=_lib.TIDAL_SAMPLE_DTYPE)
+    st = _lib.nb_tidal_stats()
+    check(call(handle, pts.ctypes.data, pts.shape[0], out.ctypes.data, C.byref(st)))
+    t = out["tensor"]
+    tensor = t[:, [0, 3, 4, 3, 1, 5, 4, 5, 2]].reshape(-1, 3, 3)  # xx, yy, zz, xy, xz, yz -> symmetric rows
+    return TidalField(tensor, out["coincident"].copy(), int(st.step_num), int(st.n), int(st.nonfinite),
+                      int(st.points), int(st.nonfinite_points), int(st.launches))
+
+
+def _disc_frequencies(field_call, tidal_call, handle, radii, axis, center, n_phi) -> DiscFrequencies:
+    cv = _circular_velocity(field_call, handle, radii, axis, center, n_phi, False)
+    r = cv.radii
+    pts = field_rings(r, axis=axis, center=center, n_phi=n_phi)
+    t = _tidal_tensor(tidal_call, handle, pts)
+    samples = np.zeros(pts.shape[0], dtype=_lib.TIDAL_SAMPLE_DTYPE)
+    samples["tensor"] = t.tensor.reshape(-1, 9)[:, [0, 4, 8, 1, 2, 5]]
+    rings = np.zeros(r.shape[0], dtype=_lib.FIELD_RING_DTYPE)
+    rings["a_R"], rings["a_n"], rings["potential"], rings["v_c"] = cv.a_R, cv.a_n, cv.potential, cv.v_c
+    out = np.zeros(r.shape[0], dtype=_lib.TIDAL_RING_DTYPE)
+    check(_lib.lib().nb_tidal_ring_means(_vec3(center), _vec3(axis), r.ctypes.data_as(C.POINTER(C.c_double)),
+                                         r.shape[0], int(n_phi), pts.ctypes.data, samples.ctypes.data,
+                                         rings.ctypes.data, out.ctypes.data))
+    return DiscFrequencies(r, out["omega2"].copy(), out["kappa2"].copy(), out["nu2"].copy(), cv.v_c,
+                           out["t_RR"].copy(), out["t_pp"].copy(), out["t_nn"].copy(), out["t_Rn"].copy(), cv, t)
 
 
 def map_frame(axis):
@@ -2016,6 +2151,24 @@ class _Passes:
         """The rotation curve from the force: field() on n_phi points of each ring of field_rings(), then
         the ring means (nb_field_ring_means): v_c = sqrt(max(0, -R a_R)).  A several-GPU runner refuses."""
         return _circular_velocity(self._pass("field"), self._h, radii, axis, center, n_phi, potential)
+
+    def tidal_tensor(self, points) -> TidalField:
+        """The exact tidal tensor T_ab = d acc_a / d x_b of the current state at `points` ((M, 3), float32), summed
+        pair by pair over all bodies on the device (nb_tidal_sim): whether a clump is stretched or compressed by the
+        rest of the system (eigenvalues(), compressive_axes()).  A body at a point itself adds nothing and is counted
+        in `.coincident`.  A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _tidal_tensor(getattr(_lib.lib(), "nb_tidal_" + suffix), self._h, points)
+
+    def disc_frequencies(self, radii, *, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0),
+                         n_phi: int = 16) -> DiscFrequencies:
+        """Omega(R), the epicyclic frequency kappa(R) and the vertical frequency nu(R) of a disc about `axis` through
+        `center`: field() and tidal_tensor() on n_phi points of each ring of field_rings(), then the ring means
+        (nb_field_ring_means, nb_tidal_ring_means).  DiscFrequencies.resonances() sets them against a pattern speed
+        of disc_modes().  A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _disc_frequencies(self._pass("field"), getattr(_lib.lib(), "nb_tidal_" + suffix), self._h, radii, axis,
+                                 center, n_phi)
 
     def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                       depth=None, velocities: bool = True) -> ProjectedMap:

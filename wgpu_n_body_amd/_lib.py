@@ -96,6 +96,18 @@ class nb_field_ring(C.Structure):
     _fields_ = [("a_R", C.c_double), ("a_n", C.c_double), ("potential", C.c_double), ("v_c", C.c_double)]
 
 
+class nb_tidal_sample(C.Structure):
+    _fields_ = [("tensor", C.c_double * 6), ("coincident", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+nb_tidal_stats = nb_field_stats  # (the header's typedef)
+
+
+class nb_tidal_ring(C.Structure):
+    _fields_ = [("t_RR", C.c_double), ("t_pp", C.c_double), ("t_nn", C.c_double), ("t_Rn", C.c_double),
+                ("omega2", C.c_double), ("kappa2", C.c_double), ("nu2", C.c_double)]
+
+
 class nb_map_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -304,6 +316,11 @@ BOUND_GROUP_DTYPE = np.dtype([("label", "<u4"), ("count", "<u4"), ("bound_count"
 FIELD_SAMPLE_DTYPE = np.dtype([("acc", "<f8", (3,)), ("potential", "<f8"), ("coincident", "<u4"), ("reserved", "<u4")])
 FIELD_RING_DTYPE = np.dtype([("a_R", "<f8"), ("a_n", "<f8"), ("potential", "<f8"), ("v_c", "<f8")])
 
+# nb_tidal_sample[] and nb_tidal_ring[] as numpy record arrays
+TIDAL_SAMPLE_DTYPE = np.dtype([("tensor", "<f8", (6,)), ("coincident", "<u4"), ("reserved", "<u4")])
+TIDAL_RING_DTYPE = np.dtype([("t_RR", "<f8"), ("t_pp", "<f8"), ("t_nn", "<f8"), ("t_Rn", "<f8"), ("omega2", "<f8"),
+                             ("kappa2", "<f8"), ("nu2", "<f8")])
+
 # nb_halo_head[] as a numpy record array
 HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
                             ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
@@ -335,6 +352,8 @@ assert C.sizeof(nb_radial_bin) == 88 == RADIAL_BIN_DTYPE.itemsize
 assert C.sizeof(nb_radial_params) == 88 and C.sizeof(nb_radial_profile) == 192
 assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.sizeof(nb_field_stats) == 48
 assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
+assert C.sizeof(nb_tidal_sample) == 56 == TIDAL_SAMPLE_DTYPE.itemsize
+assert C.sizeof(nb_tidal_ring) == 56 == TIDAL_RING_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
@@ -365,6 +384,7 @@ NB_RADIAL_MAX_BINS = 256
 NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM = 1, 2
 NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
+NB_TIDAL_K = 33
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_PHASE_CENTER_COM, NB_PHASE_WEIGHT, NB_PHASE_ANY_STEP = 1, 2, 0xFFFFFFFFFFFFFFFF
@@ -400,6 +420,7 @@ ABI_SYMBOLS = [
     "nb_sim_set_tuning", "nb_sim_debug_buffer", "nb_sim_diagnostics",
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
+    "nb_tidal_sim", "nb_tidal_runner", "nb_tidal_ring_means",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
@@ -501,6 +522,10 @@ def lib() -> C.CDLL:
     phase_map = [vp, P(nb_phase_params), vp, vp, P(nb_phase_stats)]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_phase_map_" + suffix).argtypes = phase_map
+    # ... and the sixteenth (include/nbody.h "Tidal tensor probes")
+    tidal = [vp, vp, sz, vp, P(nb_tidal_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_tidal_" + suffix).argtypes = tidal
     L.nb_phase_quantity.argtypes = [C.c_char_p, P(C.c_uint32)]
     L.nb_phase_quantity_name.argtypes = [C.c_uint32]
     L.nb_phase_quantity_name.restype = C.c_char_p
@@ -512,6 +537,8 @@ def lib() -> C.CDLL:
     L.nb_field_rings.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp]
     L.nb_field_ring_means.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp, vp,
                                       vp]
+    L.nb_tidal_ring_means.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double), C.c_uint32, C.c_uint32, vp, vp,
+                                      vp, vp]
     L.nb_hop_regroup.argtypes = [vp, vp, sz, vp, sz, P(nb_hop_regroup_params), vp, vp, vp, sz, P(sz)]
     L.nb_shape_eigen.argtypes = [P(C.c_double), P(C.c_double), P(C.c_double)]
     L.nb_halo_enclosed.argtypes = [vp, vp, C.c_uint32, P(C.c_double)]

@@ -56,6 +56,9 @@ SOURCES = [
     ("nb_modes.hip", ["-ffp-contract=off"]),
     # the quantities and the cell rule are specified operation by operation: no FMA contraction
     ("nb_phase.hip", ["-ffp-contract=off"]),
+    # the pair arithmetic is specified operation by operation, and the bound counts its roundings: no
+    # FMA contraction
+    ("nb_tidal.hip", ["-ffp-contract=off"]),
     # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
     ("nb_simbase.cpp", []),

@@ -8,6 +8,8 @@
 //             [--radial-center com|X,Y,Z]]
 //            [--rotcurve K --rotcurve-range RMIN,RMAX [--rotcurve-bins B] [--rotcurve-phi Q]
 //             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
+//            [--freq K --freq-range RMIN,RMAX [--freq-bins B] [--freq-phi Q] [--freq-axis X,Y,Z]
+//             [--freq-center X,Y,Z]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
@@ -51,6 +53,10 @@
 // points per ring (--rotcurve-phi, default 16) about --rotcurve-axis (default 0,1,0) through
 // --rotcurve-center (default 0,0,0).  One line per ring "rotcurve <step> <R> <a_R> <a_n> <v_c>" (%.9e).
 // The time they take is not part of any "Step Duration"; without --rotcurve the output is unchanged.
+// --freq K prints the disc's frequencies from the force and its gradient (nb_runner_field and nb_tidal_runner on
+// the same rings, nb_field_ring_means, nb_tidal_ring_means) of step 0 and of every K-th step; --freq-range,
+// --freq-bins, --freq-phi, --freq-axis and --freq-center as --rotcurve's.  One line per ring
+// "freq <step> <R> <Omega> <kappa> <nu> <v_c>" (%.9e; nan where the square of a frequency is negative).
 //
 // --maps DIR writes the projected map (nb_runner_map) of step 0 and of every K-th step (--map-every,
 // default 1) as DIR/map_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape (7, H, W) -- the counts as
@@ -236,6 +242,18 @@ static void print_rotcurve(nbody::OfflineHeadless<Sim> &runner, const RotcurveOp
     for (uint32_t i = 0; i < ro.bins; ++i)
         std::printf("rotcurve %llu %.9e %.9e %.9e %.9e\n", (unsigned long long)r.field.stats.step_num, radii[i],
                     r.rings[i].a_R, r.rings[i].a_n, r.rings[i].v_c);
+}
+
+// --freq: the rings are --rotcurve's, so are the options
+template <class Sim>
+static void print_freq(nbody::OfflineHeadless<Sim> &runner, const RotcurveOptions &fo) {
+    std::vector<double> radii(fo.bins);
+    for (uint32_t i = 0; i < fo.bins; ++i)
+        radii[i] = fo.bins > 1 ? fo.rmin + (fo.rmax - fo.rmin) * (double)i / (double)(fo.bins - 1) : fo.rmin;
+    const nbody::DiscFrequencies f = runner.disc_frequencies(radii, fo.axis, fo.center, fo.phi);
+    for (uint32_t i = 0; i < fo.bins; ++i)
+        std::printf("freq %llu %.9e %.9e %.9e %.9e %.9e\n", (unsigned long long)f.tidal.stats.step_num, radii[i],
+                    f.omega(i), f.kappa(i), f.nu(i), f.means.rings[i].v_c);
 }
 
 // DIR/<name>: NumPy format 1.0, <f8, shape (1 + planes, H, W): the counts as doubles, then the planes
@@ -649,7 +667,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
-               const ModesOptions &modes, const PhaseOptions &phase) {
+               const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -657,6 +675,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (diag > 0) print_diag(runner, diag_potential);
     if (radial.every > 0) print_radial(runner, radial);
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
+    if (freq.every > 0) print_freq(runner, freq);
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
@@ -679,6 +698,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (diag > 0 && (i + 1) % diag == 0) print_diag(runner, diag_potential);
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
+        if (freq.every > 0 && (i + 1) % freq.every == 0) print_freq(runner, freq);
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
@@ -713,7 +733,7 @@ int main(int argc, char **argv) {
     bool diag_potential = false;
     FrameOptions frames;
     RadialOptions radial;
-    RotcurveOptions rotcurve;
+    RotcurveOptions rotcurve, freq;
     MapOptions maps;
     SmapOptions smaps;
     FofOptions fof;
@@ -784,6 +804,23 @@ int main(int argc, char **argv) {
         }
         else if (k == "--rotcurve-axis" || k == "--rotcurve-center") {
             double *a = k == "--rotcurve-axis" ? rotcurve.axis.data() : rotcurve.center.data();
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
+                std::fprintf(stderr, "%s takes X,Y,Z, not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--freq") freq.every = std::atoi(v.c_str());
+        else if (k == "--freq-bins") freq.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--freq-phi") freq.phi = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--freq-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &freq.rmin, &freq.rmax) != 2) {
+                std::fprintf(stderr, "--freq-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            freq.have_range = true;
+        }
+        else if (k == "--freq-axis" || k == "--freq-center") {
+            double *a = k == "--freq-axis" ? freq.axis.data() : freq.center.data();
             if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &a[0], &a[1], &a[2]) != 3) {
                 std::fprintf(stderr, "%s takes X,Y,Z, not %s\n", k.c_str(), v.c_str());
                 return 2;
@@ -1024,6 +1061,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--radial needs --radial-range RMIN,RMAX\n");
         return 2;
     }
+    if (freq.every > 0 && !freq.have_range) {
+        std::fprintf(stderr, "--freq needs --freq-range RMIN,RMAX\n");
+        return 2;
+    }
     if (rotcurve.every > 0 && !rotcurve.have_range) {
         std::fprintf(stderr, "--rotcurve needs --rotcurve-range RMIN,RMAX\n");
         return 2;
@@ -1091,9 +1132,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

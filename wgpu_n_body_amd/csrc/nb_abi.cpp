@@ -133,6 +133,12 @@ static int pass_field(H *h, const float *points, size_t m, uint32_t flags, nb_fi
 }
 
 template <class H>
+static int pass_tidal(H *h, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats) {
+    if (int rc = tidal_check_args(points, m, out)) return rc;
+    return on_sim(h, "tidal", [&](SimBase &s) { return sim_tidal(s, points, m, out, stats); });
+}
+
+template <class H>
 static int pass_map(H *h, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
@@ -478,6 +484,18 @@ int nb_field_rings(const double center[3], const double axis[3], const double *r
 int nb_field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
                         uint32_t n_phi, const float *points, const nb_field_sample *samples, nb_field_ring *out) {
     return field_ring_means(center, axis, radii, k, n_phi, points, samples, out);
+}
+
+int nb_tidal_sim(nb_sim *sim, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats) {
+    return pass_tidal(sim, points, m, out, stats);
+}
+int nb_tidal_runner(nb_runner *runner, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats) {
+    return pass_tidal(runner, points, m, out, stats);
+}
+int nb_tidal_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k,
+                        uint32_t n_phi, const float *points, const nb_tidal_sample *samples,
+                        const nb_field_ring *rings, nb_tidal_ring *out) {
+    return tidal_ring_means(center, axis, radii, k, n_phi, points, samples, rings, out);
 }
 
 int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {

@@ -130,7 +130,20 @@ int field_check_args(const float *points, size_t m, uint32_t flags, const nb_fie
     return NB_OK;
 }
 
-// nb_field_rings / nb_field_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
+// nb_tidal_sim: everything about the arguments that can be refused without a device
+int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out) {
+    if (m > 0 && (!points || !out)) {
+        set_error("tidal: null %s", !points ? "points" : "out");
+        return NB_ERR_INVALID;
+    }
+    if (m > NB_FIELD_MAX_POINTS) {
+        set_error("tidal: at most %u points (got %zu)", NB_FIELD_MAX_POINTS, m);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_field_rings / nb_field_ring_means / nb_tidal_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
 static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
                       uint32_t n_phi, double n[3], double e1[3], double e2[3]) {
     if (!center || !axis || (k && !radii)) {
@@ -909,6 +922,62 @@ int field_ring_means(const double center[3], const double axis[3], const double 
         r.a_n = a_n / (double)n_phi;
         r.potential = pot / (double)n_phi;
         r.v_c = std::sqrt(std::fmax(0.0, -radii[i] * r.a_R));
+        out[i] = r;
+    }
+    return NB_OK;
+}
+
+int tidal_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                     const float *points, const nb_tidal_sample *samples, const nb_field_ring *rings,
+                     nb_tidal_ring *out) {
+    double n[3], e1[3], e2[3];
+    if (int rc = ring_basis("tidal_ring_means", center, axis, radii, k, n_phi, n, e1, e2)) return rc;
+    if (k && (!points || !samples || !rings || !out)) {
+        set_error("tidal_ring_means: null %s", !points ? "points" : !samples ? "samples" : !rings ? "rings" : "out");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        double t_rr = 0.0, t_pp = 0.0, t_nn = 0.0, t_rn = 0.0;
+        for (uint32_t q = 0; q < n_phi; ++q) {
+            const size_t j = (size_t)i * n_phi + q;
+            const double *s = samples[j].tensor;  // xx, yy, zz, xy, xz, yz
+            const double t[3][3] = {{s[0], s[3], s[4]}, {s[3], s[1], s[5]}, {s[4], s[5], s[2]}};
+            double d[3], h = 0.0;  // the fp32 point actually used, from the centre; its height along n
+            for (int a = 0; a < 3; ++a) {
+                d[a] = (double)points[3 * j + a] - center[a];
+                h += d[a] * n[a];
+            }
+            double len = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                d[a] -= h * n[a];
+                len += d[a] * d[a];
+            }
+            len = std::sqrt(len);
+            double tn[3];  // T n
+            for (int a = 0; a < 3; ++a) tn[a] = t[a][0] * n[0] + t[a][1] * n[1] + t[a][2] * n[2];
+            t_nn += n[0] * tn[0] + n[1] * tn[1] + n[2] * tn[2];
+            if (!(len > 0.0)) continue;  // on the axis: no rhat
+            double rh[3], ph[3], tr[3], tp[3];
+            for (int a = 0; a < 3; ++a) rh[a] = d[a] / len;
+            ph[0] = n[1] * rh[2] - n[2] * rh[1];  // phihat = n x rhat
+            ph[1] = n[2] * rh[0] - n[0] * rh[2];
+            ph[2] = n[0] * rh[1] - n[1] * rh[0];
+            for (int a = 0; a < 3; ++a) {
+                tr[a] = t[a][0] * rh[0] + t[a][1] * rh[1] + t[a][2] * rh[2];
+                tp[a] = t[a][0] * ph[0] + t[a][1] * ph[1] + t[a][2] * ph[2];
+            }
+            t_rr += rh[0] * tr[0] + rh[1] * tr[1] + rh[2] * tr[2];
+            t_pp += ph[0] * tp[0] + ph[1] * tp[1] + ph[2] * tp[2];
+            t_rn += rh[0] * tn[0] + rh[1] * tn[1] + rh[2] * tn[2];
+        }
+        nb_tidal_ring r{};
+        r.t_RR = t_rr / (double)n_phi;
+        r.t_pp = t_pp / (double)n_phi;
+        r.t_nn = t_nn / (double)n_phi;
+        r.t_Rn = t_rn / (double)n_phi;
+        r.omega2 = radii[i] > 0.0 ? -rings[i].a_R / radii[i] : std::nan("");
+        r.kappa2 = -r.t_RR + 3.0 * r.omega2;
+        r.nu2 = -r.t_nn;
         out[i] = r;
     }
     return NB_OK;

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -164,6 +164,10 @@ int radial_edges(const char *what, bool log, double rmin, double rmax, uint32_t 
 int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out);
 int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_field_sample *out, nb_field_stats *stats);
 
+// nb_tidal.hip: nb_tidal_sim behind the handle
+int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out);
+int sim_tidal(SimBase &sim, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
+
 // nb_map.hip: nb_sim_map behind the handle; map_check_params also forms the frame and the cell sizes
 struct MapPlan {
     double n[3], e1[3], e2[3];  // axis_frame of the caller's axis
@@ -250,6 +254,9 @@ int field_rings(const double center[3], const double axis[3], const double *radi
                 float *points);
 int field_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
                      const float *points, const nb_field_sample *samples, nb_field_ring *out);
+int tidal_ring_means(const double center[3], const double axis[3], const double *radii, uint32_t k, uint32_t n_phi,
+                     const float *points, const nb_tidal_sample *samples, const nb_field_ring *rings,
+                     nb_tidal_ring *out);
 int halo_enclosed(const nb_halo_head *head, const nb_radial_bin *bins, uint32_t nbins, double *out);
 int halo_overdensity(const nb_halo_head *head, const nb_radial_bin *bins, const double *edges, uint32_t nbins,
                      double rho, double *r, double *mass);

@@ -37,6 +37,8 @@ using RadialParams = nb_radial_params;    // bins, flags, centre, axis and edges
 using RadialBin = nb_radial_bin;          // 88 B
 using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and coincident count at a point
 using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
+using TidalSample = nb_tidal_sample;      // 56 B: the tidal tensor (xx, yy, zz, xy, xz, yz) and coincident count at a point
+using TidalRing = nb_tidal_ring;          // a ring's means of the tensor, and omega2, kappa2, nu2
 using MapParams = nb_map_params;          // grid, window, line of sight and centre of a projected map
 using MapStats = nb_map_stats;
 using PhaseParams = nb_phase_params;      // quantities, flags, centre and axis of a phase map (the edges are set by the call)
@@ -257,6 +259,66 @@ RingMeans circular_velocity(int (*call)(H *, const float *, size_t, uint32_t, nb
     r.rings.resize(radii.size());
     check(nb_field_ring_means(center.data(), axis.data(), radii.data(), (uint32_t)radii.size(), n_phi, pts.data(),
                               r.field.samples.data(), r.rings.data()));
+    return r;
+}
+}  // namespace detail
+
+// The tidal tensor at a set of points (no reference counterpart): the samples and what the call measured
+struct TidalField {
+    std::vector<TidalSample> samples;
+    nb_tidal_stats stats{};
+    // the eigenvalues of sample i, descending, and their unit vectors (nb_shape_eigen)
+    void eigen(size_t i, double lambda[3], double axes[9]) const {
+        const double *s = samples[i].tensor;
+        const double t[6] = {s[0], s[3], s[4], s[1], s[5], s[2]};  // nb_shape_eigen's order: xx, xy, xz, yy, yz, zz
+        check(nb_shape_eigen(t, lambda, axes));
+    }
+    // the count of negative eigenvalues, 0 to 3: the cosmic-web class of the point (-1 where the tensor is not finite)
+    int compressive_axes(size_t i) const {
+        for (double v : samples[i].tensor)
+            if (!std::isfinite(v)) return -1;
+        double lambda[3], axes[9];
+        eigen(i, lambda, axes);
+        return (lambda[0] < 0.0) + (lambda[1] < 0.0) + (lambda[2] < 0.0);
+    }
+};
+
+// A disc's frequencies from the force and its gradient: per ring the means of nb_tidal_ring_means, the field's ring
+// means behind omega2 and v_c, and the tidal samples behind the rest
+struct DiscFrequencies {
+    std::vector<double> radii;
+    std::vector<TidalRing> rings;
+    RingMeans means;
+    TidalField tidal;
+    static double root(double x) { return x >= 0.0 ? std::sqrt(x) : std::nan(""); }  // NaN where the square is negative
+    double omega(size_t i) const { return root(rings[i].omega2); }
+    double kappa(size_t i) const { return root(rings[i].kappa2); }
+    double nu(size_t i) const { return root(rings[i].nu2); }
+};
+
+namespace detail {
+template <class H>
+TidalField tidal_tensor(int (*call)(H *, const float *, size_t, nb_tidal_sample *, nb_tidal_stats *), H *h,
+                        const std::vector<float> &points) {
+    TidalField f;
+    f.samples.resize(points.size() / 3);
+    check(call(h, points.data(), points.size() / 3, f.samples.data(), &f.stats));
+    return f;
+}
+template <class H>
+DiscFrequencies disc_frequencies(int (*field_call)(H *, const float *, size_t, uint32_t, nb_field_sample *,
+                                                   nb_field_stats *),
+                                 int (*tidal_call)(H *, const float *, size_t, nb_tidal_sample *, nb_tidal_stats *),
+                                 H *h, const std::vector<double> &radii, const std::array<double, 3> &axis,
+                                 const std::array<double, 3> &center, uint32_t n_phi) {
+    DiscFrequencies r;
+    r.radii = radii;
+    r.means = circular_velocity(field_call, h, radii, axis, center, n_phi, false);
+    const std::vector<float> pts = field_rings(radii, axis, center, n_phi);
+    r.tidal = tidal_tensor(tidal_call, h, pts);
+    r.rings.resize(radii.size());
+    check(nb_tidal_ring_means(center.data(), axis.data(), radii.data(), (uint32_t)radii.size(), n_phi, pts.data(),
+                              r.tidal.samples.data(), r.means.rings.data(), r.rings.data()));
     return r;
 }
 }  // namespace detail
@@ -915,6 +977,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto group_radii = nb_group_radii_sim;
     static constexpr auto disc_modes = nb_disc_modes_sim;
     static constexpr auto phase_map = nb_phase_map_sim;
+    static constexpr auto tidal = nb_tidal_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -934,6 +997,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto group_radii = nb_group_radii_runner;
     static constexpr auto disc_modes = nb_disc_modes_runner;
     static constexpr auto phase_map = nb_phase_map_runner;
+    static constexpr auto tidal = nb_tidal_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -1039,6 +1103,14 @@ class Passes {
                                 const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16,
                                 bool potential = false) {
         return detail::circular_velocity(Abi::field, h_, radii, axis, center, n_phi, potential);
+    }
+    // the exact tidal tensor T_ab = d acc_a / d x_b of the current state at the points
+    TidalField tidal_tensor(const std::vector<float> &points) { return detail::tidal_tensor(Abi::tidal, h_, points); }
+    // Omega, kappa and nu of a disc on n_phi points of each ring: the force and its gradient on the same rings
+    DiscFrequencies disc_frequencies(const std::vector<double> &radii,
+                                     const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
+                                     const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16) {
+        return detail::disc_frequencies(Abi::field, Abi::tidal, h_, radii, axis, center, n_phi);
     }
     // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
     Frame render(const RenderParams &p, bool counts = false) {
