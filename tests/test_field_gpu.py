@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import field_ref as F
+from tests import tidal_ref as T
 from tests.diag_ref import psi64
 from tests.helpers import DT, E, G, ROOT, bits, make_state
 
@@ -173,6 +174,40 @@ def test_chunks_and_bands(gpu, kind):
     for bad in (15, 41):
         with pytest.raises(nb.NBodyError):
             sim.set_tuning("field_launch_pairs_log2", bad)
+    sim.destroy()
+
+
+@pytest.mark.parametrize("m,n", [(5, 300_000), (257, 140_000)])
+def test_several_tiles_per_chunk(gpu, m, n):
+    """The double-buffered loop of a block runs once per tile of its chunk, and a chunk gets a second tile only from
+    about 87,000 bodies on: the counterpart of tests/test_tidal_gpu.py's case for the field's instantiations of the
+    same loop (csrc/nb_probe.hpp), with the acceleration alone, the potential alone and both.  The flags change the
+    points per lane and not the tiles per chunk, two here (asserted from the restated plan).  The prefetch, the
+    other buffer and the masked-body count carried from tile to tile: non-finite bodies and bodies at the origin in
+    the first, second and last tile of a chunk, and a point at the origin."""
+    nb = gpu
+    acc_ib = 4 if m >= 256 else 2 if m > 64 else 1     # points_per_lane of csrc/nb_field.hip; 2 with the potential
+    assert acc_ib != 2                                 # (so the flags do change the points per lane)
+    (_, cj, chunks), (_, cj2, chunks2) = T.plan(m, n, acc_ib), T.plan(m, n, 2)
+    assert cj == cj2 == 2 and chunks == chunks2 and (acc_ib, cj, chunks) == T.DEEP[(m, n)]
+    state = make_state("uniform", n, seed=70 + cj)
+    first, second, last = 256 * cj * 3, 256 * (cj * 3 + 1), 256 * (cj * 4 + cj - 1)  # tiles of chunks 3 and 4
+    state[first + 7, 0:3] = 0.0
+    state[second + 9, 0:3] = 0.0
+    state[first + 100, 4] = np.nan
+    state[second + 3, 0] = np.inf
+    state[second + 200, 9] = np.nan
+    state[last + 255, 2] = np.nan
+    state[n - 1, 5] = -np.inf            # (the call's last tile too)
+    sim = _sim(nb, "naive", state)
+    pts, _ = _points(state[np.isfinite(state).all(1)], m, seed=n % 97)
+    pts[0] = 0.0                         # on two bodies and on every masked body's stand-in
+    ref = F.field64(state, pts, G, E)
+    assert ref["nonfinite"] == 5
+    for kw in (dict(potential=False), dict(accel=False), dict()):
+        f = sim.field(pts, **kw)
+        assert f.nonfinite == 5 and f.coincident[0] == 2 and f.launches == 1, kw
+        _check(f, ref, accel=kw.get("accel", True), potential=kw.get("potential", True))
     sim.destroy()
 
 

@@ -91,10 +91,12 @@ def points(state, m, seed, e):
     return pts, on
 
 
-def plan(m, n):
-    """(ib, cj, chunks) of a call with m points on n bodies: the plan of csrc/nb_tidal.hip restated -- points per
-    lane, 256-body tiles per chunk (the iterations of a block's double-buffered loop), chunks (blockIdx.y)."""
-    ib = 4 if m >= 256 else 2 if m > 64 else 1
+def plan(m, n, ib=None):
+    """(ib, cj, chunks) of a call with m points on n bodies: the plan of csrc/nb_probe.hpp restated -- points per
+    lane (nb_tidal.hip's, unless the caller gives nb_field.hip's), 256-body tiles per chunk (the iterations of a
+    block's double-buffered loop), chunks (blockIdx.y)."""
+    if ib is None:
+        ib = 4 if m >= 256 else 2 if m > 64 else 1
     tile_pts = 64 * ib
     p_tiles, n_tiles = -(-m // tile_pts), -(-n // 256)
     if m == 0 or n == 0:

@@ -1,182 +1,80 @@
 // nb_field.hip -- nb_sim_field: the exact acceleration and potential of a simulator's current state at
 // arbitrary points (include/nbody.h "Field probes"; no reference counterpart).
 //
-// M points against the N bodies of the float4 SoA state the simulator hands out (SimBase::diag_state):
-//   field   -- a block of 256 threads owns a tile of 64 IB points, IB per lane in VGPRs, the same points in
-//              each of its four waves.  blockIdx.y cuts the bodies into chunks of 256-body tiles; the block
-//              stages each tile through LDS (double-buffered, one barrier per tile) with the diagnostics'
-//              predicate applied on load -- an absent or non-finite body is massless at the origin -- and
-//              wave w reads back bodies [64 w, 64 w + 64) of the tile as wave-uniform broadcasts: one fp32
-//              run of 64 pairs per point, folded into the wave's fp64 sums.  At the end the four waves'
-//              sums meet in LDS in wave order and the block writes four doubles and a coincident count per
-//              point into slab[chunk][field][point of the band].  The point tiles go in bands, one launch per
-//              band, each bounded in pairs so that no launch runs for long on a shared GPU;
+// M points against the N bodies of the float4 SoA state the simulator hands out, tiled, staged, summed and
+// sequenced by nb_probe.hpp; here are the rule and what follows from it:
+//   field   -- probe_kernel<FieldRule<MODE>, IB>, MODE the requested fields: per pair the arithmetic of the step
+//              (nb_naive.hip's pair()) and, for the potential, m psi(r); four fp64 sums per point -- ax, ay, az
+//              and the psi sum -- of which an instantiation writes those of its MODE, and the coincident count;
 //   finish  -- after each band, one thread per point adds the chunks in order, scales by g and writes the
-//              nb_field_sample; the samples are copied once into pinned host memory ahead of the one
-//              synchronisation.
+//              nb_field_sample.
 // The non-finite count is the diagnostics' own (diag_enqueue_moments on the same stream).
 // No float atomics; the grid and the chunking depend on (M, N, flags) alone and every lane runs the same
 // operations in the same order, so the result is bitwise reproducible and does not depend on where in
 // the array a point stands.
-#include <cmath>
-#include <cstring>
-
-#include "nb_analysis.hpp"
-#include "nb_common.hpp"
+#include "nb_probe.hpp"
 #include "nb_psi.hpp"
-#include "nb_sim.hpp"
 
 namespace nb {
 
-namespace {
+using namespace probe;
 
-constexpr uint32_t kThreads = 256;      // 4 waves per block
-constexpr uint32_t kWaves = kThreads / kWave;
-constexpr uint32_t kTile = 256;         // bodies per staged tile: one run of kRun per wave
-constexpr uint32_t kRun = kTile / kWaves;  // pairs summed in fp32 before folding into fp64 (R = 64)
-constexpr uint32_t kBlocks = 1024;      // with few point tiles, chunks enough for this many blocks (4 per CU)
-// pairs per launch by default: the budget the diagnostics' pair pass was measured for (nb_diag.hip)
-constexpr uint64_t kPairsPerLaunch = 1ull << 35;
-constexpr uint32_t kSlabFields = 5;     // ax, ay, az, psi sum, coincident count
-static_assert(kRun == 64, "the stated error bound is for runs of 64");
+namespace {
 
 enum : int { kAcc = NB_FIELD_ACCEL, kPot = NB_FIELD_POTENTIAL };
 
-// One tile of bodies for one wave: bodies [0, kRun) of `run` against the lane's IB points.
-template <int MODE, int IB>
-__device__ __forceinline__ void run_pairs(const float4 *run, const float (&px)[IB], const float (&py)[IB],
-                                          const float (&pz)[IB], float e, const PsiConst &c, double (&sum)[IB][4],
-                                          uint32_t (&cnt)[IB]) {
-    float ax[IB], ay[IB], az[IB], ph[IB];
+template <int MODE>
+struct FieldRule {
+    static constexpr int kSums = 4;  // ax, ay, az, psi sum
+    using Const = PsiConst;
+    static constexpr bool writes(int f) { return MODE & (f < 3 ? kAcc : kPot); }
+
+    // One tile of bodies for one wave: bodies [0, kRun) of `run` against the lane's IB points.
+    template <int IB>
+    static __device__ __forceinline__ void run_pairs(const float4 *run, const float (&px)[IB], const float (&py)[IB],
+                                                     const float (&pz)[IB], const PsiConst &c, double (&sum)[IB][4],
+                                                     uint32_t (&cnt)[IB]) {
+        const float e = c.e;
+        float ax[IB], ay[IB], az[IB], ph[IB];
 #pragma unroll
-    for (int k = 0; k < IB; ++k) ax[k] = ay[k] = az[k] = ph[k] = 0.f;
+        for (int k = 0; k < IB; ++k) ax[k] = ay[k] = az[k] = ph[k] = 0.f;
 #pragma unroll 4
-    for (uint32_t j = 0; j < kRun; ++j) {
-        const float4 q = run[j];  // wave-uniform address: LDS broadcast
-#pragma unroll
-        for (int k = 0; k < IB; ++k) {
-            const float dx = q.x - px[k], dy = q.y - py[k], dz = q.z - pz[k];
-            const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-            const bool coincident = r2 == 0.f;  // adds nothing (not m / 0 or m psi(0))
-            cnt[k] += coincident ? 1u : 0u;
-            if (MODE & kAcc) {  // the pair arithmetic of nb_naive.hip's pair()
-                const float r = __builtin_amdgcn_sqrtf(r2);       // v_sqrt_f32
-                const float den = __builtin_fmaf(e, r, r2 * r2);  // r^4 + e r
-                float w = __builtin_amdgcn_rcpf(den) * q.w;       // v_rcp_f32
-                w = coincident ? 0.f : w;
-                ax[k] = __builtin_fmaf(w, dx, ax[k]);
-                ay[k] = __builtin_fmaf(w, dy, ay[k]);
-                az[k] = __builtin_fmaf(w, dz, az[k]);
-            }
-            if (MODE & kPot) {
-                const float t = q.w * psi_f32(r2, c);
-                ph[k] += coincident ? 0.f : t;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < IB; ++k) {
-        if (MODE & kAcc) {
-            sum[k][0] += (double)ax[k];
-            sum[k][1] += (double)ay[k];
-            sum[k][2] += (double)az[k];
-        }
-        if (MODE & kPot) sum[k][3] += (double)ph[k];
-    }
-}
-
-// ---- field: block (x, y) = point tile tile0 + x against body tiles [y cj, min(n_tiles, (y + 1) cj)) ----
-// Point k of lane l of the tile is tile * 64 IB + 64 k + l.  The slab holds one band:
-// slab[(y * kSlabFields + f) * stride + (point - tile0 * 64 IB)]; only the fields of MODE and the count are written.
-template <int MODE, int IB>
-__global__ __launch_bounds__(kThreads) void field_kernel(const float4 *__restrict__ posm,
-                                                         const float4 *__restrict__ vel, uint32_t n,
-                                                         uint32_t n_tiles, uint32_t cj,
-                                                         const float4 *__restrict__ pts, uint32_t m, uint32_t stride,
-                                                         uint32_t tile0, PsiConst c, double *__restrict__ slab) {
-    __shared__ float4 tile[2][kTile];
-    __shared__ double red[IB][kSlabFields][kWave];
-    const uint32_t tid = threadIdx.x, lane = tid % kWave;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const uint32_t p0 = (tile0 + blockIdx.x) * (kWave * IB) + lane;
-    const uint32_t j_begin = blockIdx.y * cj, j_end = min(n_tiles, j_begin + cj);  // (never empty: see plan)
-
-    float px[IB], py[IB], pz[IB];
-    bool at_origin[IB];  // the point coincides with the bodies masked to the origin
-    uint32_t cnt[IB];
-    double sum[IB][4];
-#pragma unroll
-    for (int k = 0; k < IB; ++k) {
-        const uint32_t p = p0 + kWave * k;
-        const float4 pt = p < m ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
-        px[k] = pt.x;
-        py[k] = pt.y;
-        pz[k] = pt.z;
-        at_origin[k] = __builtin_fmaf(pt.z, pt.z, __builtin_fmaf(pt.y, pt.y, pt.x * pt.x)) == 0.f;
-        cnt[k] = 0;
-        for (int f = 0; f < 4; ++f) sum[k][f] = 0.0;
-    }
-
-    // a tile's body for this thread: absent or non-finite -> massless at the origin
-    auto load = [&](uint32_t jt, bool *masked) {
-        const uint32_t j = jt * kTile + tid;
-        float4 pj = make_float4(0.f, 0.f, 0.f, 0.f);
-        *masked = true;
-        if (j < n) {
-            const float4 q = posm[j];
-            if (body_ok(q, vel[j])) {
-                pj = q;
-                *masked = false;
-            }
-        }
-        return pj;
-    };
-    bool masked = false;
-    uint32_t n_masked = 0, buf = 0;
-    tile[0][tid] = load(j_begin, &masked);
-    for (uint32_t jt = j_begin; jt < j_end; ++jt) {
-        n_masked += __syncthreads_count(masked);  // tile[buf] is whole; tile[buf ^ 1] has been read
-        float4 next = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (jt + 1 < j_end) next = load(jt + 1, &masked);  // in flight while this tile is summed
-        run_pairs<MODE, IB>(&tile[buf][wave * kRun], px, py, pz, c.e, c, sum, cnt);
-        buf ^= 1;
-        if (jt + 1 < j_end) tile[buf][tid] = next;
-    }
-
-    // the four waves' sums in wave order; wave 0 writes the slab
-    for (uint32_t w = 1; w < kWaves; ++w) {
-        __syncthreads();
-        if (wave == w) {
+        for (uint32_t j = 0; j < kRun; ++j) {
+            const float4 q = run[j];  // wave-uniform address: LDS broadcast
 #pragma unroll
             for (int k = 0; k < IB; ++k) {
-                for (int f = 0; f < 4; ++f) red[k][f][lane] = sum[k][f];
-                red[k][4][lane] = (double)cnt[k];
+                const float dx = q.x - px[k], dy = q.y - py[k], dz = q.z - pz[k];
+                const float r2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                const bool coincident = r2 == 0.f;  // adds nothing (not m / 0 or m psi(0))
+                cnt[k] += coincident ? 1u : 0u;
+                if (MODE & kAcc) {  // the pair arithmetic of nb_naive.hip's pair()
+                    const float r = __builtin_amdgcn_sqrtf(r2);       // v_sqrt_f32
+                    const float den = __builtin_fmaf(e, r, r2 * r2);  // r^4 + e r
+                    float w = __builtin_amdgcn_rcpf(den) * q.w;       // v_rcp_f32
+                    w = coincident ? 0.f : w;
+                    ax[k] = __builtin_fmaf(w, dx, ax[k]);
+                    ay[k] = __builtin_fmaf(w, dy, ay[k]);
+                    az[k] = __builtin_fmaf(w, dz, az[k]);
+                }
+                if (MODE & kPot) {
+                    const float t = q.w * psi_f32(r2, c);
+                    ph[k] += coincident ? 0.f : t;
+                }
             }
         }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int k = 0; k < IB; ++k) {
-                for (int f = 0; f < 4; ++f) sum[k][f] += red[k][f][lane];
-                cnt[k] += (uint32_t)red[k][4][lane];
-            }
-        }
-    }
-    if (wave == 0) {
-        double *out = slab + (size_t)blockIdx.y * kSlabFields * stride;
-        const uint32_t q0 = blockIdx.x * (kWave * IB) + lane;  // the point's place in the band
 #pragma unroll
         for (int k = 0; k < IB; ++k) {
-            const uint32_t p = p0 + kWave * k;
-            if (p >= m) continue;
-            const uint32_t q = q0 + kWave * k;
-            if (MODE & kAcc)
-                for (int f = 0; f < 3; ++f) out[(size_t)f * stride + q] = sum[k][f];
-            if (MODE & kPot) out[(size_t)3 * stride + q] = sum[k][3];
-            out[(size_t)4 * stride + q] = (double)(cnt[k] - (at_origin[k] ? n_masked : 0u));
+            if (MODE & kAcc) {
+                sum[k][0] += (double)ax[k];
+                sum[k][1] += (double)ay[k];
+                sum[k][2] += (double)az[k];
+            }
+            if (MODE & kPot) sum[k][3] += (double)ph[k];
         }
     }
-}
+};
+
+constexpr uint32_t kSlabFields = FieldRule<kAcc>::kSums + 1;  // ... and the coincident count
 
 // ---- finish: the chunks of every point of a band [p0, p1) in order, scaled by g once -> nb_field_sample ----
 __global__ __launch_bounds__(kThreads) void field_finish_kernel(const double *__restrict__ slab, uint32_t chunks,
@@ -204,35 +102,20 @@ __global__ __launch_bounds__(kThreads) void field_finish_kernel(const double *__
 }
 
 // the instantiations points_per_lane() can ask for
-void launch_field(uint32_t flags, int ib, dim3 grid, hipStream_t stream, const float4 *posm, const float4 *vel,
-                  uint32_t n, uint32_t n_tiles, uint32_t cj, const float4 *pts, uint32_t m, uint32_t stride,
-                  uint32_t tile0, const PsiConst &c, double *slab) {
-#define NB_FIELD_LAUNCH(MODE, IB)                                                                                  \
-    hipLaunchKernelGGL((field_kernel<MODE, IB>), grid, dim3(kThreads), 0, stream, posm, vel, n, n_tiles, cj, pts, m, \
-                       stride, tile0, c, slab)
+void launch_field(uint32_t flags, int ib, const Band<nb_field_sample> &b, const PsiConst &c) {
     if (flags == NB_FIELD_POTENTIAL)
-        NB_FIELD_LAUNCH(kPot, 2);
+        launch_pairs<FieldRule<kPot>, 2>(b, c);
     else if (flags != NB_FIELD_ACCEL)
-        NB_FIELD_LAUNCH(kAcc | kPot, 2);
+        launch_pairs<FieldRule<kAcc | kPot>, 2>(b, c);
     else if (ib == 1)
-        NB_FIELD_LAUNCH(kAcc, 1);
+        launch_pairs<FieldRule<kAcc>, 1>(b, c);
     else if (ib == 2)
-        NB_FIELD_LAUNCH(kAcc, 2);
+        launch_pairs<FieldRule<kAcc>, 2>(b, c);
     else
-        NB_FIELD_LAUNCH(kAcc, 4);
-#undef NB_FIELD_LAUNCH
+        launch_pairs<FieldRule<kAcc>, 4>(b, c);
 }
 
 }  // namespace
-
-struct FieldWork : Workspace {  // (all but the last grow to the largest call so far)
-    DeviceBuf<float4> pts;             // [padded points]
-    PinnedBuf<float4> h_pts;           // as pts
-    DeviceBuf<nb_field_sample> out;    // [padded points]
-    PinnedBuf<nb_field_sample> h_out;  // as out
-    DeviceBuf<double> slab;            // [chunks][kSlabFields][points of one band]
-    PinnedBuf<double> h_bad;           // [1] the diagnostics' non-finite count
-};
 
 // Points per lane, by measurement: a function of m and the flags alone.  The acceleration
 // alone runs fastest with whole tiles of 256 points, four per lane, and with a handful of points on the
@@ -251,100 +134,16 @@ int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_fi
         return NB_ERR_INVALID;
     }
     if (int rc = sim.bind_device()) return rc;
-    FieldWork *work = nullptr;
-    if (int rc = workspace(sim, kWorkField, &work, [](FieldWork &f) {
-            NB_HIP_TRY(f.h_bad.reserve(1));
-            return NB_OK;
-        }))
-        return rc;
-    FieldWork &w = *work;
-    const uint32_t n = sim.n, mm = (uint32_t)m;
-
-    // the plan: a function of (m, n, flags) alone
     const int ib = points_per_lane(m, flags);
-    const uint32_t tile_pts = kWave * ib;
-    const uint32_t p_tiles = (mm + tile_pts - 1) / tile_pts, m_pad = p_tiles * tile_pts;
-    const uint32_t n_tiles = (n + kTile - 1) / kTile;
-    uint32_t cj = 0, chunks = 0;
-    if (mm > 0 && n > 0) {
-        // (sized for a band of the default budget, whatever "field_launch_pairs_log2" says: the key must
-        // not change a sum)
-        const uint64_t tile_pairs = (uint64_t)tile_pts * n;
-        const uint32_t wide = (uint32_t)std::min<uint64_t>(p_tiles, std::max<uint64_t>(1, kPairsPerLaunch / tile_pairs));
-        const uint32_t want = std::min(n_tiles, std::max(1u, (kBlocks + wide - 1) / wide));
-        cj = (n_tiles + want - 1) / want;        // body tiles per chunk
-        chunks = (n_tiles + cj - 1) / cj;        // every chunk holds at least one tile
-    }
-
-    NB_HIP_TRY(w.pts.reserve(m_pad));
-    NB_HIP_TRY(w.out.reserve(m_pad));
-    NB_HIP_TRY(w.h_pts.reserve(m_pad));
-    NB_HIP_TRY(w.h_out.reserve(m_pad));
-    // bands of point tiles: a tile meets tile_pts * n pairs; at least one tile per launch.  The slab holds one band.
-    uint32_t band = p_tiles;
-    if (mm > 0 && n > 0)
-        band = (uint32_t)std::min<uint64_t>(p_tiles, std::max<uint64_t>(1, (1ull << sim.field_pairs_log2) / ((uint64_t)tile_pts * n)));
-    const uint32_t stride = band * tile_pts;
-    NB_HIP_TRY(w.slab.reserve((size_t)chunks * kSlabFields * stride));
-
-    uint64_t bad_points = 0;
-    uint32_t launches = 0;
-    *w.h_bad = 0.0;
-    if (mm > 0) {
-        for (uint32_t i = 0; i < mm; ++i) {
-            const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
-            w.h_pts[i] = make_float4(x, y, z, 0.f);
-            bad_points += !(std::isfinite(x) && std::isfinite(y) && std::isfinite(z));
-        }
-        // from here the pinned points are being read: an error drains the stream before it returns
-        const int rc = [&]() -> int {
-            NB_HIP_TRY(hipMemcpyAsync(w.pts, w.h_pts, sizeof(float4) * mm, hipMemcpyHostToDevice, sim.stream));
-            const float4 *posm = nullptr, *vel = nullptr;
-            PsiConst c{};
-            if (n > 0) {
-                sim.diag_state(&posm, &vel);
-                const double *mom = nullptr;  // the bodies nb_sim_diagnostics counts as non-finite
-                if (int rc = diag_enqueue_moments(sim, &mom)) return rc;
-                NB_HIP_TRY(hipMemcpyAsync(w.h_bad, mom + kDiagResBad, sizeof(double), hipMemcpyDeviceToHost, sim.stream));
-                c = psi_const(e);
-            }
-            for (uint32_t t0 = 0; t0 < p_tiles; t0 += band) {
-                const uint32_t tiles = std::min(band, p_tiles - t0);
-                const uint32_t p0 = t0 * tile_pts, p1 = std::min(mm, (t0 + tiles) * tile_pts);
-                if (n > 0) {
-                    launch_field(flags, ib, dim3(tiles, chunks), sim.stream, posm, vel, n, n_tiles, cj, w.pts, mm, stride, t0,
-                                 c, w.slab);
-                    NB_HIP_TRY(hipGetLastError());
-                    ++launches;
-                }
-                hipLaunchKernelGGL(field_finish_kernel, dim3((p1 - p0 + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                                   sim.stream, w.slab, chunks, w.pts, p0, p1, stride, flags, (double)sim.params.g, w.out);
-                NB_HIP_TRY(hipGetLastError());
-            }
-            NB_HIP_TRY(hipMemcpyAsync(w.h_out, w.out, sizeof(nb_field_sample) * mm, hipMemcpyDeviceToHost, sim.stream));
-            return NB_OK;
-        }();
-        if (rc != NB_OK) {
-            (void)hipStreamSynchronize(sim.stream);
-            return rc;
-        }
-    }
-    NB_HIP_TRY(hipStreamSynchronize(sim.stream));
-    if (int rc = sim.diag_status()) return rc;
-    if (mm > 0) std::memcpy(out, w.h_out, sizeof(nb_field_sample) * mm);
-
-    if (stats) {
-        nb_field_stats s{};
-        s.step_num = sim.step_num;
-        s.n = n;
-        s.nonfinite = (uint64_t)*w.h_bad;
-        s.points = m;
-        s.nonfinite_points = bad_points;
-        s.flags = flags;
-        s.launches = launches;
-        *stats = s;
-    }
-    return NB_OK;
+    const PsiConst c = sim.n > 0 ? psi_const(e) : PsiConst{};
+    const double g = (double)sim.params.g;
+    return run(
+        sim, kWorkField, points, m, ib, kSlabFields, flags, out, stats,
+        [&](const Band<nb_field_sample> &b) { launch_field(flags, ib, b, c); },
+        [&](const Band<nb_field_sample> &b) {
+            hipLaunchKernelGGL(field_finish_kernel, finish_grid(b), dim3(kThreads), 0, b.stream, b.slab, b.chunks, b.pts,
+                               b.p0, b.p1, b.stride, flags, g, b.out);
+        });
 }
 
 }  // namespace nb

@@ -113,34 +113,30 @@ int radial_edges(const char *what, bool log, double rmin, double rmax, uint32_t 
     return NB_OK;
 }
 
-// nb_sim_field: everything about the arguments that can be refused without a device
-int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out) {
+// nb_sim_field / nb_tidal_sim: what can be refused about the points of a probe without a device
+static int probe_check_args(const char *name, const float *points, size_t m, const void *out) {
     if (m > 0 && (!points || !out)) {
-        set_error("field: null %s", !points ? "points" : "out");
-        return NB_ERR_INVALID;
-    }
-    if (!flags || (flags & ~(NB_FIELD_ACCEL | NB_FIELD_POTENTIAL))) {
-        set_error("field: flags must be NB_FIELD_ACCEL, NB_FIELD_POTENTIAL or both (got 0x%x)", flags);
+        set_error("%s: null %s", name, !points ? "points" : "out");
         return NB_ERR_INVALID;
     }
     if (m > NB_FIELD_MAX_POINTS) {
-        set_error("field: at most %u points (got %zu)", NB_FIELD_MAX_POINTS, m);
+        set_error("%s: at most %u points (got %zu)", name, NB_FIELD_MAX_POINTS, m);
         return NB_ERR_INVALID;
     }
     return NB_OK;
 }
 
-// nb_tidal_sim: everything about the arguments that can be refused without a device
-int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out) {
-    if (m > 0 && (!points || !out)) {
-        set_error("tidal: null %s", !points ? "points" : "out");
-        return NB_ERR_INVALID;
-    }
-    if (m > NB_FIELD_MAX_POINTS) {
-        set_error("tidal: at most %u points (got %zu)", NB_FIELD_MAX_POINTS, m);
+int field_check_args(const float *points, size_t m, uint32_t flags, const nb_field_sample *out) {
+    if (int rc = probe_check_args("field", points, m, out)) return rc;
+    if (!flags || (flags & ~(NB_FIELD_ACCEL | NB_FIELD_POTENTIAL))) {
+        set_error("field: flags must be NB_FIELD_ACCEL, NB_FIELD_POTENTIAL or both (got 0x%x)", flags);
         return NB_ERR_INVALID;
     }
     return NB_OK;
+}
+
+int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out) {
+    return probe_check_args("tidal", points, m, out);
 }
 
 // nb_field_rings / nb_field_ring_means / nb_tidal_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
