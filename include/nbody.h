@@ -1247,6 +1247,120 @@ int nb_hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t 
                    double *out_peak, size_t out_capacity, size_t *out_count);
 
 /* ------------------------------------------------------------------------- */
+/* Local kinematics -- how the neighbours of every body move: the velocity    */
+/* moments and the velocity gradient over its k nearest neighbours (no        */
+/* reference counterpart)                                                     */
+/* ------------------------------------------------------------------------- */
+/* For every body of the state nb_sim_read_particles would return: the mass and
+ * velocity moments of its k nearest neighbours relative to the body itself, and,
+ * when asked for, the sums a least-squares velocity gradient is solved from;
+ * nb_local_kinematics_derive turns them on the host into the mean velocity, the
+ * dispersion sigma, the pseudo-phase-space density rho / sigma^3 and the gradient
+ * with its divergence, vorticity and shear.  The rule, which DESIGN.md 6s states
+ * in full: binary64 from the binary32 state, one rounding per operation, no
+ * contraction; `counted`, d2 and the order (d2, j) are nb_sim_knn's, word for word.
+ *   list      for a counted body i, 1 <= k <= NB_KNN_MAX_K and c > k: the first k
+ *             bodies of i's order, in that order
+ *   member j  m = (double)m_j, dx_a = (double)x_j,a - (double)x_i,a,
+ *             du_a = (double)v_j,a - (double)v_i,a
+ *   moments   NB_KIN_MOMENTS = 10 doubles per body:
+ *             [0]      S0 = sum m; with NB_KIN_SELF it starts from (double)m_i, not 0
+ *             [1..3]   S1_a = sum m du_a, the term one product
+ *             [4..9]   S2_ab = sum (m du_a) du_b for ab = xx, xy, xz, yy, yz, zz, the
+ *                      term two products in that association
+ *   gradient  NB_KIN_GRADS = 15 doubles per body, only when `grads` is given:
+ *             [0..5]   D_ab = sum (m dx_a) dx_b for ab = xx, xy, xz, yy, yz, zz
+ *             [6..14]  C_ab = sum (m du_a) dx_b, row-major in (a, b)
+ *   order     every sum is added in list order from its start value, left to right
+ *             (the order of mass_in)
+ *   knn       r2, kth, mass_in and density are nb_sim_knn's at the same k, bit for bit
+ *   special   a body that is not counted: every moment and gradient sum NaN, and
+ *             nb_sim_knn's presets; c <= k: every counted body has every sum 0 (S0 too,
+ *             with or without NB_KIN_SELF), nb_sim_knn's presets, short_of_k = c;
+ *             r2[i] == 0 is `degenerate` as in nb_sim_knn: the sums are still formed
+ * Everything per body is unique given the state: every double and integer is exact
+ * and bit-identical between calls.  No float atomics.  The tuning keys are
+ * nb_sim_knn's "knn_span_cells" and "knn_block_queries"; neither changes a bit.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends with
+ * one synchronisation, reports a TreeSim's status words as nb_sim_read_particles
+ * does, and does not change the trajectory. */
+#define NB_KIN_SELF 1u /* params.flags: the body's own mass starts S0 */
+#define NB_KIN_MOMENTS 10u
+#define NB_KIN_GRADS 15u
+/* status bits of nb_kin_derived */
+#define NB_KIN_SHORT 1u       /* counted, but c <= k */
+#define NB_KIN_NOT_COUNTED 2u /* a non-finite body */
+#define NB_KIN_DEGENERATE 4u  /* r2 == 0 */
+#define NB_KIN_SINGULAR 8u    /* the gradient was asked for and D is singular by the rule below */
+
+typedef struct nb_kin_params { /* 16 bytes */
+    uint32_t k;        /* 1 .. NB_KNN_MAX_K */
+    uint32_t flags;    /* NB_KIN_SELF */
+    uint64_t reserved; /* 0 */
+} nb_kin_params;
+
+typedef struct nb_kin_stats { /* 56 bytes */
+    uint64_t step_num, n, nonfinite, counted, degenerate, short_of_k;
+    uint32_t k, flags;
+} nb_kin_stats;
+
+typedef struct nb_kin_derived { /* 256 bytes: one body */
+    double mass;                 /* S0 */
+    double relative_velocity[3]; /* u_a = S1_a / S0: the neighbours' mean velocity relative to the body */
+    double mean_velocity[3];     /* (double)v_i,a + u_a; NaN without `velocities` */
+    double dispersion[6];        /* Sigma_ab = S2_ab / S0 - u_a u_b for ab = xx, xy, xz, yy, yz, zz */
+    double sigma2;               /* ((Sigma_xx + Sigma_yy) + Sigma_zz) / 3 */
+    double sigma;                /* sqrt(sigma2), 0 when sigma2 < 0 */
+    double phase_space_density;  /* Q = density / (sigma2 sigma); NaN without `density` */
+    double gradient[9];          /* G_ab = d u_a / d x_b, row-major; NaN without `grads` or when singular */
+    double det;                  /* det D; NaN without `grads` */
+    double divergence;           /* (G_xx + G_yy) + G_zz */
+    double vorticity[3];         /* (G_zy - G_yz, G_xz - G_zx, G_yx - G_xy) */
+    double shear;                /* the Frobenius norm of the traceless symmetric part of G */
+    uint32_t status;             /* NB_KIN_SHORT | NB_KIN_NOT_COUNTED | NB_KIN_DEGENERATE | NB_KIN_SINGULAR */
+    uint32_t reserved;
+} nb_kin_derived;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_kin_params) == 16 && sizeof(nb_kin_stats) == 56 && sizeof(nb_kin_derived) == 256,
+              "nb_kin_* layouts");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_kin_params) == 16 && sizeof(nb_kin_stats) == 56 && sizeof(nb_kin_derived) == 256,
+               "nb_kin_* layouts");
+#endif
+
+/* moments: n NB_KIN_MOMENTS doubles; grads: n NB_KIN_GRADS doubles; r2, kth, mass_in, density: n each, as
+ * nb_sim_knn.  Every output pointer may be null: what is not asked for is neither computed nor copied (the
+ * moments are formed with the gradient sums; a call with no per-body output runs the search alone for the
+ * stats; a call with no output at all synchronises and measures nothing).  The outputs are written only by a
+ * call that succeeds.  NB_ERR_INVALID for a null handle or params, k == 0, k > NB_KNN_MAX_K, unknown flags or
+ * reserved != 0 -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement
+ * world > 1). */
+int nb_local_kinematics_sim(nb_sim *sim, const nb_kin_params *params, double *moments, double *grads, double *r2,
+                            uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats);
+/* Host only, a pure function of its arguments, no device call: out[n] from what nb_local_kinematics_sim
+ * filled.  moments and r2 are required; grads, density and velocities (3 floats per body, the state's) may be
+ * null.  Per body, each step evaluated as written in binary64, no contraction:
+ *   u_a = S1_a / S0;  Sigma_ab = S2_ab / S0 - u_a u_b;  sigma2 = ((Sigma_xx + Sigma_yy) + Sigma_zz) / 3;
+ *   sigma = sqrt(sigma2), 0 when sigma2 < 0;  mean_velocity_a = (double)v_i,a + u_a;
+ *   Q = density / (sigma2 sigma).
+ * With grads, G = C D^-1, the least-squares fit du = G dx through body i with no intercept, by cofactors:
+ *   adj_xx = D_yy D_zz - D_yz D_yz   adj_xy = D_xz D_yz - D_xy D_zz   adj_xz = D_xy D_yz - D_xz D_yy
+ *   adj_yy = D_xx D_zz - D_xz D_xz   adj_yz = D_xy D_xz - D_xx D_yz   adj_zz = D_xx D_yy - D_xy D_xy
+ *   det = (D_xx adj_xx + D_xy adj_xy) + D_xz adj_xz        (adj is symmetric)
+ *   G_ab = ((C_a0 adj_0b + C_a1 adj_1b) + C_a2 adj_2b) / det
+ * A body is singular when !(det > 2^-30 ((D_xx D_yy) D_zz)): the ratio is scale-free and lies in [0, 1] by
+ * Hadamard's inequality; coplanar, collinear and coincident neighbours give 0.  Then G and what follows from
+ * it are NaN and NB_KIN_SINGULAR is set.  divergence = (G_xx + G_yy) + G_zz; vorticity = (G_zy - G_yz,
+ * G_xz - G_zx, G_yx - G_xy); with t = divergence / 3, s_aa = G_aa - t and s_ab = (G_ab + G_ba) / 2,
+ * shear = sqrt(((s_xx s_xx + s_yy s_yy) + s_zz s_zz) + 2 ((s_xy s_xy + s_xz s_xz) + s_yz s_yz)).
+ * status: NB_KIN_NOT_COUNTED for r2 NaN, NB_KIN_SHORT for r2 = +inf, NB_KIN_DEGENERATE for r2 == 0.  A body
+ * that is short or not counted has NaN in every derived double but mass.  NB_ERR_INVALID for null moments,
+ * r2 or out with n > 0. */
+int nb_local_kinematics_derive(const double *moments, const double *grads, const double *r2, const double *density,
+                               const float *velocities, size_t n, nb_kin_derived *out);
+
+/* ------------------------------------------------------------------------- */
 /* Halo profiles -- the spherical radial profile about many centres in one    */
 /* call (no reference counterpart)                                            */
 /* ------------------------------------------------------------------------- */
@@ -2057,6 +2171,10 @@ int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32
 /* nb_tidal_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
  * runner. */
 int nb_tidal_runner(nb_runner *runner, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
+/* nb_local_kinematics_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a
+ * several-GPU runner. */
+int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,
+                               double *r2, uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

@@ -43,6 +43,8 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
+           "LocalKinematics", "KinStats", "kinematics_derive", "KIN_SHORT", "KIN_NOT_COUNTED", "KIN_DEGENERATE",
+           "KIN_SINGULAR",
            "HopGroups", "HopStats", "HOP_NONE",
            "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
            "GroupRadii", "RadiiStats",
@@ -1300,6 +1302,154 @@ def _knn_density(call, handle, n, k, density, neighbours) -> KnnDensity:
     return KnnDensity(kk, r2, kth, mass_in, rho, _knn_stats(st))
 
 
+KIN_SHORT, KIN_NOT_COUNTED = _lib.NB_KIN_SHORT, _lib.NB_KIN_NOT_COUNTED
+KIN_DEGENERATE, KIN_SINGULAR = _lib.NB_KIN_DEGENERATE, _lib.NB_KIN_SINGULAR
+
+
+@dataclass(frozen=True)
+class KinStats:
+    """nb_kin_stats (include/nbody.h "Local kinematics")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    counted: int
+    degenerate: int   # counted bodies with at least k others at their own position
+    short_of_k: int   # the counted bodies when there are no more than k of them, else 0
+    k: int
+    flags: int
+
+
+def _sym33(six: np.ndarray) -> np.ndarray:
+    """(n, 6) xx, xy, xz, yy, yz, zz -> (n, 3, 3)."""
+    return six[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+
+
+@dataclass(frozen=True)
+class LocalKinematics:
+    """nb_local_kinematics_sim's per-body sums over the k nearest neighbours and what nb_local_kinematics_derive
+    makes of them (include/nbody.h "Local kinematics"; no reference counterpart).  moments (n, 10): S0, S1[3],
+    S2[6]; grads (n, 15) with gradient=True: D[6], C[9]; r2, mass_in, density as knn_density(k) returns them; kth
+    with neighbours=True; derived: _lib.KIN_DERIVED_DTYPE records, one per body, which the properties read.  A body
+    that is short of k or not counted has NaN in every derived value (status says which)."""
+    k: int
+    moments: np.ndarray
+    grads: Optional[np.ndarray]
+    r2: np.ndarray
+    kth: Optional[np.ndarray]
+    mass_in: np.ndarray
+    density: np.ndarray
+    derived: np.ndarray
+    stats: KinStats
+
+    @property
+    def r_k(self) -> np.ndarray:
+        """sqrt(r2): the distance to the k-th neighbour."""
+        return np.sqrt(self.r2)
+
+    @property
+    def mass(self) -> np.ndarray:
+        """S0: the mass of the neighbours (and, with include_self, of the body)."""
+        return self.derived["mass"]
+
+    @property
+    def mean_velocity(self) -> np.ndarray:
+        """(n, 3): the bulk velocity at the body, its own velocity plus relative_velocity."""
+        return self.derived["mean_velocity"]
+
+    @property
+    def relative_velocity(self) -> np.ndarray:
+        """(n, 3): the neighbours' mass-weighted mean velocity relative to the body, S1 / S0."""
+        return self.derived["relative_velocity"]
+
+    @property
+    def dispersion_tensor(self) -> np.ndarray:
+        """(n, 3, 3): S2 / S0 - u u."""
+        return _sym33(self.derived["dispersion"])
+
+    @property
+    def sigma(self) -> np.ndarray:
+        """The one-dimensional velocity dispersion sqrt(trace / 3)."""
+        return self.derived["sigma"]
+
+    @property
+    def phase_space_density(self) -> np.ndarray:
+        """Q = density / sigma^3."""
+        return self.derived["phase_space_density"]
+
+    @property
+    def status(self) -> np.ndarray:
+        """KIN_SHORT | KIN_NOT_COUNTED | KIN_DEGENERATE | KIN_SINGULAR per body."""
+        return self.derived["status"]
+
+    def _needs_gradient(self):
+        if self.grads is None:
+            raise ValueError("local_kinematics(gradient=True) makes the velocity gradient")
+
+    @property
+    def velocity_gradient(self) -> np.ndarray:
+        """(n, 3, 3): G[a, b] = d u_a / d x_b by least squares over the neighbours; NaN where KIN_SINGULAR."""
+        self._needs_gradient()
+        return self.derived["gradient"].reshape(-1, 3, 3)
+
+    @property
+    def divergence(self) -> np.ndarray:
+        self._needs_gradient()
+        return self.derived["divergence"]
+
+    @property
+    def vorticity(self) -> np.ndarray:
+        self._needs_gradient()
+        return self.derived["vorticity"]
+
+    @property
+    def shear(self) -> np.ndarray:
+        self._needs_gradient()
+        return self.derived["shear"]
+
+
+def kinematics_derive(moments, grads, r2, density, velocities) -> np.ndarray:
+    """nb_local_kinematics_derive: _lib.KIN_DERIVED_DTYPE records from the raw sums (host only).  grads, density and
+    velocities ((n, 3) float32) may be None."""
+    moments = np.ascontiguousarray(moments, dtype=np.float64).reshape(-1, _lib.NB_KIN_MOMENTS)
+    n = moments.shape[0]
+
+    def arr(a, dtype, width):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size != n * width:
+            raise ValueError(f"expected {n} x {width} values, got {a.size}")
+        return a
+
+    grads, r2 = arr(grads, np.float64, _lib.NB_KIN_GRADS), arr(r2, np.float64, 1)
+    density, velocities = arr(density, np.float64, 1), arr(velocities, np.float32, 3)
+    out = np.zeros(n, dtype=_lib.KIN_DERIVED_DTYPE)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(_lib.lib().nb_local_kinematics_derive(moments.ctypes.data, ptr(grads), ptr(r2), ptr(density),
+                                                ptr(velocities), n, out.ctypes.data))
+    return out
+
+
+def _local_kinematics(call, owner, n, k, gradient, include_self, neighbours) -> LocalKinematics:
+    p = _lib.nb_kin_params()
+    kk = int(k)
+    p.k, p.reserved = (kk if 0 <= kk <= 0xFFFFFFFF else 0), 0  # (the call refuses 0 itself)
+    p.flags = _lib.NB_KIN_SELF if include_self else 0
+    moments = np.empty((n, _lib.NB_KIN_MOMENTS), dtype=np.float64)
+    grads = np.empty((n, _lib.NB_KIN_GRADS), dtype=np.float64) if gradient else None
+    r2, mass_in, rho = (np.empty(n, dtype=np.float64) for _ in range(3))
+    kth = np.empty(n, dtype=np.uint32) if neighbours else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    st = _lib.nb_kin_stats()
+    check(call(owner._h, C.byref(p), moments.ctypes.data, ptr(grads), r2.ctypes.data, ptr(kth), mass_in.ctypes.data,
+               rho.ctypes.data, C.byref(st)))
+    vel = np.ascontiguousarray(owner.read_particles()["velocity"], dtype=np.float32)
+    derived = kinematics_derive(moments, grads, r2, rho, vel)
+    stats = KinStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.counted), int(st.degenerate),
+                     int(st.short_of_k), int(st.k), int(st.flags))
+    return LocalKinematics(kk, moments, grads, r2, kth, mass_in, rho, derived, stats)
+
+
 HALO_CENTER_NONFINITE = _lib.NB_HALO_CENTER_NONFINITE
 
 
@@ -2256,6 +2406,18 @@ class _Passes:
         A several-GPU runner refuses."""
         return _knn_density(self._pass("knn"), self._h, int(self.sim_params().particle_num), k, density,
                             neighbours)
+
+    def local_kinematics(self, k: int = 32, *, gradient: bool = False, include_self: bool = True,
+                         neighbours: bool = False) -> LocalKinematics:
+        """How the k nearest neighbours of every body of the current state move (nb_local_kinematics_sim, then
+        nb_local_kinematics_derive on the host): the local mean velocity, the dispersion tensor and sigma, the
+        pseudo-phase-space density rho / sigma^3 with knn_density(k)'s rho, and with gradient=True the least-squares
+        velocity gradient with its divergence, vorticity and shear.  include_self: the body's own mass starts the
+        mass sum.  neighbours=True also returns kth.  The body indices are those of read_particles() now: a TreeSim
+        reorders its bodies at every step.  A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _local_kinematics(getattr(_lib.lib(), "nb_local_kinematics_" + suffix), self,
+                                 int(self.sim_params().particle_num), k, gradient, include_self, neighbours)
 
     def halo_profiles(self, centers=None, *, bodies=None, velocities=None, edges=None, nbins: int = 32, rmin=None,
                       rmax=None, log: bool = True) -> HaloProfiles:

@@ -192,6 +192,15 @@ class nb_knn_stats(C.Structure):
                 ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_kin_params(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_kin_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("counted", C.c_uint64),
+                ("degenerate", C.c_uint64), ("short_of_k", C.c_uint64), ("k", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class nb_hop_params(C.Structure):
     _fields_ = [("k_density", C.c_uint32), ("k_hop", C.c_uint32), ("k_merge", C.c_uint32),
                 ("min_members", C.c_uint32), ("density_min", C.c_double), ("flags", C.c_uint32),
@@ -342,6 +351,13 @@ MODES_BIN_DTYPE = np.dtype([("count", "<u8"), ("m_r", "<f8"), ("m_h2", "<f8")])
 MODES_DERIVED_DTYPE = np.dtype([("amplitude", "<f8"), ("phase", "<f8"), ("pattern_speed", "<f8"),
                                 ("bend_amplitude", "<f8"), ("bend_phase", "<f8")])
 
+# nb_kin_derived[] as a numpy record array
+KIN_DERIVED_DTYPE = np.dtype([("mass", "<f8"), ("relative_velocity", "<f8", (3,)), ("mean_velocity", "<f8", (3,)),
+                              ("dispersion", "<f8", (6,)), ("sigma2", "<f8"), ("sigma", "<f8"),
+                              ("phase_space_density", "<f8"), ("gradient", "<f8", (9,)), ("det", "<f8"),
+                              ("divergence", "<f8"), ("vorticity", "<f8", (3,)), ("shear", "<f8"),
+                              ("status", "<u4"), ("reserved", "<u4")])
+
 # nb_radial_bin[] as a numpy record array
 RADIAL_BIN_DTYPE = np.dtype([("count", "<u8"), ("mass", "<f8"), ("m_r", "<f8"), ("m_ur", "<f8"), ("m_ur2", "<f8"),
                              ("m_uphi", "<f8"), ("m_uphi2", "<f8"), ("m_u2", "<f8"), ("ang", "<f8", (3,))])
@@ -361,6 +377,7 @@ assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
 assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
+assert C.sizeof(nb_kin_params) == 16 and C.sizeof(nb_kin_stats) == 56 and KIN_DERIVED_DTYPE.itemsize == 256
 assert C.sizeof(nb_hop_params) == 40 and C.sizeof(nb_hop_stats) == 96 and C.sizeof(nb_hop_regroup_params) == 24
 assert C.sizeof(nb_hop_boundary) == 24 == HOP_BOUNDARY_DTYPE.itemsize
 assert C.sizeof(nb_halo_params) == 48 and C.sizeof(nb_halo_stats) == 64
@@ -393,6 +410,8 @@ NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
 NB_BOUND_MAX_ITER = 64
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_KIN_SELF, NB_KIN_MOMENTS, NB_KIN_GRADS = 1, 10, 15
+NB_KIN_SHORT, NB_KIN_NOT_COUNTED, NB_KIN_DEGENERATE, NB_KIN_SINGULAR = 1, 2, 4, 8
 NB_HOP_NONE = 0xFFFFFFFF
 NB_HALO_MAX_BINS, NB_HALO_MAX_CENTERS, NB_HALO_MAX_ROWS = 64, 1 << 20, 1 << 22
 NB_HALO_MAX_CELLS_PER_AXIS, NB_HALO_CHUNK, NB_HALO_EXTRA_ITEMS = 1024, 4096, 1 << 16
@@ -426,6 +445,7 @@ ABI_SYMBOLS = [
     "nb_sim_fof", "nb_runner_fof",
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
+    "nb_local_kinematics_sim", "nb_local_kinematics_runner", "nb_local_kinematics_derive",
     "nb_sim_hop", "nb_runner_hop", "nb_hop_regroup",
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
@@ -526,6 +546,11 @@ def lib() -> C.CDLL:
     tidal = [vp, vp, sz, vp, P(nb_tidal_stats)]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_tidal_" + suffix).argtypes = tidal
+    # ... and the seventeenth (include/nbody.h "Local kinematics")
+    local_kinematics = [vp, P(nb_kin_params), vp, vp, vp, vp, vp, vp, P(nb_kin_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_local_kinematics_" + suffix).argtypes = local_kinematics
+    L.nb_local_kinematics_derive.argtypes = [vp, vp, vp, vp, vp, sz, vp]
     L.nb_phase_quantity.argtypes = [C.c_char_p, P(C.c_uint32)]
     L.nb_phase_quantity_name.argtypes = [C.c_uint32]
     L.nb_phase_quantity_name.restype = C.c_char_p

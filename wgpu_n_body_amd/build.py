@@ -38,6 +38,9 @@ SOURCES = [
     ("nb_bound.hip", ["-ffp-contract=off"]),
     # the neighbour order and the density are specified operation by operation: no FMA contraction
     ("nb_knn.hip", ["-ffp-contract=off"]),
+    # the neighbour list, the terms and the ordered sums are specified operation by operation: no FMA
+    # contraction
+    ("nb_kinematics.hip", ["-ffp-contract=off"]),
     # the density order and the boundary values are specified operation by operation: no FMA
     # contraction
     ("nb_hop.hip", ["-ffp-contract=off"]),

@@ -25,6 +25,7 @@
 //            [--modes K --modes-range RMIN,RMAX [--modes-bins B] [--modes-m M] [--modes-log 0|1]
 //             [--modes-axis X,Y,Z] [--modes-center com|X,Y,Z]]
 //            [--knn K [--knn-k 6]]
+//            [--kin K [--kin-k 32] [--kin-gradient 0|1]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
 //             [--halo-rho RHO]]
@@ -136,6 +137,14 @@
 // <peak_density> <peak_index>" (every real %.17g): the density centre and its velocity, the largest density and
 // the body that holds it.  The time it takes is not part of any "Step Duration"; without --knn the output is
 // unchanged.
+//
+// --kin K measures how the k nearest neighbours of every body move (nb_local_kinematics_runner, k = --kin-k, default
+// 32; --kin-gradient 1 adds the velocity gradient) at step 0 and at every K-th step and prints one line "kin <step>
+// <counted> <degenerate> <singular> <mean_sigma> <max_Q> <max_Q_index>" (every real %.17g): the bodies whose gradient
+// is singular (0 without --kin-gradient), the mean of sigma weighted by the bodies' own masses over the bodies with a
+// finite sigma, the largest finite Q = rho / sigma^3 and the first body that holds it (nan and 4294967295 when there
+// is none), all formed on the host in body order.  The time it takes is not part of any "Step Duration"; without
+// --kin the output is unchanged.
 //
 // --hop K finds the density-peak groups (nb_runner_hop; --hop-k DENS,HOP,MERGE, default 64,16,4; --hop-min M, default
 // 1; --hop-density-min D, default none) of step 0 and of every K-th step.  One line "hop <step> <peaks> <groups>
@@ -540,6 +549,36 @@ static void print_knn(nbody::OfflineHeadless<Sim> &runner, const KnnOptions &ko)
                 d.stats.peak_index);
 }
 
+struct KinOptions {
+    int every = 0;
+    uint32_t k = 32;
+    bool gradient = false;
+};
+
+template <class Sim>
+static void print_kin(nbody::OfflineHeadless<Sim> &runner, const KinOptions &ko) {
+    const nbody::LocalKinematics d = runner.local_kinematics(ko.k, ko.gradient, true, false);
+    const std::vector<nbody::Particle> parts = runner.read_particles();
+    unsigned long long singular = 0;
+    double ms = 0.0, m = 0.0, q_max = std::nan("");
+    uint32_t q_at = 0xFFFFFFFFu;
+    for (size_t i = 0; i < d.derived.size(); ++i) {
+        const nbody::KinDerived &r = d.derived[i];
+        if (r.status & NB_KIN_SINGULAR) ++singular;
+        if (std::isfinite(r.sigma)) {
+            ms += (double)parts[i].mass * r.sigma;
+            m += (double)parts[i].mass;
+        }
+        if (std::isfinite(r.phase_space_density) && !(r.phase_space_density <= q_max)) {
+            q_max = r.phase_space_density;
+            q_at = (uint32_t)i;
+        }
+    }
+    std::printf("kin %llu %llu %llu %llu %.17g %.17g %u\n", (unsigned long long)d.stats.step_num,
+                (unsigned long long)d.stats.counted, (unsigned long long)d.stats.degenerate, singular, ms / m, q_max,
+                q_at);
+}
+
 struct HopOptions {
     int every = 0, top = 0;
     nbody::HopParams params;
@@ -667,7 +706,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const RotcurveOptions &rotcurve, const MapOptions &maps, const SmapOptions &smaps, const FofOptions &fof,
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
-               const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq) {
+               const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
+               const KinOptions &kin) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -681,6 +721,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (fof.every > 0) print_fof(runner, fof);
     if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
+    if (kin.every > 0) print_kin(runner, kin);
     if (hop.every > 0) print_hop(runner, hop);
     if (halo.every > 0) print_halo(runner, halo);
     if (shapes.every > 0) print_shapes(runner, shapes);
@@ -704,6 +745,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
         if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
+        if (kin.every > 0 && (i + 1) % kin.every == 0) print_kin(runner, kin);
         if (hop.every > 0 && (i + 1) % hop.every == 0) print_hop(runner, hop);
         if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
         if (shapes.every > 0 && (i + 1) % shapes.every == 0) print_shapes(runner, shapes);
@@ -738,6 +780,7 @@ int main(int argc, char **argv) {
     SmapOptions smaps;
     FofOptions fof;
     KnnOptions knn;
+    KinOptions kin;
     BoundOptions bound;
     HaloOptions halo;
     HopOptions hop;
@@ -1035,6 +1078,9 @@ int main(int argc, char **argv) {
         } else if (k == "--hop-top") hop.top = std::atoi(v.c_str());
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--kin") kin.every = std::atoi(v.c_str());
+        else if (k == "--kin-k") kin.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--kin-gradient") kin.gradient = std::atoi(v.c_str()) != 0;
         else if (k == "--halo") halo.every = std::atoi(v.c_str());
         else if (k == "--halo-link") halo.link = std::atof(v.c_str());
         else if (k == "--halo-range") {
@@ -1132,9 +1178,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

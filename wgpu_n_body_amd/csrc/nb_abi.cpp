@@ -172,6 +172,15 @@ static int pass_knn(H *h, const nb_knn_params *params, double *r2, uint32_t *kth
 }
 
 template <class H>
+static int pass_local_kinematics(H *h, const nb_kin_params *params, double *moments, double *grads, double *r2,
+                                 uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats) {
+    if (int rc = kin_check_params(params)) return rc;
+    return on_sim(h, "local_kinematics", [&](SimBase &s) {
+        return sim_local_kinematics(s, *params, moments, grads, r2, kth, mass_in, density, stats);
+    });
+}
+
+template <class H>
 static int pass_hop(H *h, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of, double *density,
                     nb_fof_group *groups, double *peak_density, size_t group_capacity, nb_hop_boundary *boundaries,
                     size_t boundary_capacity, nb_hop_stats *stats) {
@@ -546,6 +555,19 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
 int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, uint32_t *kth, double *mass_in,
                   double *density, nb_knn_stats *stats) {
     return pass_knn(runner, params, r2, kth, mass_in, density, stats);
+}
+
+int nb_local_kinematics_sim(nb_sim *sim, const nb_kin_params *params, double *moments, double *grads, double *r2,
+                            uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats) {
+    return pass_local_kinematics(sim, params, moments, grads, r2, kth, mass_in, density, stats);
+}
+int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,
+                               double *r2, uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats) {
+    return pass_local_kinematics(runner, params, moments, grads, r2, kth, mass_in, density, stats);
+}
+int nb_local_kinematics_derive(const double *moments, const double *grads, const double *r2, const double *density,
+                               const float *velocities, size_t n, nb_kin_derived *out) {
+    NB_GUARD({ return kin_derive(moments, grads, r2, density, velocities, n, out); })
 }
 
 int nb_sim_hop(nb_sim *sim, const nb_hop_params *params, uint32_t *labels, uint32_t *group_of, double *density,

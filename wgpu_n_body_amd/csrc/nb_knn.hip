@@ -56,7 +56,6 @@ constexpr uint32_t kAxisMax = kKnnAxisMax;
 constexpr unsigned long long kKeyNone = 1ull << 63;        // past every Morton code
 constexpr uint32_t kSumFields = kKnnSumFields, kSumLive = 9;  // the eight sums and the degenerate bodies
 constexpr uint32_t kFinishGroups = 16;                     // G of sum_over_blocks
-constexpr double kSphere = NB_KNN_SPHERE;                  // C = 4 pi / 3
 
 // (the plan and the reduced results of a call, KnnInfo, and ordered64: nb_knn.hpp)
 __host__ inline double unordered64(unsigned long long e) {
@@ -155,15 +154,14 @@ __global__ __launch_bounds__(kThreads) void knn_search_kernel(const KnnInfo *__r
     knn_search(q, info, keys, sidx, spos, c, p, k, span);
 
     // lane l < k holds the (l + 1)-th body of the order
-    const double ml = q.lane + 1 < k && q.lj != NB_KNN_NONE ? (double)posm[q.lj].w : 0.0;
-    double mass = 0.0;
-    for (uint32_t l = 0; l + 1 < k; ++l) mass += __shfl(ml, (int)l);
+    double mass, rho;
+    knn_mass_density(q, posm, k, &mass, &rho);
     if (q.lane == 0) {
         const uint32_t body = sidx[p];
         r2[body] = q.kd;
         kth[body] = q.kj;
         mass_in[body] = mass;
-        density[body] = q.kd == 0.0 ? (double)INFINITY : mass / (kSphere * (q.kd * sqrt(q.kd)));
+        density[body] = rho;
     }
 }
 
@@ -260,7 +258,7 @@ int knn_work(SimBase &sim, KnnWork **out) {
     });
 }
 
-int knn_enqueue(SimBase &sim, KnnWork &w, uint32_t k) {
+int knn_enqueue_sorted(SimBase &sim, KnnWork &w) {
     const uint32_t n = sim.n;
     if (n > 0x7fffffffu) {
         set_error("knn: %u bodies are more than one call takes", n);
@@ -268,7 +266,6 @@ int knn_enqueue(SimBase &sim, KnnWork &w, uint32_t k) {
     }
     const uint32_t blocks = (n + kThreads - 1) / kThreads;
     const SortShape shape = sort_shape(n);
-    const uint32_t per_block = (uint32_t)sim.knn_block_queries, span = (uint32_t)sim.knn_span_cells;
     if (int rc = w.sort.reserve(n, shape, [](auto &b, size_t count) { return knn_reserve(b, count); })) return rc;
     if (int rc = knn_reserve(w.slabs, (size_t)std::max(kBoundFields, kSumFields) * blocks)) return rc;
     if (int rc = knn_reserve(w.spos, n)) return rc;
@@ -293,6 +290,18 @@ int knn_enqueue(SimBase &sim, KnnWork &w, uint32_t k) {
     hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, sidx,
                        w.spos, w.r2, w.kth, w.mass_in, w.density);
     NB_HIP_TRY(hipGetLastError());
+    return NB_OK;
+}
+
+int knn_enqueue(SimBase &sim, KnnWork &w, uint32_t k) {
+    if (int rc = knn_enqueue_sorted(sim, w)) return rc;
+    const uint32_t n = sim.n;
+    const uint32_t per_block = (uint32_t)sim.knn_block_queries, span = (uint32_t)sim.knn_span_cells;
+    const float4 *posm = nullptr, *vel = nullptr;
+    sim.diag_state(&posm, &vel);
+    const KnnInfo *info = w.info;
+    const unsigned long long *keys = w.sort.keys[0];
+    const uint32_t *sidx = w.sort.idx[0];
     // one wave per sorted position; those past the counted bodies, and all of them in a state short of k,
     // return at once: no host round trip decides the launch
     hipLaunchKernelGGL(knn_search_kernel, dim3((n + per_block - 1) / per_block), dim3(per_block * kWave), 0,

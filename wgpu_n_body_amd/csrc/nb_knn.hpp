@@ -1,7 +1,8 @@
 // nb_knn.hpp -- what the passes that start from the neighbour search share (nb_knn.hip: nb_sim_knn itself;
-// nb_hop.hip: nb_sim_hop): the plan and the reduced results of the search on the device, its workspace, the part
-// of it that only enqueues, and the device code of the search itself up to "lane l < k holds the (l + 1)-th body
-// of the order" -- both epilogues call one search.
+// nb_hop.hip: nb_sim_hop; nb_kinematics.hip: nb_local_kinematics_sim): the plan and the reduced results of the
+// search on the device, its workspace, the part of it that only enqueues, and the device code of the search itself
+// up to "lane l < k holds the (l + 1)-th body of the order", with the mass and the density that follow from it --
+// every epilogue calls one search.
 #pragma once
 
 #include <algorithm>
@@ -45,6 +46,10 @@ struct KnnWork : Workspace {  // (all grow to the largest call so far)
 // w.mass_in, w.density.
 int knn_work(SimBase &sim, KnnWork **out);
 int knn_enqueue(SimBase &sim, KnnWork &w, uint32_t k);
+// ... and the same without the search kernel, for a pass that runs the search under an epilogue of its own
+// (nb_kinematics.hip): afterwards w.info, the sorted (key, body index), w.spos, and the four per-body arrays at
+// their presets (a body that is not counted, or a state short of k)
+int knn_enqueue_sorted(SimBase &sim, KnnWork &w);
 
 #ifdef __HIPCC__
 
@@ -258,6 +263,18 @@ __device__ inline void knn_search(Query &q, const KnnInfo *__restrict__ info,
             }
         }
     }
+}
+
+// After knn_search: mass_in, added over lanes 0 .. k - 2 in order, and the density formed as written (the rule of
+// include/nbody.h), the same on every lane.
+__device__ inline void knn_mass_density(const Query &q, const float4 *__restrict__ posm, uint32_t k, double *mass_in,
+                                        double *density) {
+#pragma clang fp contract(off)
+    const double ml = q.lane + 1 < k && q.lj != NB_KNN_NONE ? (double)posm[q.lj].w : 0.0;
+    double mass = 0.0;
+    for (uint32_t l = 0; l + 1 < k; ++l) mass += __shfl(ml, (int)l);
+    *mass_in = mass;
+    *density = q.kd == 0.0 ? (double)INFINITY : mass / (NB_KNN_SPHERE * (q.kd * sqrt(q.kd)));
 }
 
 #endif  // __HIPCC__

@@ -439,6 +439,99 @@ int knn_check_params(const nb_knn_params *p) {
     return NB_OK;
 }
 
+// nb_local_kinematics_sim: everything that can be refused without a device
+int kin_check_params(const nb_kin_params *p) {
+    if (!p) {
+        set_error("local_kinematics: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->k < 1 || p->k > NB_KNN_MAX_K) {
+        set_error("local_kinematics: k must be 1..%u (got %u)", NB_KNN_MAX_K, p->k);
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~NB_KIN_SELF) || p->reserved) {
+        set_error("local_kinematics: unknown flag bits 0x%x or reserved %llu != 0", p->flags & ~NB_KIN_SELF,
+                  (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_local_kinematics_derive
+int kin_derive(const double *moments, const double *grads, const double *r2, const double *density,
+               const float *velocities, size_t n, nb_kin_derived *out) {
+#pragma clang fp contract(off)
+    if (n > 0 && (!moments || !r2 || !out)) {
+        set_error("local_kinematics_derive: null %s", !moments ? "moments" : !r2 ? "r2" : "out");
+        return NB_ERR_INVALID;
+    }
+    const double nan = std::nan("");
+    for (size_t i = 0; i < n; ++i) {
+        const double *s = moments + i * NB_KIN_MOMENTS;
+        nb_kin_derived d{};
+        const auto fill = [nan](double *a, int count) {
+            for (int q = 0; q < count; ++q) a[q] = nan;
+        };
+        d.mass = s[0];
+        fill(d.relative_velocity, 3);
+        fill(d.mean_velocity, 3);
+        fill(d.dispersion, 6);
+        d.sigma2 = d.sigma = d.phase_space_density = nan;
+        fill(d.gradient, 9);
+        d.det = d.divergence = d.shear = nan;
+        fill(d.vorticity, 3);
+        d.status = std::isnan(r2[i]) ? NB_KIN_NOT_COUNTED : std::isinf(r2[i]) ? NB_KIN_SHORT
+                   : r2[i] == 0.0    ? NB_KIN_DEGENERATE
+                                     : 0u;
+        if (!(d.status & (NB_KIN_NOT_COUNTED | NB_KIN_SHORT))) {
+            double u[3];
+            for (int a = 0; a < 3; ++a) {
+                u[a] = s[1 + a] / s[0];
+                d.relative_velocity[a] = u[a];
+                if (velocities) d.mean_velocity[a] = (double)velocities[3 * i + a] + u[a];
+            }
+            static const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
+            for (int q = 0; q < 6; ++q) d.dispersion[q] = s[4 + q] / s[0] - u[ia[q]] * u[ib[q]];
+            d.sigma2 = ((d.dispersion[0] + d.dispersion[3]) + d.dispersion[5]) / 3.0;
+            d.sigma = d.sigma2 < 0.0 ? 0.0 : std::sqrt(d.sigma2);
+            if (density) d.phase_space_density = density[i] / (d.sigma2 * d.sigma);
+            if (grads) {
+                const double *g = grads + i * NB_KIN_GRADS, *c = g + 6;
+                const double xx = g[0], xy = g[1], xz = g[2], yy = g[3], yz = g[4], zz = g[5];
+                double adj[3][3];
+                adj[0][0] = yy * zz - yz * yz;
+                adj[0][1] = adj[1][0] = xz * yz - xy * zz;
+                adj[0][2] = adj[2][0] = xy * yz - xz * yy;
+                adj[1][1] = xx * zz - xz * xz;
+                adj[1][2] = adj[2][1] = xy * xz - xx * yz;
+                adj[2][2] = xx * yy - xy * xy;
+                const double det = (xx * adj[0][0] + xy * adj[0][1]) + xz * adj[0][2];
+                d.det = det;
+                if (!(det > 0x1p-30 * ((xx * yy) * zz))) {
+                    d.status |= NB_KIN_SINGULAR;
+                } else {
+                    double *G = d.gradient;
+                    for (int a = 0; a < 3; ++a)
+                        for (int b = 0; b < 3; ++b)
+                            G[3 * a + b] =
+                                ((c[3 * a] * adj[0][b] + c[3 * a + 1] * adj[1][b]) + c[3 * a + 2] * adj[2][b]) / det;
+                    d.divergence = (G[0] + G[4]) + G[8];
+                    d.vorticity[0] = G[7] - G[5];
+                    d.vorticity[1] = G[2] - G[6];
+                    d.vorticity[2] = G[3] - G[1];
+                    const double t = d.divergence / 3.0;
+                    const double sxx = G[0] - t, syy = G[4] - t, szz = G[8] - t;
+                    const double sxy = (G[1] + G[3]) / 2.0, sxz = (G[2] + G[6]) / 2.0, syz = (G[5] + G[7]) / 2.0;
+                    d.shear = std::sqrt(((sxx * sxx + syy * syy) + szz * szz) +
+                                        2.0 * ((sxy * sxy + sxz * sxz) + syz * syz));
+                }
+            }
+        }
+        out[i] = d;
+    }
+    return NB_OK;
+}
+
 // nb_sim_hop: everything that can be refused without a device
 int hop_check_params(const nb_hop_params *p) {
     if (!p) {

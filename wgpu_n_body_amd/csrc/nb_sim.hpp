@@ -14,7 +14,8 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal, kWorkSlots };
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal,
+                      kWorkKin, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -230,6 +231,13 @@ int modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m,
 int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);
+// nb_kinematics.hip: nb_local_kinematics_sim behind the handle; kin_derive: nb_local_kinematics_derive behind the
+// ABI boundary
+int kin_check_params(const nb_kin_params *p);
+int sim_local_kinematics(SimBase &sim, const nb_kin_params &params, double *moments, double *grads, double *r2,
+                         uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats);
+int kin_derive(const double *moments, const double *grads, const double *r2, const double *density,
+               const float *velocities, size_t n, nb_kin_derived *out);
 // nb_hop.hip: nb_sim_hop behind the handle
 int hop_check_params(const nb_hop_params *p);
 int sim_hop(SimBase &sim, const nb_hop_params &params, uint32_t *labels, uint32_t *group_of, double *density,

@@ -54,6 +54,8 @@ using RadiiStats = nb_radii_stats;
 using HopBoundary = nb_hop_boundary;      // 24 B: two labels, their body pairs and the largest pair density
 using HopStats = nb_hop_stats;
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
+using KinStats = nb_kin_stats;            // the counts of nb_local_kinematics_sim
+using KinDerived = nb_kin_derived;        // 256 B: a body's local mean velocity, dispersion, Q and velocity gradient
 using HaloHead = nb_halo_head;            // 64 B: what lies inside edges[0], the centre and velocity used, flags
 using HaloStats = nb_halo_stats;
 using SmoothParams = nb_smooth_params;    // a map's parameters and the bounds of the smoothing lengths
@@ -803,6 +805,46 @@ KnnDensity knn_density(int (*call)(H *, const nb_knn_params *, double *, uint32_
 }
 }  // namespace detail
 
+// nb_local_kinematics_sim's per-body sums over the k nearest neighbours (no reference counterpart) and the rows
+// nb_local_kinematics_derive makes of them: moments 10 and grads 15 doubles per body, grads and kth empty when not
+// asked for; derived[i].mean_velocity is NaN until derive() is given the state's velocities
+struct LocalKinematics {
+    uint32_t k = 0;
+    std::vector<double> moments, grads, r2, mass_in, density;
+    std::vector<uint32_t> kth;
+    std::vector<KinDerived> derived;
+    KinStats stats{};
+    // nb_local_kinematics_derive again, with the velocities (3 floats per body) of the state the sums were made from
+    void derive(const std::vector<float> *velocities = nullptr) {
+        derived.resize(r2.size());
+        check(nb_local_kinematics_derive(moments.data(), grads.empty() ? nullptr : grads.data(), r2.data(),
+                                         density.data(), velocities ? velocities->data() : nullptr, r2.size(),
+                                         derived.data()));
+    }
+};
+
+namespace detail {
+template <class H>
+LocalKinematics local_kinematics(int (*call)(H *, const nb_kin_params *, double *, double *, double *, uint32_t *,
+                                             double *, double *, nb_kin_stats *),
+                                 H *h, size_t n, uint32_t k, bool gradient, bool include_self, bool neighbours) {
+    LocalKinematics d;
+    nb_kin_params p{};
+    p.k = d.k = k;
+    p.flags = include_self ? NB_KIN_SELF : 0u;
+    d.moments.resize(n * NB_KIN_MOMENTS);
+    if (gradient) d.grads.resize(n * NB_KIN_GRADS);
+    d.r2.resize(n);
+    d.mass_in.resize(n);
+    d.density.resize(n);
+    if (neighbours) d.kth.resize(n);
+    check(call(h, &p, d.moments.data(), gradient ? d.grads.data() : nullptr, d.r2.data(),
+               neighbours ? d.kth.data() : nullptr, d.mass_in.data(), d.density.data(), &d.stats));
+    d.derive();
+    return d;
+}
+}  // namespace detail
+
 // The spherical radial profiles of a state about many centres (nb_sim_halo_profiles; no reference counterpart):
 // heads[c] and bins[c * nbins + k] for centre c and bin k, the edges shared by all centres
 struct HaloProfiles {
@@ -978,6 +1020,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto disc_modes = nb_disc_modes_sim;
     static constexpr auto phase_map = nb_phase_map_sim;
     static constexpr auto tidal = nb_tidal_sim;
+    static constexpr auto local_kinematics = nb_local_kinematics_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -998,6 +1041,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto disc_modes = nb_disc_modes_runner;
     static constexpr auto phase_map = nb_phase_map_runner;
     static constexpr auto tidal = nb_tidal_runner;
+    static constexpr auto local_kinematics = nb_local_kinematics_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -1077,6 +1121,12 @@ class Passes {
     }
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(Abi::knn, h_, n_bodies(), k, density, neighbours);
+    }
+    // how the k nearest neighbours of every body move: the moments, with gradient the velocity-gradient sums, and
+    // the derived rows (sigma, rho / sigma^3, divergence, vorticity, shear)
+    LocalKinematics local_kinematics(uint32_t k = 32, bool gradient = false, bool include_self = true,
+                                     bool neighbours = false) {
+        return detail::local_kinematics(Abi::local_kinematics, h_, n_bodies(), k, gradient, include_self, neighbours);
     }
     // the profiles about points (centers: x y z per centre) or about bodies; velocities: empty, or three per centre
     HaloProfiles halo_profiles(const std::vector<double> &edges, const std::vector<double> &centers,
