@@ -631,6 +631,117 @@ int nb_tidal_ring_means(const double center[3], const double axis[3], const doub
                         const nb_field_ring *rings, nb_tidal_ring *out);
 
 /* ------------------------------------------------------------------------- */
+/* Orbits -- test particles in the frozen field of the current state, at rest  */
+/* or rotating rigidly at a pattern speed (no reference counterpart)           */
+/* ------------------------------------------------------------------------- */
+/* m massless tracers are integrated for `steps` leapfrog steps in the field of
+ * "Field probes" above, sampled from the state nb_sim_read_particles would return
+ * and frozen there: the bodies do not move, and with omega != 0 their frozen
+ * pattern turns rigidly about `axis` through `center` at the pattern speed omega
+ * (nb_disc_modes_derive's).  The tracers stay on the device between the force
+ * evaluations and every step is enqueued up front; the call ends with one
+ * synchronisation.  Orbit families of a bar, surfaces of section, trapping at
+ * corotation and the Jacobi integral as a quality check are read from the
+ * records.  The rule, which DESIGN.md 6t states in full.
+ * Everything outside the field sample is binary64 +, -, x, each rounded once, no
+ * contraction.  (e1, e2, n) = nb_map_frame(axis); c = center; h = dt / 2;
+ * (C_k, S_k) = nb_orbit_phase(omega, dt, step0 + k): the cosine and sine of
+ * theta_k = omega * ((double)(step0 + k) * dt), computed on the host by the C
+ * library and handed to the device by value; omega == 0 gives exactly (1, 0).
+ * Evaluation k of a tracer at x (tracers move in the inertial frame; the field is
+ * sampled at the point the frozen pattern has under x):
+ *   omega == 0   q = x
+ *   otherwise    d = x - c
+ *                a = (dx e1x + dy e1y) + dz e1z,  b and l likewise with e2 and n
+ *                a' = a C_k + b S_k,  b' = b C_k - a S_k         (turned by -theta_k)
+ *                q_i = c_i + ((a' e1_i + b' e2_i) + l n_i)
+ *   p = (float)q, component by component
+ *   sample       nb_sim_field's at p, bit for bit, for the m points of the call's
+ *                tracers and flags F_k = NB_FIELD_ACCEL | NB_FIELD_POTENTIAL when
+ *                NB_ORBIT_ENERGY is set and state k is recorded, NB_FIELD_ACCEL
+ *                otherwise: the same points per lane, plan, chunk order and x g
+ *   A_snap = accel_scale * sample.acc,  Phi = accel_scale * sample.potential
+ *   omega == 0   A = A_snap
+ *   otherwise    u = (Ax e1x + Ay e1y) + Az e1z,  v and t likewise with e2 and n
+ *                u' = u C_k - v S_k,  v' = v C_k + u S_k         (turned by +theta_k)
+ *                A_i = (u' e1_i + v' e2_i) + t n_i
+ * Integrator, kick-drift-kick with one evaluation per step and one at the start:
+ *   w = v_k + A_k h,   x_{k+1} = x_k + w dt,   v_{k+1} = w + A_{k+1} h
+ * each component as one multiply and one add.  State k has time
+ * t_k = (double)(step0 + k) * dt.
+ * A state is recorded at k = 0, every, 2 every, ... and at k = steps;
+ * nb_orbit_records(steps, every) is their number R, and record r of tracer i is
+ * tracks[r * m + i]: x_k, v_k, and with NB_ORBIT_ENERGY
+ *   potential = Phi_k
+ *   energy    = (0.5 ((vx vx + vy vy) + vz vz) + Phi) - omega (n . ((x - c) x v)),
+ *               the last term as  L = (n_x (dy vz - dz vy) + n_y (dz vx - dx vz))
+ *               + n_z (dx vy - dy vx),  d = x - c, and omega L subtracted; with
+ *               omega == 0 it is not formed.  With omega != 0 this is the Jacobi
+ *               integral, conserved to the integrator's order; the plain energy
+ *               is not.
+ * Without NB_ORBIT_ENERGY potential and energy are NaN.
+ * coincident[i] sums the samples' coincident counts over the steps + 1
+ * evaluations of tracer i.  A tracer that starts with a non-finite coordinate or
+ * velocity has NaN in every field of every record and is counted in
+ * stats.nonfinite_tracers; one that becomes non-finite (its point no longer an
+ * fp32 number included) is NaN from there on through the field's rule for
+ * non-finite points; the other tracers keep their bits.  Non-finite bodies are
+ * left out and counted in stats.nonfinite as by nb_sim_field.  n = 0 gives
+ * straight lines.  m = 0 is valid and only synchronises.
+ * Consequences: two calls return the same bits; permuting the tracers permutes
+ * the tracks; "field_launch_pairs_log2" partitions the tracers into bands
+ * (stats.pair_launches counts the pair launches) and cannot change a bit; and a run
+ * of 2 S steps equals a run of S steps followed by a run of S steps from the first
+ * run's last record with step0 + S, bit for bit, whenever S is a multiple of
+ * `every` (state S is then recorded by all three runs, so every evaluation has
+ * the same flags in the whole run and in its half).
+ * The call does not change the trajectory and reports a TreeSim's status words as
+ * nb_sim_read_particles does. */
+#define NB_ORBIT_ENERGY 1u
+#define NB_ORBIT_MAX_TRACERS (1u << 20)
+#define NB_ORBIT_MAX_STEPS (1u << 20)
+#define NB_ORBIT_MAX_SAMPLES (1u << 22) /* records * tracers */
+#define NB_ORBIT_MAX_PAIRS_LOG2 44      /* padded tracers * n * (steps + 1) */
+
+typedef struct nb_orbit_params {
+    double dt;      /* finite, non-zero; negative integrates backwards */
+    uint64_t step0; /* number of the first state: time t_k = (double)(step0 + k) * dt */
+    uint32_t steps, every, flags, reserved;
+    double accel_scale; /* acceleration = accel_scale * nb_sim_field's; finite */
+    double omega;       /* pattern speed about `axis` through `center`; 0: no rotation */
+    double axis[3], center[3];
+} nb_orbit_params;
+
+typedef struct nb_orbit_sample { /* 64 bytes */
+    double pos[3], vel[3], potential, energy;
+} nb_orbit_sample;
+
+typedef struct nb_orbit_stats {
+    uint64_t step_num; /* the step the measured state is the result of */
+    uint64_t n;        /* bodies of the simulator */
+    uint64_t nonfinite;
+    uint64_t tracers, nonfinite_tracers;
+    uint32_t records, pair_launches, flags, reserved;
+} nb_orbit_stats;
+
+/* The orbits of m tracers from pos, vel (3 doubles per tracer) in the field of a simulator's current state
+ * into tracks[0 .. records * m), record-major.  coincident ([m]) and stats may be null.  NB_ERR_INVALID for a
+ * null handle or params, null pos, vel or tracks with m > 0, steps = 0 or above NB_ORBIT_MAX_STEPS, every = 0,
+ * unknown flag bits or reserved != 0, m > NB_ORBIT_MAX_TRACERS, records * m > NB_ORBIT_MAX_SAMPLES, a dt or
+ * accel_scale that is not finite, dt = 0, a non-finite omega or center, with omega != 0 a zero or non-finite
+ * axis, or NB_ORBIT_ENERGY with e < 0 -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded
+ * simulator (placement world > 1) and for a call above 2^NB_ORBIT_MAX_PAIRS_LOG2 pairs, which the caller
+ * splits: step0 makes the split exact.  No single launch exceeds the budget of "field_launch_pairs_log2". */
+int nb_orbits_sim(nb_sim *sim, const nb_orbit_params *params, const double *pos, const double *vel, size_t m,
+                  nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats);
+/* Host only: the number of recorded states, steps / every + 1 and one more when every does not divide steps;
+ * 0 for every = 0. */
+uint32_t nb_orbit_records(uint32_t steps, uint32_t every);
+/* Host only: *c, *s = cos, sin of omega * ((double)k * dt) by the C library; exactly (1, 0) for omega == 0.
+ * NB_ERR_INVALID for a null pointer or a non-finite omega or dt. */
+int nb_orbit_phase(double omega, double dt, uint64_t k, double *c, double *s);
+
+/* ------------------------------------------------------------------------- */
 /* Projected maps -- per-cell mass and velocity moments on a 2-D grid (no     */
 /* reference counterpart: structure in two dimensions, without symmetry)      */
 /* ------------------------------------------------------------------------- */
@@ -2171,6 +2282,10 @@ int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32
 /* nb_tidal_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
  * runner. */
 int nb_tidal_runner(nb_runner *runner, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
+/* nb_orbits_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_orbits_runner(nb_runner *runner, const nb_orbit_params *params, const double *pos, const double *vel,
+                     size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats);
 /* nb_local_kinematics_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a
  * several-GPU runner. */
 int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,

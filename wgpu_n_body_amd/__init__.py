@@ -38,7 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
-           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "ProjectedMap", "map_frame", "map_edges",
+           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "ProjectedMap", "map_frame", "map_edges",
            "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
            "FofGroups", "FofStats", "FOF_NONE",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
@@ -607,6 +607,96 @@ def _disc_frequencies(field_call, tidal_call, handle, radii, axis, center, n_phi
                                          rings.ctypes.data, out.ctypes.data))
     return DiscFrequencies(r, out["omega2"].copy(), out["kappa2"].copy(), out["nu2"].copy(), cv.v_c,
                            out["t_RR"].copy(), out["t_pp"].copy(), out["t_nn"].copy(), out["t_Rn"].copy(), cv, t)
+
+
+@dataclass(frozen=True)
+class OrbitStats:
+    """nb_orbit_stats: what an orbits() call measured."""
+    step_num: int
+    n: int
+    nonfinite: int           # bodies left out, as diagnostics() counts them
+    tracers: int
+    nonfinite_tracers: int   # tracers that started non-finite: NaN in every record
+    records: int
+    pair_launches: int       # pair launches in all: evaluations x bands
+    flags: int
+
+
+@dataclass(frozen=True)
+class Orbits:
+    """nb_orbit_sample[R][M] + nb_orbit_stats (include/nbody.h "Orbits"; no reference counterpart): M test particles
+    integrated through the frozen field of the state read_particles would return, the pattern at rest (omega = 0) or
+    turning rigidly about `axis` through `center`.  Positions and velocities are inertial; with energy=True `energy`
+    is the Jacobi integral (the plain energy for omega = 0), otherwise it and `potential` are NaN."""
+    pos: np.ndarray          # (R, M, 3) float64
+    vel: np.ndarray          # (R, M, 3) float64
+    potential: np.ndarray    # (R, M) float64
+    energy: np.ndarray       # (R, M) float64
+    step: np.ndarray         # (R,) uint64: step0 + k of every record
+    time: np.ndarray         # (R,) float64: (double)(step0 + k) * dt
+    coincident: np.ndarray   # (M,) uint32: bodies at a tracer's point, summed over its evaluations
+    stats: OrbitStats
+    dt: float
+    omega: float
+    axis: np.ndarray
+    center: np.ndarray
+
+    def in_pattern_frame(self) -> np.ndarray:
+        """(R, M, 3): the positions in the frame that turns with the pattern -- each record turned back by its
+        theta_k about `axis` through `center`, with the phases of nb_orbit_phase the device used."""
+        if self.omega == 0.0:
+            return self.pos.copy()
+        n, e1, e2 = map_frame(self.axis)
+        out = np.empty_like(self.pos)
+        c, s_ = C.c_double(), C.c_double()
+        for r, k in enumerate(self.step):
+            check(_lib.lib().nb_orbit_phase(self.omega, self.dt, int(k), C.byref(c), C.byref(s_)))
+            d = self.pos[r] - self.center
+            a, b, l = d @ e1, d @ e2, d @ n
+            ar, br = a * c.value + b * s_.value, b * c.value - a * s_.value
+            out[r] = self.center + (ar[:, None] * e1 + br[:, None] * e2) + l[:, None] * n
+        return out
+
+    def energy_range(self) -> np.ndarray:
+        """(M,): max - min of `energy` over the records, per tracer (NaN without energy=True)."""
+        return self.energy.max(axis=0) - self.energy.min(axis=0)
+
+    def final(self):
+        """(pos, vel, step): the last record and its step number -- what a continuing call takes as pos, vel and
+        step0.  The continuation is exact when this call's `steps` is a multiple of its `every`."""
+        return self.pos[-1].copy(), self.vel[-1].copy(), int(self.step[-1])
+
+
+def _orbits(call, handle, pos, vel, dt, steps, every, energy, omega, axis, center, accel_scale, step0) -> Orbits:
+    x = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+    if x.shape != v.shape:
+        raise ValueError(f"orbits: pos {x.shape} and vel {v.shape} differ")
+    for name, val in (("steps", steps), ("every", every)):
+        if not 0 <= int(val) <= 0xFFFFFFFF:
+            raise ValueError(f"orbits: {name} = {val} is not a 32-bit count")
+    p = _lib.nb_orbit_params()
+    p.dt, p.step0, p.steps, p.every = float(dt), int(step0), int(steps), int(every)
+    p.flags, p.reserved = (_lib.NB_ORBIT_ENERGY if energy else 0), 0
+    p.accel_scale, p.omega = float(accel_scale), float(omega)
+    for k in range(3):
+        p.axis[k], p.center[k] = float(axis[k]), float(center[k])
+    m = x.shape[0]
+    records = int(_lib.lib().nb_orbit_records(p.steps, p.every))
+    # (the call refuses what it does not take, before it writes)
+    big = m > _lib.NB_ORBIT_MAX_TRACERS or records * m > _lib.NB_ORBIT_MAX_SAMPLES
+    tracks = np.zeros((0 if big else records, m), dtype=_lib.ORBIT_SAMPLE_DTYPE)
+    coincident = np.zeros(m, dtype=np.uint32)
+    st = _lib.nb_orbit_stats()
+    check(call(handle, C.byref(p), x.ctypes.data, v.ctypes.data, m, tracks.ctypes.data, coincident.ctypes.data,
+               C.byref(st)))
+    ks = np.array([k for k in range(p.steps + 1) if k % p.every == 0 or k == p.steps], dtype=np.uint64)
+    step = ks + np.uint64(p.step0)
+    stats = OrbitStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.tracers), int(st.nonfinite_tracers),
+                       int(st.records), int(st.pair_launches), int(st.flags))
+    return Orbits(tracks["pos"].copy(), tracks["vel"].copy(), tracks["potential"].copy(), tracks["energy"].copy(),
+                  step, step.astype(np.float64) * p.dt, coincident, stats, float(p.dt), float(p.omega),
+                  np.array(list(p.axis)), np.array(list(p.center)))
 
 
 def map_frame(axis):
@@ -2319,6 +2409,43 @@ class _Passes:
         suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
         return _disc_frequencies(self._pass("field"), getattr(_lib.lib(), "nb_tidal_" + suffix), self._h, radii, axis,
                                  center, n_phi)
+
+    def _accel_scale(self, coupling) -> float:
+        if isinstance(coupling, str):
+            if coupling == "field":
+                return 1.0
+            if coupling == "step":
+                return float(self.sim_params().dt)
+            raise ValueError('coupling is "field", "step" or a number')
+        return float(coupling)
+
+    def orbits(self, pos, vel, *, dt: float, steps: int, every: int = 1, energy: bool = False, omega: float = 0.0,
+               axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), coupling="field", step0: int = 0) -> Orbits:
+        """Test particles from `pos`, `vel` ((M, 3), float64) through `steps` leapfrog steps of `dt` in the frozen
+        field of the current state (nb_orbits_sim): the tracers stay on the device and every step is enqueued up
+        front.  omega: the pattern speed (DiscModes.pattern_speed) at which the frozen bodies turn rigidly about `axis`
+        through `center`; 0 holds them at rest.  A state is recorded every `every` steps and at the end;
+        energy=True also records the potential and the Jacobi integral.  coupling sets the acceleration's scale:
+        "field" is field()'s own (the convention of circular_velocity() and disc_frequencies()), "step" multiplies it
+        by the simulator's dt, the g dt with which its own bodies move (the diagnostics' coupling); a number is used
+        as given.  step0 numbers the first state, so that Orbits.final() continues a run exactly.  A several-GPU
+        runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _orbits(getattr(_lib.lib(), "nb_orbits_" + suffix), self._h, pos, vel, dt, steps, every, energy, omega,
+                       axis, center, self._accel_scale(coupling), step0)
+
+    def circular_orbits(self, radii, *, dt: float, steps: int, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0),
+                        n_phi: int = 16, speed: float = 1.0, **kw) -> Orbits:
+        """orbits() of one tracer per radius, started at the first point of its field_rings() ring with `speed` times
+        the circular velocity of circular_velocity() (field()'s coupling) along the direction of rotation there:
+        speed = 1 is the circular orbit of the azimuthally averaged force.  The other arguments are orbits()'s."""
+        r = np.ascontiguousarray(np.atleast_1d(radii), dtype=np.float64)
+        cv = self.circular_velocity(r, axis=axis, center=center, n_phi=n_phi)
+        pts = field_rings(r, axis=axis, center=center, n_phi=n_phi)
+        _, _, e2 = map_frame(axis)
+        pos = pts[:: max(int(n_phi), 1)].astype(np.float64)
+        vel = (float(speed) * cv.v_c)[:, None] * e2[None, :]
+        return self.orbits(pos, vel, dt=dt, steps=steps, axis=axis, center=center, **kw)
 
     def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                       depth=None, velocities: bool = True) -> ProjectedMap:

@@ -108,6 +108,22 @@ class nb_tidal_ring(C.Structure):
                 ("omega2", C.c_double), ("kappa2", C.c_double), ("nu2", C.c_double)]
 
 
+class nb_orbit_params(C.Structure):
+    _fields_ = [("dt", C.c_double), ("step0", C.c_uint64), ("steps", C.c_uint32), ("every", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32), ("accel_scale", C.c_double), ("omega", C.c_double),
+                ("axis", C.c_double * 3), ("center", C.c_double * 3)]
+
+
+class nb_orbit_sample(C.Structure):
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("potential", C.c_double), ("energy", C.c_double)]
+
+
+class nb_orbit_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("tracers", C.c_uint64),
+                ("nonfinite_tracers", C.c_uint64), ("records", C.c_uint32), ("pair_launches", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class nb_map_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -330,6 +346,9 @@ TIDAL_SAMPLE_DTYPE = np.dtype([("tensor", "<f8", (6,)), ("coincident", "<u4"), (
 TIDAL_RING_DTYPE = np.dtype([("t_RR", "<f8"), ("t_pp", "<f8"), ("t_nn", "<f8"), ("t_Rn", "<f8"), ("omega2", "<f8"),
                              ("kappa2", "<f8"), ("nu2", "<f8")])
 
+# nb_orbit_sample[] as a numpy record array
+ORBIT_SAMPLE_DTYPE = np.dtype([("pos", "<f8", (3,)), ("vel", "<f8", (3,)), ("potential", "<f8"), ("energy", "<f8")])
+
 # nb_halo_head[] as a numpy record array
 HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
                             ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
@@ -370,6 +389,8 @@ assert C.sizeof(nb_field_sample) == 40 == FIELD_SAMPLE_DTYPE.itemsize and C.size
 assert C.sizeof(nb_field_ring) == 32 == FIELD_RING_DTYPE.itemsize
 assert C.sizeof(nb_tidal_sample) == 56 == TIDAL_SAMPLE_DTYPE.itemsize
 assert C.sizeof(nb_tidal_ring) == 56 == TIDAL_RING_DTYPE.itemsize
+assert C.sizeof(nb_orbit_params) == 96 and C.sizeof(nb_orbit_stats) == 56
+assert C.sizeof(nb_orbit_sample) == 64 == ORBIT_SAMPLE_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
@@ -402,6 +423,8 @@ NB_RADIAL_CYLINDRICAL, NB_RADIAL_CENTER_COM = 1, 2
 NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
 NB_TIDAL_K = 33
+NB_ORBIT_ENERGY = 1
+NB_ORBIT_MAX_TRACERS, NB_ORBIT_MAX_STEPS, NB_ORBIT_MAX_SAMPLES, NB_ORBIT_MAX_PAIRS_LOG2 = 1 << 20, 1 << 20, 1 << 22, 44
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_PHASE_CENTER_COM, NB_PHASE_WEIGHT, NB_PHASE_ANY_STEP = 1, 2, 0xFFFFFFFFFFFFFFFF
@@ -440,6 +463,7 @@ ABI_SYMBOLS = [
     "nb_sim_radial_profile", "nb_radial_edges_log", "nb_radial_edges_linear", "nb_radial_lagrangian",
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_tidal_sim", "nb_tidal_runner", "nb_tidal_ring_means",
+    "nb_orbits_sim", "nb_orbits_runner", "nb_orbit_records", "nb_orbit_phase",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
@@ -551,6 +575,13 @@ def lib() -> C.CDLL:
     for suffix in ("sim", "runner"):
         getattr(L, "nb_local_kinematics_" + suffix).argtypes = local_kinematics
     L.nb_local_kinematics_derive.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+    # ... and the eighteenth (include/nbody.h "Orbits")
+    orbits = [vp, P(nb_orbit_params), vp, vp, sz, vp, vp, P(nb_orbit_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_orbits_" + suffix).argtypes = orbits
+    L.nb_orbit_records.argtypes = [C.c_uint32, C.c_uint32]
+    L.nb_orbit_records.restype = C.c_uint32
+    L.nb_orbit_phase.argtypes = [C.c_double, C.c_double, u64, P(C.c_double), P(C.c_double)]
     L.nb_phase_quantity.argtypes = [C.c_char_p, P(C.c_uint32)]
     L.nb_phase_quantity_name.argtypes = [C.c_uint32]
     L.nb_phase_quantity_name.restype = C.c_char_p

@@ -10,6 +10,8 @@
 //             [--rotcurve-axis X,Y,Z] [--rotcurve-center X,Y,Z]]
 //            [--freq K --freq-range RMIN,RMAX [--freq-bins B] [--freq-phi Q] [--freq-axis X,Y,Z]
 //             [--freq-center X,Y,Z]]
+//            [--orbits DIR [--orbits-at K] --orbits-range RMIN,RMAX [--orbits-bins B] --orbits-dt DT --orbits-steps S
+//             [--orbits-every E] [--orbits-omega W] [--orbits-speed F] [--orbits-axis X,Y,Z] [--orbits-center X,Y,Z]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
@@ -58,6 +60,14 @@
 // the same rings, nb_field_ring_means, nb_tidal_ring_means) of step 0 and of every K-th step; --freq-range,
 // --freq-bins, --freq-phi, --freq-axis and --freq-center as --rotcurve's.  One line per ring
 // "freq <step> <R> <Omega> <kappa> <nu> <v_c>" (%.9e; nan where the square of a frequency is negative).
+// --orbits DIR integrates test particles in the frozen field (nb_orbits_runner) of the state after step K
+// (--orbits-at, default 0: the initial state): one tracer per ring of B radii (--orbits-bins, default 32) linear from
+// RMIN to RMAX about --orbits-axis (default 0,1,0) through --orbits-center (default 0,0,0), started on the ring's first
+// point with F (--orbits-speed, default 1) times the circular velocity of --rotcurve's construction, through S steps of
+// DT, the pattern turning at W (--orbits-omega, default 0), a record every E steps (--orbits-every, default 1) with
+// the potential and the Jacobi integral.  Written as DIR/orbits_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape
+// (R, B, 8) -- position, velocity, potential, energy -- and one line "orbits <step> <records> <tracers>
+// <nonfinite_tracers> <pair_launches>".  The time it takes is not part of any "Step Duration".
 //
 // --maps DIR writes the projected map (nb_runner_map) of step 0 and of every K-th step (--map-every,
 // default 1) as DIR/map_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape (7, H, W) -- the counts as
@@ -295,6 +305,53 @@ static bool write_npy_planes(const std::string &path, uint32_t width, uint32_t h
         std::fprintf(stderr, "cannot write %s\n", path.c_str());
         return false;
     }
+    return true;
+}
+
+struct OrbitsOptions {
+    std::string dir;
+    int at = 0;
+    uint32_t bins = 32, steps = 0, every = 1;
+    bool have_range = false;
+    double rmin = 0.0, rmax = 0.0, dt = 0.0, omega = 0.0, speed = 1.0;
+    std::array<double, 3> axis{0.0, 1.0, 0.0}, center{0.0, 0.0, 0.0};
+};
+
+template <class Sim>
+static bool write_orbits(nbody::OfflineHeadless<Sim> &runner, const OrbitsOptions &oo) {
+    std::vector<double> radii(oo.bins);
+    for (uint32_t i = 0; i < oo.bins; ++i)
+        radii[i] = oo.bins > 1 ? oo.rmin + (oo.rmax - oo.rmin) * (double)i / (double)(oo.bins - 1) : oo.rmin;
+    const nb_orbit_params p = nbody::orbit_params(oo.dt, oo.steps, oo.every, true, oo.omega, oo.axis, oo.center);
+    const nbody::Orbits o = runner.circular_orbits(p, radii, 16, oo.speed);
+    char name[64];
+    std::snprintf(name, sizeof name, "/orbits_%06llu.npy", (unsigned long long)o.stats.step_num);
+    const std::string path = oo.dir + name;
+    std::FILE *out = std::fopen(path.c_str(), "wb");
+    if (!out) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    // the header of write_npy_planes; an nb_orbit_sample is eight doubles
+    char dict[128];
+    const int len = std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (%u, %zu, 8), }",
+                                  o.records, o.tracers);
+    const size_t total = (10 + (size_t)len + 1 + 63) / 64 * 64, hlen = total - 10;
+    std::string head("\x93NUMPY\x01\x00", 8);
+    head += (char)(hlen & 0xff);
+    head += (char)(hlen >> 8);
+    head += dict;
+    head.append(total - 1 - head.size(), ' ');
+    head += '\n';
+    static_assert(sizeof(nbody::OrbitSample) == 8 * sizeof(double), "a sample is eight doubles");
+    const bool ok = std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
+                    std::fwrite(o.tracks.data(), sizeof(nbody::OrbitSample), o.tracks.size(), out) == o.tracks.size();
+    if (std::fclose(out) != 0 || !ok) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("orbits %llu %u %zu %llu %u\n", (unsigned long long)o.stats.step_num, o.records, o.tracers,
+                (unsigned long long)o.stats.nonfinite_tracers, o.stats.pair_launches);
     return true;
 }
 
@@ -707,7 +764,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
-               const KinOptions &kin) {
+               const KinOptions &kin, const OrbitsOptions &orbits) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -716,6 +773,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (radial.every > 0) print_radial(runner, radial);
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (freq.every > 0) print_freq(runner, freq);
+    if (!orbits.dir.empty() && orbits.at == 0 && !write_orbits(runner, orbits)) return 1;
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
@@ -740,6 +798,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (radial.every > 0 && (i + 1) % radial.every == 0) print_radial(runner, radial);
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (freq.every > 0 && (i + 1) % freq.every == 0) print_freq(runner, freq);
+        if (!orbits.dir.empty() && i + 1 == orbits.at && !write_orbits(runner, orbits)) return 1;
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
@@ -781,6 +840,7 @@ int main(int argc, char **argv) {
     FofOptions fof;
     KnnOptions knn;
     KinOptions kin;
+    OrbitsOptions orbits;
     BoundOptions bound;
     HaloOptions halo;
     HopOptions hop;
@@ -1078,6 +1138,28 @@ int main(int argc, char **argv) {
         } else if (k == "--hop-top") hop.top = std::atoi(v.c_str());
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--orbits") orbits.dir = v;
+        else if (k == "--orbits-at") orbits.at = std::atoi(v.c_str());
+        else if (k == "--orbits-bins") orbits.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--orbits-steps") orbits.steps = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--orbits-every") orbits.every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--orbits-dt") orbits.dt = std::atof(v.c_str());
+        else if (k == "--orbits-omega") orbits.omega = std::atof(v.c_str());
+        else if (k == "--orbits-speed") orbits.speed = std::atof(v.c_str());
+        else if (k == "--orbits-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &orbits.rmin, &orbits.rmax) != 2) {
+                std::fprintf(stderr, "--orbits-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            orbits.have_range = true;
+        }
+        else if (k == "--orbits-axis" || k == "--orbits-center") {
+            double *a = k == "--orbits-axis" ? orbits.axis.data() : orbits.center.data();
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", a, a + 1, a + 2) != 3) {
+                std::fprintf(stderr, "%s takes X,Y,Z, not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--kin") kin.every = std::atoi(v.c_str());
         else if (k == "--kin-k") kin.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--kin-gradient") kin.gradient = std::atoi(v.c_str()) != 0;
@@ -1109,6 +1191,10 @@ int main(int argc, char **argv) {
     }
     if (freq.every > 0 && !freq.have_range) {
         std::fprintf(stderr, "--freq needs --freq-range RMIN,RMAX\n");
+        return 2;
+    }
+    if (!orbits.dir.empty() && (!orbits.have_range || orbits.steps == 0 || orbits.dt == 0.0 || orbits.at < 0)) {
+        std::fprintf(stderr, "--orbits needs --orbits-range RMIN,RMAX, --orbits-dt DT and --orbits-steps S\n");
         return 2;
     }
     if (rotcurve.every > 0 && !rotcurve.have_range) {
@@ -1178,9 +1264,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

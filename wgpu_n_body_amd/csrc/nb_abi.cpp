@@ -139,6 +139,17 @@ static int pass_tidal(H *h, const float *points, size_t m, nb_tidal_sample *out,
 }
 
 template <class H>
+static int pass_orbits(H *h, const nb_orbit_params *params, const double *pos, const double *vel, size_t m,
+                       nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
+    OrbitPlan plan{};
+    if (int rc = orbits_check_args(params, pos, vel, m, tracks, &plan)) return rc;
+    return on_sim(h, "orbits", [&](SimBase &s) {
+        if (int rc = orbits_check_e(s, params)) return rc;
+        return sim_orbits(s, *params, plan, pos, vel, m, tracks, coincident, stats);
+    });
+}
+
+template <class H>
 static int pass_map(H *h, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
@@ -505,6 +516,19 @@ int nb_tidal_ring_means(const double center[3], const double axis[3], const doub
                         uint32_t n_phi, const float *points, const nb_tidal_sample *samples,
                         const nb_field_ring *rings, nb_tidal_ring *out) {
     return tidal_ring_means(center, axis, radii, k, n_phi, points, samples, rings, out);
+}
+
+int nb_orbits_sim(nb_sim *sim, const nb_orbit_params *params, const double *pos, const double *vel, size_t m,
+                  nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
+    return pass_orbits(sim, params, pos, vel, m, tracks, coincident, stats);
+}
+int nb_orbits_runner(nb_runner *runner, const nb_orbit_params *params, const double *pos, const double *vel,
+                     size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
+    return pass_orbits(runner, params, pos, vel, m, tracks, coincident, stats);
+}
+uint32_t nb_orbit_records(uint32_t steps, uint32_t every) { return orbit_records(steps, every); }
+int nb_orbit_phase(double omega, double dt, uint64_t k, double *c, double *s) {
+    return orbit_phase(omega, dt, k, c, s);
 }
 
 int nb_sim_map(nb_sim *sim, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {

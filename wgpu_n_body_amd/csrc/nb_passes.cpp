@@ -139,6 +139,96 @@ int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out) 
     return probe_check_args("tidal", points, m, out);
 }
 
+// nb_orbits_sim: the recorded states, the phase of a state, and everything that can be refused without a device
+// (the softening is the simulator's: orbits_check_e)
+uint32_t orbit_records(uint32_t steps, uint32_t every) {
+    if (every == 0) return 0;
+    return steps / every + 1u + (steps % every ? 1u : 0u);
+}
+
+int orbit_phase(double omega, double dt, uint64_t k, double *c, double *s) {
+    if (!c || !s) {
+        set_error("orbit_phase: null %s", !c ? "c" : "s");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(omega) || !std::isfinite(dt)) {
+        set_error("orbit_phase: omega and dt must be finite (got %g, %g)", omega, dt);
+        return NB_ERR_INVALID;
+    }
+    if (omega == 0.0) {
+        *c = 1.0;
+        *s = 0.0;
+        return NB_OK;
+    }
+    const double t = (double)k * dt, theta = omega * t;
+    *c = std::cos(theta);
+    *s = std::sin(theta);
+    return NB_OK;
+}
+
+int orbits_check_args(const nb_orbit_params *p, const double *pos, const double *vel, size_t m,
+                      const nb_orbit_sample *tracks, OrbitPlan *plan) {
+    if (!p) {
+        set_error("orbits: null params");
+        return NB_ERR_INVALID;
+    }
+    if (m > 0 && (!pos || !vel || !tracks)) {
+        set_error("orbits: null %s", !pos ? "pos" : !vel ? "vel" : "tracks");
+        return NB_ERR_INVALID;
+    }
+    if (p->steps < 1 || p->steps > NB_ORBIT_MAX_STEPS) {
+        set_error("orbits: steps must be 1..%u (got %u)", NB_ORBIT_MAX_STEPS, p->steps);
+        return NB_ERR_INVALID;
+    }
+    if (p->every < 1) {
+        set_error("orbits: every must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if ((p->flags & ~NB_ORBIT_ENERGY) || p->reserved) {
+        set_error("orbits: unknown flag bits 0x%x or reserved %u != 0", p->flags & ~NB_ORBIT_ENERGY, p->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (m > NB_ORBIT_MAX_TRACERS) {
+        set_error("orbits: at most %u tracers (got %zu)", NB_ORBIT_MAX_TRACERS, m);
+        return NB_ERR_INVALID;
+    }
+    plan->records = orbit_records(p->steps, p->every);
+    if ((uint64_t)plan->records * m > NB_ORBIT_MAX_SAMPLES) {
+        set_error("orbits: %u records of %zu tracers are more than %u samples", plan->records, m, NB_ORBIT_MAX_SAMPLES);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->dt) || p->dt == 0.0) {
+        set_error("orbits: dt must be finite and not zero (got %g)", p->dt);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->accel_scale)) {
+        set_error("orbits: accel_scale must be finite (got %g)", p->accel_scale);
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->omega)) {
+        set_error("orbits: omega must be finite (got %g)", p->omega);
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(p->center[a])) {
+            set_error("orbits: center must be finite");
+            return NB_ERR_INVALID;
+        }
+    for (int a = 0; a < 3; ++a) plan->n[a] = plan->e1[a] = plan->e2[a] = 0.0;
+    if (p->omega != 0.0 && !axis_frame(p->axis, plan->n, plan->e1, plan->e2)) {
+        set_error("orbits: a pattern speed needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+int orbits_check_e(const SimBase &s, const nb_orbit_params *p) {
+    if ((p->flags & NB_ORBIT_ENERGY) && !(s.params.e >= 0.f)) {
+        set_error("orbits: the potential needs e >= 0 (e = %g)", (double)s.params.e);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_field_rings / nb_field_ring_means / nb_tidal_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
 static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
                       uint32_t n_phi, double n[3], double e1[3], double e2[3]) {

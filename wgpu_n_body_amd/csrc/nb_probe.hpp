@@ -177,11 +177,38 @@ dim3 finish_grid(const Band<Sample> &b) {  // one thread per point of the band
     return dim3((b.p1 - b.p0 + kThreads - 1) / kThreads);
 }
 
+// The plan of m points, ib per lane, against n bodies: a function of (m, n, ib) alone but for the band, which
+// "field_launch_pairs_log2" (pairs_log2) sizes.  The chunking is sized for a band of the default budget whatever the
+// key says, so the key only partitions the points and cannot change a sum.
+struct Plan {
+    uint32_t tile_pts, p_tiles, m_pad;  // points per tile, point tiles, points padded to whole tiles
+    uint32_t n_tiles, cj, chunks;       // body tiles, body tiles per chunk, chunks (0, 0 with no pairs)
+    uint32_t band, stride;              // point tiles per launch, points of a band: the slab holds one band
+};
+inline Plan plan(uint32_t m, uint32_t n, int ib, int pairs_log2) {
+    Plan p{};
+    p.tile_pts = kWave * ib;
+    p.p_tiles = (m + p.tile_pts - 1) / p.tile_pts;
+    p.m_pad = p.p_tiles * p.tile_pts;
+    p.n_tiles = (n + kTile - 1) / kTile;
+    p.band = p.p_tiles;
+    if (m > 0 && n > 0) {
+        const uint64_t tile_pairs = (uint64_t)p.tile_pts * n;
+        const uint32_t wide = (uint32_t)std::min<uint64_t>(p.p_tiles, std::max<uint64_t>(1, kPairsPerLaunch / tile_pairs));
+        const uint32_t want = std::min(p.n_tiles, std::max(1u, (kBlocks + wide - 1) / wide));
+        p.cj = (p.n_tiles + want - 1) / want;        // body tiles per chunk
+        p.chunks = (p.n_tiles + p.cj - 1) / p.cj;    // every chunk holds at least one tile
+        // bands of point tiles: a tile meets tile_pts * n pairs; at least one tile per launch
+        p.band = (uint32_t)std::min<uint64_t>(p.p_tiles, std::max<uint64_t>(1, (1ull << pairs_log2) / tile_pairs));
+    }
+    p.stride = p.band * p.tile_pts;
+    return p;
+}
+
 // A call: m points, ib per lane, into out[m] and *stats (stats->flags = flags), with the workspace of `slot` and
 // a slab of slab_fields fields.  pairs(band) launches the unit's probe_kernel instantiation for a band -- only
 // with n > 0 -- and finish(band) its finish kernel.
-// The plan is a function of (m, n, ib) alone: the chunking is sized for a band of the default budget whatever
-// "field_launch_pairs_log2" says, so the key only partitions the points and cannot change a sum.
+// The plan is plan()'s.
 template <class Sample, class Pairs, class Finish>
 int run(SimBase &sim, WorkSlot slot, const float *points, size_t m, int ib, uint32_t slab_fields, uint32_t flags,
         Sample *out, nb_field_stats *stats, Pairs pairs, Finish finish) {
@@ -194,27 +221,14 @@ int run(SimBase &sim, WorkSlot slot, const float *points, size_t m, int ib, uint
     Work<Sample> &w = *work;
     const uint32_t n = sim.n, mm = (uint32_t)m;
 
-    const uint32_t tile_pts = kWave * ib;
-    const uint32_t p_tiles = (mm + tile_pts - 1) / tile_pts, m_pad = p_tiles * tile_pts;
-    const uint32_t n_tiles = (n + kTile - 1) / kTile;
-    uint32_t cj = 0, chunks = 0;
-    if (mm > 0 && n > 0) {
-        const uint64_t tile_pairs = (uint64_t)tile_pts * n;
-        const uint32_t wide = (uint32_t)std::min<uint64_t>(p_tiles, std::max<uint64_t>(1, kPairsPerLaunch / tile_pairs));
-        const uint32_t want = std::min(n_tiles, std::max(1u, (kBlocks + wide - 1) / wide));
-        cj = (n_tiles + want - 1) / want;        // body tiles per chunk
-        chunks = (n_tiles + cj - 1) / cj;        // every chunk holds at least one tile
-    }
+    const Plan pl = plan(mm, n, ib, sim.field_pairs_log2);
+    const uint32_t tile_pts = pl.tile_pts, p_tiles = pl.p_tiles, m_pad = pl.m_pad, n_tiles = pl.n_tiles;
+    const uint32_t cj = pl.cj, chunks = pl.chunks, band = pl.band, stride = pl.stride;
 
     NB_HIP_TRY(w.pts.reserve(m_pad));
     NB_HIP_TRY(w.out.reserve(m_pad));
     NB_HIP_TRY(w.h_pts.reserve(m_pad));
     NB_HIP_TRY(w.h_out.reserve(m_pad));
-    // bands of point tiles: a tile meets tile_pts * n pairs; at least one tile per launch.  The slab holds one band.
-    uint32_t band = p_tiles;
-    if (mm > 0 && n > 0)
-        band = (uint32_t)std::min<uint64_t>(p_tiles, std::max<uint64_t>(1, (1ull << sim.field_pairs_log2) / ((uint64_t)tile_pts * n)));
-    const uint32_t stride = band * tile_pts;
     NB_HIP_TRY(w.slab.reserve((size_t)chunks * slab_fields * stride));
 
     uint64_t bad_points = 0;

@@ -15,7 +15,7 @@ struct Workspace {
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
                       kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal,
-                      kWorkKin, kWorkSlots };
+                      kWorkKin, kWorkOrbits, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -168,6 +168,20 @@ int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_fi
 // nb_tidal.hip: nb_tidal_sim behind the handle
 int tidal_check_args(const float *points, size_t m, const nb_tidal_sample *out);
 int sim_tidal(SimBase &sim, const float *points, size_t m, nb_tidal_sample *out, nb_tidal_stats *stats);
+
+// nb_field.hip: nb_orbits_sim behind the handle (the orbit unit shares the field's pair kernels); orbits_check_args
+// also forms the frame; orbit_records / orbit_phase: nb_orbit_records / nb_orbit_phase behind the ABI boundary
+struct OrbitPlan {
+    double n[3], e1[3], e2[3];  // axis_frame of the caller's axis (omega != 0)
+    uint32_t records;
+};
+int orbits_check_args(const nb_orbit_params *p, const double *pos, const double *vel, size_t m,
+                      const nb_orbit_sample *tracks, OrbitPlan *plan);
+int orbits_check_e(const SimBase &sim, const nb_orbit_params *p);
+int sim_orbits(SimBase &sim, const nb_orbit_params &params, const OrbitPlan &plan, const double *pos, const double *vel,
+               size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats);
+uint32_t orbit_records(uint32_t steps, uint32_t every);
+int orbit_phase(double omega, double dt, uint64_t k, double *c, double *s);
 
 // nb_map.hip: nb_sim_map behind the handle; map_check_params also forms the frame and the cell sizes
 struct MapPlan {

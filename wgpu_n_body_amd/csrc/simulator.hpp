@@ -38,6 +38,7 @@ using RadialBin = nb_radial_bin;          // 88 B
 using FieldSample = nb_field_sample;      // 40 B: acceleration, potential and coincident count at a point
 using FieldRing = nb_field_ring;          // a ring's means: a_R, a_n, potential, v_c
 using TidalSample = nb_tidal_sample;      // 56 B: the tidal tensor (xx, yy, zz, xy, xz, yz) and coincident count at a point
+using OrbitSample = nb_orbit_sample;      // 64 B: position, velocity, potential and energy of a tracer at a recorded state
 using TidalRing = nb_tidal_ring;          // a ring's means of the tensor, and omega2, kappa2, nu2
 using MapParams = nb_map_params;          // grid, window, line of sight and centre of a projected map
 using MapStats = nb_map_stats;
@@ -322,6 +323,62 @@ DiscFrequencies disc_frequencies(int (*field_call)(H *, const float *, size_t, u
     check(nb_tidal_ring_means(center.data(), axis.data(), radii.data(), (uint32_t)radii.size(), n_phi, pts.data(),
                               r.tidal.samples.data(), r.means.rings.data(), r.rings.data()));
     return r;
+}
+}  // namespace detail
+
+// Test particles in the frozen field of the current state (no reference counterpart): records * tracers samples,
+// record-major, the coincident count per tracer, and what the call measured
+struct Orbits {
+    uint32_t records = 0;
+    size_t tracers = 0;
+    std::vector<OrbitSample> tracks;
+    std::vector<uint32_t> coincident;
+    nb_orbit_stats stats{};
+    nb_orbit_params params{};
+    const OrbitSample &at(uint32_t record, size_t tracer) const { return tracks[(size_t)record * tracers + tracer]; }
+    // the step number of a record: step0 + k
+    uint64_t step(uint32_t record) const {
+        const uint64_t k = std::min<uint64_t>((uint64_t)record * params.every, params.steps);
+        return params.step0 + k;
+    }
+};
+
+// dt, steps and the rest of an orbits() call; accel_scale 1 is field()'s own coupling
+inline nb_orbit_params orbit_params(double dt, uint32_t steps, uint32_t every = 1, bool energy = false,
+                                    double omega = 0.0, const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
+                                    const std::array<double, 3> &center = {0.0, 0.0, 0.0}, double accel_scale = 1.0,
+                                    uint64_t step0 = 0) {
+    nb_orbit_params p{};
+    p.dt = dt;
+    p.step0 = step0;
+    p.steps = steps;
+    p.every = every;
+    p.flags = energy ? NB_ORBIT_ENERGY : 0u;
+    p.accel_scale = accel_scale;
+    p.omega = omega;
+    for (int a = 0; a < 3; ++a) {
+        p.axis[a] = axis[(size_t)a];
+        p.center[a] = center[(size_t)a];
+    }
+    return p;
+}
+
+namespace detail {
+template <class H>
+Orbits orbits(int (*call)(H *, const nb_orbit_params *, const double *, const double *, size_t, nb_orbit_sample *,
+                          uint32_t *, nb_orbit_stats *),
+              H *h, const nb_orbit_params &p, const std::vector<double> &pos, const std::vector<double> &vel) {
+    if (pos.size() != vel.size() || pos.size() % 3) throw Error(NB_ERR_INVALID, "orbits: pos and vel are 3 doubles per tracer");
+    Orbits o;
+    o.params = p;
+    o.tracers = pos.size() / 3;
+    o.records = nb_orbit_records(p.steps, p.every);
+    // (the call refuses what it does not take, before it writes)
+    const bool big = o.tracers > NB_ORBIT_MAX_TRACERS || (uint64_t)o.records * o.tracers > NB_ORBIT_MAX_SAMPLES;
+    o.tracks.resize(big ? 0 : (size_t)o.records * o.tracers);
+    o.coincident.resize(o.tracers);
+    check(call(h, &p, pos.data(), vel.data(), o.tracers, o.tracks.data(), o.coincident.data(), &o.stats));
+    return o;
 }
 }  // namespace detail
 
@@ -1020,6 +1077,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto disc_modes = nb_disc_modes_sim;
     static constexpr auto phase_map = nb_phase_map_sim;
     static constexpr auto tidal = nb_tidal_sim;
+    static constexpr auto orbits = nb_orbits_sim;
     static constexpr auto local_kinematics = nb_local_kinematics_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
@@ -1041,6 +1099,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto disc_modes = nb_disc_modes_runner;
     static constexpr auto phase_map = nb_phase_map_runner;
     static constexpr auto tidal = nb_tidal_runner;
+    static constexpr auto orbits = nb_orbits_runner;
     static constexpr auto local_kinematics = nb_local_kinematics_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
@@ -1161,6 +1220,28 @@ class Passes {
                                      const std::array<double, 3> &axis = {0.0, 1.0, 0.0},
                                      const std::array<double, 3> &center = {0.0, 0.0, 0.0}, uint32_t n_phi = 16) {
         return detail::disc_frequencies(Abi::field, Abi::tidal, h_, radii, axis, center, n_phi);
+    }
+    // test particles from pos, vel (3 doubles per tracer) through the frozen field of the current state, the
+    // pattern turning at p.omega (orbit_params)
+    Orbits orbits(const nb_orbit_params &p, const std::vector<double> &pos, const std::vector<double> &vel) {
+        return detail::orbits(Abi::orbits, h_, p, pos, vel);
+    }
+    // ... one tracer per radius from the first point of its ring, with speed times the circular velocity along the
+    // direction of rotation there (p.axis and p.center are the rings')
+    Orbits circular_orbits(const nb_orbit_params &p, const std::vector<double> &radii, uint32_t n_phi = 16,
+                           double speed = 1.0) {
+        const std::array<double, 3> axis{p.axis[0], p.axis[1], p.axis[2]}, center{p.center[0], p.center[1], p.center[2]};
+        const RingMeans cv = circular_velocity(radii, axis, center, n_phi);
+        const std::vector<float> pts = field_rings(radii, axis, center, n_phi);
+        double n[3], e1[3], e2[3];
+        check(nb_map_frame(axis.data(), n, e1, e2));
+        std::vector<double> pos(3 * radii.size()), vel(3 * radii.size());
+        for (size_t i = 0; i < radii.size(); ++i)
+            for (size_t a = 0; a < 3; ++a) {
+                pos[3 * i + a] = (double)pts[3 * (i * n_phi) + a];
+                vel[3 * i + a] = (speed * cv.rings[i].v_c) * e2[a];
+            }
+        return orbits(p, pos, vel);
     }
     // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
     Frame render(const RenderParams &p, bool counts = false) {
