@@ -1038,6 +1038,74 @@ int nb_sim_fof(nb_sim *sim, const nb_fof_params *params, uint32_t *labels, uint3
                nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Phase-space groups -- friends-of-friends in position and velocity (no      */
+/* reference counterpart: what overlaps in space but moves apart, separated)  */
+/* ------------------------------------------------------------------------- */
+/* Partitions the state nb_sim_read_particles would return into the connected
+ * components of a "friends" graph in six dimensions (the 6DFOF of Diemand et al.
+ * 2006, the first stage of ROCKSTAR, Behroozi et al. 2013) and sums a catalogue of
+ * the larger ones.  The rule, which DESIGN.md 6u states in full: binary64 from the
+ * binary32 state, one rounding per operation, no contraction:
+ *   counted   exactly as in nb_sim_fof: position, mass and velocity all finite;
+ *             every other body is `nonfinite`, has label NB_FOF_NONE and belongs to
+ *             no group
+ *   constants formed once on the host: b2 = link * link, v2 = vlink * vlink,
+ *             rhs = b2 * v2
+ *   friends   bodies i != j are friends iff both clauses hold:
+ *             1. d2 <= b2, d2 being nb_sim_fof's own expression:
+ *                dx = (double)x_i - (double)x_j, dy and dz likewise,
+ *                d2 = (dx dx + dy dy) + dz dz
+ *             2. (d2 * v2 + u2 * b2) <= rhs, with du = (double)vx_i - (double)vx_j,
+ *                dv and dw likewise, u2 = (du du + dv dv) + dw dw
+ *             This is (dx / b)^2 + (dv / b_v)^2 <= 1 without a division, symmetric
+ *             in i and j.  Every term is non-negative: a sum may become +inf but
+ *             never NaN, so both clauses may be evaluated for every pair
+ *   groups, labels, catalogue, group_of
+ *             word for word those of nb_sim_fof: a group is a connected component,
+ *             its label the smallest body index (in the order nb_sim_read_particles
+ *             returns at that moment), the rows with count >= min_members in
+ *             ascending label order, each an nb_fof_group with nb_sim_fof's nine
+ *             sums in its summation order
+ * Three consequences:
+ *   refinement        clause 1 is nb_sim_fof's predicate, so every phase-space group
+ *                     lies inside exactly one group of nb_sim_fof(link)
+ *   equal velocities  with all counted velocities equal u2 = 0 and clause 2 follows
+ *                     from clause 1 (d2 <= b2 gives d2 * v2 <= b2 * v2: rounding is
+ *                     monotone, and adding 0 is exact); labels, group_of, the rows
+ *                     and the integer stats are then those of nb_sim_fof(link,
+ *                     min_members), byte for byte
+ *   frame, uniqueness the predicate sees only differences, so the partition does not
+ *                     depend on the frame (as long as the shifted binary32 state
+ *                     keeps its differences); it is unique, so labels, group_of,
+ *                     counts and every integer of the stats are exact and
+ *                     bit-identical between calls
+ * The sums, the cells (the position grid of nb_sim_fof at the same link: cells and
+ * cell_side of the stats are its), the refusal of a state that needs more than
+ * NB_FOF_MAX_CELLS_PER_AXIS cells on an axis (NB_ERR_INVALID, after the call's one
+ * synchronisation, outputs untouched) and the behaviour on the stream are
+ * nb_sim_fof's.  No float atomics.
+ * "fof_chunk_len" applies as it does there.  "fof6_boxes" (0 or 1, default 1; speed
+ * and testing only): use per-cell position and velocity boxes to skip or link whole
+ * cell pairs, a cell with itself included, without pair tests.  Neither changes a bit
+ * of the result.  A cell of P bodies whose boxes decide nothing costs P (P - 1) / 2
+ * pair tests. */
+typedef struct nb_fof6_params {
+    double link;          /* b: finite, > 0 */
+    double vlink;         /* b_v: finite, > 0 */
+    uint32_t min_members; /* >= 1: the smallest component the catalogue holds */
+    uint32_t flags;       /* 0 */
+    uint64_t reserved;    /* 0 */
+} nb_fof6_params;
+
+/* The phase-space groups of a simulator's current state; the outputs are nb_sim_fof's and every output
+ * pointer may be null with its meaning there.  NB_ERR_INVALID for a null handle or params, a link or vlink
+ * that is not finite or not > 0, a b2, v2 or rhs that is not a positive finite double, min_members == 0,
+ * unknown flags or reserved != 0 -- all checked before any device call -- and for a state that needs too
+ * many cells; NB_ERR_UNSUPPORTED for a sharded simulator (placement world > 1). */
+int nb_fof6_sim(nb_sim *sim, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of,
+                nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
+
+/* ------------------------------------------------------------------------- */
 /* Bound groups -- which friends-of-friends groups hold together (no reference */
 /* counterpart: every catalogued group unbound on the device)                 */
 /* ------------------------------------------------------------------------- */
@@ -2290,6 +2358,10 @@ int nb_orbits_runner(nb_runner *runner, const nb_orbit_params *params, const dou
  * several-GPU runner. */
 int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,
                                double *r2, uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats);
+/* nb_fof6_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_fof6_runner(nb_runner *runner, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of,
+                   nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

@@ -40,7 +40,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
            "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "ProjectedMap", "map_frame", "map_edges",
            "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
-           "FofGroups", "FofStats", "FOF_NONE",
+           "FofGroups", "FofStats", "FOF_NONE", "PhaseSpaceGroups",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
            "LocalKinematics", "KinStats", "kinematics_derive", "KIN_SHORT", "KIN_NOT_COUNTED", "KIN_DEGENERATE",
@@ -1068,6 +1068,42 @@ def _fof_groups(call, handle, n, link, min_members, labels) -> FofGroups:
                      int(st.grouped_bodies), int(st.largest_count), int(st.largest_label),
                      tuple(int(c) for c in st.cells), float(st.cell_side))
     return FofGroups(lab, gof, rows[:stats.groups], float(link), mm, stats)
+
+
+@dataclass(frozen=True)
+class PhaseSpaceGroups(FofGroups):
+    """nb_fof6_sim's partition and catalogue (include/nbody.h "Phase-space groups"; no reference counterpart):
+    bodies are friends when (dx / link)^2 + (dv / vlink)^2 <= 1 and dx <= link, a group is a connected component.
+    The fields and properties are FofGroups'; every group lies inside one group of fof_groups(link)."""
+    vlink: float = float("nan")
+
+    def parent_rows(self, parent: FofGroups) -> np.ndarray:
+        """Per row, the catalogue row of `parent` -- a fof_groups(link) of the same step -- that holds it, or FOF_NONE
+        when that group is not in the parent's catalogue: the parent's group_of at the row's label."""
+        if parent.stats.step_num != self.stats.step_num:
+            raise ValueError(f"parent_rows: the parent was made at step {parent.stats.step_num}, these groups at "
+                             f"step {self.stats.step_num}")
+        if parent.link != self.link:
+            raise ValueError(f"parent_rows: the parent's link {parent.link} is not these groups' {self.link}")
+        return parent.group_of[self.rows["label"].astype(np.int64)]
+
+
+def _phase_space_groups(call, handle, n, link, vlink, min_members, labels) -> PhaseSpaceGroups:
+    p = _lib.nb_fof6_params()
+    p.link, p.vlink, p.flags, p.reserved = float(link), float(vlink), 0, 0
+    mm = int(min_members)
+    p.min_members = mm if 0 <= mm <= 0xFFFFFFFF else 0  # (the call refuses 0 itself)
+    cap = n // mm if mm >= 1 else 0  # the most there can be
+    lab = np.empty(n, dtype=np.uint32) if labels else None
+    gof = np.empty(n, dtype=np.uint32)
+    rows = np.zeros(cap, dtype=_lib.FOF_GROUP_DTYPE)
+    st = _lib.nb_fof_stats()
+    check(call(handle, C.byref(p), lab.ctypes.data if labels else None, gof.ctypes.data, rows.ctypes.data, cap,
+               C.byref(st)))
+    stats = FofStats(int(st.step_num), int(st.n), int(st.nonfinite), int(st.components), int(st.groups),
+                     int(st.grouped_bodies), int(st.largest_count), int(st.largest_label),
+                     tuple(int(c) for c in st.cells), float(st.cell_side))
+    return PhaseSpaceGroups(lab, gof, rows[:stats.groups], float(link), mm, stats, float(vlink))
 
 
 HOP_NONE = _lib.NB_HOP_NONE
@@ -2503,6 +2539,18 @@ class _Passes:
         bodies at every step.  labels=False leaves the per-body labels on the device.  A several-GPU runner refuses."""
         return _fof_groups(self._pass("fof"), self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
+
+    def phase_space_groups(self, link: float, vlink: float, *, min_members: int = 20,
+                           labels: bool = True) -> PhaseSpaceGroups:
+        """The phase-space groups of the current state (nb_fof6_sim): friends-of-friends in position and velocity.
+        Bodies within `link` of each other with (dx / link)^2 + (dv / vlink)^2 <= 1 are friends, a group is a
+        connected component; the catalogue holds the groups of at least min_members bodies.  Two streams that cross,
+        or a cold clump inside a hot halo, are one group to fof_groups(link) and separate ones here.  The body indices
+        are those of read_particles() now.  labels=False leaves the per-body labels on the device.
+        A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _phase_space_groups(getattr(_lib.lib(), "nb_fof6_" + suffix), self._h,
+                                   int(self.sim_params().particle_num), link, vlink, min_members, labels)
 
     def bound_groups(self, link: float, *, min_members: int = 20, min_bound: Optional[int] = None,
                      max_iter: int = 32, max_group: int = 262144, per_body: bool = True) -> BoundGroups:

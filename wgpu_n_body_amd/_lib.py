@@ -161,6 +161,11 @@ class nb_fof_params(C.Structure):
     _fields_ = [("link", C.c_double), ("min_members", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
 
+class nb_fof6_params(C.Structure):
+    _fields_ = [("link", C.c_double), ("vlink", C.c_double), ("min_members", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
 class nb_fof_group(C.Structure):
     _fields_ = [("label", C.c_uint32), ("count", C.c_uint32), ("mass", C.c_double), ("mx", C.c_double * 3),
                 ("mv", C.c_double * 3), ("mr2", C.c_double), ("mv2", C.c_double)]
@@ -394,7 +399,7 @@ assert C.sizeof(nb_orbit_sample) == 64 == ORBIT_SAMPLE_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
-assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize
+assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize and C.sizeof(nb_fof6_params) == 32
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
 assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
@@ -467,6 +472,7 @@ ABI_SYMBOLS = [
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
+    "nb_fof6_sim", "nb_fof6_runner",
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
     "nb_local_kinematics_sim", "nb_local_kinematics_runner", "nb_local_kinematics_derive",
@@ -579,6 +585,10 @@ def lib() -> C.CDLL:
     orbits = [vp, P(nb_orbit_params), vp, vp, sz, vp, vp, P(nb_orbit_stats)]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_orbits_" + suffix).argtypes = orbits
+    # ... and the nineteenth (include/nbody.h "Phase-space groups")
+    fof6 = [vp, P(nb_fof6_params), vp, vp, vp, sz, P(nb_fof_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_fof6_" + suffix).argtypes = fof6
     L.nb_orbit_records.argtypes = [C.c_uint32, C.c_uint32]
     L.nb_orbit_records.restype = C.c_uint32
     L.nb_orbit_phase.argtypes = [C.c_double, C.c_double, u64, P(C.c_double), P(C.c_double)]

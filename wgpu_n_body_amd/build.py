@@ -34,6 +34,8 @@ SOURCES = [
     ("nb_map.hip", ["-ffp-contract=off"]),
     # the friends rule is specified operation by operation: no FMA contraction
     ("nb_fof.hip", ["-ffp-contract=off"]),
+    # the six-dimensional friends rule likewise
+    ("nb_fof6.hip", ["-ffp-contract=off"]),
     # the energy rule is specified operation by operation: no FMA contraction
     ("nb_bound.hip", ["-ffp-contract=off"]),
     # the neighbour order and the density are specified operation by operation: no FMA contraction

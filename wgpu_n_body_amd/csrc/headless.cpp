@@ -17,6 +17,7 @@
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
 //             [--smap-center com|X,Y,Z] [--smap-depth LO,HI] [--smap-k 32] [--smap-max PIXELS]]
 //            [--fof K --fof-link B [--fof-min M] [--fof-top T]]
+//            [--fof6 K --fof6-link B --fof6-vlink V [--fof6-min M] [--fof6-top T]]
 //            [--bound K --bound-link B [--bound-min M] [--bound-iter I] [--bound-max-group G] [--bound-top T]]
 //            [--shapes K --shapes-link B [--shapes-min M] [--shapes-radius KRMS] [--shapes-reduced 0|1]
 //             [--shapes-iter I] [--shapes-top T]]
@@ -462,6 +463,29 @@ static void print_fof(nbody::OfflineHeadless<Sim> &runner, const FofOptions &fo)
     }
 }
 
+struct Fof6Options {
+    int every = 0, top = 0;
+    double link = 0.0, vlink = 0.0;
+    uint32_t min_members = 20;
+};
+
+// --fof6 K: the phase-space groups (nb_fof6_runner) of step 0 and of every K-th step -- friends are within --fof6-link
+// B in position and --fof6-vlink V in velocity, (dx / B)^2 + (dv / V)^2 <= 1 -- printed as --fof prints its groups,
+// the lines starting "fof6" and "fof6_group"
+template <class Sim>
+static void print_fof6(nbody::OfflineHeadless<Sim> &runner, const Fof6Options &fo) {
+    const nbody::PhaseSpaceGroups g = runner.phase_space_groups(fo.link, fo.vlink, fo.min_members, false);
+    const unsigned long long step = (unsigned long long)g.stats.step_num;
+    std::printf("fof6 %llu %llu %llu %u\n", step, (unsigned long long)g.stats.groups,
+                (unsigned long long)g.stats.grouped_bodies, g.stats.largest_count);
+    const std::vector<uint32_t> order = g.by_size();
+    for (size_t k = 0; k < order.size() && k < (size_t)fo.top; ++k) {
+        const nbody::FofGroup &r = g.groups[order[k]];
+        std::printf("fof6_group %llu %u %u %u %.9e %.9e %.9e %.9e\n", step, order[k], r.label, r.count, r.mass,
+                    r.mx[0] / r.mass, r.mx[1] / r.mass, r.mx[2] / r.mass);
+    }
+}
+
 struct BoundOptions {
     int every = 0, top = 0;
     double link = 0.0;
@@ -764,7 +788,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
-               const KinOptions &kin, const OrbitsOptions &orbits) {
+               const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -777,6 +801,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
+    if (fof6.every > 0) print_fof6(runner, fof6);
     if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
     if (kin.every > 0) print_kin(runner, kin);
@@ -802,6 +827,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
+        if (fof6.every > 0 && (i + 1) % fof6.every == 0) print_fof6(runner, fof6);
         if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
         if (kin.every > 0 && (i + 1) % kin.every == 0) print_kin(runner, kin);
@@ -841,6 +867,7 @@ int main(int argc, char **argv) {
     KnnOptions knn;
     KinOptions kin;
     OrbitsOptions orbits;
+    Fof6Options fof6;
     BoundOptions bound;
     HaloOptions halo;
     HopOptions hop;
@@ -985,6 +1012,11 @@ int main(int argc, char **argv) {
         else if (k == "--fof-link") fof.link = std::atof(v.c_str());
         else if (k == "--fof-min") fof.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--fof-top") fof.top = std::atoi(v.c_str());
+        else if (k == "--fof6") fof6.every = std::atoi(v.c_str());
+        else if (k == "--fof6-link") fof6.link = std::atof(v.c_str());
+        else if (k == "--fof6-vlink") fof6.vlink = std::atof(v.c_str());
+        else if (k == "--fof6-min") fof6.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--fof6-top") fof6.top = std::atoi(v.c_str());
         else if (k == "--bound") bound.every = std::atoi(v.c_str());
         else if (k == "--bound-link") bound.link = std::atof(v.c_str());
         else if (k == "--bound-min") bound.min_members = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
@@ -1226,6 +1258,10 @@ int main(int argc, char **argv) {
         return 2;
     }
     hop.regroup = hop_saddle;
+    if (fof6.every > 0 && (!(fof6.link > 0.0) || !(fof6.vlink > 0.0))) {
+        std::fprintf(stderr, "--fof6 needs --fof6-link B > 0 and --fof6-vlink V > 0\n");
+        return 2;
+    }
     if (fof.every > 0 && !(fof.link > 0.0)) {
         std::fprintf(stderr, "--fof needs --fof-link B > 0\n");
         return 2;
@@ -1264,9 +1300,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

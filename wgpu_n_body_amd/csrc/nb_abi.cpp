@@ -166,6 +166,15 @@ static int pass_fof(H *h, const nb_fof_params *params, uint32_t *labels, uint32_
 }
 
 template <class H>
+static int pass_fof6(H *h, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+                     size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = fof6_check_params(params)) return rc;
+    return on_sim(h, "fof6", [&](SimBase &s) {
+        return sim_fof6(s, *params, labels, group_of, groups, group_capacity, stats);
+    });
+}
+
+template <class H>
 static int pass_bound(H *h, const nb_bound_params *params, uint32_t *group_of, uint32_t *bound_of, double *energy,
                       nb_bound_group *groups, size_t group_capacity, nb_bound_stats *stats) {
     if (int rc = bound_check_params(params)) return rc;
@@ -291,6 +300,7 @@ static const TuningKey kTuningKeys[] = {
     {"fof_chunk_len", &SimBase::fof_chunk_len, "a multiple of 64 in 64..65536",
      [](int v) { return multiple_in(v, 64, 65536); }},
     {"fof_cell_boxes", &SimBase::fof_cell_boxes, "0 or 1", [](int v) { return v == 0 || v == 1; }},
+    {"fof6_boxes", &SimBase::fof6_boxes, "0 or 1", [](int v) { return v == 0 || v == 1; }},
     {"bound_chunk_len", &SimBase::bound_chunk_len, "a multiple of 64 in 64..1048576",
      [](int v) { return multiple_in(v, 64, 1048576); }},
     {"shape_chunk_len", &SimBase::shape_chunk_len, "a multiple of 64 in 64..65536",
@@ -581,6 +591,14 @@ int nb_runner_knn(nb_runner *runner, const nb_knn_params *params, double *r2, ui
     return pass_knn(runner, params, r2, kth, mass_in, density, stats);
 }
 
+int nb_fof6_sim(nb_sim *sim, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+                size_t group_capacity, nb_fof_stats *stats) {
+    return pass_fof6(sim, params, labels, group_of, groups, group_capacity, stats);
+}
+int nb_fof6_runner(nb_runner *runner, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of,
+                   nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats) {
+    return pass_fof6(runner, params, labels, group_of, groups, group_capacity, stats);
+}
 int nb_local_kinematics_sim(nb_sim *sim, const nb_kin_params *params, double *moments, double *grads, double *r2,
                             uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats) {
     return pass_local_kinematics(sim, params, moments, grads, r2, kth, mass_in, density, stats);

@@ -54,7 +54,7 @@ constexpr uint32_t kThreads = kBlock;
 constexpr uint32_t kMaxPasses = 8;       // a 64-bit key
 constexpr uint32_t kTerms = 9;           // the sums of a catalogue row
 constexpr uint32_t kRowLanes = 16;       // lanes per row of the combine kernel
-constexpr uint32_t kNeighbours = 62;     // forward neighbours within +-2 cells per axis: (5^3 - 1) / 2
+constexpr uint32_t kNeighbours = kFofNeighbours;
 constexpr double kMaxCells = (double)NB_FOF_MAX_CELLS_PER_AXIS;
 
 __host__ __device__ inline uint32_t bits_of(unsigned long long x) {
@@ -64,15 +64,6 @@ __host__ __device__ inline uint32_t bits_of(unsigned long long x) {
         x >>= 1;
     }
     return b;
-}
-
-// the order-preserving encoding of a finite float as an unsigned integer
-__device__ inline uint32_t ordered(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float unordered(uint32_t e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
 }
 
 // One block: the bounds into the plan.  A refusal leaves no sort pass to run (passes[1] stays 0: the rows' plan
@@ -229,58 +220,10 @@ __global__ __launch_bounds__(kThreads) void fof_parent_kernel(FofInfo *__restric
     spos[p] = q;
     if (!use_boxes) return;
     uint32_t e[6] = {~ordered(q.x), ~ordered(q.y), ~ordered(q.z), ordered(q.x), ordered(q.y), ordered(q.z)};
-    // a wave whose active lanes share one cell sends one lane's six atomics
-    const unsigned long long active = __ballot(true);
-    const int first = __ffsll((long long)active) - 1;
-    const uint32_t c0 = __shfl(c, first);
-    if (__ballot(c != c0) == 0ull && active == ~0ull) {
-        for (int o = 32; o > 0; o >>= 1)
-            for (int a = 0; a < 6; ++a) e[a] = std::max(e[a], (uint32_t)__shfl_xor(e[a], o));
-        if (threadIdx.x % kWave == 0)
-            for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
-    } else {
-        for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
-    }
+    box_raise(boxes, c, e);
 }
 
 // ---- union ----------------------------------------------------------------------------------------
-__device__ inline uint32_t load_parent(const uint32_t *parent, uint32_t i) {
-    return __atomic_load_n(parent + i, __ATOMIC_RELAXED);
-}
-// parent[x] < x unless x is a root: the walk ends
-__device__ inline uint32_t find_root(const uint32_t *parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = load_parent(parent, x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-// ... and on the way points every second node at its grandparent (path halving).  Only a node that is not a
-// root is written, with a smaller ancestor of its own tree, and a node never becomes a root again: the
-// exchange in unite, which expects a root, is not disturbed, and parent[x] < x holds on.
-__device__ inline uint32_t find_root_halving(uint32_t *parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = load_parent(parent, x);
-        if (p == x) return x;
-        const uint32_t g = load_parent(parent, p);
-        if (g != p) __atomic_store_n(parent + x, g, __ATOMIC_RELAXED);
-        x = g;
-    }
-}
-// Hook the larger root under the smaller.  A failed exchange means another thread hooked that root first:
-// find both roots again.  Nothing waits on another thread.
-__device__ inline void unite(uint32_t *parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = find_root_halving(parent, a);
-        b = find_root_halving(parent, b);
-        if (a == b) return;
-        const uint32_t hi = std::max(a, b), lo = std::min(a, b);
-        if (atomicCAS(parent + hi, hi, lo) == hi) return;
-        a = hi;
-        b = lo;
-    }
-}
-
 // the rule of include/nbody.h
 __device__ inline bool friends(float4 p, float4 q, double b2) {
 #pragma clang fp contract(off)
@@ -307,35 +250,15 @@ __global__ __launch_bounds__(kWave) void fof_union_kernel(const FofInfo *__restr
     // lane l: the l-th forward neighbour, its place in the cell table and its class by the boxes
     uint32_t nb = 0, cls = 0;  // 0 none or apart, 1 test the pairs, 2 all friends
     if (lane < kNeighbours) {
-        const unsigned long long nx = info->nx, ny = info->ny, nz = info->nz, key = cell_key[c];
-        const long long cx = (long long)(key % nx), cy = (long long)((key / nx) % ny), cz = (long long)(key / (nx * ny));
-        const uint32_t t = lane + kNeighbours + 1;  // offsets after (0, 0, 0) in (z, y, x) order
-        const long long ox = (long long)(t % 5) - 2, oy = (long long)((t / 5) % 5) - 2, oz = (long long)(t / 25) - 2;
-        const long long x = cx + ox, y = cy + oy, z = cz + oz;
-        if (x >= 0 && x < (long long)nx && y >= 0 && y < (long long)ny && z >= 0 && z < (long long)nz) {
-            const unsigned long long want = ((unsigned long long)z * ny + (unsigned long long)y) * nx + (unsigned long long)x;
-            uint32_t lo = c + 1, hi = ncells;  // (a forward neighbour has a larger key)
-            while (lo < hi) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (cell_key[mid] < want) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < ncells && cell_key[lo] == want) {
-                nb = lo;
-                cls = 1;
-                if (use_boxes) {
-                    // per axis the gap between the boxes and their farthest extent; the pair rule's own
-                    // operations on them bound every pair's d2 from below and from above (rounding is monotone)
-                    double gap[3], far[3];
-                    for (int a = 0; a < 3; ++a) {
-                        const double alo = unordered(~boxes[(size_t)6 * c + a]), ahi = unordered(boxes[(size_t)6 * c + 3 + a]);
-                        const double blo = unordered(~boxes[(size_t)6 * nb + a]), bhi = unordered(boxes[(size_t)6 * nb + 3 + a]);
-                        gap[a] = fmax(0.0, fmax(blo - ahi, alo - bhi));
-                        far[a] = fmax(bhi - alo, ahi - blo);
-                    }
-                    if ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2] > b2) cls = 0;
-                    else if ((far[0] * far[0] + far[1] * far[1]) + far[2] * far[2] <= b2) cls = 2;
-                }
+        if (forward_neighbour(info, cell_key, ncells, c, lane, &nb)) {
+            cls = 1;
+            if (use_boxes) {
+                // per axis the gap between the boxes and their farthest extent; the pair rule's own
+                // operations on them bound every pair's d2 from below and from above (rounding is monotone)
+                double gap[3], far[3];
+                box_gap_far(boxes, c, nb, gap, far);
+                if ((gap[0] * gap[0] + gap[1] * gap[1]) + gap[2] * gap[2] > b2) cls = 0;
+                else if ((far[0] * far[0] + far[1] * far[1]) + far[2] * far[2] <= b2) cls = 2;
             }
         }
     }
@@ -582,12 +505,13 @@ int fof_work(SimBase &sim, FofWork **out) {
     });
 }
 
-int fof_refused(const nb_fof_params &params) {
-    set_error("fof: link %g needs more than %u cells on an axis over this state's extent: it is below the "
+int fof_refused(const char *pass, double link) {
+    set_error("%s: link %g needs more than %u cells on an axis over this state's extent: it is below the "
               "resolution of binary32 coordinates there",
-              params.link, NB_FOF_MAX_CELLS_PER_AXIS);
+              pass, link, NB_FOF_MAX_CELLS_PER_AXIS);
     return NB_ERR_INVALID;
 }
+int fof_refused(const nb_fof_params &params) { return fof_refused("fof", params.link); }
 
 int fof_catalogue_reserve(FofWork &w, uint32_t n, uint32_t rows_cap) {
     const SortShape shape = sort_shape(n);
@@ -661,75 +585,83 @@ int fof_catalogue_enqueue(SimBase &sim, FofWork &w, const uint32_t *parent, uint
     return NB_OK;
 }
 
-int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t rows_cap, bool want_group_of,
-                bool sums) {
-    const uint32_t n = sim.n;
-    const double b2 = params.link * params.link;  // (positive and finite: fof_check_params)
-    const double h = fof_cell_side(params.link);
-    const uint32_t len = (uint32_t)sim.fof_chunk_len, use_boxes = (uint32_t)sim.fof_cell_boxes;
-    const unsigned long long union_items = (unsigned long long)n / len + n + 1;
-    if (union_items > 0x7fffffffull) {
-        set_error("fof: %u bodies are more than one call takes", n);
-        return NB_ERR_UNSUPPORTED;
+uint32_t fof_union_items(const SimBase &sim, const char *pass) {
+    const unsigned long long items = (unsigned long long)sim.n / (uint32_t)sim.fof_chunk_len + sim.n + 1;
+    if (items > 0x7fffffffull) {
+        set_error("%s: %u bodies are more than one call takes", pass, sim.n);
+        return 0;
     }
-    {
-        const uint32_t blocks = (n + kThreads - 1) / kThreads;
-        const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
-        const SortShape shape = sort_shape(n);
-        if (int rc = fof_catalogue_reserve(w, n, rows_cap)) return rc;
-        if (int rc = fof_reserve(w.slabs, (size_t)kBoundFields * blocks)) return rc;
-        if (int rc = fof_reserve(w.cell_key, n)) return rc;
-        if (int rc = fof_reserve(w.cell_start, (size_t)n + 1)) return rc;
-        if (int rc = fof_reserve(w.boxes, (size_t)6 * n)) return rc;
-        if (int rc = fof_reserve(w.spos, n)) return rc;
-        if (int rc = fof_reserve(w.parent, n)) return rc;
+    return (uint32_t)items;
+}
 
-        const float4 *posm = nullptr, *vel = nullptr;
-        sim.diag_state(&posm, &vel);
-        FofInfo *info = w.info;
-        const auto &keys = w.sort.keys;  // both sides go to the kernels: the plan says where the sorted arrays are
-        const auto &idx = w.sort.idx;
-        uint32_t *scan_total = w.block_tot + scan_blocks;
-        hipLaunchKernelGGL(bounds_kernel<>, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_plan_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, blocks, h, info);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, keys[0]);
-        NB_HIP_TRY(hipGetLastError());
-        if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, kMaxPasses, 0, &info->passes[0])) return rc;
-        // the cell table
-        hipLaunchKernelGGL(fof_heads_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
-                           w.flags);
-        NB_HIP_TRY(hipGetLastError());
-        if (int rc = enqueue_scan(sim, w, scan_blocks, scan_total)) return rc;
-        hipLaunchKernelGGL(fof_cells_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
-                           w.excl, w.block_tot, w.flags, w.cell_key, w.cell_start);
-        NB_HIP_TRY(hipGetLastError());
-        if (use_boxes) NB_HIP_TRY(hipMemsetAsync(w.boxes, 0, sizeof(uint32_t) * 6 * n, sim.stream));
-        hipLaunchKernelGGL(fof_parent_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, posm, idx[0], idx[1],
-                           n, w.flags, w.cell_start, scan_total, w.spos, w.parent, w.boxes, use_boxes);
-        NB_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(fof_union_kernel, dim3((uint32_t)union_items), dim3(kWave), 0, sim.stream, info, w.cell_key,
-                           w.cell_start, w.boxes, idx[0], idx[1], w.spos, w.parent, len, b2, use_boxes);
-        NB_HIP_TRY(hipGetLastError());
-        if (int rc = fof_catalogue_enqueue(sim, w, w.parent, params.min_members, rows_cap, want_group_of, sums))
-            return rc;
-    }
+int fof_cells_enqueue(SimBase &sim, FofWork &w, double link, uint32_t rows_cap, uint32_t use_boxes) {
+    const uint32_t n = sim.n;
+    const double h = fof_cell_side(link);
+    const uint32_t blocks = (n + kThreads - 1) / kThreads;
+    const uint32_t scan_blocks = (n + kScanThreads - 1) / kScanThreads;
+    const SortShape shape = sort_shape(n);
+    if (int rc = fof_catalogue_reserve(w, n, rows_cap)) return rc;
+    if (int rc = fof_reserve(w.slabs, (size_t)kBoundFields * blocks)) return rc;
+    if (int rc = fof_reserve(w.cell_key, n)) return rc;
+    if (int rc = fof_reserve(w.cell_start, (size_t)n + 1)) return rc;
+    if (int rc = fof_reserve(w.boxes, (size_t)6 * n)) return rc;
+    if (int rc = fof_reserve(w.spos, n)) return rc;
+    if (int rc = fof_reserve(w.parent, n)) return rc;
+
+    const float4 *posm = nullptr, *vel = nullptr;
+    sim.diag_state(&posm, &vel);
+    FofInfo *info = w.info;
+    const auto &keys = w.sort.keys;  // both sides go to the kernels: the plan says where the sorted arrays are
+    const auto &idx = w.sort.idx;
+    uint32_t *scan_total = w.block_tot + scan_blocks;
+    hipLaunchKernelGGL(bounds_kernel<>, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, w.slabs);
+    NB_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fof_plan_kernel, dim3(1), dim3(kThreads), 0, sim.stream, w.slabs, blocks, h, info);
+    NB_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fof_key_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, posm, vel, n, info, keys[0]);
+    NB_HIP_TRY(hipGetLastError());
+    if (int rc = enqueue_sort(sim.stream, w.sort, n, shape, kMaxPasses, 0, &info->passes[0])) return rc;
+    // the cell table
+    hipLaunchKernelGGL(fof_heads_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
+                       w.flags);
+    NB_HIP_TRY(hipGetLastError());
+    if (int rc = enqueue_scan(sim, w, scan_blocks, scan_total)) return rc;
+    hipLaunchKernelGGL(fof_cells_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, keys[0], keys[1], n,
+                       w.excl, w.block_tot, w.flags, w.cell_key, w.cell_start);
+    NB_HIP_TRY(hipGetLastError());
+    if (use_boxes) NB_HIP_TRY(hipMemsetAsync(w.boxes, 0, sizeof(uint32_t) * 6 * n, sim.stream));
+    hipLaunchKernelGGL(fof_parent_kernel, dim3(blocks), dim3(kThreads), 0, sim.stream, info, posm, idx[0], idx[1],
+                       n, w.flags, w.cell_start, scan_total, w.spos, w.parent, w.boxes, use_boxes);
+    NB_HIP_TRY(hipGetLastError());
     return NB_OK;
 }
 
-int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
-            size_t group_capacity, nb_fof_stats *stats) {
-    if (int rc = analysis_begin(sim, "fof")) return rc;
+int fof_enqueue(SimBase &sim, FofWork &w, const nb_fof_params &params, uint32_t rows_cap, bool want_group_of,
+                bool sums) {
+    const double b2 = params.link * params.link;  // (positive and finite: fof_check_params)
+    const uint32_t len = (uint32_t)sim.fof_chunk_len, use_boxes = (uint32_t)sim.fof_cell_boxes;
+    const uint32_t union_items = fof_union_items(sim, "fof");
+    if (!union_items) return NB_ERR_UNSUPPORTED;
+    if (int rc = fof_cells_enqueue(sim, w, params.link, rows_cap, use_boxes)) return rc;
+    const auto &idx = w.sort.idx;
+    hipLaunchKernelGGL(fof_union_kernel, dim3(union_items), dim3(kWave), 0, sim.stream, w.info, w.cell_key,
+                       w.cell_start, w.boxes, idx[0], idx[1], w.spos, w.parent, len, b2, use_boxes);
+    NB_HIP_TRY(hipGetLastError());
+    return fof_catalogue_enqueue(sim, w, w.parent, params.min_members, rows_cap, want_group_of, sums);
+}
+
+int fof_call(SimBase &sim, const char *pass, double link, uint32_t min_members, const FofEnqueue &enqueue,
+             uint32_t *labels, uint32_t *group_of, nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats) {
+    if (int rc = analysis_begin(sim, pass)) return rc;
     if (!groups) group_capacity = 0;
     if (!labels && !group_of && !groups && !stats) {  // nothing to measure
         NB_HIP_TRY(hipStreamSynchronize(sim.stream));
         return sim.diag_status();
     }
     const uint32_t n = sim.n;
-    const double h = fof_cell_side(params.link);
+    const double h = fof_cell_side(link);
     // the most rows there can be, and those the caller has room for
-    const uint32_t rows_cap = fof_rows_cap(n, group_capacity, params.min_members);
+    const uint32_t rows_cap = fof_rows_cap(n, group_capacity, min_members);
     FofWork *work = nullptr;
     if (int rc = fof_work(sim, &work)) return rc;
     FofWork &w = *work;
@@ -744,7 +676,7 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
             if (int rc = fof_reserve(w.h_group_of, n)) return rc;
         if (rows_cap > 0)
             if (int rc = fof_reserve(w.h_rows, rows_cap)) return rc;
-        if (int rc = fof_enqueue(sim, w, params, rows_cap, group_of != nullptr, true)) return rc;
+        if (int rc = enqueue(w, rows_cap, group_of != nullptr)) return rc;
         NB_HIP_TRY(hipMemcpyAsync(w.h_info, w.info, sizeof(FofInfo), hipMemcpyDeviceToHost, sim.stream));
         if (labels)
             NB_HIP_TRY(hipMemcpyAsync(w.h_labels, w.labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, sim.stream));
@@ -756,7 +688,7 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
     }
     NB_HIP_TRY(hipStreamSynchronize(sim.stream));
     if (int rc = sim.diag_status()) return rc;
-    if (res.status) return fof_refused(params);
+    if (res.status) return fof_refused(pass, link);
     if (n > 0) {
         if (labels) std::memcpy(labels, w.h_labels, sizeof(uint32_t) * n);
         if (group_of) std::memcpy(group_of, w.h_group_of, sizeof(uint32_t) * n);
@@ -779,6 +711,16 @@ int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_
         *stats = o;
     }
     return NB_OK;
+}
+
+int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+            size_t group_capacity, nb_fof_stats *stats) {
+    return fof_call(
+        sim, "fof", params.link, params.min_members,
+        [&](FofWork &w, uint32_t rows_cap, bool want_group_of) {
+            return fof_enqueue(sim, w, params, rows_cap, want_group_of, true);
+        },
+        labels, group_of, groups, group_capacity, stats);
 }
 
 }  // namespace nb

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <functional>
 
 #include "nb_analysis.hpp"
 #include "nb_analysis_sort.hpp"
@@ -70,8 +71,124 @@ int fof_catalogue_enqueue(SimBase &sim, FofWork &w, const uint32_t *parent, uint
                           bool want_group_of, bool sums);
 // the error of a refused plan (info->status), reported after the call's synchronisation
 int fof_refused(const nb_fof_params &params);
+int fof_refused(const char *pass, double link);
+// The stages of the pass before its union, which every finder on the cell grid shares (nb_fof6.hip calls them with
+// its own union behind): bounds, plan and key, the sort, the cell table (w.cell_key, w.cell_start, info->ncells),
+// w.flags[p] = the cell of sorted position p, the positions gathered in sorted order (w.spos), w.parent[i] = the first
+// body of i's cell (NB_FOF_NONE for a body that does not count) and, with use_boxes, the cells' position boxes
+// (w.boxes).  The sorted body indices are on side info->passes[0] & 1 of w.sort.idx.  It reserves what it writes and,
+// by fof_catalogue_reserve, what the catalogue needs.
+int fof_cells_enqueue(SimBase &sim, FofWork &w, double link, uint32_t rows_cap, uint32_t use_boxes);
+// work items of a union kernel over the chunks of the occupied cells (item_chunk below); 0 and an error when n bodies
+// are more than one call takes
+uint32_t fof_union_items(const SimBase &sim, const char *pass);
+// The host sequence of a finder on the cell grid, around the kernels `enqueue` puts on the stream (they end with
+// fof_catalogue_enqueue): the preamble, the workspace and the pinned staging, the copies, the one synchronisation,
+// the refusal of a plan, and the outputs and stats of nb_sim_fof, written only by a call that succeeds.
+using FofEnqueue = std::function<int(FofWork &w, uint32_t rows_cap, bool want_group_of)>;
+int fof_call(SimBase &sim, const char *pass, double link, uint32_t min_members, const FofEnqueue &enqueue,
+             uint32_t *labels, uint32_t *group_of, nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
 
 #ifdef __HIPCC__
+
+// the order-preserving encoding of a finite float as an unsigned integer
+__device__ inline uint32_t ordered(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float unordered(uint32_t e) {
+    return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
+}
+
+// boxes[6 c + a] of cell c raised to the six encodings e of a body (a < 3: ~ordered(x_a), the minimum complemented;
+// else ordered(x_a)) by integer atomic maxima.  A full wave whose lanes share one cell sends one lane's six atomics.
+__device__ inline void box_raise(uint32_t *__restrict__ boxes, uint32_t c, uint32_t (&e)[6]) {
+    const unsigned long long active = __ballot(true);
+    const int first = __ffsll((long long)active) - 1;
+    const uint32_t c0 = __shfl(c, first);
+    if (__ballot(c != c0) == 0ull && active == ~0ull) {
+        for (int o = 32; o > 0; o >>= 1)
+            for (int a = 0; a < 6; ++a) e[a] = std::max(e[a], (uint32_t)__shfl_xor(e[a], o));
+        if (threadIdx.x % kWave == 0)
+            for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
+    } else {
+        for (int a = 0; a < 6; ++a) atomicMax(&boxes[(size_t)6 * c + a], e[a]);
+    }
+}
+// per axis the gap between the boxes of cells c and nb and their farthest extent, in binary64 (exact differences of
+// binary32 numbers, rounded once)
+__device__ inline void box_gap_far(const uint32_t *__restrict__ boxes, uint32_t c, uint32_t nb, double (&gap)[3],
+                                   double (&far)[3]) {
+    for (int a = 0; a < 3; ++a) {
+        const double alo = unordered(~boxes[(size_t)6 * c + a]), ahi = unordered(boxes[(size_t)6 * c + 3 + a]);
+        const double blo = unordered(~boxes[(size_t)6 * nb + a]), bhi = unordered(boxes[(size_t)6 * nb + 3 + a]);
+        gap[a] = fmax(0.0, fmax(blo - ahi, alo - bhi));
+        far[a] = fmax(bhi - alo, ahi - blo);
+    }
+}
+
+// ---- the lock-free forest ------------------------------------------------------------------------------
+__device__ inline uint32_t load_parent(const uint32_t *parent, uint32_t i) {
+    return __atomic_load_n(parent + i, __ATOMIC_RELAXED);
+}
+// parent[x] < x unless x is a root: the walk ends
+__device__ inline uint32_t find_root(const uint32_t *parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = load_parent(parent, x);
+        if (p == x) return x;
+        x = p;
+    }
+}
+// ... and on the way points every second node at its grandparent (path halving).  Only a node that is not a
+// root is written, with a smaller ancestor of its own tree, and a node never becomes a root again: the
+// exchange in unite, which expects a root, is not disturbed, and parent[x] < x holds on.
+__device__ inline uint32_t find_root_halving(uint32_t *parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = load_parent(parent, x);
+        if (p == x) return x;
+        const uint32_t g = load_parent(parent, p);
+        if (g != p) __atomic_store_n(parent + x, g, __ATOMIC_RELAXED);
+        x = g;
+    }
+}
+// Hook the larger root under the smaller.  A failed exchange means another thread hooked that root first:
+// find both roots again.  Nothing waits on another thread.
+__device__ inline void unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = find_root_halving(parent, a);
+        b = find_root_halving(parent, b);
+        if (a == b) return;
+        const uint32_t hi = std::max(a, b), lo = std::min(a, b);
+        if (atomicCAS(parent + hi, hi, lo) == hi) return;
+        a = hi;
+        b = lo;
+    }
+}
+
+constexpr uint32_t kFofNeighbours = 62;  // forward neighbours within +-2 cells per axis: (5^3 - 1) / 2
+
+// The cell table's entry of the l-th forward neighbour (l < kFofNeighbours) of occupied cell c within +-2 cells per axis, in
+// (z, y, x) order after (0, 0, 0); false when it is outside the grid or holds no body.
+__device__ inline bool forward_neighbour(const FofInfo *__restrict__ info,
+                                         const unsigned long long *__restrict__ cell_key, uint32_t ncells, uint32_t c,
+                                         uint32_t l, uint32_t *nb) {
+    const unsigned long long nx = info->nx, ny = info->ny, nz = info->nz, key = cell_key[c];
+    const long long cx = (long long)(key % nx), cy = (long long)((key / nx) % ny), cz = (long long)(key / (nx * ny));
+    const uint32_t t = l + kFofNeighbours + 1;
+    const long long ox = (long long)(t % 5) - 2, oy = (long long)((t / 5) % 5) - 2, oz = (long long)(t / 25) - 2;
+    const long long x = cx + ox, y = cy + oy, z = cz + oz;
+    if (!(x >= 0 && x < (long long)nx && y >= 0 && y < (long long)ny && z >= 0 && z < (long long)nz)) return false;
+    const unsigned long long want = ((unsigned long long)z * ny + (unsigned long long)y) * nx + (unsigned long long)x;
+    uint32_t lo = c + 1, hi = ncells;  // (a forward neighbour has a larger key)
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (cell_key[mid] < want) lo = mid + 1;
+        else hi = mid;
+    }
+    if (!(lo < ncells && cell_key[lo] == want)) return false;
+    *nb = lo;
+    return true;
+}
 
 // The list of work item g among lists l = 0 .. count - 1 of positions [start[l], start[l + 1]), cut into chunks
 // of len: list l owns the items start[l] / len + l onwards, which are at least its chunks.  False for an item

@@ -289,6 +289,33 @@ int fof_check_params(const nb_fof_params *p) {
     return NB_OK;
 }
 
+// nb_fof6_sim: everything that can be refused without a device
+int fof6_check_params(const nb_fof6_params *p) {
+    if (!p) {
+        set_error("fof6: null params");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(p->link) || !(p->link > 0.0) || !std::isfinite(p->vlink) || !(p->vlink > 0.0)) {
+        set_error("fof6: link and vlink must be finite and > 0 (got %g, %g)", p->link, p->vlink);
+        return NB_ERR_INVALID;
+    }
+    const double b2 = p->link * p->link, v2 = p->vlink * p->vlink, rhs = b2 * v2;  // what the rule compares with
+    if (!(b2 > 0.0) || !std::isfinite(b2) || !(v2 > 0.0) || !std::isfinite(v2) || !(rhs > 0.0) || !std::isfinite(rhs)) {
+        set_error("fof6: link %g squared, vlink %g squared or their product is not a positive finite double", p->link,
+                  p->vlink);
+        return NB_ERR_INVALID;
+    }
+    if (p->min_members < 1) {
+        set_error("fof6: min_members must be at least 1");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved) {
+        set_error("fof6: unknown flag bits 0x%x or reserved %llu != 0", p->flags, (unsigned long long)p->reserved);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // nb_sim_bound: everything that can be refused without a device (the softening is the simulator's: bound_check_e)
 int bound_check_params(const nb_bound_params *p) {
     if (!p) {

@@ -15,7 +15,7 @@ struct Workspace {
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
                       kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal,
-                      kWorkKin, kWorkOrbits, kWorkSlots };
+                      kWorkKin, kWorkOrbits, kWorkFof6, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -130,6 +130,7 @@ class SimBase {
     int smooth_segment_len = 4096;  // "smooth_segment_len": entries of a tile summed by one block of nb_sim_smooth_map
     int fof_chunk_len = 1024;    // "fof_chunk_len": bodies of a cell or a catalogue row per work item of nb_sim_fof
     int fof_cell_boxes = 1;      // "fof_cell_boxes": per-cell bounding boxes decide neighbour cells where they can
+    int fof6_boxes = 1;          // "fof6_boxes": per-cell position and velocity boxes decide cell pairs of nb_fof6_sim
     int bound_chunk_len = 1024;  // "bound_chunk_len": j positions of a group per work item of nb_sim_bound's pair pass
     int bound_tile = 0;          // "bound_tile": members per i-tile of that pass, 64 or 256; 0 chooses by the group's size
     int shape_chunk_len = 1024;  // "shape_chunk_len": positions of a row's list per work item of nb_sim_group_shapes
@@ -208,6 +209,10 @@ const char *phase_quantity_name(uint32_t id);
 int fof_check_params(const nb_fof_params *p);
 int sim_fof(SimBase &sim, const nb_fof_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
             size_t group_capacity, nb_fof_stats *stats);
+// nb_fof6.hip: nb_fof6_sim behind the handle
+int fof6_check_params(const nb_fof6_params *p);
+int sim_fof6(SimBase &sim, const nb_fof6_params &params, uint32_t *labels, uint32_t *group_of, nb_fof_group *groups,
+             size_t group_capacity, nb_fof_stats *stats);
 // nb_halo.hip: nb_sim_halo_profiles behind the handle (the body indices need n: they are checked there)
 int halo_check_params(const nb_halo_params *p);
 int sim_halo_profiles(SimBase &sim, const nb_halo_params &params, nb_halo_head *heads, nb_radial_bin *bins,

@@ -536,6 +536,42 @@ FofGroups fof_groups(int (*call)(H *, const nb_fof_params *, uint32_t *, uint32_
 }
 }  // namespace detail
 
+// The phase-space groups of a state (nb_fof6_sim; no reference counterpart): friends-of-friends in position and
+// velocity, with FofGroups' fields.  Every group lies inside one group of fof_groups(link).
+struct PhaseSpaceGroups : FofGroups {
+    double link = 0.0, vlink = 0.0;
+    // per row the catalogue row of `parent` -- fof_groups(link) of the same step -- that holds it, or NB_FOF_NONE
+    std::vector<uint32_t> parent_rows(const FofGroups &parent) const {
+        if (parent.stats.step_num != stats.step_num)
+            throw Error(NB_ERR_INVALID, "parent_rows: the parent was made at another step");
+        std::vector<uint32_t> o(groups.size());
+        for (size_t r = 0; r < o.size(); ++r) o[r] = parent.group_of[groups[r].label];
+        return o;
+    }
+};
+
+namespace detail {
+template <class H>
+PhaseSpaceGroups phase_space_groups(int (*call)(H *, const nb_fof6_params *, uint32_t *, uint32_t *, nb_fof_group *,
+                                                size_t, nb_fof_stats *),
+                                    H *h, size_t n, double link, double vlink, uint32_t min_members, bool labels) {
+    PhaseSpaceGroups g;
+    g.link = link;
+    g.vlink = vlink;
+    nb_fof6_params p{};
+    p.link = link;
+    p.vlink = vlink;
+    p.min_members = min_members;
+    const size_t cap = min_members ? n / min_members : 0;  // the most there can be (the call refuses 0 itself)
+    if (labels) g.labels.resize(n);
+    g.group_of.resize(n);
+    g.groups.resize(cap);
+    check(call(h, &p, labels ? g.labels.data() : nullptr, g.group_of.data(), g.groups.data(), cap, &g.stats));
+    g.groups.resize((size_t)g.stats.groups);
+    return g;
+}
+}  // namespace detail
+
 // The bound groups of a state (nb_sim_bound; no reference counterpart): per body the catalogue row of its
 // friends-of-friends group, the row whose bound set it belongs to (NB_FOF_NONE: none) and its energy in the last
 // round it was active in; the catalogue in ascending label order.  bound_of and energy are empty when not asked for
@@ -1079,6 +1115,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto tidal = nb_tidal_sim;
     static constexpr auto orbits = nb_orbits_sim;
     static constexpr auto local_kinematics = nb_local_kinematics_sim;
+    static constexpr auto fof6 = nb_fof6_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
     static constexpr auto render = nb_sim_render;
 };
@@ -1101,6 +1138,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto tidal = nb_tidal_runner;
     static constexpr auto orbits = nb_orbits_runner;
     static constexpr auto local_kinematics = nb_local_kinematics_runner;
+    static constexpr auto fof6 = nb_fof6_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
     static constexpr auto render = nb_runner_render;
 };
@@ -1141,6 +1179,9 @@ class Passes {
     // the friends-of-friends groups of the current state: bodies within `link` are friends
     FofGroups fof_groups(double link, uint32_t min_members = 20, bool labels = true) {
         return detail::fof_groups(Abi::fof, h_, n_bodies(), link, min_members, labels);
+    }
+    PhaseSpaceGroups phase_space_groups(double link, double vlink, uint32_t min_members = 20, bool labels = true) {
+        return detail::phase_space_groups(Abi::fof6, h_, n_bodies(), link, vlink, min_members, labels);
     }
     // those groups unbound: min_bound 0 stands for min_members, max_group 0 for no limit
     BoundGroups bound_groups(double link, uint32_t min_members = 20, uint32_t min_bound = 0, uint32_t max_iter = 32,
