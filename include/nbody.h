@@ -742,6 +742,103 @@ uint32_t nb_orbit_records(uint32_t steps, uint32_t every);
 int nb_orbit_phase(double omega, double dt, uint64_t k, double *c, double *s);
 
 /* ------------------------------------------------------------------------- */
+/* Orbit sections -- the crossings of a plane and a running summary per tracer, */
+/* taken by the orbit's own step kernel (no reference counterpart)             */
+/* ------------------------------------------------------------------------- */
+/* nb_orbit_sections_sim is nb_orbits_sim -- the same tracers, states, records, pair launches and bits -- whose
+ * step kernel also looks at every consecutive pair of states: it stores the states interpolated onto a plane of
+ * the pattern frame (a surface of section) and keeps a fixed-size summary per tracer (peri- and apocentres,
+ * extrema, windings), so that neither needs a recorded state.  The rule, which DESIGN.md 6v states in full.
+ * Everything is binary64 +, -, x and one /, each rounded once, no contraction; the only comparisons are < and >=.
+ * State k is (x_k, v_k) of "Orbits"; (e1, e2, n) = nb_map_frame(axis), formed for omega == 0 too; c = center;
+ * (C_k, S_k) = nb_orbit_phase(omega, dt, step0 + k).
+ * Pattern-frame state of state k:
+ *   d = x_k - c
+ *   a = (dx e1x + dy e1y) + dz e1z,  b and l likewise with e2 and n
+ *   a' = a C_k + b S_k,  b' = b C_k - a S_k            (omega == 0: the same lines with (1, 0))
+ *   xi_k = (a', b', l)
+ *   u = (vx e1x + vy e1y) + vz e1z,  v and t likewise with e2 and n     (v_k in the frame)
+ *   u' = u C_k + v S_k,  v' = v C_k - u S_k
+ *   eta_k = (u' + omega b', v' - omega a', t)          (omega == 0: (u', v', t), the omega terms not formed)
+ * Scalars of state k, normal = (N_a, N_b, N_l) given in the pattern frame:
+ *   s_k = ((N_a a' + N_b b') + N_l l) - offset
+ *   D_k = (dx vx + dy vy) + dz vz
+ *   L_k = (n_x (dy vz - dz vy) + n_y (dz vx - dx vz)) + n_z (dx vy - dy vx)       (the L of "Orbits")
+ *   r2 = (a' a' + b' b') + l l,   R2 = a' a' + b' b'
+ * Sign change of a scalar y over the bracket (k, k+1), the one test used everywhere:
+ *   up    y_k < 0 and y_{k+1} >= 0
+ *   down  y_k >= 0 and y_{k+1} < 0
+ * so ups and downs alternate strictly, a NaN triggers neither, and y_k - y_{k+1} is not 0 when one fires.
+ * Section crossing: bracket (k, k+1) crosses on an up of s if direction >= 0 and on a down of s if
+ * direction <= 0.  f = s_k / (s_k - s_{k+1}), and the record is
+ *   xi[i]  = xi_k[i] + f (xi_{k+1}[i] - xi_k[i]),   eta[i] likewise
+ *   time   = (double)(step0 + k) * dt + f * dt,     step = step0 + k
+ * Linear interpolation, on purpose: its error is (Omega dt)^2 / 8 of the orbit's scale, the leapfrog's own order.
+ * Tracer i stores its first max_crossings records at crossings[i * max_crossings + j] in time order; counts[i]
+ * is the number of all its crossings, stored or not; slots never written are zero bytes.
+ * Summary of tracer i, over the states 0 .. steps and the brackets 0 .. steps - 1:
+ *   r2_min, r2_max, R2_min, R2_max, lz_min, lz_max of r2, R2 and L; h_max of |l|.  They start at +inf (minima)
+ *   and -inf (maxima, h_max) and are replaced on  y < min  or  y > max, so a NaN state leaves them alone.
+ *   pericentres = ups of D, apocentres = downs of D, plane_ups = ups of l;
+ *   first_peri, last_peri = step0 + k + 1 of the first and last bracket with an up of D, UINT64_MAX for none;
+ *   winding_pattern  +1 on an up of b' and -1 on a down of b' whose interpolated a' is > 0:
+ *                    a'_k + f_b (a'_{k+1} - a'_k),  f_b = b'_k / (b'_k - b'_{k+1});
+ *   winding_inertial the same on the unturned (a, b).
+ * A tracer that is non-finite has no crossings and untouched extrema; the others keep their bits.
+ * Consequences: besides those of "Orbits", a run of 2 S steps equals a run of S steps followed by one of S steps
+ * from the first run's last record with step0 + S whenever S is a multiple of `every`: the counts add, the stored
+ * crossings concatenate (given room), and the summaries combine by nb_orbit_summary_merge.  Bracket (S-1, S)
+ * belongs to the first run and (S, S+1) to the second; state S is in both, which the extrema do not notice.
+ * No launch is added: stats.orbit.pair_launches and the step launches are those of nb_orbits_sim. */
+#define NB_ORBIT_SECTION_MAX_CROSSINGS (1u << 22) /* m * max_crossings */
+#define NB_ORBIT_NO_STEP UINT64_MAX
+
+typedef struct nb_orbit_section_params {
+    double normal[3];       /* (N_a, N_b, N_l) in the pattern frame; finite, not all zero; need not be a unit vector */
+    double offset;          /* the plane is N . xi = offset; finite */
+    int32_t direction;      /* +1: ups of s, -1: downs, 0: both */
+    uint32_t max_crossings; /* stored per tracer */
+    uint32_t flags, reserved; /* both 0 */
+} nb_orbit_section_params;
+
+typedef struct nb_orbit_crossing { /* 64 bytes */
+    double xi[3], eta[3], time;
+    uint64_t step;
+} nb_orbit_crossing;
+
+typedef struct nb_orbit_summary { /* 96 bytes: 7 doubles at 0, 2 uint64 at 56, 6 32-bit words at 72 */
+    double r2_min, r2_max, R2_min, R2_max, h_max, lz_min, lz_max;
+    uint64_t first_peri, last_peri;
+    uint32_t pericentres, apocentres, plane_ups;
+    int32_t winding_pattern, winding_inertial;
+    uint32_t reserved;
+} nb_orbit_summary;
+
+typedef struct nb_orbit_section_stats {
+    nb_orbit_stats orbit;
+    uint64_t crossings;  /* the sum of counts */
+    uint64_t stored;     /* the sum of min(counts, max_crossings) */
+    uint64_t overflowed; /* tracers with counts > max_crossings */
+} nb_orbit_section_stats;
+
+/* nb_orbits_sim with the section: tracks, its R = nb_orbit_records(steps, every) records and coincident are that
+ * call's (a section run passes every = steps and gets the two end states); crossings is [m * max_crossings],
+ * counts [m], summaries [m].  crossings, counts, summaries, coincident and stats may be null, except that null
+ * crossings with max_crossings > 0 and m > 0 is invalid.  NB_ERR_INVALID for everything nb_orbits_sim refuses,
+ * null section params, a non-finite or all-zero normal, a non-finite offset, a direction outside {-1, 0, 1},
+ * section flags or reserved != 0, m * max_crossings > NB_ORBIT_SECTION_MAX_CROSSINGS, or a zero or non-finite
+ * axis (the frame is needed for omega == 0 too) -- all checked before the handle is looked at; NB_ERR_UNSUPPORTED
+ * as nb_orbits_sim. */
+int nb_orbit_sections_sim(nb_sim *sim, const nb_orbit_params *params, const nb_orbit_section_params *section,
+                          const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                          uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                          nb_orbit_summary *summaries, nb_orbit_section_stats *stats);
+/* Host only: the summary of a run followed by its continuation -- min of the minima, max of the maxima, the
+ * counters and windings added, first_peri the first present (a's, else b's), last_peri the last present (b's,
+ * else a's).  out may be a or b.  NB_ERR_INVALID for a null pointer. */
+int nb_orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out);
+
+/* ------------------------------------------------------------------------- */
 /* Projected maps -- per-cell mass and velocity moments on a 2-D grid (no     */
 /* reference counterpart: structure in two dimensions, without symmetry)      */
 /* ------------------------------------------------------------------------- */
@@ -2354,6 +2451,12 @@ int nb_tidal_runner(nb_runner *runner, const float *points, size_t m, nb_tidal_s
  * runner. */
 int nb_orbits_runner(nb_runner *runner, const nb_orbit_params *params, const double *pos, const double *vel,
                      size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats);
+/* nb_orbit_sections_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_orbit_sections_runner(nb_runner *runner, const nb_orbit_params *params, const nb_orbit_section_params *section,
+                             const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                             uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                             nb_orbit_summary *summaries, nb_orbit_section_stats *stats);
 /* nb_local_kinematics_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a
  * several-GPU runner. */
 int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,

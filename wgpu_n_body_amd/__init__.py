@@ -38,7 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
-           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "ProjectedMap", "map_frame", "map_edges",
+           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "OrbitSections", "OrbitSectionStats", "ProjectedMap", "map_frame", "map_edges",
            "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
            "FofGroups", "FofStats", "FOF_NONE", "PhaseSpaceGroups",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
@@ -697,6 +697,147 @@ def _orbits(call, handle, pos, vel, dt, steps, every, energy, omega, axis, cente
     return Orbits(tracks["pos"].copy(), tracks["vel"].copy(), tracks["potential"].copy(), tracks["energy"].copy(),
                   step, step.astype(np.float64) * p.dt, coincident, stats, float(p.dt), float(p.omega),
                   np.array(list(p.axis)), np.array(list(p.center)))
+
+
+@dataclass(frozen=True)
+class OrbitSectionStats:
+    """nb_orbit_section_stats: what an orbit_sections() call measured."""
+    orbit: OrbitStats
+    crossings: int    # all crossings of all tracers
+    stored: int       # those that found room
+    overflowed: int   # tracers with more crossings than max_crossings
+
+
+_SUMMARY_FIELDS = ("r2_min", "r2_max", "R2_min", "R2_max", "h_max", "lz_min", "lz_max", "first_peri", "last_peri",
+                   "pericentres", "apocentres", "plane_ups", "winding_pattern", "winding_inertial")
+
+
+@dataclass(frozen=True)
+class OrbitSections:
+    """nb_orbit_crossing[M][K] + nb_orbit_summary[M] (include/nbody.h "Orbit sections"; no reference counterpart):
+    the states of M tracers interpolated onto a plane of the pattern frame -- a surface of section -- and a running
+    summary per tracer, both taken inside the orbit's step kernel.  xi = (a', b', l) is the position and eta the
+    velocity the turning pattern sees, in the frame of map_frame(axis) about `center`."""
+    orbits: Orbits           # the recorded states of the same call
+    count: np.ndarray        # (M,) uint32: all crossings of a tracer
+    stored: np.ndarray       # (M,) uint32: min(count, K)
+    xi: np.ndarray           # (M, K, 3) float64
+    eta: np.ndarray          # (M, K, 3) float64
+    time: np.ndarray         # (M, K) float64
+    step: np.ndarray         # (M, K) uint64: the step the bracket began at
+    valid: np.ndarray        # (M, K) bool: slot j < stored
+    summary: np.ndarray      # (M,) ORBIT_SUMMARY_DTYPE
+    stats: OrbitSectionStats
+
+    def __getattr__(self, name):
+        if name in _SUMMARY_FIELDS and "summary" in self.__dict__:
+            return self.summary[name]
+        raise AttributeError(name)
+
+    @property
+    def r_min(self) -> np.ndarray:
+        return np.sqrt(self.summary["r2_min"])
+
+    @property
+    def r_max(self) -> np.ndarray:
+        return np.sqrt(self.summary["r2_max"])
+
+    def points(self, coord: int = 0, vel: int = 0):
+        """(xi[coord], eta[vel]) of every stored crossing, flattened: the two arrays of a scatter plot."""
+        return self.xi[..., coord][self.valid], self.eta[..., vel][self.valid]
+
+    def radial_period(self) -> np.ndarray:
+        """(M,): (last_peri - first_peri) dt / (pericentres - 1); NaN below two pericentres."""
+        n = self.summary["pericentres"].astype(np.int64)
+        span = (self.summary["last_peri"].astype(np.float64) - self.summary["first_peri"].astype(np.float64))
+        with np.errstate(all="ignore"):
+            return np.where(n >= 2, span * self.orbits.dt / np.maximum(n - 1, 1), np.nan)
+
+    def frequency_ratio(self) -> np.ndarray:
+        """(M,): winding_pattern / pericentres -- turns about the pattern's axis per radial oscillation (NaN
+        without a pericentre)."""
+        n = self.summary["pericentres"].astype(np.float64)
+        with np.errstate(all="ignore"):
+            return np.where(n > 0, self.summary["winding_pattern"] / np.where(n > 0, n, 1.0), np.nan)
+
+    def merge(self, other: "OrbitSections") -> "OrbitSections":
+        """This run followed by `other`, its continuation from orbits.final(): the counts added, the stored
+        crossings concatenated, the summaries combined by nb_orbit_summary_merge.  `.orbits` is the continuation's."""
+        m = self.count.shape[0]
+        if other.count.shape[0] != m:
+            raise ValueError("merge: the two runs have different tracers")
+        summary = np.zeros(m, dtype=_lib.ORBIT_SUMMARY_DTYPE)
+        a, b = np.ascontiguousarray(self.summary), np.ascontiguousarray(other.summary)
+        size = _lib.ORBIT_SUMMARY_DTYPE.itemsize
+        for i in range(m):
+            check(_lib.lib().nb_orbit_summary_merge(a.ctypes.data + i * size, b.ctypes.data + i * size,
+                                                    summary.ctypes.data + i * size))
+        k = self.xi.shape[1] + other.xi.shape[1]
+        rec = np.zeros((m, k), dtype=_lib.ORBIT_CROSSING_DTYPE)
+        stored = np.zeros(m, dtype=np.uint32)
+        for i in range(m):
+            rows = np.concatenate([self._records()[i, :self.stored[i]], other._records()[i, :other.stored[i]]])
+            rec[i, :rows.shape[0]] = rows
+            stored[i] = rows.shape[0]
+        count = self.count + other.count
+        valid = np.arange(k)[None, :] < stored[:, None]
+        stats = OrbitSectionStats(other.stats.orbit, int(count.sum()), int(stored.sum()), int((count > stored).sum()))
+        return OrbitSections(other.orbits, count, stored, rec["xi"].copy(), rec["eta"].copy(), rec["time"].copy(),
+                             rec["step"].copy(), valid, summary, stats)
+
+    def _records(self) -> np.ndarray:
+        rec = np.zeros(self.time.shape, dtype=_lib.ORBIT_CROSSING_DTYPE)
+        rec["xi"], rec["eta"], rec["time"], rec["step"] = self.xi, self.eta, self.time, self.step
+        return rec
+
+
+def _orbit_sections(call, handle, pos, vel, dt, steps, normal, offset, direction, max_crossings, every, energy, omega,
+                    axis, center, accel_scale, step0) -> OrbitSections:
+    x = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+    if x.shape != v.shape:
+        raise ValueError(f"orbit_sections: pos {x.shape} and vel {v.shape} differ")
+    every = steps if every is None else every
+    for name, val in (("steps", steps), ("every", every), ("max_crossings", max_crossings)):
+        if not 0 <= int(val) <= 0xFFFFFFFF:
+            raise ValueError(f"orbit_sections: {name} = {val} is not a 32-bit count")
+    if not -0x80000000 <= int(direction) <= 0x7FFFFFFF:
+        raise ValueError(f"orbit_sections: direction = {direction}")
+    p = _lib.nb_orbit_params()
+    p.dt, p.step0, p.steps, p.every = float(dt), int(step0), int(steps), int(every)
+    p.flags, p.reserved = (_lib.NB_ORBIT_ENERGY if energy else 0), 0
+    p.accel_scale, p.omega = float(accel_scale), float(omega)
+    s = _lib.nb_orbit_section_params()
+    for k in range(3):
+        p.axis[k], p.center[k], s.normal[k] = float(axis[k]), float(center[k]), float(normal[k])
+    s.offset, s.direction, s.max_crossings = float(offset), int(direction), int(max_crossings)
+    m, cap = x.shape[0], int(max_crossings)
+    records = int(_lib.lib().nb_orbit_records(p.steps, p.every))
+    # (the call refuses what it does not take, before it writes)
+    big = (m > _lib.NB_ORBIT_MAX_TRACERS or records * m > _lib.NB_ORBIT_MAX_SAMPLES
+           or m * cap > _lib.NB_ORBIT_SECTION_MAX_CROSSINGS)
+    tracks = np.zeros((0 if big else records, m), dtype=_lib.ORBIT_SAMPLE_DTYPE)
+    rec = np.zeros((m, 0 if big else cap), dtype=_lib.ORBIT_CROSSING_DTYPE)
+    coincident = np.zeros(m, dtype=np.uint32)
+    count = np.zeros(m, dtype=np.uint32)
+    summary = np.zeros(m, dtype=_lib.ORBIT_SUMMARY_DTYPE)
+    st = _lib.nb_orbit_section_stats()
+    check(call(handle, C.byref(p), C.byref(s), x.ctypes.data, v.ctypes.data, m, tracks.ctypes.data,
+               coincident.ctypes.data, rec.ctypes.data if rec.size else None, count.ctypes.data, summary.ctypes.data,
+               C.byref(st)))
+    ks = np.array([k for k in range(p.steps + 1) if k % p.every == 0 or k == p.steps], dtype=np.uint64)
+    step = ks + np.uint64(p.step0)
+    so = st.orbit
+    ostats = OrbitStats(int(so.step_num), int(so.n), int(so.nonfinite), int(so.tracers), int(so.nonfinite_tracers),
+                        int(so.records), int(so.pair_launches), int(so.flags))
+    orbits = Orbits(tracks["pos"].copy(), tracks["vel"].copy(), tracks["potential"].copy(), tracks["energy"].copy(),
+                    step, step.astype(np.float64) * p.dt, coincident, ostats, float(p.dt), float(p.omega),
+                    np.array(list(p.axis)), np.array(list(p.center)))
+    stored = np.minimum(count, np.uint32(cap)).astype(np.uint32)
+    valid = np.arange(cap)[None, :] < stored[:, None]
+    return OrbitSections(orbits, count, stored, rec["xi"].copy(), rec["eta"].copy(), rec["time"].copy(),
+                         rec["step"].copy(), valid, summary,
+                         OrbitSectionStats(ostats, int(st.crossings), int(st.stored), int(st.overflowed)))
 
 
 def map_frame(axis):
@@ -2482,6 +2623,49 @@ class _Passes:
         pos = pts[:: max(int(n_phi), 1)].astype(np.float64)
         vel = (float(speed) * cv.v_c)[:, None] * e2[None, :]
         return self.orbits(pos, vel, dt=dt, steps=steps, axis=axis, center=center, **kw)
+
+    def orbit_sections(self, pos, vel, *, dt: float, steps: int, normal=(0.0, 1.0, 0.0), offset: float = 0.0,
+                       direction: int = 1, max_crossings: int = 256, every=None, energy: bool = False,
+                       omega: float = 0.0, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0), coupling="field",
+                       step0: int = 0) -> OrbitSections:
+        """orbits() whose step kernel also takes a surface of section and a summary per tracer
+        (nb_orbit_sections_sim): every crossing of the plane normal . xi = offset of the pattern frame -- xi = (a', b',
+        l) in map_frame(axis) about `center`, turned with the pattern -- interpolated linearly between the two states
+        around it, the first `max_crossings` per tracer stored; and peri- and apocentres, extrema of r, R, |l| and L_z
+        and the windings about the axis, counted over every step.  direction: +1 keeps the crossings towards positive
+        normal . xi, -1 the others, 0 both.  every=None records the two end states only; the other arguments are
+        orbits()'s, and no launch is added to that call's.  A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _orbit_sections(getattr(_lib.lib(), "nb_orbit_sections_" + suffix), self._h, pos, vel, dt, steps,
+                               normal, offset, direction, max_crossings, every, energy, omega, axis, center,
+                               self._accel_scale(coupling), step0)
+
+    def jacobi_launch(self, energy: float, a, *, omega: float, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0),
+                      coupling="field"):
+        """(pos, vel), inertial, of tracers that all have the Jacobi integral `energy`: on the pattern's a' axis at
+        a' = `a` (an array), b' = l = 0, moving along b' alone in the pattern frame with
+        b'' = sqrt(2 (E_J - Phi_eff)), Phi_eff = Phi - omega^2 a'^2 / 2, Phi the potential of field() at the point an
+        orbits() call samples at state 0 of step0 = 0 (where the two frames coincide).  Where Phi_eff > E_J the
+        position is forbidden and both rows are NaN.  Every curve of one orbit_sections() plot then shares E_J."""
+        a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64)
+        n, e1, e2 = map_frame(axis)
+        c = np.asarray(center, dtype=np.float64)
+        omega, scale = float(omega), self._accel_scale(coupling)
+        pos = c + a[:, None] * e1
+        q = pos
+        if omega != 0.0:  # the point of evaluation 0, line by line
+            d = pos - c
+            da, db, dl = ((d[:, 0] * f[0] + d[:, 1] * f[1]) + d[:, 2] * f[2] for f in (e1, e2, n))
+            ar, br = da * 1.0 + db * 0.0, db * 1.0 - da * 0.0
+            q = c + ((ar[:, None] * e1 + br[:, None] * e2) + dl[:, None] * n)
+        with np.errstate(all="ignore"):
+            phi = scale * self.field(q.astype(np.float32), accel=False, potential=True).potential
+            phi_eff = phi - 0.5 * (omega * omega) * (a * a)
+            speed = np.sqrt(2.0 * (float(energy) - phi_eff))
+        vel = (speed + omega * a)[:, None] * e2
+        bad = ~np.isfinite(speed)
+        pos[bad], vel[bad] = np.nan, np.nan
+        return pos, vel
 
     def projected_map(self, width: int, height: int, *, extent, axis=(0.0, 1.0, 0.0), center="com", velocity=None,
                       depth=None, velocities: bool = True) -> ProjectedMap:

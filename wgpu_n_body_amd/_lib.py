@@ -124,6 +124,28 @@ class nb_orbit_stats(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_orbit_section_params(C.Structure):
+    _fields_ = [("normal", C.c_double * 3), ("offset", C.c_double), ("direction", C.c_int32),
+                ("max_crossings", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class nb_orbit_crossing(C.Structure):
+    _fields_ = [("xi", C.c_double * 3), ("eta", C.c_double * 3), ("time", C.c_double), ("step", C.c_uint64)]
+
+
+class nb_orbit_summary(C.Structure):
+    _fields_ = [("r2_min", C.c_double), ("r2_max", C.c_double), ("R2_min", C.c_double), ("R2_max", C.c_double),
+                ("h_max", C.c_double), ("lz_min", C.c_double), ("lz_max", C.c_double),
+                ("first_peri", C.c_uint64), ("last_peri", C.c_uint64),
+                ("pericentres", C.c_uint32), ("apocentres", C.c_uint32), ("plane_ups", C.c_uint32),
+                ("winding_pattern", C.c_int32), ("winding_inertial", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class nb_orbit_section_stats(C.Structure):
+    _fields_ = [("orbit", nb_orbit_stats), ("crossings", C.c_uint64), ("stored", C.c_uint64),
+                ("overflowed", C.c_uint64)]
+
+
 class nb_map_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -354,6 +376,14 @@ TIDAL_RING_DTYPE = np.dtype([("t_RR", "<f8"), ("t_pp", "<f8"), ("t_nn", "<f8"), 
 # nb_orbit_sample[] as a numpy record array
 ORBIT_SAMPLE_DTYPE = np.dtype([("pos", "<f8", (3,)), ("vel", "<f8", (3,)), ("potential", "<f8"), ("energy", "<f8")])
 
+# nb_orbit_crossing[] and nb_orbit_summary[] as numpy record arrays
+ORBIT_CROSSING_DTYPE = np.dtype([("xi", "<f8", (3,)), ("eta", "<f8", (3,)), ("time", "<f8"), ("step", "<u8")])
+ORBIT_SUMMARY_DTYPE = np.dtype([("r2_min", "<f8"), ("r2_max", "<f8"), ("R2_min", "<f8"), ("R2_max", "<f8"),
+                                ("h_max", "<f8"), ("lz_min", "<f8"), ("lz_max", "<f8"), ("first_peri", "<u8"),
+                                ("last_peri", "<u8"), ("pericentres", "<u4"), ("apocentres", "<u4"),
+                                ("plane_ups", "<u4"), ("winding_pattern", "<i4"), ("winding_inertial", "<i4"),
+                                ("reserved", "<u4")])
+
 # nb_halo_head[] as a numpy record array
 HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
                             ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
@@ -396,6 +426,9 @@ assert C.sizeof(nb_tidal_sample) == 56 == TIDAL_SAMPLE_DTYPE.itemsize
 assert C.sizeof(nb_tidal_ring) == 56 == TIDAL_RING_DTYPE.itemsize
 assert C.sizeof(nb_orbit_params) == 96 and C.sizeof(nb_orbit_stats) == 56
 assert C.sizeof(nb_orbit_sample) == 64 == ORBIT_SAMPLE_DTYPE.itemsize
+assert C.sizeof(nb_orbit_section_params) == 48 and C.sizeof(nb_orbit_section_stats) == 80
+assert C.sizeof(nb_orbit_crossing) == 64 == ORBIT_CROSSING_DTYPE.itemsize
+assert C.sizeof(nb_orbit_summary) == 96 == ORBIT_SUMMARY_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
@@ -429,6 +462,7 @@ NB_FIELD_ACCEL, NB_FIELD_POTENTIAL = 1, 2
 NB_FIELD_MAX_POINTS = 1 << 24
 NB_TIDAL_K = 33
 NB_ORBIT_ENERGY = 1
+NB_ORBIT_SECTION_MAX_CROSSINGS, NB_ORBIT_NO_STEP = 1 << 22, (1 << 64) - 1
 NB_ORBIT_MAX_TRACERS, NB_ORBIT_MAX_STEPS, NB_ORBIT_MAX_SAMPLES, NB_ORBIT_MAX_PAIRS_LOG2 = 1 << 20, 1 << 20, 1 << 22, 44
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
@@ -469,6 +503,7 @@ ABI_SYMBOLS = [
     "nb_sim_field", "nb_field_rings", "nb_field_ring_means", "nb_runner_field",
     "nb_tidal_sim", "nb_tidal_runner", "nb_tidal_ring_means",
     "nb_orbits_sim", "nb_orbits_runner", "nb_orbit_records", "nb_orbit_phase",
+    "nb_orbit_sections_sim", "nb_orbit_sections_runner", "nb_orbit_summary_merge",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
@@ -589,6 +624,12 @@ def lib() -> C.CDLL:
     fof6 = [vp, P(nb_fof6_params), vp, vp, vp, sz, P(nb_fof_stats)]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_fof6_" + suffix).argtypes = fof6
+    # ... and the orbits' sections (include/nbody.h "Orbit sections")
+    orbit_sections = [vp, P(nb_orbit_params), P(nb_orbit_section_params), vp, vp, sz, vp, vp, vp, vp, vp,
+                      P(nb_orbit_section_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_orbit_sections_" + suffix).argtypes = orbit_sections
+    L.nb_orbit_summary_merge.argtypes = [vp, vp, vp]
     L.nb_orbit_records.argtypes = [C.c_uint32, C.c_uint32]
     L.nb_orbit_records.restype = C.c_uint32
     L.nb_orbit_phase.argtypes = [C.c_double, C.c_double, u64, P(C.c_double), P(C.c_double)]

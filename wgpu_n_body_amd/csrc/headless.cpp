@@ -12,6 +12,10 @@
 //             [--freq-center X,Y,Z]]
 //            [--orbits DIR [--orbits-at K] --orbits-range RMIN,RMAX [--orbits-bins B] --orbits-dt DT --orbits-steps S
 //             [--orbits-every E] [--orbits-omega W] [--orbits-speed F] [--orbits-axis X,Y,Z] [--orbits-center X,Y,Z]]
+//            [--sections DIR [--sections-at K] --sections-range RMIN,RMAX [--sections-bins B] --sections-dt DT
+//             --sections-steps S [--sections-omega W] [--sections-speed F] [--sections-axis X,Y,Z]
+//             [--sections-center X,Y,Z] [--sections-normal A,B,L] [--sections-offset D] [--sections-direction -1|0|1]
+//             [--sections-max K]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
@@ -69,6 +73,14 @@
 // the potential and the Jacobi integral.  Written as DIR/orbits_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape
 // (R, B, 8) -- position, velocity, potential, energy -- and one line "orbits <step> <records> <tracers>
 // <nonfinite_tracers> <pair_launches>".  The time it takes is not part of any "Step Duration".
+// --sections DIR takes a surface of section (nb_orbit_sections_runner) of the state after step K (--sections-at,
+// default 0), the tracers launched as --orbits launches them (--sections-range, -bins, -speed, -axis, -center, -dt,
+// -steps, -omega): the crossings of the plane A a' + B b' + L l = D of the pattern frame (--sections-normal, default
+// 0,1,0; --sections-offset, default 0) upwards, downwards or both (--sections-direction 1, -1 or 0, default 1), the
+// first K of each tracer (--sections-max, default 256).  Written as DIR/sections_<step, 6 digits>.npy: <f8, shape
+// (B, K, 8) -- xi, eta, time and the step as a double, zero where no crossing is stored -- and
+// DIR/sections_<step>_counts.npy: <f8, shape (B,), all crossings of each tracer; and one line "sections <step>
+// <tracers> <crossings> <stored> <overflowed> <pair_launches>".  The time it takes is not part of any "Step Duration".
 //
 // --maps DIR writes the projected map (nb_runner_map) of step 0 and of every K-th step (--map-every,
 // default 1) as DIR/map_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape (7, H, W) -- the counts as
@@ -353,6 +365,78 @@ static bool write_orbits(nbody::OfflineHeadless<Sim> &runner, const OrbitsOption
     }
     std::printf("orbits %llu %u %zu %llu %u\n", (unsigned long long)o.stats.step_num, o.records, o.tracers,
                 (unsigned long long)o.stats.nonfinite_tracers, o.stats.pair_launches);
+    return true;
+}
+
+struct SectionsOptions {
+    OrbitsOptions launch;  // dir, at, the rings, dt, steps, omega, speed, axis, center
+    std::array<double, 3> normal{0.0, 1.0, 0.0};
+    double offset = 0.0;
+    int direction = 1;
+    uint32_t max_crossings = 256;
+};
+
+// NumPy format 1.0, <f8, C order: the header for `shape` (the text between the brackets)
+static std::string npy_head_f8(const char *shape) {
+    char dict[128];
+    const int len = std::snprintf(dict, sizeof dict, "{'descr': '<f8', 'fortran_order': False, 'shape': (%s), }", shape);
+    const size_t total = (10 + (size_t)len + 1 + 63) / 64 * 64, hlen = total - 10;
+    std::string head("\x93NUMPY\x01\x00", 8);
+    head += (char)(hlen & 0xff);
+    head += (char)(hlen >> 8);
+    head += dict;
+    head.append(total - 1 - head.size(), ' ');
+    head += '\n';
+    return head;
+}
+
+static bool write_f8(const std::string &path, const char *shape, const std::vector<double> &data) {
+    std::FILE *out = std::fopen(path.c_str(), "wb");
+    const std::string head = npy_head_f8(shape);
+    const bool ok = out && std::fwrite(head.data(), 1, head.size(), out) == head.size() &&
+                    std::fwrite(data.data(), sizeof(double), data.size(), out) == data.size();
+    if (!out || std::fclose(out) != 0 || !ok) {
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+        return false;
+    }
+    return true;
+}
+
+template <class Sim>
+static bool write_sections(nbody::OfflineHeadless<Sim> &runner, const SectionsOptions &so) {
+    const OrbitsOptions &oo = so.launch;
+    std::vector<double> radii(oo.bins);
+    for (uint32_t i = 0; i < oo.bins; ++i)
+        radii[i] = oo.bins > 1 ? oo.rmin + (oo.rmax - oo.rmin) * (double)i / (double)(oo.bins - 1) : oo.rmin;
+    const nb_orbit_params p = nbody::orbit_params(oo.dt, oo.steps, oo.steps, false, oo.omega, oo.axis, oo.center);
+    const nb_orbit_section_params sec = nbody::orbit_section_params(so.normal, so.offset, so.direction, so.max_crossings);
+    const nbody::OrbitSections o = runner.circular_orbit_sections(p, sec, radii, 16, oo.speed);
+    const size_t m = o.orbits.tracers, cap = o.max_crossings;
+    std::vector<double> rows(m * cap * 8, 0.0), counts(m);
+    for (size_t i = 0; i < m; ++i) {
+        counts[i] = (double)o.counts[i];
+        for (uint32_t j = 0; j < o.stored(i); ++j) {
+            const nb_orbit_crossing &c = o.at(i, j);
+            double *r = rows.data() + (i * cap + j) * 8;
+            for (int a = 0; a < 3; ++a) {
+                r[a] = c.xi[a];
+                r[3 + a] = c.eta[a];
+            }
+            r[6] = c.time;
+            r[7] = (double)c.step;
+        }
+    }
+    char name[64], shape[64];
+    const unsigned long long step = (unsigned long long)o.stats.orbit.step_num;
+    std::snprintf(name, sizeof name, "/sections_%06llu.npy", step);
+    std::snprintf(shape, sizeof shape, "%zu, %zu, 8", m, cap);
+    if (!write_f8(so.launch.dir + name, shape, rows)) return false;
+    std::snprintf(name, sizeof name, "/sections_%06llu_counts.npy", step);
+    std::snprintf(shape, sizeof shape, "%zu,", m);
+    if (!write_f8(so.launch.dir + name, shape, counts)) return false;
+    std::printf("sections %llu %zu %llu %llu %llu %u\n", step, m, (unsigned long long)o.stats.crossings,
+                (unsigned long long)o.stats.stored, (unsigned long long)o.stats.overflowed,
+                o.stats.orbit.pair_launches);
     return true;
 }
 
@@ -788,7 +872,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const KnnOptions &knn, const BoundOptions &bound, const HaloOptions &halo, const HopOptions &hop,
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
-               const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6) {
+               const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6,
+               const SectionsOptions &sections) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -798,6 +883,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (rotcurve.every > 0) print_rotcurve(runner, rotcurve);
     if (freq.every > 0) print_freq(runner, freq);
     if (!orbits.dir.empty() && orbits.at == 0 && !write_orbits(runner, orbits)) return 1;
+    if (!sections.launch.dir.empty() && sections.launch.at == 0 && !write_sections(runner, sections)) return 1;
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
@@ -824,6 +910,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (rotcurve.every > 0 && (i + 1) % rotcurve.every == 0) print_rotcurve(runner, rotcurve);
         if (freq.every > 0 && (i + 1) % freq.every == 0) print_freq(runner, freq);
         if (!orbits.dir.empty() && i + 1 == orbits.at && !write_orbits(runner, orbits)) return 1;
+        if (!sections.launch.dir.empty() && i + 1 == sections.launch.at && !write_sections(runner, sections)) return 1;
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
@@ -867,6 +954,7 @@ int main(int argc, char **argv) {
     KnnOptions knn;
     KinOptions kin;
     OrbitsOptions orbits;
+    SectionsOptions sections;
     Fof6Options fof6;
     BoundOptions bound;
     HaloOptions halo;
@@ -1192,6 +1280,32 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (k == "--sections") sections.launch.dir = v;
+        else if (k == "--sections-at") sections.launch.at = std::atoi(v.c_str());
+        else if (k == "--sections-bins") sections.launch.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--sections-steps") sections.launch.steps = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--sections-dt") sections.launch.dt = std::atof(v.c_str());
+        else if (k == "--sections-omega") sections.launch.omega = std::atof(v.c_str());
+        else if (k == "--sections-speed") sections.launch.speed = std::atof(v.c_str());
+        else if (k == "--sections-offset") sections.offset = std::atof(v.c_str());
+        else if (k == "--sections-direction") sections.direction = std::atoi(v.c_str());
+        else if (k == "--sections-max") sections.max_crossings = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--sections-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &sections.launch.rmin, &sections.launch.rmax) != 2) {
+                std::fprintf(stderr, "--sections-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            sections.launch.have_range = true;
+        }
+        else if (k == "--sections-axis" || k == "--sections-center" || k == "--sections-normal") {
+            double *a = k == "--sections-axis"     ? sections.launch.axis.data()
+                        : k == "--sections-center" ? sections.launch.center.data()
+                                                   : sections.normal.data();
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", a, a + 1, a + 2) != 3) {
+                std::fprintf(stderr, "%s takes three numbers X,Y,Z, not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--kin") kin.every = std::atoi(v.c_str());
         else if (k == "--kin-k") kin.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--kin-gradient") kin.gradient = std::atoi(v.c_str()) != 0;
@@ -1227,6 +1341,11 @@ int main(int argc, char **argv) {
     }
     if (!orbits.dir.empty() && (!orbits.have_range || orbits.steps == 0 || orbits.dt == 0.0 || orbits.at < 0)) {
         std::fprintf(stderr, "--orbits needs --orbits-range RMIN,RMAX, --orbits-dt DT and --orbits-steps S\n");
+        return 2;
+    }
+    if (!sections.launch.dir.empty() && (!sections.launch.have_range || sections.launch.steps == 0 ||
+                                         sections.launch.dt == 0.0 || sections.launch.at < 0)) {
+        std::fprintf(stderr, "--sections needs --sections-range RMIN,RMAX, --sections-dt DT and --sections-steps S\n");
         return 2;
     }
     if (rotcurve.every > 0 && !rotcurve.have_range) {
@@ -1300,9 +1419,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -150,6 +150,20 @@ static int pass_orbits(H *h, const nb_orbit_params *params, const double *pos, c
 }
 
 template <class H>
+static int pass_orbit_sections(H *h, const nb_orbit_params *params, const nb_orbit_section_params *section,
+                               const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                               uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                               nb_orbit_summary *summaries, nb_orbit_section_stats *stats) {
+    OrbitPlan plan{};
+    if (int rc = orbit_sections_check_args(params, section, pos, vel, m, tracks, crossings, &plan)) return rc;
+    return on_sim(h, "orbit_sections", [&](SimBase &s) {
+        if (int rc = orbits_check_e(s, params)) return rc;
+        return sim_orbit_sections(s, *params, *section, plan, pos, vel, m, tracks, coincident, crossings, counts,
+                                  summaries, stats);
+    });
+}
+
+template <class H>
 static int pass_map(H *h, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
@@ -535,6 +549,23 @@ int nb_orbits_sim(nb_sim *sim, const nb_orbit_params *params, const double *pos,
 int nb_orbits_runner(nb_runner *runner, const nb_orbit_params *params, const double *pos, const double *vel,
                      size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
     return pass_orbits(runner, params, pos, vel, m, tracks, coincident, stats);
+}
+int nb_orbit_sections_sim(nb_sim *sim, const nb_orbit_params *params, const nb_orbit_section_params *section,
+                          const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                          uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                          nb_orbit_summary *summaries, nb_orbit_section_stats *stats) {
+    return pass_orbit_sections(sim, params, section, pos, vel, m, tracks, coincident, crossings, counts, summaries,
+                               stats);
+}
+int nb_orbit_sections_runner(nb_runner *runner, const nb_orbit_params *params,
+                             const nb_orbit_section_params *section, const double *pos, const double *vel, size_t m,
+                             nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_crossing *crossings,
+                             uint32_t *counts, nb_orbit_summary *summaries, nb_orbit_section_stats *stats) {
+    return pass_orbit_sections(runner, params, section, pos, vel, m, tracks, coincident, crossings, counts, summaries,
+                               stats);
+}
+int nb_orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out) {
+    return orbit_summary_merge(a, b, out);
 }
 uint32_t nb_orbit_records(uint32_t steps, uint32_t every) { return orbit_records(steps, every); }
 int nb_orbit_phase(double omega, double dt, uint64_t k, double *c, double *s) {

@@ -12,6 +12,9 @@
 //              the frozen field by the same pair launches; per step and band one more kernel, one thread per
 //              tracer, is the finish above and everything else of the step.  Its lines are compiled without
 //              contraction (the pragma); the pair kernels are the instantiations field() launches.
+//   sections -- nb_orbit_sections_sim (include/nbody.h "Orbit sections"): the same sequence with the
+//              step kernel's sibling, which also compares every state with the tracer's previous one, stores the
+//              plane crossings and keeps the tracer's summary.  No launch is added.
 // The non-finite count is the diagnostics' own (diag_enqueue_moments on the same stream).
 // No float atomics; the grid and the chunking depend on (M, N, flags) alone and every lane runs the same
 // operations in the same order, so the result is bitwise reproducible and does not depend on where in
@@ -167,16 +170,134 @@ __global__ __launch_bounds__(kThreads) void orbit_stage_kernel(uint32_t m, Orbit
     pts[p] = orbit_point(x, f, rotating, c, s);
 }
 
+// ---- orbit sections (include/nbody.h "Orbit sections"): what the step kernel does with state k
+// besides the step.  One thread per tracer, so a tracer's list needs no atomics and is in time order; every row is
+// indexed by the tracer, never by its place in a band.
+enum : int { kPrevXi = 0, kPrevEta = 3, kPrevS = 6, kPrevD = 7, kPrevA = 8, kPrevB = 9, kPrevFields = 10 };
+struct OrbitSection {
+    double normal[3], offset;
+    int32_t direction;
+    uint32_t max_crossings, m;
+    uint64_t step;               // step0 + k of this state; the bracket that ends here began at step - 1
+    double *prev;                // [kPrevFields][m] the previous state's xi, eta, s, D, a, b
+    nb_orbit_crossing *cross;    // [m][max_crossings], zeroed before the first launch
+    uint32_t *counts;            // [m]
+    nb_orbit_summary *summary;   // [m]
+};
+
+__device__ __forceinline__ bool sign_up(double y0, double y1) { return y0 < 0.0 && y1 >= 0.0; }
+__device__ __forceinline__ bool sign_down(double y0, double y1) { return y0 >= 0.0 && y1 < 0.0; }
+
+__device__ __forceinline__ void orbit_section(uint32_t p, const double (&x)[3], const double (&v)[3],
+                                              const OrbitStep &st, const OrbitFrame &f, const OrbitSection &sc) {
+#pragma clang fp contract(off)
+    const double dx = x[0] - f.c[0], dy = x[1] - f.c[1], dz = x[2] - f.c[2];
+    const double a = (dx * f.e1[0] + dy * f.e1[1]) + dz * f.e1[2];
+    const double b = (dx * f.e2[0] + dy * f.e2[1]) + dz * f.e2[2];
+    const double l = (dx * f.n[0] + dy * f.n[1]) + dz * f.n[2];
+    const double ar = a * st.ck + b * st.sk, br = b * st.ck - a * st.sk;
+    const double u = (v[0] * f.e1[0] + v[1] * f.e1[1]) + v[2] * f.e1[2];
+    const double w = (v[0] * f.e2[0] + v[1] * f.e2[1]) + v[2] * f.e2[2];
+    const double t = (v[0] * f.n[0] + v[1] * f.n[1]) + v[2] * f.n[2];
+    const double ur = u * st.ck + w * st.sk, wr = w * st.ck - u * st.sk;
+    const double xi[3] = {ar, br, l};
+    double eta[3] = {ur, wr, t};
+    if (st.rotating) {
+        eta[0] = ur + st.omega * br;
+        eta[1] = wr - st.omega * ar;
+    }
+    const double s = ((sc.normal[0] * ar + sc.normal[1] * br) + sc.normal[2] * l) - sc.offset;
+    const double D = (dx * v[0] + dy * v[1]) + dz * v[2];
+    const double L = (f.n[0] * (dy * v[2] - dz * v[1]) + f.n[1] * (dz * v[0] - dx * v[2])) +
+                     f.n[2] * (dx * v[1] - dy * v[0]);
+    const double R2 = ar * ar + br * br, r2 = R2 + l * l, h = fabs(l);
+
+    nb_orbit_summary sm;
+    uint32_t count = 0;
+    if (st.first) {
+        sm = nb_orbit_summary{};
+        sm.r2_min = sm.R2_min = sm.lz_min = (double)INFINITY;
+        sm.r2_max = sm.R2_max = sm.lz_max = sm.h_max = -(double)INFINITY;
+        sm.first_peri = sm.last_peri = NB_ORBIT_NO_STEP;
+    } else {
+        sm = sc.summary[p];
+        count = sc.counts[p];
+    }
+    if (r2 < sm.r2_min) sm.r2_min = r2;
+    if (r2 > sm.r2_max) sm.r2_max = r2;
+    if (R2 < sm.R2_min) sm.R2_min = R2;
+    if (R2 > sm.R2_max) sm.R2_max = R2;
+    if (h > sm.h_max) sm.h_max = h;
+    if (L < sm.lz_min) sm.lz_min = L;
+    if (L > sm.lz_max) sm.lz_max = L;
+
+    double *prev = sc.prev + p;
+    const size_t m = sc.m;
+    if (!st.first) {
+        double pxi[3], peta[3];
+        for (int i = 0; i < 3; ++i) {
+            pxi[i] = prev[(kPrevXi + i) * m];
+            peta[i] = prev[(kPrevEta + i) * m];
+        }
+        const double ps = prev[kPrevS * m], pD = prev[kPrevD * m], pa = prev[kPrevA * m], pb = prev[kPrevB * m];
+        const bool up = sign_up(ps, s), down = sign_down(ps, s);
+        if ((up && sc.direction >= 0) || (down && sc.direction <= 0)) {
+            if (count < sc.max_crossings) {
+                const double fr = ps / (ps - s);
+                nb_orbit_crossing c;
+                for (int i = 0; i < 3; ++i) {
+                    c.xi[i] = pxi[i] + fr * (xi[i] - pxi[i]);
+                    c.eta[i] = peta[i] + fr * (eta[i] - peta[i]);
+                }
+                c.time = (double)(sc.step - 1) * st.dt + fr * st.dt;
+                c.step = sc.step - 1;
+                sc.cross[(size_t)p * sc.max_crossings + count] = c;
+            }
+            ++count;
+        }
+        if (sign_up(pD, D)) {
+            ++sm.pericentres;
+            if (sm.first_peri == NB_ORBIT_NO_STEP) sm.first_peri = sc.step;
+            sm.last_peri = sc.step;
+        }
+        if (sign_down(pD, D)) ++sm.apocentres;
+        if (sign_up(pxi[2], l)) ++sm.plane_ups;
+        // windings: a sign change of the second coordinate on the positive side of the first
+        const bool bu = sign_up(pxi[1], br), bd = sign_down(pxi[1], br);
+        if (bu || bd) {
+            const double fb = pxi[1] / (pxi[1] - br);
+            if (pxi[0] + fb * (ar - pxi[0]) > 0.0) sm.winding_pattern += bu ? 1 : -1;
+        }
+        const bool iu = sign_up(pb, b), id = sign_down(pb, b);
+        if (iu || id) {
+            const double fb = pb / (pb - b);
+            if (pa + fb * (a - pa) > 0.0) sm.winding_inertial += iu ? 1 : -1;
+        }
+    }
+    sc.summary[p] = sm;
+    sc.counts[p] = count;
+    if (st.last) return;
+    for (int i = 0; i < 3; ++i) {
+        prev[(kPrevXi + i) * m] = xi[i];
+        prev[(kPrevEta + i) * m] = eta[i];
+    }
+    prev[kPrevS * m] = s;
+    prev[kPrevD * m] = D;
+    prev[kPrevA * m] = a;
+    prev[kPrevB * m] = b;
+}
+
 // after the pairs of evaluation k for the band [p0, p1): the chunks in order and the scaling by g as
 // field_finish_kernel has them, then accel_scale, the turn back, the second half-kick, the record if one is due
 // (rec = the record's row, or null), the first half-kick and the drift of the next step, and the next point.
 // vs holds v_0 on entry to evaluation 0 and w afterwards.
-__global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__restrict__ slab, uint32_t chunks,
-                                                              uint32_t stride, uint32_t p0, uint32_t p1, OrbitStep st,
-                                                              OrbitFrame f, double *__restrict__ xs,
-                                                              double *__restrict__ vs, uint32_t *__restrict__ coinc,
-                                                              float4 *__restrict__ pts,
-                                                              nb_orbit_sample *__restrict__ rec) {
+// With SECTION the state of the evaluation is also handed to orbit_section (below) before the next step begins.
+template <bool SECTION>
+__device__ __forceinline__ void orbit_step(const double *__restrict__ slab, uint32_t chunks, uint32_t stride,
+                                           uint32_t p0, uint32_t p1, const OrbitStep &st, const OrbitFrame &f,
+                                           double *__restrict__ xs, double *__restrict__ vs,
+                                           uint32_t *__restrict__ coinc, float4 *__restrict__ pts,
+                                           nb_orbit_sample *__restrict__ rec, const OrbitSection *sec) {
 #pragma clang fp contract(off)
     const uint32_t q = blockIdx.x * kThreads + threadIdx.x, p = p0 + q;
     if (p >= p1) return;
@@ -232,6 +353,7 @@ __global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__re
         }
         rec[p] = r;
     }
+    if (SECTION) orbit_section(p, x, v, st, f, *sec);
     if (st.last) return;
     for (int i = 0; i < 3; ++i) {
         v[i] = v[i] + kick[i];      // w = v_k + A_k h
@@ -240,6 +362,23 @@ __global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__re
         vs[3 * (size_t)p + i] = v[i];
     }
     pts[p] = orbit_point(x, f, st.rotating, st.cn, st.sn);
+}
+
+__global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__restrict__ slab, uint32_t chunks,
+                                                              uint32_t stride, uint32_t p0, uint32_t p1, OrbitStep st,
+                                                              OrbitFrame f, double *__restrict__ xs,
+                                                              double *__restrict__ vs, uint32_t *__restrict__ coinc,
+                                                              float4 *__restrict__ pts,
+                                                              nb_orbit_sample *__restrict__ rec) {
+    orbit_step<false>(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, nullptr);
+}
+
+// the same step with the section riding in it (include/nbody.h "Orbit sections")
+__global__ __launch_bounds__(kThreads) void orbit_section_step_kernel(
+    const double *__restrict__ slab, uint32_t chunks, uint32_t stride, uint32_t p0, uint32_t p1, OrbitStep st,
+    OrbitFrame f, double *__restrict__ xs, double *__restrict__ vs, uint32_t *__restrict__ coinc,
+    float4 *__restrict__ pts, nb_orbit_sample *__restrict__ rec, OrbitSection sec) {
+    orbit_step<true>(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, &sec);
 }
 
 struct OrbitWork : Workspace {  // (all but the last grow to the largest call so far)
@@ -252,6 +391,14 @@ struct OrbitWork : Workspace {  // (all but the last grow to the largest call so
     PinnedBuf<nb_orbit_sample> h_tracks;
     PinnedBuf<uint32_t> h_coinc;
     PinnedBuf<double> h_bad;  // [1] the diagnostics' non-finite count
+    // orbit sections: the previous state's row, the lists, their lengths and the summaries, by tracer
+    DeviceBuf<double> prev;              // [kPrevFields][m]
+    DeviceBuf<nb_orbit_crossing> cross;  // [m][max_crossings]
+    DeviceBuf<uint32_t> counts;          // [m]
+    DeviceBuf<nb_orbit_summary> summary;  // [m]
+    PinnedBuf<nb_orbit_crossing> h_cross;
+    PinnedBuf<uint32_t> h_counts;
+    PinnedBuf<nb_orbit_summary> h_summary;
 };
 
 }  // namespace
@@ -285,9 +432,21 @@ int sim_field(SimBase &sim, const float *points, size_t m, uint32_t flags, nb_fi
         });
 }
 
-int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos, const double *vel,
-               size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
-    if (int rc = refuse_sharded(sim, "orbits")) return rc;
+// what an nb_orbit_sections_sim call adds to the arguments of nb_orbits_sim
+struct SectionCall {
+    const nb_orbit_section_params &params;
+    nb_orbit_crossing *crossings;
+    uint32_t *counts;
+    nb_orbit_summary *summaries;
+    nb_orbit_section_stats *stats;
+};
+
+// nb_orbits_sim, and with `section` nb_orbit_sections_sim: the same sequence, the step kernel's sibling in the place
+// of the step kernel, a memset up front and three copies at the end
+static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos,
+                      const double *vel, size_t m, nb_orbit_sample *tracks, uint32_t *coincident,
+                      nb_orbit_stats *stats, const SectionCall *section) {
+    if (int rc = refuse_sharded(sim, section ? "orbit_sections" : "orbits")) return rc;
     const uint32_t n = sim.n, mm = (uint32_t)m, steps = P.steps, records = frame.records;
     const bool energy = P.flags & NB_ORBIT_ENERGY, rotating = P.omega != 0.0;
     // the plans of the two kinds of evaluation: field()'s own for m points and the flags of each
@@ -322,6 +481,26 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
     const size_t slab_a = (size_t)plan_a.chunks * kSlabFields * plan_a.stride;
     const size_t slab_e = (size_t)plan_e.chunks * kSlabFields * plan_e.stride;
     NB_HIP_TRY(w.slab.reserve(energy ? std::max(slab_a, slab_e) : slab_a));
+    OrbitSection sc{};
+    const size_t slots = section ? (size_t)mm * section->params.max_crossings : 0;
+    if (section) {
+        NB_HIP_TRY(w.prev.reserve((size_t)kPrevFields * mm));
+        NB_HIP_TRY(w.cross.reserve(slots));
+        NB_HIP_TRY(w.counts.reserve(mm));
+        NB_HIP_TRY(w.summary.reserve(mm));
+        NB_HIP_TRY(w.h_cross.reserve(slots));
+        NB_HIP_TRY(w.h_counts.reserve(mm));
+        NB_HIP_TRY(w.h_summary.reserve(mm));
+        for (int a = 0; a < 3; ++a) sc.normal[a] = section->params.normal[a];
+        sc.offset = section->params.offset;
+        sc.direction = section->params.direction;
+        sc.max_crossings = section->params.max_crossings;
+        sc.m = mm;
+        sc.prev = w.prev;
+        sc.cross = w.cross;
+        sc.counts = w.counts;
+        sc.summary = w.summary;
+    }
 
     OrbitFrame f{};
     for (int a = 0; a < 3; ++a) {
@@ -371,6 +550,8 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
                 if (int rc = diag_enqueue_moments(sim, &mom)) return rc;
                 NB_HIP_TRY(hipMemcpyAsync(w.h_bad, mom + kDiagResBad, sizeof(double), hipMemcpyDeviceToHost, sim.stream));
             }
+            if (slots)
+                NB_HIP_TRY(hipMemsetAsync((nb_orbit_crossing *)w.cross, 0, sizeof(nb_orbit_crossing) * slots, sim.stream));
             if (int rc = orbit_phase(P.omega, P.dt, P.step0, &st.cn, &st.sn)) return rc;
             hipLaunchKernelGGL(orbit_stage_kernel, dim3((mm + kThreads - 1) / kThreads), dim3(kThreads), 0, sim.stream,
                                mm, f, st.rotating, st.cn, st.sn, (double *)w.x, (double *)w.v, (uint32_t *)w.coinc,
@@ -390,6 +571,7 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
                 if (!st.last)
                     if (int rc = orbit_phase(P.omega, P.dt, P.step0 + k + 1, &st.cn, &st.sn)) return rc;
                 nb_orbit_sample *rec = due ? (nb_orbit_sample *)w.tracks + (size_t)r++ * mm : nullptr;
+                sc.step = P.step0 + k;
                 b.n_tiles = pl.n_tiles;
                 b.cj = pl.cj;
                 b.chunks = pl.chunks;
@@ -403,15 +585,30 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
                         NB_HIP_TRY(hipGetLastError());
                         ++launches;
                     }
-                    hipLaunchKernelGGL(orbit_step_kernel, finish_grid(b), dim3(kThreads), 0, sim.stream,
-                                       (const double *)w.slab, b.chunks, b.stride, b.p0, b.p1, st, f, (double *)w.x,
-                                       (double *)w.v, (uint32_t *)w.coinc, (float4 *)w.pts, rec);
+                    if (section)
+                        hipLaunchKernelGGL(orbit_section_step_kernel, finish_grid(b), dim3(kThreads), 0, sim.stream,
+                                           (const double *)w.slab, b.chunks, b.stride, b.p0, b.p1, st, f,
+                                           (double *)w.x, (double *)w.v, (uint32_t *)w.coinc, (float4 *)w.pts, rec,
+                                           sc);
+                    else
+                        hipLaunchKernelGGL(orbit_step_kernel, finish_grid(b), dim3(kThreads), 0, sim.stream,
+                                           (const double *)w.slab, b.chunks, b.stride, b.p0, b.p1, st, f,
+                                           (double *)w.x, (double *)w.v, (uint32_t *)w.coinc, (float4 *)w.pts, rec);
                     NB_HIP_TRY(hipGetLastError());
                 }
             }
             NB_HIP_TRY(hipMemcpyAsync(w.h_tracks, w.tracks, sizeof(nb_orbit_sample) * samples, hipMemcpyDeviceToHost,
                                       sim.stream));
             NB_HIP_TRY(hipMemcpyAsync(w.h_coinc, w.coinc, sizeof(uint32_t) * mm, hipMemcpyDeviceToHost, sim.stream));
+            if (section) {
+                if (slots)
+                    NB_HIP_TRY(hipMemcpyAsync(w.h_cross, w.cross, sizeof(nb_orbit_crossing) * slots,
+                                              hipMemcpyDeviceToHost, sim.stream));
+                NB_HIP_TRY(hipMemcpyAsync(w.h_counts, w.counts, sizeof(uint32_t) * mm, hipMemcpyDeviceToHost,
+                                          sim.stream));
+                NB_HIP_TRY(hipMemcpyAsync(w.h_summary, w.summary, sizeof(nb_orbit_summary) * mm,
+                                          hipMemcpyDeviceToHost, sim.stream));
+            }
             return NB_OK;
         }();
         if (rc != NB_OK) {
@@ -424,6 +621,22 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
     if (mm > 0) {
         std::memcpy(tracks, w.h_tracks, sizeof(nb_orbit_sample) * samples);
         if (coincident) std::memcpy(coincident, w.h_coinc, sizeof(uint32_t) * mm);
+    }
+    if (section) {
+        nb_orbit_section_stats ss{};
+        const uint32_t cap = section->params.max_crossings;
+        for (uint32_t i = 0; i < mm; ++i) {
+            const uint32_t c = w.h_counts[i];
+            ss.crossings += c;
+            ss.stored += std::min(c, cap);
+            ss.overflowed += c > cap;
+        }
+        if (mm > 0) {
+            if (slots) std::memcpy(section->crossings, w.h_cross, sizeof(nb_orbit_crossing) * slots);
+            if (section->counts) std::memcpy(section->counts, w.h_counts, sizeof(uint32_t) * mm);
+            if (section->summaries) std::memcpy(section->summaries, w.h_summary, sizeof(nb_orbit_summary) * mm);
+        }
+        if (section->stats) *section->stats = ss;
     }
     if (stats) {
         nb_orbit_stats s{};
@@ -438,6 +651,19 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, c
         *stats = s;
     }
     return NB_OK;
+}
+
+int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos, const double *vel,
+               size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
+    return orbits_run(sim, P, frame, pos, vel, m, tracks, coincident, stats, nullptr);
+}
+
+int sim_orbit_sections(SimBase &sim, const nb_orbit_params &P, const nb_orbit_section_params &sec,
+                       const OrbitPlan &frame, const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                       uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                       nb_orbit_summary *summaries, nb_orbit_section_stats *stats) {
+    const SectionCall call{sec, crossings, counts, summaries, stats};
+    return orbits_run(sim, P, frame, pos, vel, m, tracks, coincident, stats ? &stats->orbit : nullptr, &call);
 }
 
 }  // namespace nb

@@ -229,6 +229,76 @@ int orbits_check_e(const SimBase &s, const nb_orbit_params *p) {
     return NB_OK;
 }
 
+// nb_orbit_sections_sim: nb_orbits_sim's refusals, then the section's; the frame is formed for omega == 0 too
+int orbit_sections_check_args(const nb_orbit_params *p, const nb_orbit_section_params *sec, const double *pos,
+                              const double *vel, size_t m, const nb_orbit_sample *tracks,
+                              const nb_orbit_crossing *crossings, OrbitPlan *plan) {
+    if (int rc = orbits_check_args(p, pos, vel, m, tracks, plan)) return rc;
+    if (!sec) {
+        set_error("orbit_sections: null section params");
+        return NB_ERR_INVALID;
+    }
+    bool finite = true, zero = true;
+    for (int a = 0; a < 3; ++a) {
+        finite = finite && std::isfinite(sec->normal[a]);
+        zero = zero && sec->normal[a] == 0.0;
+    }
+    if (!finite || zero) {
+        set_error("orbit_sections: normal must be finite and not all zero");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(sec->offset)) {
+        set_error("orbit_sections: offset must be finite (got %g)", sec->offset);
+        return NB_ERR_INVALID;
+    }
+    if (sec->direction < -1 || sec->direction > 1) {
+        set_error("orbit_sections: direction must be -1, 0 or 1 (got %d)", (int)sec->direction);
+        return NB_ERR_INVALID;
+    }
+    if (sec->flags || sec->reserved) {
+        set_error("orbit_sections: unknown flag bits 0x%x or reserved %u != 0", sec->flags, sec->reserved);
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)m * sec->max_crossings > NB_ORBIT_SECTION_MAX_CROSSINGS) {
+        set_error("orbit_sections: %zu tracers of %u crossings are more than %u records", m, sec->max_crossings,
+                  NB_ORBIT_SECTION_MAX_CROSSINGS);
+        return NB_ERR_INVALID;
+    }
+    if (m > 0 && sec->max_crossings > 0 && !crossings) {
+        set_error("orbit_sections: null crossings with max_crossings = %u", sec->max_crossings);
+        return NB_ERR_INVALID;
+    }
+    if (!axis_frame(p->axis, plan->n, plan->e1, plan->e2)) {
+        set_error("orbit_sections: the section's frame needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+int orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out) {
+    if (!a || !b || !out) {
+        set_error("orbit_summary_merge: null %s", !a ? "a" : !b ? "b" : "out");
+        return NB_ERR_INVALID;
+    }
+    nb_orbit_summary r{};
+    r.r2_min = std::fmin(a->r2_min, b->r2_min);
+    r.r2_max = std::fmax(a->r2_max, b->r2_max);
+    r.R2_min = std::fmin(a->R2_min, b->R2_min);
+    r.R2_max = std::fmax(a->R2_max, b->R2_max);
+    r.h_max = std::fmax(a->h_max, b->h_max);
+    r.lz_min = std::fmin(a->lz_min, b->lz_min);
+    r.lz_max = std::fmax(a->lz_max, b->lz_max);
+    r.first_peri = a->first_peri != NB_ORBIT_NO_STEP ? a->first_peri : b->first_peri;
+    r.last_peri = b->last_peri != NB_ORBIT_NO_STEP ? b->last_peri : a->last_peri;
+    r.pericentres = a->pericentres + b->pericentres;
+    r.apocentres = a->apocentres + b->apocentres;
+    r.plane_ups = a->plane_ups + b->plane_ups;
+    r.winding_pattern = a->winding_pattern + b->winding_pattern;
+    r.winding_inertial = a->winding_inertial + b->winding_inertial;
+    *out = r;
+    return NB_OK;
+}
+
 // nb_field_rings / nb_field_ring_means / nb_tidal_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
 static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
                       uint32_t n_phi, double n[3], double e1[3], double e2[3]) {

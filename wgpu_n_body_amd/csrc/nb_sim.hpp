@@ -183,6 +183,16 @@ int sim_orbits(SimBase &sim, const nb_orbit_params &params, const OrbitPlan &pla
                size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats);
 uint32_t orbit_records(uint32_t steps, uint32_t every);
 int orbit_phase(double omega, double dt, uint64_t k, double *c, double *s);
+// ... nb_orbit_sections_sim (include/nbody.h "Orbit sections"): the same call whose step kernel also takes the
+// crossings and the summaries; orbit_sections_check_args runs orbits_check_args and forms the frame for omega == 0 too
+int orbit_sections_check_args(const nb_orbit_params *p, const nb_orbit_section_params *sec, const double *pos,
+                              const double *vel, size_t m, const nb_orbit_sample *tracks,
+                              const nb_orbit_crossing *crossings, OrbitPlan *plan);
+int sim_orbit_sections(SimBase &sim, const nb_orbit_params &params, const nb_orbit_section_params &sec,
+                       const OrbitPlan &plan, const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
+                       uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
+                       nb_orbit_summary *summaries, nb_orbit_section_stats *stats);
+int orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out);
 
 // nb_map.hip: nb_sim_map behind the handle; map_check_params also forms the frame and the cell sizes
 struct MapPlan {

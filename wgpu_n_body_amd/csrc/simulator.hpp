@@ -382,6 +382,63 @@ Orbits orbits(int (*call)(H *, const nb_orbit_params *, const double *, const do
 }
 }  // namespace detail
 
+// The surface of section and the summaries of an orbits() call (include/nbody.h "Orbit sections"): max_crossings
+// slots per tracer, tracer-major, of which min(counts, max_crossings) are written, and one summary per tracer
+struct OrbitSections {
+    Orbits orbits;
+    uint32_t max_crossings = 0;
+    std::vector<nb_orbit_crossing> crossings;
+    std::vector<uint32_t> counts;
+    std::vector<nb_orbit_summary> summaries;
+    nb_orbit_section_stats stats{};
+    nb_orbit_section_params section{};
+    uint32_t stored(size_t tracer) const { return std::min(counts[tracer], max_crossings); }
+    const nb_orbit_crossing &at(size_t tracer, uint32_t j) const { return crossings[tracer * max_crossings + j]; }
+};
+
+// the plane normal . xi = offset of the pattern frame, the crossings kept (+1 up, -1 down, 0 both) and the room
+inline nb_orbit_section_params orbit_section_params(const std::array<double, 3> &normal = {0.0, 1.0, 0.0},
+                                                    double offset = 0.0, int32_t direction = 1,
+                                                    uint32_t max_crossings = 256) {
+    nb_orbit_section_params s{};
+    for (int a = 0; a < 3; ++a) s.normal[a] = normal[(size_t)a];
+    s.offset = offset;
+    s.direction = direction;
+    s.max_crossings = max_crossings;
+    return s;
+}
+
+namespace detail {
+template <class H>
+OrbitSections orbit_sections(int (*call)(H *, const nb_orbit_params *, const nb_orbit_section_params *, const double *,
+                                         const double *, size_t, nb_orbit_sample *, uint32_t *, nb_orbit_crossing *,
+                                         uint32_t *, nb_orbit_summary *, nb_orbit_section_stats *),
+                             H *h, const nb_orbit_params &p, const nb_orbit_section_params &sec,
+                             const std::vector<double> &pos, const std::vector<double> &vel) {
+    if (pos.size() != vel.size() || pos.size() % 3)
+        throw Error(NB_ERR_INVALID, "orbit_sections: pos and vel are 3 doubles per tracer");
+    OrbitSections o;
+    o.section = sec;
+    o.max_crossings = sec.max_crossings;
+    Orbits &t = o.orbits;
+    t.params = p;
+    t.tracers = pos.size() / 3;
+    t.records = nb_orbit_records(p.steps, p.every);
+    // (the call refuses what it does not take, before it writes)
+    const bool big = t.tracers > NB_ORBIT_MAX_TRACERS || (uint64_t)t.records * t.tracers > NB_ORBIT_MAX_SAMPLES ||
+                     (uint64_t)t.tracers * sec.max_crossings > NB_ORBIT_SECTION_MAX_CROSSINGS;
+    t.tracks.resize(big ? 0 : (size_t)t.records * t.tracers);
+    t.coincident.resize(t.tracers);
+    o.crossings.resize(big ? 0 : t.tracers * sec.max_crossings);
+    o.counts.resize(t.tracers);
+    o.summaries.resize(t.tracers);
+    check(call(h, &p, &sec, pos.data(), vel.data(), t.tracers, t.tracks.data(), t.coincident.data(),
+               o.crossings.empty() ? nullptr : o.crossings.data(), o.counts.data(), o.summaries.data(), &o.stats));
+    t.stats = o.stats.orbit;
+    return o;
+}
+}  // namespace detail
+
 // A projected map (no reference counterpart): width * height counts, row 0 the smallest b, the planes
 // (1, or 6 with NB_MAP_VELOCITY: mass, m_ua, m_ub, m_w, m_w2, m_u2) plane-major, and what the call measured
 struct ProjectedMap {
@@ -1114,6 +1171,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto phase_map = nb_phase_map_sim;
     static constexpr auto tidal = nb_tidal_sim;
     static constexpr auto orbits = nb_orbits_sim;
+    static constexpr auto orbit_sections = nb_orbit_sections_sim;
     static constexpr auto local_kinematics = nb_local_kinematics_sim;
     static constexpr auto fof6 = nb_fof6_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
@@ -1137,6 +1195,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto phase_map = nb_phase_map_runner;
     static constexpr auto tidal = nb_tidal_runner;
     static constexpr auto orbits = nb_orbits_runner;
+    static constexpr auto orbit_sections = nb_orbit_sections_runner;
     static constexpr auto local_kinematics = nb_local_kinematics_runner;
     static constexpr auto fof6 = nb_fof6_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
@@ -1271,18 +1330,38 @@ class Passes {
     // direction of rotation there (p.axis and p.center are the rings')
     Orbits circular_orbits(const nb_orbit_params &p, const std::vector<double> &radii, uint32_t n_phi = 16,
                            double speed = 1.0) {
+        std::vector<double> pos, vel;
+        circular_launch(p, radii, n_phi, speed, pos, vel);
+        return orbits(p, pos, vel);
+    }
+    // orbits() whose step kernel also takes the crossings of the plane `sec` of the pattern frame and a summary per
+    // tracer (orbit_section_params); no launch is added
+    OrbitSections orbit_sections(const nb_orbit_params &p, const nb_orbit_section_params &sec,
+                                 const std::vector<double> &pos, const std::vector<double> &vel) {
+        return detail::orbit_sections(Abi::orbit_sections, h_, p, sec, pos, vel);
+    }
+    // ... launched as circular_orbits() launches
+    OrbitSections circular_orbit_sections(const nb_orbit_params &p, const nb_orbit_section_params &sec,
+                                          const std::vector<double> &radii, uint32_t n_phi = 16, double speed = 1.0) {
+        std::vector<double> pos, vel;
+        circular_launch(p, radii, n_phi, speed, pos, vel);
+        return orbit_sections(p, sec, pos, vel);
+    }
+    // the tracers of circular_orbits()
+    void circular_launch(const nb_orbit_params &p, const std::vector<double> &radii, uint32_t n_phi, double speed,
+                         std::vector<double> &pos, std::vector<double> &vel) {
         const std::array<double, 3> axis{p.axis[0], p.axis[1], p.axis[2]}, center{p.center[0], p.center[1], p.center[2]};
         const RingMeans cv = circular_velocity(radii, axis, center, n_phi);
         const std::vector<float> pts = field_rings(radii, axis, center, n_phi);
         double n[3], e1[3], e2[3];
         check(nb_map_frame(axis.data(), n, e1, e2));
-        std::vector<double> pos(3 * radii.size()), vel(3 * radii.size());
+        pos.assign(3 * radii.size(), 0.0);
+        vel.assign(3 * radii.size(), 0.0);
         for (size_t i = 0; i < radii.size(); ++i)
             for (size_t a = 0; a < 3; ++a) {
                 pos[3 * i + a] = (double)pts[3 * (i * n_phi) + a];
                 vel[3 * i + a] = (speed * cv.rings[i].v_c) * e2[a];
             }
-        return orbits(p, pos, vel);
     }
     // the current state drawn on the device (OnlineRenderer::render, online_renderer.rs:331-367)
     Frame render(const RenderParams &p, bool counts = false) {
