@@ -9,7 +9,10 @@ comparison is at the level of the method's own error; the exact statements teste
   * world = 1: the protocol is the single TreeSim, bit for bit;
   * pruning is decision-exact: exporting whole octrees instead of LETs changes no bit;
   * theta -> 0: all-pairs (oracle), to fp32 summation tolerance;
-  * the force error against all-pairs is that of the single tree."""
+  * the force error against all-pairs is that of the single tree.
+Against the method restated -- every rank's tree walked for every rank's bodies -- there IS an exact reference:
+tests/test_let_precision_gpu.py holds every rank's node moments, every body's force and the counters of one step to
+the binary64 tests/let_ref.py."""
 import ctypes as C
 import os
 

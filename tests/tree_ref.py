@@ -4,7 +4,8 @@ bodies at once, and the tolerance a binary64 prefix difference rounded once to b
 (tree, numbering, body order) is pinned bit for bit against the oracle elsewhere; nothing here rebuilds a tree.
 
 Used by tests/test_tree_ref.py (this reference against the oracle, on the CPU), tests/test_tree_precision_gpu.py
-(the kernels against this reference) and tools/tree_fuzz.py.
+(the kernels against this reference), tools/tree_fuzz.py and tests/let_ref.py (the multi-domain step: walk64 per pair
+of ranks).
 
 Measured on the CPU over CASES (tests/test_tree_ref.py prints the table with `-s`): the oracle's fp32 walk -- ~6
 correctly rounded operations per term, a sequential sum -- against walk64 of the same tree, in units of
@@ -174,15 +175,21 @@ def check_moments(tree, src):
 
 # ---- walk -------------------------------------------------------------------------------------------------------
 
-def walk64(tree, root_width, order, x_new, theta, g, e, dt, delta=FLAG_DELTA, bodies=None, chunk=2048):
+def walk64(tree, root_width, order, x_new, theta, g, e, dt, delta=FLAG_DELTA, bodies=None, chunk=2048,
+           foreign=False, lone=False, size_scale=None):
     """The walk of tree.wgsl:41-90 (intended semantics: oracle flags = INTENDED) for all bodies at once, in
     binary64 from the binary32 cog and mass of the tree it is given; g, e, dt, theta widened from their fp32 values.
     x_new: the bodies' drifted positions in SORTED order (float32[n, 3]); order[k]: source index of sorted body k;
     bodies: the sorted positions to walk for (default: all).
+    For the multi-domain step (tests/let_ref.py) -- the defaults are the single tree's walk:
+      foreign: the walkers are not the tree's bodies (another rank's tree): no leaf is anybody's own, whatever
+               children[0] it carries -- an index into ANOTHER set of bodies;
+      lone:    walk also where there are fewer than two walkers (the shortcut below is the single tree's);
+      size_scale[node]: factor on a cell's size in its acceptance test (tests of the tests: a mutated walk).
     Returns dict(acc[k, 3], sum_abs[k] -- the sum of the terms' Euclidean norms --, flagged[k] -- some internal cell
     had |size / r - theta| <= delta theta --, visits, accepts), rows in the order of `bodies`."""
     theta, g, e, dt = (float(np.float32(v)) for v in (theta, g, e, dt))
-    n = len(order)
+    n = len(x_new) if foreign else len(order)
     sel = np.arange(n) if bodies is None else np.asarray(bodies, dtype=np.int64)
     cog = tree["cog"].astype(np.float64)
     mass = tree["mass"].astype(np.float64)
@@ -191,14 +198,15 @@ def walk64(tree, root_width, order, x_new, theta, g, e, dt, delta=FLAG_DELTA, bo
     leaf[0] = False
     self_src = np.where(leaf, children[:, 0], -1)
     x_all = np.asarray(x_new, dtype=np.float32).astype(np.float64)
-    order = np.asarray(order, dtype=np.int64)
+    order = np.full(n, -2, dtype=np.int64) if foreign else np.asarray(order, dtype=np.int64)
+    scale = None if size_scale is None else np.asarray(size_scale, dtype=np.float64)
     acc = np.zeros((len(sel), 3))
     sum_abs = np.zeros(len(sel))
     flagged = np.zeros(len(sel), dtype=bool)
     visits = accepts = 0
     # (a lone body feels nothing and nothing is walked for it: the oracle and the product alike -- the reference's
     # tree of one body is ill-formed)
-    for c0 in range(0, len(sel) if n >= 2 else 0, chunk):
+    for c0 in range(0, len(sel) if n >= 2 or lone else 0, chunk):
         who = sel[c0:c0 + chunk]
         k = len(who)
         x, me = x_all[who], order[who]
@@ -213,7 +221,7 @@ def walk64(tree, root_width, order, x_new, theta, g, e, dt, delta=FLAG_DELTA, bo
             d = cog[node] - x[body]
             with np.errstate(invalid="ignore", divide="ignore"):
                 r = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-                ratio = size / r
+                ratio = (size if scale is None else size * scale[node]) / r
                 is_leaf = leaf[node]
                 take = is_leaf | (ratio < theta)  # a comparison with NaN is false: the cell is opened
                 close = ~is_leaf & (np.abs(ratio - theta) <= delta * theta)
