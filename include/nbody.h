@@ -839,6 +839,106 @@ int nb_orbit_sections_sim(nb_sim *sim, const nb_orbit_params *params, const nb_o
 int nb_orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out);
 
 /* ------------------------------------------------------------------------- */
+/* Orbit stability -- deviation vectors carried by the tangent map of the     */
+/* orbit's step, renormalised by exact powers of two (no reference counterpart) */
+/* ------------------------------------------------------------------------- */
+/* nb_orbit_stability_sim is nb_orbits_sim -- the same tracers, states, records and bits of the tracks -- whose pair
+ * kernel also sums the tidal tensor at every evaluation point and whose step kernel moves D deviation vectors per
+ * tracer, delta = (dx, dv), by the exact derivative of the step.  From their growth come the finite-time Lyapunov
+ * exponent and the alignment indices SALI / GALI_2 (nb_orbit_stability_derive): regular or chaotic, without
+ * differencing two orbits, whose separation would be below the fp32 rounding of the evaluation points.  The rule,
+ * which DESIGN.md 6w derives.  Everything outside the sums is binary64 +, -, x, each rounded once, no contraction;
+ * the scalings are ldexp; there is no division, square root or logarithm on the device.
+ * (e1, e2, n), c, h = dt / 2 and (C_k, S_k) are those of "Orbits".  NB_ORBIT_ENERGY is refused: the tracks are
+ * nb_orbits_sim's, which gives the energies.
+ * Evaluation k of a tracer, at the fp32 point p of "Orbits":
+ *   A_snap       as "Orbits" (flags NB_FIELD_ACCEL): nb_sim_field's acc at p bit for bit, x accel_scale
+ *   tensor       nb_tidal_sim's at p, bit for bit, for the m points of the call's tracers: the same seven sums
+ *                (S_xx, S_yy, S_zz, S_xy, S_xz, S_yz, W), points per lane, plan and chunk order, finished as that
+ *                call finishes them -- g (S_aa - W) on the diagonal, g S_ab off it, NaN at a non-finite point
+ *   T_snap = accel_scale * tensor, component by component (symmetric: T_ba = T_ab)
+ * Kick of a deviation (dx, dv) at evaluation k:
+ *   omega == 0   q = dx
+ *   otherwise    a = (dx_x e1x + dx_y e1y) + dx_z e1z,  b and l likewise with e2 and n   (no centre)
+ *                a' = a C_k + b S_k,  b' = b C_k - a S_k
+ *                q_i = (a' e1_i + b' e2_i) + l n_i                                       (not rounded to fp32)
+ *   t_a = (T_a0 q_0 + T_a1 q_1) + T_a2 q_2
+ *   omega == 0   z = t;  otherwise z = t turned back by the three lines that turn A_snap back in "Orbits"
+ *   kappa_i = z_i h
+ * One evaluation, for every vector, in this order -- the lines the step runs for v and x:
+ *   1. k > 0:      dv <- dv + kappa
+ *   2. k >= 0:     mu = the largest |component| of the six.  If all six are finite and mu != 0:
+ *                    E = frexp-exponent(mu) - 1       (2^E <= mu < 2^(E+1))
+ *                    if log2 + E > peak_log2:  peak_log2 = log2 + E, peak_step = step0 + k
+ *                    if k > 0 and |E| >= renorm_log2:  all six components AND kappa are multiplied by 2^-E (ldexp),
+ *                      log2 <- log2 + E, renorms <- renorms + 1
+ *                  kappa is scaled too because line 4 adds it again: only then is a renormalised run the
+ *                  unrenormalised run times 2^log2 in every bit (as long as neither underflows or overflows).
+ *   3. record, if state k is recorded: the six components and log2
+ *   4. k < steps:  dv <- dv + kappa
+ *   5. k < steps:  dx <- dx + dv dt
+ * The vector a record stands for is d * 2^log2.  log2 starts at the caller's value; peak_log2 starts at INT64_MIN and
+ * peak_step at NB_ORBIT_NO_STEP, renorms at 0, in every call.  A zero or non-finite vector is left alone.  The
+ * vectors of a tracer that starts non-finite are NaN in every record; a tracer whose point becomes non-finite has
+ * NaN vectors from there on (its T_snap is NaN); the other tracers keep their bits.  T_snap is nb_tidal_sim's in its
+ * failures too: a body within a few 1e-9 of the point without coinciding with it overflows the tensor's fp32 pair
+ * term there and here.
+ * Records: devs[(r * m + i) * D + j] for record r (those of "Orbits"), tracer i, vector j; growth[i * D + j].
+ * Consequences: those of "Orbits"; tracks and coincident are nb_orbits_sim's for the same arguments bit for bit; a
+ * run of 2 S steps equals a run of S steps followed by one of S steps from the first run's last records (tracks and
+ * devs, log2 included) with step0 + S, whenever S is a multiple of `every`; the pair launches are as many as
+ * nb_orbits_sim's, each of this unit's pair kernel in the place of the field's. */
+#define NB_ORBIT_MAX_DEVIATIONS 6u
+#define NB_ORBIT_MAX_RENORM_LOG2 512u
+
+typedef struct nb_orbit_stability_params {
+    uint32_t deviations;  /* D, 1 .. NB_ORBIT_MAX_DEVIATIONS */
+    uint32_t renorm_log2; /* 1 .. NB_ORBIT_MAX_RENORM_LOG2 */
+    uint32_t reserved;    /* 0 */
+} nb_orbit_stability_params;
+
+typedef struct nb_orbit_deviation { /* 56 bytes */
+    double d[6];  /* dx, dv */
+    int64_t log2; /* the vector is d * 2^log2 */
+} nb_orbit_deviation;
+
+typedef struct nb_orbit_growth { /* 24 bytes */
+    int64_t peak_log2;  /* the largest log2 + E over the states 0 .. steps; INT64_MIN for none */
+    uint64_t peak_step; /* step0 + k of the first state that reached it; NB_ORBIT_NO_STEP for none */
+    uint32_t renorms, reserved;
+} nb_orbit_growth;
+
+typedef struct nb_orbit_stability_stats {
+    nb_orbit_stats orbit;
+    uint64_t renorms; /* the sum over tracers and vectors */
+    uint32_t deviations, renorm_log2;
+} nb_orbit_stability_stats;
+
+/* nb_orbits_sim with D deviation vectors per tracer from dev0 ([m * D]): tracks and coincident are that call's, devs
+ * is [records * m * D], growth [m * D].  coincident, growth and stats may be null.  NB_ERR_INVALID for everything
+ * nb_orbits_sim refuses, NB_ORBIT_ENERGY among the flags, null stability params, deviations outside
+ * 1 .. NB_ORBIT_MAX_DEVIATIONS, renorm_log2 outside 1 .. NB_ORBIT_MAX_RENORM_LOG2, reserved != 0, null dev0 or devs with
+ * m > 0, or records * m * D > NB_ORBIT_MAX_SAMPLES -- all checked before the handle is looked at; NB_ERR_UNSUPPORTED
+ * as nb_orbits_sim. */
+int nb_orbit_stability_sim(nb_sim *sim, const nb_orbit_params *params, const nb_orbit_stability_params *stability,
+                           const double *pos, const double *vel, size_t m, const nb_orbit_deviation *dev0,
+                           nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_deviation *devs,
+                           nb_orbit_growth *growth, nb_orbit_stability_stats *stats);
+/* Host only, a pure function of its arguments: what the records of a call with (dt, steps, every) say, for record r
+ * of state k, tracer i and vector j, against the call's dev0.  |.| is the Euclidean norm of the six components in
+ * the state's own units (positions and velocities are not weighted against each other), formed as
+ * 2^E sqrt(sum (d_i 2^-E)^2) with E the exponent of the largest component, so that it cannot overflow:
+ *   log_growth[(r m + i) D + j] = (log2 - log2_0) ln 2 + ln|d| - ln|d_0|          (ln of |delta_k| / |delta_0|)
+ *   lyapunov[(r m + i) D + j]   = log_growth / ((double)k * dt), NaN at k = 0
+ *   sali[r m + i]  = min(|u1 + u2|, |u1 - u2|),  gali2[r m + i] = |u1 ^ u2| = sqrt(sum_{a<b} (u1_a u2_b - u1_b u2_a)^2)
+ *                    for the unit vectors u1, u2 of vectors 0 and 1; NaN with D < 2
+ * A zero or non-finite vector gives NaN.  Any of the four outputs may be null.  NB_ERR_INVALID for null dev0 or devs
+ * with m > 0, D outside 1 .. NB_ORBIT_MAX_DEVIATIONS, steps = 0, every = 0 or a dt that is not finite or 0. */
+int nb_orbit_stability_derive(double dt, uint32_t steps, uint32_t every, size_t m, uint32_t deviations,
+                              const nb_orbit_deviation *dev0, const nb_orbit_deviation *devs, double *log_growth,
+                              double *lyapunov, double *sali, double *gali2);
+
+/* ------------------------------------------------------------------------- */
 /* Projected maps -- per-cell mass and velocity moments on a 2-D grid (no     */
 /* reference counterpart: structure in two dimensions, without symmetry)      */
 /* ------------------------------------------------------------------------- */
@@ -2457,6 +2557,12 @@ int nb_orbit_sections_runner(nb_runner *runner, const nb_orbit_params *params, c
                              const double *pos, const double *vel, size_t m, nb_orbit_sample *tracks,
                              uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
                              nb_orbit_summary *summaries, nb_orbit_section_stats *stats);
+/* nb_orbit_stability_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_orbit_stability_runner(nb_runner *runner, const nb_orbit_params *params,
+                              const nb_orbit_stability_params *stability, const double *pos, const double *vel,
+                              size_t m, const nb_orbit_deviation *dev0, nb_orbit_sample *tracks, uint32_t *coincident,
+                              nb_orbit_deviation *devs, nb_orbit_growth *growth, nb_orbit_stability_stats *stats);
 /* nb_local_kinematics_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a
  * several-GPU runner. */
 int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, double *moments, double *grads,

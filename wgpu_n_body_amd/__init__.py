@@ -38,7 +38,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "OfflineHeadless", "inits", "PARTICLE_DTYPE", "OCTANT_DTYPE", "NBodyError",
            "PARTICLES_PER_GROUP", "device_count", "version", "shard_bodies_per_rank",
            "shard_padded_bodies", "naive_variants", "Diagnostics", "RadialProfile", "radial_edges",
-           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "OrbitSections", "OrbitSectionStats", "ProjectedMap", "map_frame", "map_edges",
+           "Field", "RingMeans", "field_rings", "TidalField", "DiscFrequencies", "Orbits", "OrbitStats", "OrbitSections", "OrbitSectionStats", "OrbitStability", "OrbitStabilityStats", "ProjectedMap", "map_frame", "map_edges",
            "PhaseMap", "PhaseStats", "phase_quantity", "phase_quantities", "phase_edges",
            "FofGroups", "FofStats", "FOF_NONE", "PhaseSpaceGroups",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
@@ -838,6 +838,137 @@ def _orbit_sections(call, handle, pos, vel, dt, steps, normal, offset, direction
     return OrbitSections(orbits, count, stored, rec["xi"].copy(), rec["eta"].copy(), rec["time"].copy(),
                          rec["step"].copy(), valid, summary,
                          OrbitSectionStats(ostats, int(st.crossings), int(st.stored), int(st.overflowed)))
+
+
+@dataclass(frozen=True)
+class OrbitStabilityStats:
+    """nb_orbit_stability_stats: what an orbit_stability() call measured."""
+    orbit: OrbitStats
+    renorms: int        # renormalisations of all vectors of all tracers
+    deviations: int     # D
+    renorm_log2: int
+
+
+@dataclass(frozen=True)
+class OrbitStability:
+    """nb_orbit_deviation[R][M][D] + nb_orbit_growth[M][D] (include/nbody.h "Orbit stability"; no reference
+    counterpart): D deviation vectors per tracer carried along the orbits by the tangent map of the step.  The vector
+    of record r is dev[r] * 2^log2[r], dev = (dx, dv).  Norms are Euclidean over the six components in the state's
+    own units."""
+    orbits: Orbits           # the recorded states of the same call: orbits()'s, bit for bit
+    dev: np.ndarray          # (R, M, D, 6) float64
+    log2: np.ndarray         # (R, M, D) int64
+    growth: np.ndarray       # (M, D) ORBIT_GROWTH_DTYPE: peak_log2, peak_step, renorms
+    dev0: np.ndarray         # (M, D, 6) float64: the vectors the call began with ...
+    log2_0: np.ndarray       # (M, D) int64: ... and their exponents
+    steps: int
+    every: int
+    stats: OrbitStabilityStats
+
+    def _derive(self):
+        r, m, d = self.log2.shape
+        dev0 = np.zeros((m, d), dtype=_lib.ORBIT_DEVIATION_DTYPE)
+        dev0["d"], dev0["log2"] = self.dev0, self.log2_0
+        devs = np.zeros((r, m, d), dtype=_lib.ORBIT_DEVIATION_DTYPE)
+        devs["d"], devs["log2"] = self.dev, self.log2
+        lg, ly = np.empty((r, m, d)), np.empty((r, m, d))
+        sa, ga = np.empty((r, m)), np.empty((r, m))
+        check(_lib.lib().nb_orbit_stability_derive(self.orbits.dt, self.steps, self.every, m, d, dev0.ctypes.data,
+                                                   devs.ctypes.data, lg.ctypes.data, ly.ctypes.data, sa.ctypes.data,
+                                                   ga.ctypes.data))
+        return lg, ly, sa, ga
+
+    def log_growth(self) -> np.ndarray:
+        """(R, M, D): ln(|delta_k| / |delta_0|) of every record (nb_orbit_stability_derive)."""
+        return self._derive()[0]
+
+    def lyapunov_curve(self) -> np.ndarray:
+        """(R, M, D): the finite-time exponent log_growth / (k dt) of every record; NaN at k = 0."""
+        return self._derive()[1]
+
+    def lyapunov(self) -> np.ndarray:
+        """(M, D): the exponent at the last record."""
+        return self._derive()[1][-1]
+
+    def sali(self) -> np.ndarray:
+        """(R, M): min(|u1 + u2|, |u1 - u2|) of the unit vectors of vectors 0 and 1; NaN with D < 2."""
+        return self._derive()[2]
+
+    def gali2(self) -> np.ndarray:
+        """(R, M): |u1 ^ u2| of the same two."""
+        return self._derive()[3]
+
+    def chaotic(self, sali_below: float = 1e-8) -> np.ndarray:
+        """(M,) bool: the last record's SALI is below `sali_below` (a NaN is not)."""
+        with np.errstate(invalid="ignore"):
+            return self.sali()[-1] < float(sali_below)
+
+    def final(self):
+        """(pos, vel, dev, log2, step): the last record -- what a continuing call takes as pos, vel, deviations,
+        log2_0 and step0.  The continuation is exact when this call's `steps` is a multiple of its `every`."""
+        pos, vel, step = self.orbits.final()
+        return pos, vel, self.dev[-1].copy(), self.log2[-1].copy(), step
+
+
+def _default_deviations(count: int) -> np.ndarray:
+    """(count, 6): orthonormal vectors from numpy.random.default_rng(0) (QR of a 6 x 6 normal matrix)."""
+    q, _ = np.linalg.qr(np.random.default_rng(0).standard_normal((6, 6)))
+    return np.ascontiguousarray(q.T[:count])
+
+
+def _orbit_stability(call, handle, pos, vel, dt, steps, deviations, renorm_log2, every, log2_0, omega, axis, center,
+                     accel_scale, step0) -> OrbitStability:
+    x = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    v = np.ascontiguousarray(vel, dtype=np.float64).reshape(-1, 3)
+    if x.shape != v.shape:
+        raise ValueError(f"orbit_stability: pos {x.shape} and vel {v.shape} differ")
+    m = x.shape[0]
+    every = steps if every is None else every
+    if np.ndim(deviations) == 0:
+        d = int(deviations)
+        if not 0 <= d <= 0xFFFFFFFF:
+            raise ValueError(f"orbit_stability: deviations = {deviations} is not a 32-bit count")
+        vec = np.broadcast_to(_default_deviations(min(d, 6)), (m, min(d, 6), 6))
+    else:
+        vec = np.asarray(deviations, dtype=np.float64)
+        if vec.ndim != 3 or vec.shape[0] != m or vec.shape[2] != 6:
+            raise ValueError(f"orbit_stability: deviations {vec.shape} are not ({m}, D, 6)")
+        d = vec.shape[1]
+    for name, val in (("steps", steps), ("every", every), ("renorm_log2", renorm_log2)):
+        if not 0 <= int(val) <= 0xFFFFFFFF:
+            raise ValueError(f"orbit_stability: {name} = {val} is not a 32-bit count")
+    p = _lib.nb_orbit_params()
+    p.dt, p.step0, p.steps, p.every = float(dt), int(step0), int(steps), int(every)
+    p.flags, p.reserved = 0, 0
+    p.accel_scale, p.omega = float(accel_scale), float(omega)
+    for k in range(3):
+        p.axis[k], p.center[k] = float(axis[k]), float(center[k])
+    sp = _lib.nb_orbit_stability_params(d, int(renorm_log2), 0)
+    rows = vec.shape[1]  # (d itself when the call takes it)
+    dev0 = np.zeros((m, rows), dtype=_lib.ORBIT_DEVIATION_DTYPE)
+    dev0["d"] = vec
+    dev0["log2"] = 0 if log2_0 is None else np.broadcast_to(np.asarray(log2_0, dtype=np.int64), (m, rows))
+    records = int(_lib.lib().nb_orbit_records(p.steps, p.every))
+    # (the call refuses what it does not take, before it reads or writes)
+    big = (m > _lib.NB_ORBIT_MAX_TRACERS or rows != d or records * m * max(d, 1) > _lib.NB_ORBIT_MAX_SAMPLES)
+    tracks = np.zeros((0 if big else records, m), dtype=_lib.ORBIT_SAMPLE_DTYPE)
+    devs = np.zeros((0 if big else records, m, rows), dtype=_lib.ORBIT_DEVIATION_DTYPE)
+    growth = np.zeros((m, rows), dtype=_lib.ORBIT_GROWTH_DTYPE)
+    coincident = np.zeros(m, dtype=np.uint32)
+    st = _lib.nb_orbit_stability_stats()
+    check(call(handle, C.byref(p), C.byref(sp), x.ctypes.data, v.ctypes.data, m, dev0.ctypes.data, tracks.ctypes.data,
+               coincident.ctypes.data, devs.ctypes.data, growth.ctypes.data, C.byref(st)))
+    ks = np.array([k for k in range(p.steps + 1) if k % p.every == 0 or k == p.steps], dtype=np.uint64)
+    step = ks + np.uint64(p.step0)
+    so = st.orbit
+    ostats = OrbitStats(int(so.step_num), int(so.n), int(so.nonfinite), int(so.tracers), int(so.nonfinite_tracers),
+                        int(so.records), int(so.pair_launches), int(so.flags))
+    orbits = Orbits(tracks["pos"].copy(), tracks["vel"].copy(), tracks["potential"].copy(), tracks["energy"].copy(),
+                    step, step.astype(np.float64) * p.dt, coincident, ostats, float(p.dt), float(p.omega),
+                    np.array(list(p.axis)), np.array(list(p.center)))
+    return OrbitStability(orbits, devs["d"].copy(), devs["log2"].copy(), growth, dev0["d"].copy(), dev0["log2"].copy(),
+                          int(p.steps), int(p.every),
+                          OrbitStabilityStats(ostats, int(st.renorms), int(st.deviations), int(st.renorm_log2)))
 
 
 def map_frame(axis):
@@ -2639,6 +2770,23 @@ class _Passes:
         return _orbit_sections(getattr(_lib.lib(), "nb_orbit_sections_" + suffix), self._h, pos, vel, dt, steps,
                                normal, offset, direction, max_crossings, every, energy, omega, axis, center,
                                self._accel_scale(coupling), step0)
+
+    def orbit_stability(self, pos, vel, *, dt: float, steps: int, deviations=2, renorm_log2: int = 32, every=None,
+                        log2_0=None, omega: float = 0.0, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0),
+                        coupling="field", step0: int = 0) -> OrbitStability:
+        """orbits() that also carries deviation vectors along every orbit by the tangent map of its step
+        (nb_orbit_stability_sim): one pair kernel sums the acceleration and the tidal tensor at each evaluation point,
+        and the step kernel moves the vectors, renormalising each by an exact power of two whenever its largest
+        component leaves [2^-renorm_log2, 2^renorm_log2).  deviations: a count D (1..6) of orthonormal vectors from
+        numpy.random.default_rng(0), the same for every tracer, or an (M, D, 6) array of (dx, dv); log2_0: their
+        starting exponents (default 0).  every=None records the two end states only.  OrbitStability gives the
+        finite-time Lyapunov exponents, SALI and GALI_2; `.orbits` is orbits()'s result for the same arguments, bit for
+        bit; final() continues a run exactly.  The other arguments are orbits()'s; the energy is not taken.  A
+        several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _orbit_stability(getattr(_lib.lib(), "nb_orbit_stability_" + suffix), self._h, pos, vel, dt, steps,
+                                deviations, renorm_log2, every, log2_0, omega, axis, center,
+                                self._accel_scale(coupling), step0)
 
     def jacobi_launch(self, energy: float, a, *, omega: float, axis=(0.0, 1.0, 0.0), center=(0.0, 0.0, 0.0),
                       coupling="field"):

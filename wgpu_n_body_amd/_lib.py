@@ -146,6 +146,24 @@ class nb_orbit_section_stats(C.Structure):
                 ("overflowed", C.c_uint64)]
 
 
+class nb_orbit_stability_params(C.Structure):
+    _fields_ = [("deviations", C.c_uint32), ("renorm_log2", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class nb_orbit_deviation(C.Structure):
+    _fields_ = [("d", C.c_double * 6), ("log2", C.c_int64)]
+
+
+class nb_orbit_growth(C.Structure):
+    _fields_ = [("peak_log2", C.c_int64), ("peak_step", C.c_uint64), ("renorms", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class nb_orbit_stability_stats(C.Structure):
+    _fields_ = [("orbit", nb_orbit_stats), ("renorms", C.c_uint64), ("deviations", C.c_uint32),
+                ("renorm_log2", C.c_uint32)]
+
+
 class nb_map_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -384,6 +402,10 @@ ORBIT_SUMMARY_DTYPE = np.dtype([("r2_min", "<f8"), ("r2_max", "<f8"), ("R2_min",
                                 ("plane_ups", "<u4"), ("winding_pattern", "<i4"), ("winding_inertial", "<i4"),
                                 ("reserved", "<u4")])
 
+# nb_orbit_deviation[] and nb_orbit_growth[] as numpy record arrays
+ORBIT_DEVIATION_DTYPE = np.dtype([("d", "<f8", (6,)), ("log2", "<i8")])
+ORBIT_GROWTH_DTYPE = np.dtype([("peak_log2", "<i8"), ("peak_step", "<u8"), ("renorms", "<u4"), ("reserved", "<u4")])
+
 # nb_halo_head[] as a numpy record array
 HALO_HEAD_DTYPE = np.dtype([("inside_count", "<u4"), ("flags", "<u4"), ("inside_mass", "<f8"),
                             ("center", "<f8", (3,)), ("velocity", "<f8", (3,))])
@@ -429,6 +451,9 @@ assert C.sizeof(nb_orbit_sample) == 64 == ORBIT_SAMPLE_DTYPE.itemsize
 assert C.sizeof(nb_orbit_section_params) == 48 and C.sizeof(nb_orbit_section_stats) == 80
 assert C.sizeof(nb_orbit_crossing) == 64 == ORBIT_CROSSING_DTYPE.itemsize
 assert C.sizeof(nb_orbit_summary) == 96 == ORBIT_SUMMARY_DTYPE.itemsize
+assert C.sizeof(nb_orbit_stability_params) == 12 and C.sizeof(nb_orbit_stability_stats) == 72
+assert C.sizeof(nb_orbit_deviation) == 56 == ORBIT_DEVIATION_DTYPE.itemsize
+assert C.sizeof(nb_orbit_growth) == 24 == ORBIT_GROWTH_DTYPE.itemsize
 assert C.sizeof(nb_map_params) == 136 and C.sizeof(nb_map_stats) == 200
 assert C.sizeof(nb_phase_params) == 136 and C.sizeof(nb_phase_stats) == 224
 assert C.sizeof(nb_fof_params) == 24 and C.sizeof(nb_fof_stats) == 80
@@ -464,6 +489,7 @@ NB_TIDAL_K = 33
 NB_ORBIT_ENERGY = 1
 NB_ORBIT_SECTION_MAX_CROSSINGS, NB_ORBIT_NO_STEP = 1 << 22, (1 << 64) - 1
 NB_ORBIT_MAX_TRACERS, NB_ORBIT_MAX_STEPS, NB_ORBIT_MAX_SAMPLES, NB_ORBIT_MAX_PAIRS_LOG2 = 1 << 20, 1 << 20, 1 << 22, 44
+NB_ORBIT_MAX_DEVIATIONS, NB_ORBIT_MAX_RENORM_LOG2 = 6, 512
 NB_MAP_MAX_SIDE, NB_MAP_MAX_CELLS = 4096, 1 << 22
 NB_MAP_CENTER_COM, NB_MAP_VELOCITY = 1, 2
 NB_PHASE_CENTER_COM, NB_PHASE_WEIGHT, NB_PHASE_ANY_STEP = 1, 2, 0xFFFFFFFFFFFFFFFF
@@ -504,6 +530,7 @@ ABI_SYMBOLS = [
     "nb_tidal_sim", "nb_tidal_runner", "nb_tidal_ring_means",
     "nb_orbits_sim", "nb_orbits_runner", "nb_orbit_records", "nb_orbit_phase",
     "nb_orbit_sections_sim", "nb_orbit_sections_runner", "nb_orbit_summary_merge",
+    "nb_orbit_stability_sim", "nb_orbit_stability_runner", "nb_orbit_stability_derive",
     "nb_sim_map", "nb_runner_map", "nb_map_frame", "nb_map_edges",
     "nb_phase_map_sim", "nb_phase_map_runner", "nb_phase_quantity", "nb_phase_quantity_name",
     "nb_sim_fof", "nb_runner_fof",
@@ -630,6 +657,12 @@ def lib() -> C.CDLL:
     for suffix in ("sim", "runner"):
         getattr(L, "nb_orbit_sections_" + suffix).argtypes = orbit_sections
     L.nb_orbit_summary_merge.argtypes = [vp, vp, vp]
+    # ... and their stability (include/nbody.h "Orbit stability")
+    orbit_stability = [vp, P(nb_orbit_params), P(nb_orbit_stability_params), vp, vp, sz, vp, vp, vp, vp, vp,
+                       P(nb_orbit_stability_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_orbit_stability_" + suffix).argtypes = orbit_stability
+    L.nb_orbit_stability_derive.argtypes = [C.c_double, C.c_uint32, C.c_uint32, sz, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.nb_orbit_records.argtypes = [C.c_uint32, C.c_uint32]
     L.nb_orbit_records.restype = C.c_uint32
     L.nb_orbit_phase.argtypes = [C.c_double, C.c_double, u64, P(C.c_double), P(C.c_double)]

@@ -64,6 +64,9 @@ SOURCES = [
     # the pair arithmetic is specified operation by operation, and the bound counts its roundings: no
     # FMA contraction
     ("nb_tidal.hip", ["-ffp-contract=off"]),
+    # the pair arithmetic is nb_tidal.hip's beside nb_field.hip's explicit fmas, and the deviations' step is specified
+    # operation by operation: no FMA contraction
+    ("nb_stability.hip", ["-ffp-contract=off"]),
     # the C surface, the simulator objects behind it, and what the analysis passes do without a device
     ("nb_abi.cpp", []),
     ("nb_simbase.cpp", []),

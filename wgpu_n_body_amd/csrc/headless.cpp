@@ -16,6 +16,9 @@
 //             --sections-steps S [--sections-omega W] [--sections-speed F] [--sections-axis X,Y,Z]
 //             [--sections-center X,Y,Z] [--sections-normal A,B,L] [--sections-offset D] [--sections-direction -1|0|1]
 //             [--sections-max K]]
+//            [--stability DIR [--stability-at K] --stability-range RMIN,RMAX [--stability-bins B] --stability-dt DT
+//             --stability-steps S [--stability-omega W] [--stability-speed F] [--stability-axis X,Y,Z]
+//             [--stability-center X,Y,Z]]
 //            [--maps DIR [--map-every K] --map-size WxH --map-extent X0,X1,Y0,Y1 [--map-axis X,Y,Z]
 //             [--map-center com|X,Y,Z] [--map-depth LO,HI]]
 //            [--smaps DIR [--smap-every K] --smap-size WxH --smap-extent X0,X1,Y0,Y1 [--smap-axis X,Y,Z]
@@ -81,6 +84,12 @@
 // (B, K, 8) -- xi, eta, time and the step as a double, zero where no crossing is stored -- and
 // DIR/sections_<step>_counts.npy: <f8, shape (B,), all crossings of each tracer; and one line "sections <step>
 // <tracers> <crossings> <stored> <overflowed> <pair_launches>".  The time it takes is not part of any "Step Duration".
+// --stability DIR measures the stability (nb_orbit_stability_runner) of the orbits of the state after step K
+// (--stability-at, default 0), the tracers launched as --orbits launches them (--stability-range, -bins, -speed, -axis,
+// -center, -dt, -steps, -omega), each with two deviation vectors: the unit dx along its radius in the plane of its
+// ring, and the unit dx along the axis.  Written as DIR/stability_<step, 6 digits>.npy: <f8, shape (B, 6) -- the
+// finite-time Lyapunov exponents of the two vectors, SALI and GALI_2 at the last state, and the peak log2 of the first
+// vector with the step it was reached at -- and one line "stability <step> <tracers> <renorms> <pair_launches>".
 //
 // --maps DIR writes the projected map (nb_runner_map) of step 0 and of every K-th step (--map-every,
 // default 1) as DIR/map_<step, 6 digits>.npy: NumPy format 1.0, <f8, shape (7, H, W) -- the counts as
@@ -436,6 +445,58 @@ static bool write_sections(nbody::OfflineHeadless<Sim> &runner, const SectionsOp
     if (!write_f8(so.launch.dir + name, shape, counts)) return false;
     std::printf("sections %llu %zu %llu %llu %llu %u\n", step, m, (unsigned long long)o.stats.crossings,
                 (unsigned long long)o.stats.stored, (unsigned long long)o.stats.overflowed,
+                o.stats.orbit.pair_launches);
+    return true;
+}
+
+// --stability: --orbits' tracers with two deviation vectors each -- the unit dx along the tracer's radius in the
+// plane of its ring, and the unit dx along the axis -- and what nb_orbit_stability_derive reads at the last state
+template <class Sim>
+static bool write_stability(nbody::OfflineHeadless<Sim> &runner, const OrbitsOptions &oo) {
+    std::vector<double> radii(oo.bins);
+    for (uint32_t i = 0; i < oo.bins; ++i)
+        radii[i] = oo.bins > 1 ? oo.rmin + (oo.rmax - oo.rmin) * (double)i / (double)(oo.bins - 1) : oo.rmin;
+    const nb_orbit_params p = nbody::orbit_params(oo.dt, oo.steps, oo.steps, false, oo.omega, oo.axis, oo.center);
+    std::vector<double> pos, vel;
+    runner.circular_launch(p, radii, 16, oo.speed, pos, vel);
+    const size_t m = radii.size();
+    double n[3], e1[3], e2[3];
+    nbody::check(nb_map_frame(oo.axis.data(), n, e1, e2));
+    std::vector<nb_orbit_deviation> dev0(2 * m);
+    for (size_t i = 0; i < m; ++i) {
+        double d[3], len2 = 0.0;
+        const double *x = pos.data() + 3 * i;
+        for (int a = 0; a < 3; ++a) d[a] = x[a] - oo.center[(size_t)a];
+        const double l = (d[0] * n[0] + d[1] * n[1]) + d[2] * n[2];
+        for (int a = 0; a < 3; ++a) {
+            d[a] = d[a] - l * n[a];
+            len2 += d[a] * d[a];
+        }
+        const double len = std::sqrt(len2);
+        for (int a = 0; a < 3; ++a) {
+            dev0[2 * i].d[a] = len > 0.0 ? d[a] / len : e1[a];
+            dev0[2 * i + 1].d[a] = n[a];
+        }
+    }
+    const nbody::OrbitStability o = runner.orbit_stability(p, pos, vel, dev0);
+    const nbody::OrbitStability::Derived dv = o.derive();
+    const uint32_t last = o.orbits.records - 1;
+    std::vector<double> rows(m * 6);
+    for (size_t i = 0; i < m; ++i) {
+        double *r = rows.data() + 6 * i;
+        r[0] = dv.lyapunov[((size_t)last * m + i) * 2];
+        r[1] = dv.lyapunov[((size_t)last * m + i) * 2 + 1];
+        r[2] = dv.sali[(size_t)last * m + i];
+        r[3] = dv.gali2[(size_t)last * m + i];
+        r[4] = (double)o.growth[2 * i].peak_log2;
+        r[5] = (double)o.growth[2 * i].peak_step;
+    }
+    char name[64], shape[64];
+    const unsigned long long step = (unsigned long long)o.stats.orbit.step_num;
+    std::snprintf(name, sizeof name, "/stability_%06llu.npy", step);
+    std::snprintf(shape, sizeof shape, "%zu, 6", m);
+    if (!write_f8(oo.dir + name, shape, rows)) return false;
+    std::printf("stability %llu %zu %llu %u\n", step, m, (unsigned long long)o.stats.renorms,
                 o.stats.orbit.pair_launches);
     return true;
 }
@@ -873,7 +934,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
                const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6,
-               const SectionsOptions &sections) {
+               const SectionsOptions &sections, const OrbitsOptions &stability) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -884,6 +945,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (freq.every > 0) print_freq(runner, freq);
     if (!orbits.dir.empty() && orbits.at == 0 && !write_orbits(runner, orbits)) return 1;
     if (!sections.launch.dir.empty() && sections.launch.at == 0 && !write_sections(runner, sections)) return 1;
+    if (!stability.dir.empty() && stability.at == 0 && !write_stability(runner, stability)) return 1;
     if (!maps.dir.empty() && !write_map(runner, maps)) return 1;
     if (!smaps.dir.empty() && !write_smap(runner, smaps)) return 1;
     if (fof.every > 0) print_fof(runner, fof);
@@ -911,6 +973,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (freq.every > 0 && (i + 1) % freq.every == 0) print_freq(runner, freq);
         if (!orbits.dir.empty() && i + 1 == orbits.at && !write_orbits(runner, orbits)) return 1;
         if (!sections.launch.dir.empty() && i + 1 == sections.launch.at && !write_sections(runner, sections)) return 1;
+        if (!stability.dir.empty() && i + 1 == stability.at && !write_stability(runner, stability)) return 1;
         if (!maps.dir.empty() && (i + 1) % maps.every == 0 && !write_map(runner, maps)) return 1;
         if (!smaps.dir.empty() && (i + 1) % smaps.every == 0 && !write_smap(runner, smaps)) return 1;
         if (fof.every > 0 && (i + 1) % fof.every == 0) print_fof(runner, fof);
@@ -955,6 +1018,7 @@ int main(int argc, char **argv) {
     KinOptions kin;
     OrbitsOptions orbits;
     SectionsOptions sections;
+    OrbitsOptions stability;
     Fof6Options fof6;
     BoundOptions bound;
     HaloOptions halo;
@@ -1306,6 +1370,27 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (k == "--stability") stability.dir = v;
+        else if (k == "--stability-at") stability.at = std::atoi(v.c_str());
+        else if (k == "--stability-bins") stability.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--stability-steps") stability.steps = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--stability-dt") stability.dt = std::atof(v.c_str());
+        else if (k == "--stability-omega") stability.omega = std::atof(v.c_str());
+        else if (k == "--stability-speed") stability.speed = std::atof(v.c_str());
+        else if (k == "--stability-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &stability.rmin, &stability.rmax) != 2) {
+                std::fprintf(stderr, "--stability-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            stability.have_range = true;
+        }
+        else if (k == "--stability-axis" || k == "--stability-center") {
+            double *a = k == "--stability-axis" ? stability.axis.data() : stability.center.data();
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", a, a + 1, a + 2) != 3) {
+                std::fprintf(stderr, "%s takes X,Y,Z, not %s\n", k.c_str(), v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--kin") kin.every = std::atoi(v.c_str());
         else if (k == "--kin-k") kin.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--kin-gradient") kin.gradient = std::atoi(v.c_str()) != 0;
@@ -1346,6 +1431,11 @@ int main(int argc, char **argv) {
     if (!sections.launch.dir.empty() && (!sections.launch.have_range || sections.launch.steps == 0 ||
                                          sections.launch.dt == 0.0 || sections.launch.at < 0)) {
         std::fprintf(stderr, "--sections needs --sections-range RMIN,RMAX, --sections-dt DT and --sections-steps S\n");
+        return 2;
+    }
+    if (!stability.dir.empty() && (!stability.have_range || stability.steps == 0 || stability.dt == 0.0 ||
+                                   stability.at < 0)) {
+        std::fprintf(stderr, "--stability needs --stability-range RMIN,RMAX, --stability-dt DT and --stability-steps S\n");
         return 2;
     }
     if (rotcurve.every > 0 && !rotcurve.have_range) {
@@ -1419,9 +1509,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -164,6 +164,19 @@ static int pass_orbit_sections(H *h, const nb_orbit_params *params, const nb_orb
 }
 
 template <class H>
+static int pass_orbit_stability(H *h, const nb_orbit_params *params, const nb_orbit_stability_params *stability,
+                                const double *pos, const double *vel, size_t m, const nb_orbit_deviation *dev0,
+                                nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_deviation *devs,
+                                nb_orbit_growth *growth, nb_orbit_stability_stats *stats) {
+    OrbitPlan plan{};
+    if (int rc = orbit_stability_check_args(params, stability, pos, vel, m, dev0, tracks, devs, &plan)) return rc;
+    return on_sim(h, "orbit_stability", [&](SimBase &s) {
+        return sim_orbit_stability(s, *params, *stability, plan, pos, vel, m, dev0, tracks, coincident, devs, growth,
+                                   stats);
+    });
+}
+
+template <class H>
 static int pass_map(H *h, const nb_map_params *params, uint32_t *counts, double *planes, nb_map_stats *stats) {
     MapPlan plan{};
     if (int rc = map_check_params(params, &plan)) return rc;
@@ -563,6 +576,25 @@ int nb_orbit_sections_runner(nb_runner *runner, const nb_orbit_params *params,
                              uint32_t *counts, nb_orbit_summary *summaries, nb_orbit_section_stats *stats) {
     return pass_orbit_sections(runner, params, section, pos, vel, m, tracks, coincident, crossings, counts, summaries,
                                stats);
+}
+int nb_orbit_stability_sim(nb_sim *sim, const nb_orbit_params *params, const nb_orbit_stability_params *stability,
+                           const double *pos, const double *vel, size_t m, const nb_orbit_deviation *dev0,
+                           nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_deviation *devs,
+                           nb_orbit_growth *growth, nb_orbit_stability_stats *stats) {
+    return pass_orbit_stability(sim, params, stability, pos, vel, m, dev0, tracks, coincident, devs, growth, stats);
+}
+int nb_orbit_stability_runner(nb_runner *runner, const nb_orbit_params *params,
+                              const nb_orbit_stability_params *stability, const double *pos, const double *vel,
+                              size_t m, const nb_orbit_deviation *dev0, nb_orbit_sample *tracks, uint32_t *coincident,
+                              nb_orbit_deviation *devs, nb_orbit_growth *growth, nb_orbit_stability_stats *stats) {
+    return pass_orbit_stability(runner, params, stability, pos, vel, m, dev0, tracks, coincident, devs, growth, stats);
+}
+int nb_orbit_stability_derive(double dt, uint32_t steps, uint32_t every, size_t m, uint32_t deviations,
+                              const nb_orbit_deviation *dev0, const nb_orbit_deviation *devs, double *log_growth,
+                              double *lyapunov, double *sali, double *gali2) {
+    NB_GUARD({
+        return orbit_stability_derive(dt, steps, every, m, deviations, dev0, devs, log_growth, lyapunov, sali, gali2);
+    })
 }
 int nb_orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out) {
     return orbit_summary_merge(a, b, out);

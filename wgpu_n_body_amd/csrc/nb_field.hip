@@ -15,16 +15,19 @@
 //   sections -- nb_orbit_sections_sim (include/nbody.h "Orbit sections"): the same sequence with the
 //              step kernel's sibling, which also compares every state with the tracer's previous one, stores the
 //              plane crossings and keeps the tracer's summary.  No launch is added.
+//   The step's own lines are nb_orbit.hpp's, shared with nb_stability.hip, which joins the sequence below as a rider.
 // The non-finite count is the diagnostics' own (diag_enqueue_moments on the same stream).
 // No float atomics; the grid and the chunking depend on (M, N, flags) alone and every lane runs the same
 // operations in the same order, so the result is bitwise reproducible and does not depend on where in
 // the array a point stands.
+#include "nb_orbit.hpp"
 #include "nb_probe.hpp"
 #include "nb_psi.hpp"
 
 namespace nb {
 
 using namespace probe;
+using namespace orbit;
 
 namespace {
 
@@ -82,6 +85,8 @@ struct FieldRule {
 };
 
 constexpr uint32_t kSlabFields = FieldRule<kAcc>::kSums + 1;  // ... and the coincident count
+static_assert(kSlabFields == NoRide::kSlabFields && NoRide::kCount == FieldRule<kAcc>::kSums,
+              "orbit_step reads the slab this unit's pair kernels write");
 
 // ---- finish: the chunks of every point of a band [p0, p1) in order, scaled by g once -> nb_field_sample ----
 __global__ __launch_bounds__(kThreads) void field_finish_kernel(const double *__restrict__ slab, uint32_t chunks,
@@ -122,52 +127,14 @@ void launch_field(uint32_t flags, int ib, const Band<nb_field_sample> &b, const 
         launch_pairs<FieldRule<kAcc>, 4>(b, c);
 }
 
-// ---- orbits: what a step does besides the pairs, one thread per tracer of a band --------------------------------
-struct OrbitFrame {
-    double e1[3], e2[3], n[3], c[3];
-};
-struct OrbitStep {
-    double g, scale, h, dt, omega;
-    double ck, sk;         // the phase of this evaluation: turns the acceleration back
-    double cn, sn;         // the phase of the next one: turns the next point
-    uint32_t field_flags;  // F_k
-    uint32_t rotating, energy, first, last;
-};
-
-// q = c + R(-theta) (x - c) in the frame, rounded once to fp32: the point of an evaluation
-__device__ __forceinline__ float4 orbit_point(const double (&x)[3], const OrbitFrame &f, bool rotating, double c,
-                                               double s) {
-#pragma clang fp contract(off)
-    double q[3] = {x[0], x[1], x[2]};
-    if (rotating) {
-        const double dx = x[0] - f.c[0], dy = x[1] - f.c[1], dz = x[2] - f.c[2];
-        const double a = (dx * f.e1[0] + dy * f.e1[1]) + dz * f.e1[2];
-        const double b = (dx * f.e2[0] + dy * f.e2[1]) + dz * f.e2[2];
-        const double l = (dx * f.n[0] + dy * f.n[1]) + dz * f.n[2];
-        const double ar = a * c + b * s, br = b * c - a * s;
-        for (int i = 0; i < 3; ++i) q[i] = f.c[i] + ((ar * f.e1[i] + br * f.e2[i]) + l * f.n[i]);
-    }
-    return make_float4((float)q[0], (float)q[1], (float)q[2], 0.f);
-}
-
-// before evaluation 0: a tracer that starts non-finite is NaN throughout; the first point
+// ---- orbits: what a step does besides the pairs, one thread per tracer of a band: orbit_step of nb_orbit.hpp ----
 __global__ __launch_bounds__(kThreads) void orbit_stage_kernel(uint32_t m, OrbitFrame f, uint32_t rotating, double c,
                                                                double s, double *__restrict__ xs,
                                                                double *__restrict__ vs, uint32_t *__restrict__ coinc,
                                                                float4 *__restrict__ pts) {
     const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= m) return;
-    double x[3], v[3];
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) {
-        x[i] = xs[3 * (size_t)p + i];
-        v[i] = vs[3 * (size_t)p + i];
-        ok = ok && isfinite(x[i]) && isfinite(v[i]);
-    }
-    if (!ok)
-        for (int i = 0; i < 3; ++i) xs[3 * (size_t)p + i] = vs[3 * (size_t)p + i] = x[i] = (double)NAN;
-    coinc[p] = 0;
-    pts[p] = orbit_point(x, f, rotating, c, s);
+    orbit_stage(p, f, rotating, c, s, xs, vs, coinc, pts);
 }
 
 // ---- orbit sections (include/nbody.h "Orbit sections"): what the step kernel does with state k
@@ -287,82 +254,15 @@ __device__ __forceinline__ void orbit_section(uint32_t p, const double (&x)[3], 
     prev[kPrevB * m] = b;
 }
 
-// after the pairs of evaluation k for the band [p0, p1): the chunks in order and the scaling by g as
-// field_finish_kernel has them, then accel_scale, the turn back, the second half-kick, the record if one is due
-// (rec = the record's row, or null), the first half-kick and the drift of the next step, and the next point.
-// vs holds v_0 on entry to evaluation 0 and w afterwards.
-// With SECTION the state of the evaluation is also handed to orbit_section (below) before the next step begins.
-template <bool SECTION>
-__device__ __forceinline__ void orbit_step(const double *__restrict__ slab, uint32_t chunks, uint32_t stride,
-                                           uint32_t p0, uint32_t p1, const OrbitStep &st, const OrbitFrame &f,
-                                           double *__restrict__ xs, double *__restrict__ vs,
-                                           uint32_t *__restrict__ coinc, float4 *__restrict__ pts,
-                                           nb_orbit_sample *__restrict__ rec, const OrbitSection *sec) {
-#pragma clang fp contract(off)
-    const uint32_t q = blockIdx.x * kThreads + threadIdx.x, p = p0 + q;
-    if (p >= p1) return;
-    const float4 pt = pts[p];
-    const bool ok = isfinite(pt.x) && isfinite(pt.y) && isfinite(pt.z);
-    const uint32_t flags = st.field_flags;
-    double s[kSlabFields] = {};
-    for (uint32_t c = 0; c < chunks; ++c) {
-        const double *in = slab + (size_t)c * kSlabFields * stride + q;
-        for (int k = 0; k < 3; ++k) s[k] += in[(size_t)k * stride];
-        if (flags & NB_FIELD_POTENTIAL) s[3] += in[(size_t)3 * stride];
-        s[4] += in[(size_t)4 * stride];
+// the section as orbit_step's ride
+struct SectionRide {
+    static constexpr uint32_t kSlabFields = NoRide::kSlabFields, kCount = NoRide::kCount;
+    OrbitSection sc;
+    __device__ __forceinline__ void state(uint32_t p, const double *, uint32_t, uint32_t, bool, const double (&x)[3],
+                                          const double (&v)[3], const OrbitStep &st, const OrbitFrame &f) const {
+        orbit_section(p, x, v, st, f, sc);
     }
-    const bool pot = ok && (flags & NB_FIELD_POTENTIAL);
-    double as[3];  // A_snap
-    for (int k = 0; k < 3; ++k) as[k] = st.scale * (ok ? st.g * s[k] : (double)NAN);
-    const double phi = st.scale * (pot ? -(st.g * s[3]) : (double)NAN);
-    coinc[p] += ok ? (uint32_t)s[4] : 0u;
-
-    double a[3] = {as[0], as[1], as[2]};
-    if (st.rotating) {
-        const double u = (as[0] * f.e1[0] + as[1] * f.e1[1]) + as[2] * f.e1[2];
-        const double v = (as[0] * f.e2[0] + as[1] * f.e2[1]) + as[2] * f.e2[2];
-        const double t = (as[0] * f.n[0] + as[1] * f.n[1]) + as[2] * f.n[2];
-        const double ur = u * st.ck - v * st.sk, vr = v * st.ck + u * st.sk;
-        for (int i = 0; i < 3; ++i) a[i] = (ur * f.e1[i] + vr * f.e2[i]) + t * f.n[i];
-    }
-
-    double x[3], v[3], kick[3];
-    for (int i = 0; i < 3; ++i) {
-        x[i] = xs[3 * (size_t)p + i];
-        v[i] = vs[3 * (size_t)p + i];
-        kick[i] = a[i] * st.h;
-        if (!st.first) v[i] = v[i] + kick[i];  // v_k = w + A_k h
-    }
-    if (rec) {
-        nb_orbit_sample r;
-        for (int i = 0; i < 3; ++i) {
-            r.pos[i] = x[i];
-            r.vel[i] = v[i];
-        }
-        r.potential = r.energy = (double)NAN;
-        if (st.energy) {
-            double e = 0.5 * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + phi;
-            if (st.rotating) {
-                const double dx = x[0] - f.c[0], dy = x[1] - f.c[1], dz = x[2] - f.c[2];
-                const double l = (f.n[0] * (dy * v[2] - dz * v[1]) + f.n[1] * (dz * v[0] - dx * v[2])) +
-                                 f.n[2] * (dx * v[1] - dy * v[0]);
-                e = e - st.omega * l;
-            }
-            r.potential = phi;
-            r.energy = e;
-        }
-        rec[p] = r;
-    }
-    if (SECTION) orbit_section(p, x, v, st, f, *sec);
-    if (st.last) return;
-    for (int i = 0; i < 3; ++i) {
-        v[i] = v[i] + kick[i];      // w = v_k + A_k h
-        x[i] = x[i] + v[i] * st.dt;  // x_{k+1} = x_k + w dt
-        xs[3 * (size_t)p + i] = x[i];
-        vs[3 * (size_t)p + i] = v[i];
-    }
-    pts[p] = orbit_point(x, f, st.rotating, st.cn, st.sn);
-}
+};
 
 __global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__restrict__ slab, uint32_t chunks,
                                                               uint32_t stride, uint32_t p0, uint32_t p1, OrbitStep st,
@@ -370,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void orbit_step_kernel(const double *__re
                                                               double *__restrict__ vs, uint32_t *__restrict__ coinc,
                                                               float4 *__restrict__ pts,
                                                               nb_orbit_sample *__restrict__ rec) {
-    orbit_step<false>(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, nullptr);
+    orbit_step(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, NoRide{});
 }
 
 // the same step with the section riding in it (include/nbody.h "Orbit sections")
@@ -378,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void orbit_section_step_kernel(
     const double *__restrict__ slab, uint32_t chunks, uint32_t stride, uint32_t p0, uint32_t p1, OrbitStep st,
     OrbitFrame f, double *__restrict__ xs, double *__restrict__ vs, uint32_t *__restrict__ coinc,
     float4 *__restrict__ pts, nb_orbit_sample *__restrict__ rec, OrbitSection sec) {
-    orbit_step<true>(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, &sec);
+    orbit_step(slab, chunks, stride, p0, p1, st, f, xs, vs, coinc, pts, rec, SectionRide{sec});
 }
 
 struct OrbitWork : Workspace {  // (all but the last grow to the largest call so far)
@@ -442,11 +342,12 @@ struct SectionCall {
 };
 
 // nb_orbits_sim, and with `section` nb_orbit_sections_sim: the same sequence, the step kernel's sibling in the place
-// of the step kernel, a memset up front and three copies at the end
+// of the step kernel, a memset up front and three copies at the end; with `rider` (nb_orbit.hpp) another unit's
+// slab, pair kernel and step kernel in the same places
 static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos,
                       const double *vel, size_t m, nb_orbit_sample *tracks, uint32_t *coincident,
-                      nb_orbit_stats *stats, const SectionCall *section) {
-    if (int rc = refuse_sharded(sim, section ? "orbit_sections" : "orbits")) return rc;
+                      nb_orbit_stats *stats, const SectionCall *section, OrbitRider *rider = nullptr) {
+    if (int rc = refuse_sharded(sim, rider ? rider->name : section ? "orbit_sections" : "orbits")) return rc;
     const uint32_t n = sim.n, mm = (uint32_t)m, steps = P.steps, records = frame.records;
     const bool energy = P.flags & NB_ORBIT_ENERGY, rotating = P.omega != 0.0;
     // the plans of the two kinds of evaluation: field()'s own for m points and the flags of each
@@ -478,9 +379,13 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
     NB_HIP_TRY(w.h_in.reserve(6 * (size_t)mm));
     NB_HIP_TRY(w.h_tracks.reserve(samples));
     NB_HIP_TRY(w.h_coinc.reserve(mm));
-    const size_t slab_a = (size_t)plan_a.chunks * kSlabFields * plan_a.stride;
+    const uint32_t fields = rider ? rider->slab_fields : kSlabFields;
+    const size_t slab_a = (size_t)plan_a.chunks * fields * plan_a.stride;
     const size_t slab_e = (size_t)plan_e.chunks * kSlabFields * plan_e.stride;
     NB_HIP_TRY(w.slab.reserve(energy ? std::max(slab_a, slab_e) : slab_a));
+    if (rider)
+        if (int rc = rider->reserve(sim, mm, records)) return rc;
+    const OrbitDevice dev{w.x, w.v, w.coinc, w.pts};
     OrbitSection sc{};
     const size_t slots = section ? (size_t)mm * section->params.max_crossings : 0;
     if (section) {
@@ -553,9 +458,13 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
             if (slots)
                 NB_HIP_TRY(hipMemsetAsync((nb_orbit_crossing *)w.cross, 0, sizeof(nb_orbit_crossing) * slots, sim.stream));
             if (int rc = orbit_phase(P.omega, P.dt, P.step0, &st.cn, &st.sn)) return rc;
-            hipLaunchKernelGGL(orbit_stage_kernel, dim3((mm + kThreads - 1) / kThreads), dim3(kThreads), 0, sim.stream,
-                               mm, f, st.rotating, st.cn, st.sn, (double *)w.x, (double *)w.v, (uint32_t *)w.coinc,
-                               (float4 *)w.pts);
+            if (rider) {
+                if (int rc = rider->upload(sim.stream)) return rc;
+                rider->stage(sim.stream, mm, f, st, dev);
+            } else {
+                hipLaunchKernelGGL(orbit_stage_kernel, dim3((mm + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                                   sim.stream, mm, f, st.rotating, st.cn, st.sn, dev.x, dev.v, dev.coinc, dev.pts);
+            }
             NB_HIP_TRY(hipGetLastError());
             uint32_t r = 0;
             for (uint32_t k = 0; k <= steps; ++k) {
@@ -581,11 +490,16 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
                     b.p0 = b.tile0 * pl.tile_pts;
                     b.p1 = std::min(mm, (b.tile0 + b.tiles) * pl.tile_pts);
                     if (n > 0) {
-                        launch_field(st.field_flags, ib, b, c);
+                        if (rider)
+                            rider->pairs(ib, b);
+                        else
+                            launch_field(st.field_flags, ib, b, c);
                         NB_HIP_TRY(hipGetLastError());
                         ++launches;
                     }
-                    if (section)
+                    if (rider)
+                        rider->step(b, st, f, dev, rec, r - 1, sc.step);
+                    else if (section)
                         hipLaunchKernelGGL(orbit_section_step_kernel, finish_grid(b), dim3(kThreads), 0, sim.stream,
                                            (const double *)w.slab, b.chunks, b.stride, b.p0, b.p1, st, f,
                                            (double *)w.x, (double *)w.v, (uint32_t *)w.coinc, (float4 *)w.pts, rec,
@@ -600,6 +514,8 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
             NB_HIP_TRY(hipMemcpyAsync(w.h_tracks, w.tracks, sizeof(nb_orbit_sample) * samples, hipMemcpyDeviceToHost,
                                       sim.stream));
             NB_HIP_TRY(hipMemcpyAsync(w.h_coinc, w.coinc, sizeof(uint32_t) * mm, hipMemcpyDeviceToHost, sim.stream));
+            if (rider)
+                if (int rc = rider->download(sim.stream)) return rc;
             if (section) {
                 if (slots)
                     NB_HIP_TRY(hipMemcpyAsync(w.h_cross, w.cross, sizeof(nb_orbit_crossing) * slots,
@@ -622,6 +538,7 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
         std::memcpy(tracks, w.h_tracks, sizeof(nb_orbit_sample) * samples);
         if (coincident) std::memcpy(coincident, w.h_coinc, sizeof(uint32_t) * mm);
     }
+    if (rider && mm > 0) rider->deliver();
     if (section) {
         nb_orbit_section_stats ss{};
         const uint32_t cap = section->params.max_crossings;
@@ -656,6 +573,12 @@ static int orbits_run(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &f
 int sim_orbits(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos, const double *vel,
                size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats) {
     return orbits_run(sim, P, frame, pos, vel, m, tracks, coincident, stats, nullptr);
+}
+
+int sim_orbits_with(SimBase &sim, const nb_orbit_params &P, const OrbitPlan &frame, const double *pos,
+                    const double *vel, size_t m, nb_orbit_sample *tracks, uint32_t *coincident, nb_orbit_stats *stats,
+                    OrbitRider &rider) {
+    return orbits_run(sim, P, frame, pos, vel, m, tracks, coincident, stats, nullptr, &rider);
 }
 
 int sim_orbit_sections(SimBase &sim, const nb_orbit_params &P, const nb_orbit_section_params &sec,

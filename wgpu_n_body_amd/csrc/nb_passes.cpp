@@ -299,6 +299,118 @@ int orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb
     return NB_OK;
 }
 
+// nb_orbit_stability_sim: nb_orbits_sim's refusals, then its own
+int orbit_stability_check_args(const nb_orbit_params *p, const nb_orbit_stability_params *sp, const double *pos,
+                               const double *vel, size_t m, const nb_orbit_deviation *dev0,
+                               const nb_orbit_sample *tracks, const nb_orbit_deviation *devs, OrbitPlan *plan) {
+    if (int rc = orbits_check_args(p, pos, vel, m, tracks, plan)) return rc;
+    if (p->flags & NB_ORBIT_ENERGY) {
+        set_error("orbit_stability: NB_ORBIT_ENERGY is not taken (the tracks are nb_orbits_sim's, which gives it)");
+        return NB_ERR_INVALID;
+    }
+    if (!sp) {
+        set_error("orbit_stability: null stability params");
+        return NB_ERR_INVALID;
+    }
+    if (sp->deviations < 1 || sp->deviations > NB_ORBIT_MAX_DEVIATIONS) {
+        set_error("orbit_stability: deviations must be 1..%u (got %u)", NB_ORBIT_MAX_DEVIATIONS, sp->deviations);
+        return NB_ERR_INVALID;
+    }
+    if (sp->renorm_log2 < 1 || sp->renorm_log2 > NB_ORBIT_MAX_RENORM_LOG2) {
+        set_error("orbit_stability: renorm_log2 must be 1..%u (got %u)", NB_ORBIT_MAX_RENORM_LOG2, sp->renorm_log2);
+        return NB_ERR_INVALID;
+    }
+    if (sp->reserved) {
+        set_error("orbit_stability: reserved %u != 0", sp->reserved);
+        return NB_ERR_INVALID;
+    }
+    if (m > 0 && (!dev0 || !devs)) {
+        set_error("orbit_stability: null %s", !dev0 ? "dev0" : "devs");
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)plan->records * m * sp->deviations > NB_ORBIT_MAX_SAMPLES) {
+        set_error("orbit_stability: %u records of %zu tracers with %u vectors are more than %u samples", plan->records,
+                  m, sp->deviations, NB_ORBIT_MAX_SAMPLES);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_orbit_stability_derive: the norm of a vector as 2^E sqrt(sum (d_i 2^-E)^2), its ln, and the unit vector
+static bool deviation_unit(const nb_orbit_deviation &v, double *ln_norm, double u[6]) {
+    double mu = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        if (!std::isfinite(v.d[i])) return false;
+        mu = std::fmax(mu, std::fabs(v.d[i]));
+    }
+    if (mu == 0.0) return false;
+    int ex = 0;
+    (void)std::frexp(mu, &ex);
+    double s[6], sum = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        s[i] = std::ldexp(v.d[i], -ex);
+        sum += s[i] * s[i];
+    }
+    const double norm = std::sqrt(sum);
+    for (int i = 0; i < 6; ++i) u[i] = s[i] / norm;
+    *ln_norm = (double)ex * M_LN2 + std::log(norm);
+    return true;
+}
+
+int orbit_stability_derive(double dt, uint32_t steps, uint32_t every, size_t m, uint32_t D,
+                           const nb_orbit_deviation *dev0, const nb_orbit_deviation *devs, double *log_growth,
+                           double *lyapunov, double *sali, double *gali2) {
+    if (m > 0 && (!dev0 || !devs)) {
+        set_error("orbit_stability_derive: null %s", !dev0 ? "dev0" : "devs");
+        return NB_ERR_INVALID;
+    }
+    if (D < 1 || D > NB_ORBIT_MAX_DEVIATIONS || steps < 1 || every < 1 || !std::isfinite(dt) || dt == 0.0) {
+        set_error("orbit_stability_derive: deviations must be 1..%u, steps and every at least 1, dt finite and not "
+                  "zero (got %u, %u, %u, %g)", NB_ORBIT_MAX_DEVIATIONS, D, steps, every, dt);
+        return NB_ERR_INVALID;
+    }
+    size_t r = 0;
+    for (uint32_t k = 0; k <= steps; ++k) {
+        if (k % every != 0 && k != steps) continue;
+        for (size_t i = 0; i < m; ++i) {
+            double u[2][6] = {};
+            bool have[2] = {false, false};
+            for (uint32_t j = 0; j < D; ++j) {
+                const size_t at = (r * m + i) * D + j;
+                const nb_orbit_deviation &v = devs[at], &v0 = dev0[i * D + j];
+                double ln = 0.0, ln0 = 0.0, uj[6], u0[6];
+                const bool ok = deviation_unit(v, &ln, uj), ok0 = deviation_unit(v0, &ln0, u0);
+                const double lg = ok && ok0 ? (double)(v.log2 - v0.log2) * M_LN2 + ln - ln0 : (double)NAN;
+                if (log_growth) log_growth[at] = lg;
+                if (lyapunov) lyapunov[at] = k > 0 ? lg / ((double)k * dt) : (double)NAN;
+                if (j < 2) {
+                    have[j] = ok;
+                    for (int a = 0; a < 6; ++a) u[j][a] = uj[a];
+                }
+            }
+            double sa = NAN, ga = NAN;
+            if (D >= 2 && have[0] && have[1]) {
+                double plus = 0.0, minus = 0.0, wedge = 0.0;
+                for (int a = 0; a < 6; ++a) {
+                    const double p = u[0][a] + u[1][a], q = u[0][a] - u[1][a];
+                    plus += p * p;
+                    minus += q * q;
+                    for (int b = a + 1; b < 6; ++b) {
+                        const double c = u[0][a] * u[1][b] - u[0][b] * u[1][a];
+                        wedge += c * c;
+                    }
+                }
+                sa = std::sqrt(std::fmin(plus, minus));
+                ga = std::sqrt(wedge);
+            }
+            if (sali) sali[r * m + i] = sa;
+            if (gali2) gali2[r * m + i] = ga;
+        }
+        ++r;
+    }
+    return NB_OK;
+}
+
 // nb_field_rings / nb_field_ring_means / nb_tidal_ring_means: the unit axis n and the ring basis e1, e2 = n x e1
 static int ring_basis(const char *what, const double *center, const double *axis, const double *radii, uint32_t k,
                       uint32_t n_phi, double n[3], double e1[3], double e2[3]) {

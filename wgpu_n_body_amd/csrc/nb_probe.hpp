@@ -1,5 +1,6 @@
 // nb_probe.hpp -- what the probes of a simulator's current state at arbitrary points share (nb_field.hip: the
-// acceleration and the potential; nb_tidal.hip: the tidal tensor): M points against
+// acceleration and the potential; nb_tidal.hip: the tidal tensor; nb_stability.hip: the
+// acceleration and the tensor in one pass): M points against
 // the N bodies of the float4 SoA state the simulator hands out (SimBase::diag_state), summed pair by pair.
 //   pairs   -- probe_kernel: a block of 256 threads owns a tile of 64 IB points, IB per lane in VGPRs, the same
 //              points in each of its four waves.  blockIdx.y cuts the bodies into chunks of 256-body tiles; the

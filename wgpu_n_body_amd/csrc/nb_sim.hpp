@@ -15,7 +15,7 @@ struct Workspace {
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
                       kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal,
-                      kWorkKin, kWorkOrbits, kWorkFof6, kWorkSlots };
+                      kWorkKin, kWorkOrbits, kWorkFof6, kWorkStability, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -193,6 +193,19 @@ int sim_orbit_sections(SimBase &sim, const nb_orbit_params &params, const nb_orb
                        uint32_t *coincident, nb_orbit_crossing *crossings, uint32_t *counts,
                        nb_orbit_summary *summaries, nb_orbit_section_stats *stats);
 int orbit_summary_merge(const nb_orbit_summary *a, const nb_orbit_summary *b, nb_orbit_summary *out);
+// nb_stability.hip: nb_orbit_stability_sim behind the handle (include/nbody.h "Orbit stability"): the orbit's sequence
+// with this unit's pair kernel and step kernel; orbit_stability_check_args runs orbits_check_args and then its own
+// refusals; orbit_stability_derive: nb_orbit_stability_derive behind the ABI boundary
+int orbit_stability_check_args(const nb_orbit_params *p, const nb_orbit_stability_params *sp, const double *pos,
+                               const double *vel, size_t m, const nb_orbit_deviation *dev0,
+                               const nb_orbit_sample *tracks, const nb_orbit_deviation *devs, OrbitPlan *plan);
+int sim_orbit_stability(SimBase &sim, const nb_orbit_params &params, const nb_orbit_stability_params &sp,
+                        const OrbitPlan &plan, const double *pos, const double *vel, size_t m,
+                        const nb_orbit_deviation *dev0, nb_orbit_sample *tracks, uint32_t *coincident,
+                        nb_orbit_deviation *devs, nb_orbit_growth *growth, nb_orbit_stability_stats *stats);
+int orbit_stability_derive(double dt, uint32_t steps, uint32_t every, size_t m, uint32_t deviations,
+                           const nb_orbit_deviation *dev0, const nb_orbit_deviation *devs, double *log_growth,
+                           double *lyapunov, double *sali, double *gali2);
 
 // nb_map.hip: nb_sim_map behind the handle; map_check_params also forms the frame and the cell sizes
 struct MapPlan {

@@ -439,6 +439,74 @@ OrbitSections orbit_sections(int (*call)(H *, const nb_orbit_params *, const nb_
 }
 }  // namespace detail
 
+// The deviation vectors of an orbits() call (include/nbody.h "Orbit stability"): records * tracers * deviations
+// vectors, record-major and vector-minor, each d * 2^log2; the growth per tracer and vector; and derive(), what
+// nb_orbit_stability_derive reads from them
+struct OrbitStability {
+    Orbits orbits;
+    uint32_t deviations = 0;
+    std::vector<nb_orbit_deviation> dev0;  // [tracers][deviations] what the call began with
+    std::vector<nb_orbit_deviation> devs;  // [records][tracers][deviations]
+    std::vector<nb_orbit_growth> growth;   // [tracers][deviations]
+    nb_orbit_stability_stats stats{};
+    const nb_orbit_deviation &at(uint32_t record, size_t tracer, uint32_t j) const {
+        return devs[((size_t)record * orbits.tracers + tracer) * deviations + j];
+    }
+    struct Derived {
+        std::vector<double> log_growth, lyapunov;  // [records][tracers][deviations]
+        std::vector<double> sali, gali2;           // [records][tracers]
+    };
+    Derived derive() const {
+        Derived d;
+        const size_t rows = (size_t)orbits.records * orbits.tracers;
+        d.log_growth.resize(rows * deviations);
+        d.lyapunov.resize(rows * deviations);
+        d.sali.resize(rows);
+        d.gali2.resize(rows);
+        check(nb_orbit_stability_derive(orbits.params.dt, orbits.params.steps, orbits.params.every, orbits.tracers,
+                                        deviations, dev0.data(), devs.data(), d.log_growth.data(), d.lyapunov.data(),
+                                        d.sali.data(), d.gali2.data()));
+        return d;
+    }
+};
+
+namespace detail {
+template <class H>
+OrbitStability orbit_stability(int (*call)(H *, const nb_orbit_params *, const nb_orbit_stability_params *,
+                                           const double *, const double *, size_t, const nb_orbit_deviation *,
+                                           nb_orbit_sample *, uint32_t *, nb_orbit_deviation *, nb_orbit_growth *,
+                                           nb_orbit_stability_stats *),
+                               H *h, const nb_orbit_params &p, const std::vector<double> &pos,
+                               const std::vector<double> &vel, const std::vector<nb_orbit_deviation> &dev0,
+                               uint32_t renorm_log2) {
+    if (pos.size() != vel.size() || pos.size() % 3)
+        throw Error(NB_ERR_INVALID, "orbit_stability: pos and vel are 3 doubles per tracer");
+    OrbitStability o;
+    Orbits &t = o.orbits;
+    t.params = p;
+    t.tracers = pos.size() / 3;
+    t.records = nb_orbit_records(p.steps, p.every);
+    if (t.tracers == 0 || dev0.size() % t.tracers)
+        throw Error(NB_ERR_INVALID, "orbit_stability: dev0 holds the same number of vectors for every tracer");
+    o.deviations = (uint32_t)(dev0.size() / t.tracers);
+    o.dev0 = dev0;
+    nb_orbit_stability_params sp{};
+    sp.deviations = o.deviations;
+    sp.renorm_log2 = renorm_log2;
+    // (the call refuses what it does not take, before it writes)
+    const bool big = t.tracers > NB_ORBIT_MAX_TRACERS ||
+                     (uint64_t)t.records * t.tracers * std::max(o.deviations, 1u) > NB_ORBIT_MAX_SAMPLES;
+    t.tracks.resize(big ? 0 : (size_t)t.records * t.tracers);
+    t.coincident.resize(t.tracers);
+    o.devs.resize(big ? 0 : (size_t)t.records * dev0.size());
+    o.growth.resize(dev0.size());
+    check(call(h, &p, &sp, pos.data(), vel.data(), t.tracers, dev0.data(), t.tracks.data(), t.coincident.data(),
+               o.devs.data(), o.growth.data(), &o.stats));
+    t.stats = o.stats.orbit;
+    return o;
+}
+}  // namespace detail
+
 // A projected map (no reference counterpart): width * height counts, row 0 the smallest b, the planes
 // (1, or 6 with NB_MAP_VELOCITY: mass, m_ua, m_ub, m_w, m_w2, m_u2) plane-major, and what the call measured
 struct ProjectedMap {
@@ -1172,6 +1240,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto tidal = nb_tidal_sim;
     static constexpr auto orbits = nb_orbits_sim;
     static constexpr auto orbit_sections = nb_orbit_sections_sim;
+    static constexpr auto orbit_stability = nb_orbit_stability_sim;
     static constexpr auto local_kinematics = nb_local_kinematics_sim;
     static constexpr auto fof6 = nb_fof6_sim;
     static constexpr auto smooth_map = nb_sim_smooth_map;
@@ -1196,6 +1265,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto tidal = nb_tidal_runner;
     static constexpr auto orbits = nb_orbits_runner;
     static constexpr auto orbit_sections = nb_orbit_sections_runner;
+    static constexpr auto orbit_stability = nb_orbit_stability_runner;
     static constexpr auto local_kinematics = nb_local_kinematics_runner;
     static constexpr auto fof6 = nb_fof6_runner;
     static constexpr auto smooth_map = nb_runner_smooth_map;
@@ -1346,6 +1416,13 @@ class Passes {
         std::vector<double> pos, vel;
         circular_launch(p, radii, n_phi, speed, pos, vel);
         return orbit_sections(p, sec, pos, vel);
+    }
+    // orbits() that also carries dev0's vectors ([tracers][D], D the same for every tracer) along every orbit by the
+    // tangent map of its step, renormalised by powers of two beyond 2^+-renorm_log2; p without NB_ORBIT_ENERGY
+    OrbitStability orbit_stability(const nb_orbit_params &p, const std::vector<double> &pos,
+                                   const std::vector<double> &vel, const std::vector<nb_orbit_deviation> &dev0,
+                                   uint32_t renorm_log2 = 32) {
+        return detail::orbit_stability(Abi::orbit_stability, h_, p, pos, vel, dev0, renorm_log2);
     }
     // the tracers of circular_orbits()
     void circular_launch(const nb_orbit_params &p, const std::vector<double> &radii, uint32_t n_phi, double speed,
