@@ -2248,6 +2248,158 @@ int nb_disc_modes_sim(nb_sim *sim, const nb_modes_params *params, nb_modes_head 
 int nb_disc_modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out);
 
 /* ------------------------------------------------------------------------- */
+/* Shell modes -- spherical-harmonic sums per radial shell: triaxiality shell  */
+/* by shell, core sloshing, twists and figure rotation in three dimensions     */
+/* (no reference counterpart)                                                  */
+/* ------------------------------------------------------------------------- */
+/* Per spherical shell about a centre: sum mu Q_l^m(cos theta) sin^m theta (cos, sin)(m phi)
+ * for 0 <= m <= l <= lmax, the unnormalised real spherical harmonics of the members'
+ * directions, and with NB_SHELL_RATES their exact time derivatives along the members'
+ * velocities.  nb_shell_modes_derive forms the orthonormal coefficients, the power per l,
+ * phases, pattern speeds, the l = 1 vector and the l = 2 tensor.  The rule, which
+ * DESIGN.md 6x states in full; binary64 from the binary32 state, one rounding per
+ * operation, no contraction, no transcendental, in this order:
+ *   input     nbins in 1..NB_SHELL_MAX_BINS and nbins + 1 edges, checked exactly as
+ *             nb_disc_modes_sim checks them; lmax in 0..NB_SHELL_MAX_L, with NB_SHELL_RATES
+ *             in 0..NB_SHELL_MAX_L_RATES; a centre c and a frame velocity v_c, or
+ *             NB_SHELL_CENTER_COM: the fp64 `com` and `momentum / mass` of
+ *             nb_sim_diagnostics bit for bit, formed on the device; an axis
+ *   frame     n, e1, e2 exactly as nb_map_frame(axis) returns them: n is the polar axis,
+ *             phi = 0 is e1
+ *   per body  that counts (position, velocity and mass finite; the others are
+ *             `nonfinite`):
+ *               d = (double)x - c, u = (double)v - v_c         per component
+ *               r2 = (dx dx + dy dy) + dz dz                   nb_sim_radial_profile's
+ *                                                              spherical rule
+ *               bin: the k with edges[k]^2 <= r2 < edges[k + 1]^2 (the squares formed
+ *                    once on the host); r2 < edges[0]^2: inside; r2 >= edges[nbins]^2:
+ *                    outside; a NaN r2 (a NaN centre) is below every edge
+ *               r  = sqrt(r2)
+ *               h  = (dx nx + dy ny) + dz nz,  a with e1 and b with e2 likewise
+ *               zeta = h / r, alpha = a / r, beta = b / r      (all 0 where r2 == 0)
+ *               c_0 = 1, s_0 = 0; c_m = c_(m-1) alpha - s_(m-1) beta,
+ *                                 s_m = s_(m-1) alpha + c_(m-1) beta    m = 1 .. lmax
+ *                                 (sin^m theta cos m phi and sin^m theta sin m phi)
+ *               Q_m^m = (2m - 1)!! (1, 1, 3, 15, 105, 945, 10395), Q_(m-1)^m = 0,
+ *               Q_l^m = (((2l - 1) zeta) Q_(l-1)^m - (l + m - 1) Q_(l-2)^m) / (l - m)
+ *                                 for l > m: d^m P_l / d zeta^m, a polynomial, without
+ *                                 the Condon-Shortley sign
+ *               with mu = (double)mass the terms
+ *                 C_lm = mu (Q_l^m c_m)   0 <= m <= l,   S_lm = mu (Q_l^m s_m)   m >= 1
+ *               and once mu r and mu u_r, where s = (ux dx + uy dy) + uz dz and
+ *               u_r = s / r (0 where r2 == 0)
+ *               r2 == 0: C_00 = mu and every other term, rates included, is +0
+ *   rates     with NB_SHELL_RATES, uh = (ux nx + uy ny) + uz nz, ua and ub likewise,
+ *               zeta' = (uh - u_r zeta) / r, alpha' = (ua - u_r alpha) / r,
+ *               beta' = (ub - u_r beta) / r
+ *               c'_0 = s'_0 = 0,
+ *               c'_m = (c'_(m-1) alpha + c_(m-1) alpha') - (s'_(m-1) beta + s_(m-1) beta')
+ *               s'_m = (s'_(m-1) alpha + s_(m-1) alpha') + (c'_(m-1) beta + c_(m-1) beta')
+ *               Q'_m^m = Q'_(m-1)^m = 0,
+ *               Q'_l^m = ((2l - 1) (zeta' Q_(l-1)^m + zeta Q'_(l-1)^m)
+ *                         - (l + m - 1) Q'_(l-2)^m) / (l - m)
+ *               DC_lm = mu (Q'_l^m c_m + Q_l^m c'_m),  DS_lm likewise with s_m, s'_m
+ *             the rate of the sum over the bodies now in the shell; the flux through the
+ *             shell's edges is not in it
+ *   lists, sums, mass   word for word as nb_disc_modes_sim: ascending body index, runs of
+ *             64 places through the xor butterfly, chunks of NB_SHELL_CHUNK = 4,096 places
+ *             added left to right from +0, the chunks added left to right from +0;
+ *             mass = inside_mass + the bins' C_00 in order + outside_mass
+ * With K = (lmax + 1)^2 and B = K (2 with NB_SHELL_RATES, else 1), coef[k B + i] is sum i of
+ * bin k: i = l^2 for m = 0, l^2 + 2m - 1 for C_lm and l^2 + 2m for S_lm; the rates follow at
+ * K + i.  Inside and outside report their count and their sum of mu only.  Two calls
+ * return the same bits; a bin's bits depend on its own members, the centre and the frame
+ * alone.  No float atomics.  The call is ordered after the enqueued steps on the
+ * simulator's stream, ends with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, launches nothing inside a graph capture and does not change
+ * the trajectory.  Spelt noun first as nb_disc_modes_sim is. */
+#define NB_SHELL_MAX_BINS 256u
+#define NB_SHELL_MAX_L 6u
+#define NB_SHELL_MAX_L_RATES 4u /* (lmax + 1)^2 (1 + rates) + 2 fields are one lane each of a wave of 64 */
+#define NB_SHELL_CHUNK 4096u
+#define NB_SHELL_CENTER_COM 1u /* centre = com, frame velocity = P/M of the measured state (as NB_MODES_CENTER_COM) */
+#define NB_SHELL_RATES 2u      /* also the time derivative of every sum */
+
+typedef struct nb_shell_params {
+    uint32_t nbins, lmax; /* 1..NB_SHELL_MAX_BINS, 0..NB_SHELL_MAX_L (NB_SHELL_MAX_L_RATES with NB_SHELL_RATES) */
+    uint32_t flags;       /* NB_SHELL_CENTER_COM | NB_SHELL_RATES */
+    uint32_t reserved;    /* 0 */
+    double center[3];     /* ignored with NB_SHELL_CENTER_COM */
+    double velocity[3];   /* ignored with NB_SHELL_CENTER_COM */
+    double axis[3];       /* the polar axis: finite, non-zero; need not be a unit vector */
+    const double *edges;  /* nbins + 1 radii: finite, >= 0, strictly ascending */
+} nb_shell_params;
+
+typedef struct nb_shell_head { /* 200 bytes */
+    uint64_t step_num, n, nonfinite;
+    uint64_t inside_count, outside_count;
+    double inside_mass, outside_mass;
+    double mass;                      /* inside + the bins in order + outside */
+    double center[3], velocity[3];    /* the ones used */
+    double axis[3], e1[3], e2[3];     /* nb_map_frame of the caller's axis */
+    uint32_t nbins, lmax, flags, reserved;
+} nb_shell_head;
+
+typedef struct nb_shell_bin { /* 24 bytes */
+    uint64_t count;
+    double m_r;  /* sum mu r */
+    double m_ur; /* sum mu u_r */
+} nb_shell_bin;
+
+typedef struct nb_shell_derived { /* 232 bytes: one bin; NaN above lmax */
+    double power[NB_SHELL_MAX_L + 1];    /* sum over m of a_lm^2, over 2l + 1 */
+    double relative[NB_SHELL_MAX_L + 1]; /* sqrt(power_l / power_0) */
+    double dipole[3];                    /* the l = 1 vector, in the state's coordinates */
+    double quad_values[3];               /* the l = 2 tensor's eigenvalues, descending */
+    double quad_axes[9];                 /* and their unit vectors (nb_shape_eigen), in the state's coordinates */
+} nb_shell_derived;
+
+#if defined(__cplusplus)
+static_assert(sizeof(nb_shell_params) == 96 && sizeof(nb_shell_head) == 200 && sizeof(nb_shell_bin) == 24 &&
+                  sizeof(nb_shell_derived) == 232,
+              "nb_shell_* layouts");
+static_assert((NB_SHELL_MAX_L + 1) * (NB_SHELL_MAX_L + 1) + 2 <= 64 &&
+                  2 * (NB_SHELL_MAX_L_RATES + 1) * (NB_SHELL_MAX_L_RATES + 1) + 2 <= 64,
+              "one lane per field");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(nb_shell_params) == 96 && sizeof(nb_shell_head) == 200 && sizeof(nb_shell_bin) == 24 &&
+                   sizeof(nb_shell_derived) == 232,
+               "nb_shell_* layouts");
+#endif
+
+/* out: the head; bins: nbins records; coef: nbins B doubles (above).  NB_ERR_INVALID for a null handle or
+ * pointer, nbins outside 1..NB_SHELL_MAX_BINS, lmax above NB_SHELL_MAX_L (above NB_SHELL_MAX_L_RATES with
+ * NB_SHELL_RATES), unknown flag bits, a reserved field != 0, non-finite, negative or not strictly ascending
+ * edges, a non-finite centre or velocity (without NB_SHELL_CENTER_COM), an axis without a finite non-zero
+ * length -- all checked before any device call; NB_ERR_UNSUPPORTED for a sharded simulator (placement
+ * world > 1).  n == 0 is answered on the host: zero sums, the explicit centre or NaN for the centre of no
+ * mass. */
+int nb_shell_modes_sim(nb_sim *sim, const nb_shell_params *params, nb_shell_head *out, nb_shell_bin *bins,
+                       double *coef);
+/* Host only, a pure function of its arguments: head (nbins, lmax, flags, axis, e1, e2 are read) and coef as
+ * nb_shell_modes_sim filled them; out[nbins]; norm, phase and speed are null or nbins K doubles each, indexed
+ * as coef's first block.  One rounding per operation, no contraction:
+ *   a_i = N_lm coef_i with F = (2l + 1) / NB_SHELL_FOUR_PI, N_l0 = sqrt(F) and
+ *         N_lm = sqrt((2 F) ((l - m)! / (l + m)!)): the coefficients of the orthonormal real harmonics
+ *         (without the Condon-Shortley sign) -> norm
+ *   power_l = (a_(l^2)^2 + a_(l^2+1)^2 + ... in index order) / (2l + 1): it does not depend on the axis
+ *   relative_l = sqrt(power_l / power_0); NaN where power_0 is 0 or NaN
+ *   phase at i = l^2 + 2m - 1: atan2(S, C) / m;  speed at the same i, with NB_SHELL_RATES:
+ *         (C DS - S DC) / (m (C C + S S)), the rate at which component (l, m) of the bodies now in the shell
+ *         turns about the axis; both NaN where C C + S S is 0 or NaN, and at every other index
+ *   dipole_j = (a_11c e1_j + a_11s e2_j) + a_10 n_j                                      (lmax >= 1)
+ *   the l = 2 tensor T with x^T T x = sum_m a_2m Y_2m(x) on the unit sphere, in the frame (e1, e2, n):
+ *         q0 = N_20 a_20, q1c = N_21 a_21c, q1s, q2c = N_22 a_22c, q2s likewise;
+ *         T_11 = (-0.5 q0) + 3 q2c, T_22 = (-0.5 q0) - 3 q2c, T_33 = q0, T_12 = 3 q2s, T_13 = 1.5 q1c,
+ *         T_23 = 1.5 q1s; with R = (e1 e2 n) as columns W_ib = (R_i1 T_1b + R_i2 T_2b) + R_i3 T_3b and
+ *         M_ij = (W_i1 R_j1 + W_i2 R_j2) + W_i3 R_j3 for i <= j; its eigenvalues and axes by
+ *         nb_shape_eigen                                                                  (lmax >= 2)
+ * NB_ERR_INVALID for a null head, coef or out, nbins or lmax out of range, unknown flag bits. */
+#define NB_SHELL_FOUR_PI 12.566370614359172 /* the double nearest 4 pi */
+int nb_shell_modes_derive(const nb_shell_head *head, const double *coef, nb_shell_derived *out, double *norm,
+                          double *phase, double *speed);
+
+/* ------------------------------------------------------------------------- */
 /* Smoothed maps -- every body spread over the pixels of a 2-D grid with a    */
 /* kernel of its own radius (no reference counterpart: the image of the       */
 /* density estimate, where nb_sim_map gives shot noise)                       */
@@ -2540,6 +2692,10 @@ int nb_group_radii_runner(nb_runner *runner, const nb_radii_params *params, cons
  * runner. */
 int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_modes_head *out, nb_modes_bin *bins,
                          double *modes);
+/* nb_shell_modes_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_shell_modes_runner(nb_runner *runner, const nb_shell_params *params, nb_shell_head *out, nb_shell_bin *bins,
+                          double *coef);
 /* nb_phase_map_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
  * runner. */
 int nb_phase_map_runner(nb_runner *runner, const nb_phase_params *params, uint32_t *counts, double *planes,

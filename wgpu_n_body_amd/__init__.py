@@ -48,7 +48,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "HopGroups", "HopStats", "HOP_NONE",
            "HaloProfiles", "HaloStats", "HALO_CENTER_NONFINITE",
            "GroupRadii", "RadiiStats",
-           "DiscModes", "MODES_FIELDS",
+           "DiscModes", "MODES_FIELDS", "ShellModes", "shell_index",
            "SmoothedMap", "SmoothStats", "smooth_centres", "SMOOTH_K", "SMOOTH_PLANES",
            "Camera", "RenderParams", "RenderStats", "Frame", "write_ppm"]
 
@@ -407,6 +407,161 @@ def _disc_modes(call, handle, dt, edges, nbins, rmin, rmax, log, mmax, axis, cen
                      vec(out.center), vec(out.velocity), vec(out.axis), vec(out.e1), vec(out.e2), int(out.flags),
                      int(out.mmax), float(dt), edges.copy(), bins["count"].copy(), bins["m_r"].copy(),
                      bins["m_h2"].copy(), modes)
+
+
+def shell_index(l: int, m: int, sine: bool = False) -> int:
+    """The place of sum (l, m) in a shell's block of (lmax + 1)^2: l^2 for m = 0, l^2 + 2m - 1 for the cosine sum and
+    l^2 + 2m for the sine sum."""
+    l, m = int(l), int(m)
+    if not 0 <= m <= l or (sine and m == 0):
+        raise ValueError(f"shell_index: needs 0 <= m <= l, and m >= 1 for a sine sum (got l = {l}, m = {m})")
+    return l * l + (2 * m - (0 if sine else 1) if m else 0)
+
+
+@dataclass(frozen=True)
+class ShellModes:
+    """nb_shell_head + nb_shell_bin[nbins] + coef[nbins][(lmax + 1)^2 (1 + rates)] (include/nbody.h "Shell modes"; no
+    reference counterpart): per spherical shell of the state read_particles would return, about `center`, the sums
+    over the members of mu Q_l^m(cos theta) sin^m theta (cos, sin)(m phi), the unnormalised real spherical harmonics
+    with `axis` as the polar axis and phi = 0 along e1 (map_frame(axis)), summed on the device in a fixed order.
+    coef: (nbins, (lmax + 1)^2) float64 indexed by shell_index(); rate: their time derivatives for the bodies now in
+    the shell, or None; count: uint64; m_r: sum mu r; m_ur: sum mu u_r."""
+    step_num: int
+    n: int
+    nonfinite: int
+    inside_count: int
+    outside_count: int
+    inside_mass: float
+    outside_mass: float
+    mass: float
+    center: np.ndarray
+    velocity: np.ndarray
+    axis: np.ndarray
+    e1: np.ndarray
+    e2: np.ndarray
+    flags: int
+    lmax: int
+    dt: float              # the simulator's time step
+    edges: np.ndarray      # nbins + 1
+    count: np.ndarray
+    m_r: np.ndarray
+    m_ur: np.ndarray
+    coef: np.ndarray
+    rate: Optional[np.ndarray]
+
+    @property
+    def nbins(self) -> int:
+        return self.edges.shape[0] - 1
+
+    @property
+    def bin_mass(self) -> np.ndarray:
+        """C_00: the mass of every shell."""
+        return self.coef[:, 0]
+
+    def coefficient(self, l: int, m: int, sine: bool = False) -> np.ndarray:
+        """Sum (l, m) per bin: the cosine sum, or with sine=True the sine sum."""
+        self._check_lm(l, m, 0)
+        return self.coef[:, shell_index(l, m, sine)]
+
+    def _check_lm(self, l, m, mmin):
+        if not (mmin <= int(m) <= int(l) <= self.lmax):
+            raise ValueError(f"ShellModes: needs {mmin} <= m <= l <= lmax = {self.lmax} (got l = {l}, m = {m})")
+
+    def _derive(self, norm=False, phase=False, speed=False):
+        """nb_shell_modes_derive: (_lib.SHELL_DERIVED_DTYPE records per bin, norm, phase, speed), the arrays asked for
+        (nbins, (lmax + 1)^2), the others None."""
+        head = _lib.nb_shell_head()
+        head.nbins, head.lmax, head.flags = self.nbins, self.lmax, self.flags
+        for k in range(3):
+            head.axis[k], head.e1[k], head.e2[k] = float(self.axis[k]), float(self.e1[k]), float(self.e2[k])
+        nk = (self.lmax + 1) ** 2
+        both = self.coef if self.rate is None else np.concatenate([self.coef, self.rate], axis=1)
+        both = np.ascontiguousarray(both, dtype=np.float64)
+        out = np.zeros(self.nbins, dtype=_lib.SHELL_DERIVED_DTYPE)
+        arrays = [np.zeros((self.nbins, nk)) if want else None for want in (norm, phase, speed)]
+        check(_lib.lib().nb_shell_modes_derive(C.byref(head), both.ctypes.data, out.ctypes.data,
+                                               *[None if a is None else a.ctypes.data for a in arrays]))
+        return (out, *arrays)
+
+    def normalised(self) -> np.ndarray:
+        """The coefficients of the orthonormal real harmonics, N_lm times the sums: (nbins, (lmax + 1)^2)."""
+        return self._derive(norm=True)[1]
+
+    def power(self) -> np.ndarray:
+        """sum_m a_lm^2 / (2l + 1) per bin and l, (nbins, lmax + 1): it does not depend on the axis."""
+        return self._derive()[0]["power"][:, :self.lmax + 1]
+
+    def relative(self, l: int) -> np.ndarray:
+        """sqrt(power_l / power_0) per bin (NaN in a bin without mass)."""
+        self._check_lm(l, 0, 0)
+        return self._derive()[0]["relative"][:, int(l)]
+
+    def dipole(self) -> np.ndarray:
+        """The l = 1 vector a_11c e1 + a_11s e2 + a_10 n per bin, (nbins, 3) in the state's coordinates: the direction
+        in which the shell's mass is displaced (NaN for lmax = 0)."""
+        return self._derive()[0]["dipole"]
+
+    def quadrupole_axes(self):
+        """(values, axes): the eigenvalues (nbins, 3), descending, and unit eigenvectors (nbins, 3, 3; axes[k, j] is
+        vector j) of the traceless tensor of the l = 2 coefficients, in the state's coordinates (nb_shape_eigen).
+        NaN for lmax < 2."""
+        d = self._derive()[0]
+        return d["quad_values"], d["quad_axes"]
+
+    def phase(self, l: int, m: int) -> np.ndarray:
+        """atan2(S_lm, C_lm) / m per bin, in (-pi/m, pi/m]: the azimuth about the axis of component (l, m)."""
+        self._check_lm(l, m, 1)
+        return self._derive(phase=True)[2][:, shell_index(l, m)]
+
+    def pattern_speed(self, l: int, m: int) -> np.ndarray:
+        """(C DS - S DC) / (m (C^2 + S^2)) per bin: the rate at which component (l, m) of the bodies now in the shell
+        turns about the axis (the flux through the shell's edges is not in it).  Needs rates=True."""
+        self._check_lm(l, m, 1)
+        if self.rate is None:
+            raise ValueError("ShellModes.pattern_speed needs shell_modes(rates=True)")
+        return self._derive(speed=True)[3][:, shell_index(l, m)]
+
+    def phase_between(self, other: "ShellModes", l: int, m: int) -> np.ndarray:
+        """(other.phase(l, m) - self.phase(l, m)) wrapped into (-pi/m, pi/m] per bin: over the time between the two
+        measurements it is the pattern speed of component (l, m), flux through the edges included."""
+        return _wrap_phase(other.phase(l, m) - self.phase(l, m), int(m))
+
+
+def _shell_modes(call, handle, dt, edges, nbins, rmin, rmax, log, lmax, rates, axis, center, velocity) -> ShellModes:
+    if edges is None:
+        if rmin is None or rmax is None:
+            raise ValueError("shell_modes needs edges, or rmin and rmax")
+        edges = radial_edges(rmin, rmax, nbins, log)
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    if not 0 <= int(lmax) <= 0xFFFFFFFF:
+        raise ValueError(f"shell_modes: lmax = {lmax} is not a 32-bit count")
+    p = _lib.nb_shell_params()
+    p.nbins, p.lmax, p.reserved = max(edges.shape[0] - 1, 0), int(lmax), 0
+    p.flags = _lib.NB_SHELL_RATES if rates else 0
+    if isinstance(center, str):
+        if center != "com":
+            raise ValueError('center is "com", "density" or three coordinates')
+        if velocity is not None:
+            raise ValueError('center="com" brings its own velocity')
+        p.flags |= _lib.NB_SHELL_CENTER_COM
+    else:
+        velocity = (0.0, 0.0, 0.0) if velocity is None else velocity
+        for k in range(3):
+            p.center[k], p.velocity[k] = float(center[k]), float(velocity[k])
+    for k in range(3):
+        p.axis[k] = float(axis[k])
+    p.edges = edges.ctypes.data_as(C.POINTER(C.c_double))
+    out = _lib.nb_shell_head()
+    nb_, nk = max(int(p.nbins), 1), (min(int(p.lmax), _lib.NB_SHELL_MAX_L) + 1) ** 2  # (the call refuses the rest)
+    bins = np.zeros(nb_, dtype=_lib.SHELL_BIN_DTYPE)
+    coef = np.zeros((nb_, nk * (2 if rates else 1)), dtype=np.float64)
+    check(call(handle, C.byref(p), C.byref(out), bins.ctypes.data, coef.ctypes.data))
+    vec = lambda a: np.array(list(a), dtype=np.float64)  # noqa: E731
+    return ShellModes(int(out.step_num), int(out.n), int(out.nonfinite), int(out.inside_count),
+                      int(out.outside_count), float(out.inside_mass), float(out.outside_mass), float(out.mass),
+                      vec(out.center), vec(out.velocity), vec(out.axis), vec(out.e1), vec(out.e2), int(out.flags),
+                      int(out.lmax), float(dt), edges.copy(), bins["count"].copy(), bins["m_r"].copy(),
+                      bins["m_ur"].copy(), coef[:, :nk].copy(), coef[:, nk:].copy() if rates else None)
 
 
 @dataclass(frozen=True)
@@ -2686,6 +2841,24 @@ class _Passes:
         suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
         return _disc_modes(getattr(_lib.lib(), "nb_disc_modes_" + suffix), self._h, self.sim_params().dt, edges,
                            nbins, rmin, rmax, log, mmax, axis, center, velocity)
+
+    def shell_modes(self, edges=None, *, nbins: int = 32, rmin=None, rmax=None, log: bool = True, lmax: int = 4,
+                    rates: bool = False, axis=(0.0, 1.0, 0.0), center="com", velocity=None) -> ShellModes:
+        """The spherical-harmonic sums of the current state per radial shell (nb_shell_modes_sim): the power per
+        degree l, the l = 1 vector, the l = 2 axes, phases and pattern speeds are methods of the ShellModes it
+        returns.  edges: the nbins + 1 radii, or rmin, rmax, nbins and log for radial_edges().  lmax: the highest
+        degree, 0 to 6, with rates=True (the time derivative of every sum too) 0 to 4.  axis: the polar axis.
+        center: "com" (the centre of mass and its velocity P/M, as diagnostics() returns them), three coordinates,
+        then with `velocity` as the frame's velocity (default: at rest), or "density": the density centre and its
+        velocity of knn_density(6), passed on as explicit values.  A several-GPU runner refuses."""
+        if isinstance(center, str) and center == "density":
+            if velocity is not None:
+                raise ValueError('center="density" brings its own velocity')
+            d = self.knn_density(6, neighbours=False)
+            center, velocity = d.center, d.center_velocity
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _shell_modes(getattr(_lib.lib(), "nb_shell_modes_" + suffix), self._h, self.sim_params().dt, edges,
+                            nbins, rmin, rmax, log, lmax, rates, axis, center, velocity)
 
     def field(self, points, *, accel: bool = True, potential: bool = True) -> Field:
         """The exact acceleration and potential of the current state at `points` ((M, 3), float32), summed

@@ -351,6 +351,21 @@ class nb_modes_head(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class nb_shell_params(C.Structure):
+    _fields_ = [("nbins", C.c_uint32), ("lmax", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
+                ("edges", C.POINTER(C.c_double))]
+
+
+class nb_shell_head(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("inside_count", C.c_uint64), ("outside_count", C.c_uint64), ("inside_mass", C.c_double),
+                ("outside_mass", C.c_double), ("mass", C.c_double), ("center", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("axis", C.c_double * 3), ("e1", C.c_double * 3),
+                ("e2", C.c_double * 3), ("nbins", C.c_uint32), ("lmax", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class nb_smooth_params(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
                 ("center", C.c_double * 3), ("velocity", C.c_double * 3), ("axis", C.c_double * 3),
@@ -427,6 +442,11 @@ MODES_BIN_DTYPE = np.dtype([("count", "<u8"), ("m_r", "<f8"), ("m_h2", "<f8")])
 MODES_DERIVED_DTYPE = np.dtype([("amplitude", "<f8"), ("phase", "<f8"), ("pattern_speed", "<f8"),
                                 ("bend_amplitude", "<f8"), ("bend_phase", "<f8")])
 
+# nb_shell_bin[] and nb_shell_derived[] as numpy record arrays
+SHELL_BIN_DTYPE = np.dtype([("count", "<u8"), ("m_r", "<f8"), ("m_ur", "<f8")])
+SHELL_DERIVED_DTYPE = np.dtype([("power", "<f8", (7,)), ("relative", "<f8", (7,)), ("dipole", "<f8", (3,)),
+                                ("quad_values", "<f8", (3,)), ("quad_axes", "<f8", (3, 3))])
+
 # nb_kin_derived[] as a numpy record array
 KIN_DERIVED_DTYPE = np.dtype([("mass", "<f8"), ("relative_velocity", "<f8", (3,)), ("mean_velocity", "<f8", (3,)),
                               ("dispersion", "<f8", (6,)), ("sigma2", "<f8"), ("sigma", "<f8"),
@@ -472,6 +492,8 @@ assert C.sizeof(nb_radii_params) == 152 and C.sizeof(nb_radii_stats) == 48
 assert C.sizeof(nb_radii_group) == 264 == RADII_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_modes_params) == 96 and C.sizeof(nb_modes_head) == 200
 assert MODES_BIN_DTYPE.itemsize == 24 and MODES_DERIVED_DTYPE.itemsize == 40
+assert C.sizeof(nb_shell_params) == 96 and C.sizeof(nb_shell_head) == 200
+assert SHELL_BIN_DTYPE.itemsize == 24 and SHELL_DERIVED_DTYPE.itemsize == 232
 assert C.sizeof(nb_smooth_params) == 152 and C.sizeof(nb_smooth_stats) == 248
 assert C.sizeof(nb_camera) == 52 and C.sizeof(nb_render_params) == 100 and C.sizeof(nb_render_stats) == 64
 
@@ -509,6 +531,9 @@ NB_SHAPE_CONVERGED, NB_SHAPE_UNCONVERGED, NB_SHAPE_DEGENERATE, NB_SHAPE_EMPTY = 
 NB_SHAPE_MAX_ITER, NB_SHAPE_ANY_STEP = 64, 0xFFFFFFFFFFFFFFFF
 NB_RADII_MAX_FRACTIONS, NB_RADII_CHUNK, NB_RADII_ANY_STEP = 16, 4096, 0xFFFFFFFFFFFFFFFF
 NB_MODES_MAX_BINS, NB_MODES_MAX_M, NB_MODES_FIELDS, NB_MODES_CHUNK, NB_MODES_CENTER_COM = 256, 8, 6, 4096, 1
+NB_SHELL_MAX_BINS, NB_SHELL_MAX_L, NB_SHELL_MAX_L_RATES, NB_SHELL_CHUNK = 256, 6, 4, 4096
+NB_SHELL_CENTER_COM, NB_SHELL_RATES = 1, 2
+NB_SHELL_FOUR_PI = float("12.566370614359172")  # the header's literal
 NB_SMOOTH_CENTER_COM, NB_SMOOTH_VELOCITY = 1, 2
 NB_SMOOTH_K = float("0.95492965855137201461")  # K = 3 / pi, the header's literal
 NB_SMOOTH_MAX_ENTRIES = 1 << 28
@@ -543,6 +568,7 @@ ABI_SYMBOLS = [
     "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
     "nb_group_radii_sim", "nb_group_radii_runner",
     "nb_disc_modes_sim", "nb_disc_modes_runner", "nb_disc_modes_derive",
+    "nb_shell_modes_sim", "nb_shell_modes_runner", "nb_shell_modes_derive",
     "nb_sim_smooth_map", "nb_runner_smooth_map", "nb_smooth_centres",
     "nb_camera_default", "nb_camera_view_proj", "nb_render_params_default", "nb_sim_render", "nb_naive_variant_count", "nb_naive_variant_name", "nb_sim_destroy",
     "nb_runner_create", "nb_runner_create_multi", "nb_runner_create_multi_let", "nb_runner_step_num", "nb_runner_step", "nb_runner_step_n", "nb_runner_read_particles",
@@ -630,6 +656,11 @@ def lib() -> C.CDLL:
     disc_modes = [vp, P(nb_modes_params), P(nb_modes_head), vp, vp]
     for suffix in ("sim", "runner"):
         getattr(L, "nb_disc_modes_" + suffix).argtypes = disc_modes
+    # ... and the shells' harmonics (include/nbody.h "Shell modes")
+    shell_modes = [vp, P(nb_shell_params), P(nb_shell_head), vp, vp]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_shell_modes_" + suffix).argtypes = shell_modes
+    L.nb_shell_modes_derive.argtypes = [P(nb_shell_head), vp, vp, vp, vp, vp]
     # ... and the fifteenth (include/nbody.h "Phase maps")
     phase_map = [vp, P(nb_phase_params), vp, vp, P(nb_phase_stats)]
     for suffix in ("sim", "runner"):

@@ -59,6 +59,9 @@ SOURCES = [
     # the frame, the recurrence and the three-level sums are specified operation by operation: no FMA
     # contraction
     ("nb_modes.hip", ["-ffp-contract=off"]),
+    # the Legendre and azimuth recurrences, their derivatives and the three-level sums are specified operation by
+    # operation: no FMA contraction
+    ("nb_shell.hip", ["-ffp-contract=off"]),
     # the quantities and the cell rule are specified operation by operation: no FMA contraction
     ("nb_phase.hip", ["-ffp-contract=off"]),
     # the pair arithmetic is specified operation by operation, and the bound counts its roundings: no

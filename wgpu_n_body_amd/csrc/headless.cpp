@@ -34,6 +34,8 @@
 //             [--phase-weight NAME] [--phase-axis X,Y,Z] [--phase-center com|X,Y,Z]]
 //            [--modes K --modes-range RMIN,RMAX [--modes-bins B] [--modes-m M] [--modes-log 0|1]
 //             [--modes-axis X,Y,Z] [--modes-center com|X,Y,Z]]
+//            [--shells K --shells-range RMIN,RMAX [--shells-bins B] [--shells-l L] [--shells-log 0|1]
+//             [--shells-rates 0|1] [--shells-axis X,Y,Z] [--shells-center com|X,Y,Z]]
 //            [--knn K [--knn-k 6]]
 //            [--kin K [--kin-k 32] [--kin-gradient 0|1]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
@@ -163,6 +165,15 @@
 // A_2 / A_0 over the annuli with mass, that annulus' mass-weighted mean radius, the phase and the single-snapshot
 // pattern speed of its m = 2 mode, and the largest warp tilt of any annulus (NaN where there is none).  The time it
 // takes is not part of any "Step Duration"; without --modes the output is unchanged.
+//
+// --shells K measures the spherical-harmonic sums (nb_shell_modes_runner) of step 0 and of every K-th step in B shells
+// (--shells-bins, default 32; --shells-log, default 1: of constant ratio) between RMIN and RMAX about the centre of
+// mass, unless --shells-center gives a point, with the polar axis --shells-axis (default 0,1,0), up to degree L
+// (--shells-l, default 4, at least 2); --shells-rates 1 (L at most 4) sums the time derivatives too.  One line
+// "shells <step> <Q2> <radius> <phase> <pattern_speed> <D1>" (every real %.17g): the largest sqrt(power_2 / power_0)
+// over the shells with mass, that shell's mass-weighted mean radius, the phase and (with rates, else NaN) the pattern
+// speed of its (2, 2) component, and the largest sqrt(power_1 / power_0) of any shell (NaN where there is none).  The
+// time it takes is not part of any "Step Duration"; without --shells the output is unchanged.
 //
 // --knn K finds the k-th nearest neighbour of every body (nb_runner_knn, k = --knn-k, default 6) of step 0 and of
 // every K-th step and prints one line "knn <step> <counted> <degenerate> <x> <y> <z> <vx> <vy> <vz>
@@ -760,6 +771,45 @@ static void print_modes(nbody::OfflineHeadless<Sim> &runner, const ModesOptions 
                 phase, omega, tilt);
 }
 
+struct ShellsOptions {
+    int every = 0;
+    bool have_range = false, log = true, rates = false;
+    double rmin = 0.0, rmax = 0.0;
+    uint32_t bins = 32, lmax = 4;
+    double axis[3] = {0.0, 1.0, 0.0};
+    std::vector<double> center;  // empty: the centre of mass
+};
+
+template <class Sim>
+static void print_shells(nbody::OfflineHeadless<Sim> &runner, const ShellsOptions &so) {
+    nbody::ShellParams p{};
+    p.lmax = so.lmax;
+    p.flags = (so.center.empty() ? NB_SHELL_CENTER_COM : 0u) | (so.rates ? NB_SHELL_RATES : 0u);
+    for (int a = 0; a < 3; ++a) {
+        p.axis[a] = so.axis[a];
+        p.center[a] = so.center.empty() ? 0.0 : so.center[a];
+    }
+    const nbody::ShellModes d = runner.shell_modes(nbody::radial_edges(so.rmin, so.rmax, so.bins, so.log), p);
+    const std::vector<double> rel1 = d.relative(1), rel2 = d.relative(2);
+    const double nan = std::nan("");
+    double q2 = nan, radius = nan, phase = nan, omega = nan, d1 = nan;
+    int best = -1;
+    for (size_t k = 0; k < rel2.size(); ++k) {
+        if (std::isfinite(rel2[k]) && (best < 0 || rel2[k] > q2)) {
+            q2 = rel2[k];
+            best = (int)k;
+        }
+        if (std::isfinite(rel1[k]) && !(rel1[k] <= d1)) d1 = rel1[k];
+    }
+    if (best >= 0) {
+        radius = d.bins[best].m_r / d.coefficient(best, 0, 0);
+        phase = d.phase(2, 2)[best];
+        if (d.rates()) omega = d.pattern_speed(2, 2)[best];
+    }
+    std::printf("shells %llu %.17g %.17g %.17g %.17g %.17g\n", (unsigned long long)d.head.step_num, q2, radius, phase,
+                omega, d1);
+}
+
 struct KnnOptions {
     int every = 0;
     uint32_t k = 6;
@@ -934,7 +984,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
                const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6,
-               const SectionsOptions &sections, const OrbitsOptions &stability) {
+               const SectionsOptions &sections, const OrbitsOptions &stability, const ShellsOptions &shells) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -959,6 +1009,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (lagr.every > 0) print_lagr(runner, lagr);
     if (radii.every > 0) print_radii(runner, radii);
     if (modes.every > 0) print_modes(runner, modes);
+    if (shells.every > 0) print_shells(runner, shells);
     if (!phase.dir.empty() && !write_phase(runner, phase)) return 1;
     if (!frames.dir.empty() && !write_frame(runner, frames)) return 1;
     for (int i = 0; i < steps; ++i) {
@@ -987,6 +1038,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (lagr.every > 0 && (i + 1) % lagr.every == 0) print_lagr(runner, lagr);
         if (radii.every > 0 && (i + 1) % radii.every == 0) print_radii(runner, radii);
         if (modes.every > 0 && (i + 1) % modes.every == 0) print_modes(runner, modes);
+        if (shells.every > 0 && (i + 1) % shells.every == 0) print_shells(runner, shells);
         if (!phase.dir.empty() && (i + 1) % phase.every == 0 && !write_phase(runner, phase)) return 1;
         if (!frames.dir.empty() && (i + 1) % frames.every == 0 && !write_frame(runner, frames)) return 1;
     }
@@ -1027,6 +1079,7 @@ int main(int argc, char **argv) {
     LagrOptions lagr;
     RadiiCliOptions radii;
     ModesOptions modes;
+    ShellsOptions shells;
     PhaseOptions phase;
     bool hop_saddle = false, hop_peak = false;
     uint64_t seed = 0;
@@ -1231,6 +1284,32 @@ int main(int argc, char **argv) {
             if (v == "com") phase.center.clear();
             else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &phase.center[0], &phase.center[1], &phase.center[2]) != 3) {
                 std::fprintf(stderr, "--phase-center takes com or X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--shells") shells.every = std::atoi(v.c_str());
+        else if (k == "--shells-range") {
+            if (std::sscanf(v.c_str(), "%lf,%lf", &shells.rmin, &shells.rmax) != 2) {
+                std::fprintf(stderr, "--shells-range takes RMIN,RMAX, not %s\n", v.c_str());
+                return 2;
+            }
+            shells.have_range = true;
+        }
+        else if (k == "--shells-bins") shells.bins = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--shells-l") shells.lmax = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--shells-log") shells.log = std::atoi(v.c_str()) != 0;
+        else if (k == "--shells-rates") shells.rates = std::atoi(v.c_str()) != 0;
+        else if (k == "--shells-axis") {
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &shells.axis[0], &shells.axis[1], &shells.axis[2]) != 3) {
+                std::fprintf(stderr, "--shells-axis takes X,Y,Z, not %s\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--shells-center") {
+            shells.center.assign(3, 0.0);
+            if (v == "com") shells.center.clear();
+            else if (std::sscanf(v.c_str(), "%lf,%lf,%lf", &shells.center[0], &shells.center[1], &shells.center[2]) != 3) {
+                std::fprintf(stderr, "--shells-center takes com or X,Y,Z, not %s\n", v.c_str());
                 return 2;
             }
         }
@@ -1495,6 +1574,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--modes needs --modes-range RMIN,RMAX and --modes-m M >= 2\n");
         return 2;
     }
+    if (shells.every > 0 && (!shells.have_range || shells.lmax < 2)) {
+        std::fprintf(stderr, "--shells needs --shells-range RMIN,RMAX and --shells-l L >= 2\n");
+        return 2;
+    }
     if (radii.every > 0 && !(radii.link > 0.0)) {
         std::fprintf(stderr, "--radii needs --radii-link B > 0\n");
         return 2;
@@ -1509,9 +1592,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

@@ -275,6 +275,13 @@ static int pass_disc_modes(H *h, const nb_modes_params *params, nb_modes_head *o
 }
 
 template <class H>
+static int pass_shell_modes(H *h, const nb_shell_params *params, nb_shell_head *out, nb_shell_bin *bins,
+                            double *coef) {
+    if (int rc = shell_check_params(params, out, bins, coef)) return rc;
+    return on_sim(h, "shell_modes", [&](SimBase &s) { return sim_shell_modes(s, *params, out, bins, coef); });
+}
+
+template <class H>
 static int pass_phase_map(H *h, const nb_phase_params *params, uint32_t *counts, double *planes,
                           nb_phase_stats *stats) {
     PhasePlan plan{};
@@ -742,6 +749,18 @@ int nb_disc_modes_runner(nb_runner *runner, const nb_modes_params *params, nb_mo
 }
 int nb_disc_modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out) {
     NB_GUARD({ return modes_derive(modes, nbins, mmax, m, out); })
+}
+int nb_shell_modes_sim(nb_sim *sim, const nb_shell_params *params, nb_shell_head *out, nb_shell_bin *bins,
+                       double *coef) {
+    return pass_shell_modes(sim, params, out, bins, coef);
+}
+int nb_shell_modes_runner(nb_runner *runner, const nb_shell_params *params, nb_shell_head *out, nb_shell_bin *bins,
+                          double *coef) {
+    return pass_shell_modes(runner, params, out, bins, coef);
+}
+int nb_shell_modes_derive(const nb_shell_head *head, const double *coef, nb_shell_derived *out, double *norm,
+                          double *phase, double *speed) {
+    NB_GUARD({ return shell_derive(head, coef, out, norm, phase, speed); })
 }
 int nb_shape_eigen(const double t[6], double lambda[3], double axes[9]) {
     if (!t || !lambda || !axes) {

@@ -721,6 +721,135 @@ int modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m,
     return NB_OK;
 }
 
+// nb_shell_modes_sim: everything that can be refused without a device, as modes_check_params
+int shell_check_params(const nb_shell_params *p, const nb_shell_head *out, const nb_shell_bin *bins,
+                       const double *coef) {
+    if (!p || !out || !bins || !coef || !p->edges) {
+        set_error("shell_modes: null %s", !p ? "params" : !out ? "out" : !bins ? "bins" : !coef ? "coef" : "edges");
+        return NB_ERR_INVALID;
+    }
+    if (p->nbins < 1 || p->nbins > NB_SHELL_MAX_BINS) {
+        set_error("shell_modes: nbins must be 1..%u (got %u)", NB_SHELL_MAX_BINS, p->nbins);
+        return NB_ERR_INVALID;
+    }
+    if (p->flags & ~(NB_SHELL_CENTER_COM | NB_SHELL_RATES)) {
+        set_error("shell_modes: unknown flag bits 0x%x", p->flags & ~(NB_SHELL_CENTER_COM | NB_SHELL_RATES));
+        return NB_ERR_INVALID;
+    }
+    const uint32_t lcap = (p->flags & NB_SHELL_RATES) ? NB_SHELL_MAX_L_RATES : NB_SHELL_MAX_L;
+    if (p->lmax > lcap) {
+        set_error("shell_modes: lmax must be 0..%u%s (got %u)", lcap,
+                  (p->flags & NB_SHELL_RATES) ? " with NB_SHELL_RATES" : "", p->lmax);
+        return NB_ERR_INVALID;
+    }
+    if (p->reserved) {
+        set_error("shell_modes: a reserved field != 0");
+        return NB_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k <= p->nbins; ++k) {
+        const double e = p->edges[k];
+        if (!std::isfinite(e) || e < 0.0 || (k > 0 && !(e > p->edges[k - 1]))) {
+            set_error("shell_modes: edges must be finite, >= 0 and strictly ascending (edges[%u] = %g)", k, e);
+            return NB_ERR_INVALID;
+        }
+    }
+    if (!(p->flags & NB_SHELL_CENTER_COM))
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(p->center[k]) || !std::isfinite(p->velocity[k])) {
+                set_error("shell_modes: center and velocity must be finite");
+                return NB_ERR_INVALID;
+            }
+    double n[3], e1[3], e2[3];
+    if (!axis_frame(p->axis, n, e1, e2)) {
+        set_error("shell_modes: needs a non-zero finite axis");
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// nb_shell_modes_derive
+int shell_derive(const nb_shell_head *head, const double *coef, nb_shell_derived *out, double *norm, double *phase,
+                 double *speed) {
+#pragma clang fp contract(off)
+    if (!head || !coef || !out) {
+        set_error("shell_modes_derive: null %s", !head ? "head" : !coef ? "coef" : "out");
+        return NB_ERR_INVALID;
+    }
+    const uint32_t nbins = head->nbins, lmax = head->lmax;
+    const bool rates = (head->flags & NB_SHELL_RATES) != 0;
+    if (nbins < 1 || nbins > NB_SHELL_MAX_BINS || lmax > (rates ? NB_SHELL_MAX_L_RATES : NB_SHELL_MAX_L) ||
+        (head->flags & ~(NB_SHELL_CENTER_COM | NB_SHELL_RATES))) {
+        set_error("shell_modes_derive: needs nbins in 1..%u, lmax in 0..%u (0..%u with rates) and known flags "
+                  "(got %u, %u, 0x%x)",
+                  NB_SHELL_MAX_BINS, NB_SHELL_MAX_L, NB_SHELL_MAX_L_RATES, nbins, lmax, head->flags);
+        return NB_ERR_INVALID;
+    }
+    constexpr uint32_t kMaxK = (NB_SHELL_MAX_L + 1) * (NB_SHELL_MAX_L + 1);
+    const uint32_t nk = (lmax + 1) * (lmax + 1), stride = nk * (rates ? 2u : 1u);
+    const double nan = std::nan("");
+    double fact[2 * NB_SHELL_MAX_L + 1], nlm[kMaxK];
+    fact[0] = 1.0;
+    for (uint32_t j = 1; j <= 2 * NB_SHELL_MAX_L; ++j) fact[j] = fact[j - 1] * (double)j;  // (exact)
+    for (uint32_t l = 0; l <= lmax; ++l) {
+        const double f = (double)(2 * l + 1) / NB_SHELL_FOUR_PI;
+        nlm[l * l] = std::sqrt(f);
+        for (uint32_t m = 1; m <= l; ++m)
+            nlm[l * l + 2 * m - 1] = nlm[l * l + 2 * m] = std::sqrt((2.0 * f) * (fact[l - m] / fact[l + m]));
+    }
+    const double *fn = head->axis, *f1 = head->e1, *f2 = head->e2;
+    for (uint32_t k = 0; k < nbins; ++k) {
+        const double *c = coef + (size_t)k * stride;
+        double a[kMaxK];
+        for (uint32_t i = 0; i < nk; ++i) {
+            a[i] = nlm[i] * c[i];
+            if (norm) norm[(size_t)k * nk + i] = a[i];
+            if (phase) phase[(size_t)k * nk + i] = nan;
+            if (speed) speed[(size_t)k * nk + i] = nan;
+        }
+        nb_shell_derived d;
+        for (uint32_t l = 0; l <= NB_SHELL_MAX_L; ++l) d.power[l] = d.relative[l] = nan;
+        for (int j = 0; j < 3; ++j) d.dipole[j] = d.quad_values[j] = nan;
+        for (int j = 0; j < 9; ++j) d.quad_axes[j] = nan;
+        for (uint32_t l = 0; l <= lmax; ++l) {
+            double sum = a[l * l] * a[l * l];
+            for (uint32_t i = l * l + 1; i < (l + 1) * (l + 1); ++i) sum = sum + a[i] * a[i];
+            d.power[l] = sum / (double)(2 * l + 1);
+        }
+        if (d.power[0] != 0.0 && d.power[0] == d.power[0])
+            for (uint32_t l = 0; l <= lmax; ++l) d.relative[l] = std::sqrt(d.power[l] / d.power[0]);
+        for (uint32_t l = 1; l <= lmax; ++l)
+            for (uint32_t m = 1; m <= l; ++m) {
+                const uint32_t i = l * l + 2 * m - 1;
+                const double cc = c[i], ss = c[i + 1], p2 = cc * cc + ss * ss;
+                if (p2 == 0.0 || p2 != p2) continue;
+                if (phase) phase[(size_t)k * nk + i] = std::atan2(ss, cc) / (double)m;
+                if (speed && rates)
+                    speed[(size_t)k * nk + i] = (cc * c[nk + i + 1] - ss * c[nk + i]) / ((double)m * p2);
+            }
+        if (lmax >= 1)
+            for (int j = 0; j < 3; ++j) d.dipole[j] = (a[2] * f1[j] + a[3] * f2[j]) + a[1] * fn[j];
+        if (lmax >= 2) {
+            const double q0 = nlm[4] * a[4], q1c = nlm[5] * a[5], q1s = nlm[6] * a[6], q2c = nlm[7] * a[7],
+                         q2s = nlm[8] * a[8];
+            double t[3][3], w[3][3], m6[6];
+            t[0][0] = (-0.5 * q0) + 3.0 * q2c;
+            t[1][1] = (-0.5 * q0) - 3.0 * q2c;
+            t[2][2] = q0;
+            t[0][1] = t[1][0] = 3.0 * q2s;
+            t[0][2] = t[2][0] = 1.5 * q1c;
+            t[1][2] = t[2][1] = 1.5 * q1s;
+            for (int i = 0; i < 3; ++i)
+                for (int b = 0; b < 3; ++b) w[i][b] = (f1[i] * t[0][b] + f2[i] * t[1][b]) + fn[i] * t[2][b];
+            int e = 0;
+            for (int i = 0; i < 3; ++i)
+                for (int j = i; j < 3; ++j) m6[e++] = (w[i][0] * f1[j] + w[i][1] * f2[j]) + w[i][2] * fn[j];
+            shape_eigen_host(m6, d.quad_values, d.quad_axes);  // (xx, xy, xz, yy, yz, zz)
+        }
+        out[k] = d;
+    }
+    return NB_OK;
+}
+
 // nb_sim_knn: everything that can be refused without a device
 int knn_check_params(const nb_knn_params *p) {
     if (!p) {

@@ -14,7 +14,7 @@ struct Workspace {
     virtual ~Workspace() = default;
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
-                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkPhase, kWorkTidal,
+                      kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkShell, kWorkPhase, kWorkTidal,
                       kWorkKin, kWorkOrbits, kWorkFof6, kWorkStability, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
@@ -269,6 +269,12 @@ int modes_check_params(const nb_modes_params *p, const nb_modes_head *out, const
                        const double *modes);
 int sim_disc_modes(SimBase &sim, const nb_modes_params &params, nb_modes_head *out, nb_modes_bin *bins, double *modes);
 int modes_derive(const double *modes, uint32_t nbins, uint32_t mmax, uint32_t m, nb_modes_derived *out);
+// nb_shell.hip: nb_shell_modes_sim behind the handle; shell_derive: nb_shell_modes_derive behind the ABI boundary
+int shell_check_params(const nb_shell_params *p, const nb_shell_head *out, const nb_shell_bin *bins,
+                       const double *coef);
+int sim_shell_modes(SimBase &sim, const nb_shell_params &params, nb_shell_head *out, nb_shell_bin *bins, double *coef);
+int shell_derive(const nb_shell_head *head, const double *coef, nb_shell_derived *out, double *norm, double *phase,
+                 double *speed);
 // nb_knn.hip: nb_sim_knn behind the handle
 int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,

@@ -221,6 +221,112 @@ DiscModes disc_modes(int (*call)(H *, const nb_modes_params *, nb_modes_head *, 
 }
 }  // namespace detail
 
+// The spherical-harmonic sums per radial shell (nb_shell_modes_sim; no reference counterpart): the header, the bins,
+// coef[nbins][(lmax + 1)^2 (1 + rates)] (sum i of (l, m): l^2, l^2 + 2m - 1 for C, l^2 + 2m for S; the rates in a
+// second block) and the edges they lie between
+using ShellParams = nb_shell_params;    // 96 B
+using ShellBin = nb_shell_bin;          // 24 B: count, sum mu r, sum mu u_r
+using ShellDerived = nb_shell_derived;  // 232 B: power and relative power per l, the l = 1 vector, the l = 2 axes
+struct ShellModes {
+    nb_shell_head head{};
+    std::vector<ShellBin> bins;
+    std::vector<double> coef;
+    std::vector<double> edges;
+    double dt = 0.0;  // the simulator's time step (phase_between)
+    bool rates() const { return (head.flags & NB_SHELL_RATES) != 0; }
+    size_t terms() const { return (size_t)(head.lmax + 1) * (head.lmax + 1); }
+    static size_t index(uint32_t l, uint32_t m, bool sine = false) { return (size_t)l * l + (m ? 2 * m - (sine ? 0 : 1) : 0); }
+    // sum (l, m) of a bin: the cosine sum, or with sine the sine sum (m >= 1)
+    double coefficient(size_t bin, uint32_t l, uint32_t m, bool sine = false) const {
+        return coef[bin * terms() * (rates() ? 2 : 1) + index(l, m, sine)];
+    }
+    // ... and its time derivative (needs NB_SHELL_RATES)
+    double rate(size_t bin, uint32_t l, uint32_t m, bool sine = false) const {
+        return coef[bin * terms() * 2 + terms() + index(l, m, sine)];
+    }
+    // nb_shell_modes_derive: one record per bin; norm, phase and speed are null or resized to nbins (lmax + 1)^2
+    std::vector<ShellDerived> derived(std::vector<double> *norm = nullptr, std::vector<double> *phase = nullptr,
+                                      std::vector<double> *speed = nullptr) const {
+        std::vector<ShellDerived> d(bins.size());
+        for (std::vector<double> *v : {norm, phase, speed})
+            if (v) v->assign(bins.size() * terms(), 0.0);
+        check(nb_shell_modes_derive(&head, coef.data(), d.data(), norm ? norm->data() : nullptr,
+                                    phase ? phase->data() : nullptr, speed ? speed->data() : nullptr));
+        return d;
+    }
+    // sum_m a_lm^2 / (2l + 1) per bin, and sqrt(power_l / power_0)
+    std::vector<double> power(uint32_t l) const { return per_l(l, false); }
+    std::vector<double> relative(uint32_t l) const { return per_l(l, true); }
+    // the l = 1 vector per bin, in the state's coordinates
+    std::vector<std::array<double, 3>> dipole() const {
+        const std::vector<ShellDerived> d = derived();
+        std::vector<std::array<double, 3>> out(d.size());
+        for (size_t k = 0; k < d.size(); ++k) std::copy(d[k].dipole, d[k].dipole + 3, out[k].begin());
+        return out;
+    }
+    // the l = 2 tensor's eigenvalues, descending, and unit vectors (axes[3 j + i]: component i of vector j) per bin
+    std::pair<std::vector<std::array<double, 3>>, std::vector<std::array<double, 9>>> quadrupole_axes() const {
+        const std::vector<ShellDerived> d = derived();
+        std::vector<std::array<double, 3>> values(d.size());
+        std::vector<std::array<double, 9>> axes(d.size());
+        for (size_t k = 0; k < d.size(); ++k) {
+            std::copy(d[k].quad_values, d[k].quad_values + 3, values[k].begin());
+            std::copy(d[k].quad_axes, d[k].quad_axes + 9, axes[k].begin());
+        }
+        return {values, axes};
+    }
+    // atan2(S, C) / m of component (l, m) per bin
+    std::vector<double> phase(uint32_t l, uint32_t m) const { return column(l, m, 1); }
+    // (C DS - S DC) / (m (C^2 + S^2)) per bin: the rate at which component (l, m) turns about the axis
+    std::vector<double> pattern_speed(uint32_t l, uint32_t m) const { return column(l, m, 2); }
+    // the phase difference of component (l, m) per bin between two measurements, wrapped into (-pi/m, pi/m]
+    std::vector<double> phase_between(const ShellModes &other, uint32_t l, uint32_t m) const {
+        const std::vector<double> a = phase(l, m), b = other.phase(l, m);
+        const double period = 2.0 * 3.14159265358979323846 / (double)m;
+        std::vector<double> w(a.size());
+        for (size_t k = 0; k < a.size(); ++k) {
+            const double x = b[k] - a[k];
+            w[k] = x - period * std::ceil(x / period - 0.5);
+        }
+        return w;
+    }
+
+   private:
+    std::vector<double> per_l(uint32_t l, bool relative_to_l0) const {
+        if (l > head.lmax) throw std::invalid_argument("ShellModes: needs l <= lmax");
+        const std::vector<ShellDerived> d = derived();
+        std::vector<double> out(d.size());
+        for (size_t k = 0; k < d.size(); ++k) out[k] = relative_to_l0 ? d[k].relative[l] : d[k].power[l];
+        return out;
+    }
+    std::vector<double> column(uint32_t l, uint32_t m, int which) const {
+        if (m < 1 || m > l || l > head.lmax) throw std::invalid_argument("ShellModes: needs 1 <= m <= l <= lmax");
+        std::vector<double> all, out(bins.size());
+        derived(nullptr, which == 1 ? &all : nullptr, which == 2 ? &all : nullptr);
+        for (size_t k = 0; k < out.size(); ++k) out[k] = all[k * terms() + index(l, m)];
+        return out;
+    }
+};
+
+namespace detail {
+// p: lmax, flags (NB_SHELL_CENTER_COM, NB_SHELL_RATES), centre, velocity and axis (nbins and edges are set here)
+template <class H>
+ShellModes shell_modes(int (*call)(H *, const nb_shell_params *, nb_shell_head *, nb_shell_bin *, double *), H *h,
+                       double dt, const std::vector<double> &edges, ShellParams p) {
+    ShellModes r;
+    r.edges = edges;
+    r.dt = dt;
+    r.bins.resize(edges.size() > 1 ? edges.size() - 1 : 1);
+    const size_t lm = std::min<size_t>(p.lmax, NB_SHELL_MAX_L) + 1;
+    r.coef.resize(r.bins.size() * lm * lm * 2);  // (the call refuses what it does not take)
+    p.nbins = edges.empty() ? 0u : (uint32_t)(edges.size() - 1);
+    p.edges = r.edges.data();
+    check(call(h, &p, &r.head, r.bins.data(), r.coef.data()));
+    r.coef.resize(r.bins.size() * r.terms() * (r.rates() ? 2 : 1));
+    return r;
+}
+}  // namespace detail
+
 // The field at a set of points (no reference counterpart): the samples and what the call measured
 struct Field {
     std::vector<FieldSample> samples;
@@ -1236,6 +1342,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto group_shapes = nb_sim_group_shapes;
     static constexpr auto group_radii = nb_group_radii_sim;
     static constexpr auto disc_modes = nb_disc_modes_sim;
+    static constexpr auto shell_modes = nb_shell_modes_sim;
     static constexpr auto phase_map = nb_phase_map_sim;
     static constexpr auto tidal = nb_tidal_sim;
     static constexpr auto orbits = nb_orbits_sim;
@@ -1261,6 +1368,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto group_shapes = nb_runner_group_shapes;
     static constexpr auto group_radii = nb_group_radii_runner;
     static constexpr auto disc_modes = nb_disc_modes_runner;
+    static constexpr auto shell_modes = nb_shell_modes_runner;
     static constexpr auto phase_map = nb_phase_map_runner;
     static constexpr auto tidal = nb_tidal_runner;
     static constexpr auto orbits = nb_orbits_runner;
@@ -1297,6 +1405,13 @@ class Passes {
         SimParams sp{};
         check(Abi::sim_params(h_, &sp));
         return detail::disc_modes(Abi::disc_modes, h_, (double)sp.dt, edges, p);
+    }
+    // the spherical-harmonic sums per radial shell between `edges`, the polar axis p.axis; p: lmax, flags
+    // (NB_SHELL_CENTER_COM, NB_SHELL_RATES), centre, velocity and axis (nbins and edges are set here)
+    ShellModes shell_modes(const std::vector<double> &edges, const ShellParams &p) {
+        SimParams sp{};
+        check(Abi::sim_params(h_, &sp));
+        return detail::shell_modes(Abi::shell_modes, h_, (double)sp.dt, edges, p);
     }
     // the exact acceleration and potential of the current state at points (3 floats each); flags: NB_FIELD_*
     ProjectedMap projected_map(const MapParams &p) { return detail::projected_map(Abi::map, h_, p); }
