@@ -1506,6 +1506,86 @@ int nb_sim_knn(nb_sim *sim, const nb_knn_params *params, double *r2, uint32_t *k
                double *density, nb_knn_stats *stats);
 
 /* ------------------------------------------------------------------------- */
+/* Minimum spanning tree -- the friends-of-friends groups of every linking    */
+/* length at once (no reference counterpart)                                  */
+/* ------------------------------------------------------------------------- */
+/* The Euclidean minimum spanning tree of the counted bodies of the state
+ * nb_sim_read_particles would return.  The components of nb_sim_fof(link) are the
+ * components of the tree's edges with d2 <= link link, so the sorted edge list is the
+ * whole single-linkage hierarchy: c - 1 merges, each at a known length.  The rule,
+ * which DESIGN.md 6y states in full: binary64 from the binary32 state, one rounding
+ * per operation, no contraction:
+ *   counted     the predicate of nb_sim_knn; c is the number of counted bodies
+ *   distance    d2(i, j) of nb_sim_knn (the expression of nb_sim_fof), bitwise
+ *               symmetric in i and j
+ *   edge order  pairs of counted bodies i != j in ascending (d2(i, j), min(i, j),
+ *               max(i, j)): strict and total; the indices are those
+ *               nb_sim_read_particles returns at that moment (a TreeSim reorders
+ *               its bodies at every step)
+ *   tree        the minimum spanning tree of the complete graph on the counted
+ *               bodies under that order: unique, c - 1 edges (0 for c <= 1)
+ *   output      in ascending edge order: edge_lo[e] < edge_hi[e] (body indices) and
+ *               d2[e]; per body, degree[i] = the number of tree edges at body i, or
+ *               NB_MST_NONE for a body that is not counted
+ *   stats       edges = max(c, 1) - 1; rounds = the Boruvka rounds that ran (every
+ *               component takes the first edge of the order that leaves it, all of
+ *               them are united; rounds run while more than one component is left)
+ *               and components_after[r] = the components after round r (0 from
+ *               `rounds` on); d2_min, d2_max = the first and last d2 (0 without
+ *               edges); lo, hi, h = the bounds of the counted bodies and the side of
+ *               the finest search cell (0 for c == 0)
+ * The tree is unique given the state, and Boruvka's rounds under a total order are
+ * deterministic, so every integer and every double is exact and bit-identical
+ * between calls, whatever order the device's threads ran in.  No float atomics.
+ * The call is ordered after the enqueued steps on the simulator's stream, ends
+ * with one synchronisation, reports a TreeSim's status words as
+ * nb_sim_read_particles does, and does not change the trajectory.
+ * "mst_span_cells" (nb_sim_set_tuning, 1..8, default 3), "mst_block_queries" (1, 2 or
+ * 4, default 4), "mst_skip_runs" (0 or 1, default 1: stretches of a body's own
+ * component are stepped over) and "mst_shared_bound" (0 or 1, default 1: the bodies of
+ * a component share the smallest d2 any of them has found) are for speed and
+ * testing only: none changes a bit of the result. */
+#define NB_MST_NONE 0xFFFFFFFFu
+#define NB_MST_MAX_ROUNDS 32u
+
+typedef struct nb_mst_params {
+    uint32_t flags;      /* 0 */
+    uint32_t reserved32; /* 0 */
+    uint64_t reserved;   /* 0 */
+} nb_mst_params;
+
+typedef struct nb_mst_stats {
+    uint64_t step_num, n, nonfinite, edges;
+    uint32_t rounds, reserved;
+    uint32_t components_after[NB_MST_MAX_ROUNDS];
+    double d2_min, d2_max;
+    double lo[3], hi[3], h;
+} nb_mst_stats;
+
+/* The tree of a simulator's current state: edge_lo, edge_hi and d2 have room for n - 1 entries (n the
+ * simulator's bodies), of which the first stats->edges are written; degree has n.  Every output pointer may
+ * be null: what is not asked for is not copied; a call with none of them synchronises and measures nothing.
+ * The outputs are written only by a call that succeeds.  NB_ERR_INVALID for a null handle or params,
+ * unknown flags or a reserved field != 0 -- all checked before any device call; NB_ERR_UNSUPPORTED for a
+ * sharded simulator (placement world > 1) and for more than 2^31 - 1 bodies (the rounds enqueued, at most 31, and
+ * components_after rest on that cap). */
+int nb_mst_sim(nb_sim *sim, const nb_mst_params *params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+               uint32_t *degree, nb_mst_stats *stats);
+/* Host only.  The tree cut at `link`: the edges with d2 <= link link united (the square formed once, as
+ * nb_sim_fof forms it), labels[i] = the smallest body index of i's component, or NB_FOF_NONE for a body with
+ * degree[i] == NB_MST_NONE (degree null: every body counts); *components (may be null) = their number.  The
+ * labels are those of nb_sim_fof(link, min_members 1) on the same state.  NB_ERR_INVALID for a null array that
+ * is needed, an edge with lo >= hi or hi >= n, n > 2^32 - 1, edges >= max(n, 1), and a link that is not finite
+ * and > 0 or whose square is not a positive finite double.  There are no cells: no link is too small. */
+int nb_mst_cut(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, const double *d2,
+               const uint32_t *degree, double link, uint32_t *labels, size_t *components);
+/* Host only.  The dendrogram: per edge in order the labels (smallest body indices, label_a[e] < label_b[e]) and
+ * the sizes of the two components it joins.  Each output may be null.  NB_ERR_INVALID as nb_mst_cut, and for
+ * edges that close a cycle. */
+int nb_mst_linkage(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, uint32_t *label_a,
+                   uint32_t *label_b, uint32_t *count_a, uint32_t *count_b);
+
+/* ------------------------------------------------------------------------- */
 /* Density-peak groups -- which bodies belong to which density peak (HOP,     */
 /* Eisenstein & Hut 1998; no reference counterpart)                           */
 /* ------------------------------------------------------------------------- */
@@ -2727,6 +2807,10 @@ int nb_local_kinematics_runner(nb_runner *runner, const nb_kin_params *params, d
  * runner. */
 int nb_fof6_runner(nb_runner *runner, const nb_fof6_params *params, uint32_t *labels, uint32_t *group_of,
                    nb_fof_group *groups, size_t group_capacity, nb_fof_stats *stats);
+/* nb_mst_sim of the runner's simulator: the same refusals, and NB_ERR_UNSUPPORTED for a several-GPU
+ * runner. */
+int nb_mst_runner(nb_runner *runner, const nb_mst_params *params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+                  uint32_t *degree, nb_mst_stats *stats);
 /* nb_sim_smooth_map of the runner's simulator (no reference counterpart).
  * NB_ERR_UNSUPPORTED for a several-GPU runner (nb_runner_create_multi*). */
 int nb_runner_smooth_map(nb_runner *runner, const nb_smooth_params *params, const double *s, uint32_t *counts,

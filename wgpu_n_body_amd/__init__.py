@@ -43,6 +43,7 @@ __all__ = ["SimParams", "AddParams", "Placement", "Simulator", "NaiveSim", "Tree
            "FofGroups", "FofStats", "FOF_NONE", "PhaseSpaceGroups",
            "BoundGroups", "BoundStats", "BOUND_CONVERGED", "BOUND_DISSOLVED", "BOUND_UNCONVERGED", "BOUND_SKIPPED",
            "KnnDensity", "KnnStats", "KNN_NONE",
+           "SpanningTree", "MstStats", "MST_NONE",
            "LocalKinematics", "KinStats", "kinematics_derive", "KIN_SHORT", "KIN_NOT_COUNTED", "KIN_DEGENERATE",
            "KIN_SINGULAR",
            "HopGroups", "HopStats", "HOP_NONE",
@@ -1855,6 +1856,153 @@ def _knn_density(call, handle, n, k, density, neighbours) -> KnnDensity:
     return KnnDensity(kk, r2, kth, mass_in, rho, _knn_stats(st))
 
 
+MST_NONE = _lib.NB_MST_NONE
+
+
+@dataclass(frozen=True)
+class MstStats:
+    """nb_mst_stats (include/nbody.h "Minimum spanning tree")."""
+    step_num: int
+    n: int
+    nonfinite: int
+    edges: int
+    rounds: int                   # the Boruvka rounds that ran
+    components_after: np.ndarray  # (32,) uint32: the components after each round, 0 from `rounds` on
+    d2_min: float
+    d2_max: float
+    lo: np.ndarray                # the bounds of the counted bodies and the side of the finest search cell
+    hi: np.ndarray
+    h: float
+
+
+@dataclass(frozen=True)
+class SpanningTree:
+    """nb_mst_sim's tree (include/nbody.h "Minimum spanning tree"; no reference counterpart): the Euclidean minimum
+    spanning tree of the counted bodies under the order (d2, lo, hi).  edges: (m, 2) uint32, lo < hi, the body
+    indices of read_particles() at that moment; d2: (m,) float64, ascending; degree: (n,) uint32, MST_NONE for a body
+    that is not counted, or None when not asked for.  The components of fof_groups(link, min_members=1) are those
+    of the edges with d2 <= link^2: cut(link) returns them, for every link, without another pass over the bodies."""
+    edges: np.ndarray
+    d2: np.ndarray
+    degree: Optional[np.ndarray]
+    stats: MstStats
+
+    @property
+    def length(self) -> np.ndarray:
+        """sqrt(d2): the edges' lengths, ascending."""
+        return np.sqrt(self.d2)
+
+    @property
+    def total_length(self) -> float:
+        """The lengths added in edge order from 0 (what the C++ mirror and `headless --mst` print)."""
+        return float(np.cumsum(self.length)[-1]) if len(self.d2) else 0.0
+
+    @property
+    def counted(self) -> int:
+        return self.stats.n - self.stats.nonfinite
+
+    def longest(self):
+        """(lo, hi, length) of the last edge, the one whose removal splits the state at the largest scale; None
+        for a tree without edges."""
+        if len(self.d2) == 0:
+            return None
+        return int(self.edges[-1, 0]), int(self.edges[-1, 1]), float(math.sqrt(self.d2[-1]))
+
+    def _columns(self):
+        return np.ascontiguousarray(self.edges[:, 0]), np.ascontiguousarray(self.edges[:, 1])
+
+    def cut(self, link: float) -> np.ndarray:
+        """(n,) uint32: per body the smallest index of its component under the edges with d2 <= link^2
+        (nb_mst_cut), FOF_NONE for a body that is not counted: fof_groups(link, min_members=1).labels of the same
+        state, and an assignment shapes_of / radii_of (with m = n rows: a label is a body index) and
+        phase_map(values=...) accept.  A tree taken with degree=False of a state with bodies that are not counted
+        cannot tell them apart and raises, as to_scipy does."""
+        if self.degree is None and self.stats.nonfinite:
+            raise ValueError("cut: a state with bodies that are not counted needs degree=True")
+        n, m = self.stats.n, len(self.d2)
+        lo, hi = self._columns()
+        labels = np.empty(n, dtype=np.uint32)
+        deg = None if self.degree is None else self.degree.ctypes.data
+        check(_lib.lib().nb_mst_cut(n, m, lo.ctypes.data, hi.ctypes.data, self.d2.ctypes.data, deg, float(link),
+                                    labels.ctypes.data, None))
+        return labels
+
+    def linkage(self):
+        """The dendrogram (nb_mst_linkage): per edge in order label_a < label_b, the smallest indices of the two
+        components it joins, and count_a, count_b, their sizes; four (m,) uint32 arrays."""
+        n, m = self.stats.n, len(self.d2)
+        lo, hi = self._columns()
+        out = [np.empty(m, dtype=np.uint32) for _ in range(4)]
+        check(_lib.lib().nb_mst_linkage(n, m, lo.ctypes.data, hi.ctypes.data, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def group_counts(self, links, min_members: int = 1) -> np.ndarray:
+        """The percolation curve: per link the number of components of at least min_members bodies, from one pass
+        over the linkage: a merge changes the number by [a + b >= M] - [a >= M] - [b >= M]."""
+        mm = int(min_members)
+        if mm < 1:
+            raise ValueError("group_counts: min_members must be at least 1")
+        links = np.atleast_1d(np.asarray(links, dtype=np.float64))
+        if not np.all(np.isfinite(links) & (links > 0.0)):
+            raise ValueError("group_counts: every link must be finite and > 0")
+        _, _, ca, cb = self.linkage()
+        ca, cb = ca.astype(np.int64), cb.astype(np.int64)
+        delta = (ca + cb >= mm).astype(np.int64) - (ca >= mm) - (cb >= mm)
+        after = np.concatenate(([self.counted if mm == 1 else 0], delta)).cumsum()
+        return after[np.searchsorted(self.d2, links * links, side="right")]
+
+    def to_scipy(self) -> np.ndarray:
+        """The (m, 4) linkage matrix of scipy.cluster.hierarchy: per merge the two cluster ids (the smaller first), the
+        distance sqrt(d2) and the new cluster's size; observation k is the k-th counted body, merge e makes cluster
+        c + e."""
+        la, lb, ca, cb = self.linkage()
+        c, m = self.counted, len(self.d2)
+        if self.degree is None:
+            if self.stats.nonfinite:
+                raise ValueError("to_scipy: a state with bodies that are not counted needs degree=True")
+            obs = np.arange(self.stats.n, dtype=np.int64)
+        else:
+            obs = np.cumsum(self.degree != MST_NONE) - 1
+        cid = {}
+        z = np.empty((m, 4), dtype=np.float64)
+        dist = self.length
+        for e in range(m):
+            a, b = int(la[e]), int(lb[e])
+            x, y = cid.get(a, int(obs[a])), cid.get(b, int(obs[b]))
+            z[e] = (min(x, y), max(x, y), dist[e], int(ca[e]) + int(cb[e]))
+            cid[a] = c + e
+        return z
+
+    def largest_gap(self):
+        """(ratio, link): the largest ratio length[e + 1] / length[e] over the edges of positive length, and
+        length[e], the link just below the gap -- cut(link) unites everything shorter.  (nan, nan) with fewer than two
+        such edges."""
+        ln = self.length
+        ln = ln[ln > 0.0]
+        if len(ln) < 2:
+            return float("nan"), float("nan")
+        r = ln[1:] / ln[:-1]
+        e = int(np.argmax(r))
+        return float(r[e]), float(ln[e])
+
+
+def _spanning_tree(call, handle, n, degree) -> SpanningTree:
+    p = _lib.nb_mst_params()
+    room = max(n - 1, 0)
+    lo = np.empty(room, dtype=np.uint32)
+    hi = np.empty(room, dtype=np.uint32)
+    d2 = np.empty(room, dtype=np.float64)
+    deg = np.empty(n, dtype=np.uint32) if degree else None
+    st = _lib.nb_mst_stats()
+    check(call(handle, C.byref(p), lo.ctypes.data, hi.ctypes.data, d2.ctypes.data,
+               deg.ctypes.data if degree else None, C.byref(st)))
+    m = int(st.edges)
+    stats = MstStats(int(st.step_num), int(st.n), int(st.nonfinite), m, int(st.rounds),
+                     np.array(st.components_after[:], dtype=np.uint32), float(st.d2_min), float(st.d2_max),
+                     np.array(st.lo[:], dtype=np.float64), np.array(st.hi[:], dtype=np.float64), float(st.h))
+    return SpanningTree(np.stack((lo[:m], hi[:m]), axis=1), d2[:m].copy(), deg, stats)
+
+
 KIN_SHORT, KIN_NOT_COUNTED = _lib.NB_KIN_SHORT, _lib.NB_KIN_NOT_COUNTED
 KIN_DEGENERATE, KIN_SINGULAR = _lib.NB_KIN_DEGENERATE, _lib.NB_KIN_SINGULAR
 
@@ -3044,6 +3192,15 @@ class _Passes:
         bodies at every step.  labels=False leaves the per-body labels on the device.  A several-GPU runner refuses."""
         return _fof_groups(self._pass("fof"), self._h, int(self.sim_params().particle_num), link, min_members,
                            labels)
+
+    def spanning_tree(self, *, degree: bool = True) -> SpanningTree:
+        """The Euclidean minimum spanning tree of the current state (nb_mst_sim): its edges in ascending order are the
+        single-linkage hierarchy, so .cut(link) gives fof_groups(link, min_members=1)'s labels for every link at
+        once, .group_counts(links) the percolation curve and .linkage() the dendrogram.  The body indices are those
+        of read_particles() now.  A several-GPU runner refuses."""
+        suffix = "sim" if self._ABI == "nb_sim_" else "runner"  # (the noun-first names of include/nbody.h)
+        return _spanning_tree(getattr(_lib.lib(), "nb_mst_" + suffix), self._h,
+                              int(self.sim_params().particle_num), degree)
 
     def phase_space_groups(self, link: float, vlink: float, *, min_members: int = 20,
                            labels: bool = True) -> PhaseSpaceGroups:

@@ -253,6 +253,17 @@ class nb_knn_stats(C.Structure):
                 ("peak_index", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class nb_mst_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved32", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class nb_mst_stats(C.Structure):
+    _fields_ = [("step_num", C.c_uint64), ("n", C.c_uint64), ("nonfinite", C.c_uint64), ("edges", C.c_uint64),
+                ("rounds", C.c_uint32), ("reserved", C.c_uint32), ("components_after", C.c_uint32 * 32),
+                ("d2_min", C.c_double), ("d2_max", C.c_double), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+                ("h", C.c_double)]
+
+
 class nb_kin_params(C.Structure):
     _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
 
@@ -481,6 +492,7 @@ assert C.sizeof(nb_fof_group) == 80 == FOF_GROUP_DTYPE.itemsize and C.sizeof(nb_
 assert C.sizeof(nb_bound_params) == 40 and C.sizeof(nb_bound_stats) == 112
 assert C.sizeof(nb_bound_group) == 128 == BOUND_GROUP_DTYPE.itemsize
 assert C.sizeof(nb_knn_params) == 16 and C.sizeof(nb_knn_stats) == 128
+assert C.sizeof(nb_mst_params) == 16 and C.sizeof(nb_mst_stats) == 240
 assert C.sizeof(nb_kin_params) == 16 and C.sizeof(nb_kin_stats) == 56 and KIN_DERIVED_DTYPE.itemsize == 256
 assert C.sizeof(nb_hop_params) == 40 and C.sizeof(nb_hop_stats) == 96 and C.sizeof(nb_hop_regroup_params) == 24
 assert C.sizeof(nb_hop_boundary) == 24 == HOP_BOUNDARY_DTYPE.itemsize
@@ -520,6 +532,7 @@ NB_FOF_NONE, NB_FOF_MAX_CELLS_PER_AXIS = 0xFFFFFFFF, 1 << 21
 NB_BOUND_CONVERGED, NB_BOUND_DISSOLVED, NB_BOUND_UNCONVERGED, NB_BOUND_SKIPPED = 1, 2, 4, 8
 NB_BOUND_MAX_ITER = 64
 NB_KNN_NONE, NB_KNN_MAX_K = 0xFFFFFFFF, 64
+NB_MST_NONE, NB_MST_MAX_ROUNDS = 0xFFFFFFFF, 32
 NB_KIN_SELF, NB_KIN_MOMENTS, NB_KIN_GRADS = 1, 10, 15
 NB_KIN_SHORT, NB_KIN_NOT_COUNTED, NB_KIN_DEGENERATE, NB_KIN_SINGULAR = 1, 2, 4, 8
 NB_HOP_NONE = 0xFFFFFFFF
@@ -563,6 +576,7 @@ ABI_SYMBOLS = [
     "nb_sim_bound", "nb_runner_bound",
     "nb_sim_knn", "nb_runner_knn",
     "nb_local_kinematics_sim", "nb_local_kinematics_runner", "nb_local_kinematics_derive",
+    "nb_mst_sim", "nb_mst_runner", "nb_mst_cut", "nb_mst_linkage",
     "nb_sim_hop", "nb_runner_hop", "nb_hop_regroup",
     "nb_sim_halo_profiles", "nb_runner_halo_profiles", "nb_halo_enclosed", "nb_halo_overdensity",
     "nb_sim_group_shapes", "nb_runner_group_shapes", "nb_shape_eigen",
@@ -694,6 +708,12 @@ def lib() -> C.CDLL:
     for suffix in ("sim", "runner"):
         getattr(L, "nb_orbit_stability_" + suffix).argtypes = orbit_stability
     L.nb_orbit_stability_derive.argtypes = [C.c_double, C.c_uint32, C.c_uint32, sz, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    # ... and the spanning tree (include/nbody.h "Minimum spanning tree")
+    mst = [vp, P(nb_mst_params), vp, vp, vp, vp, P(nb_mst_stats)]
+    for suffix in ("sim", "runner"):
+        getattr(L, "nb_mst_" + suffix).argtypes = mst
+    L.nb_mst_cut.argtypes = [sz, sz, vp, vp, vp, vp, C.c_double, vp, P(sz)]
+    L.nb_mst_linkage.argtypes = [sz, sz, vp, vp, vp, vp, vp, vp]
     L.nb_orbit_records.argtypes = [C.c_uint32, C.c_uint32]
     L.nb_orbit_records.restype = C.c_uint32
     L.nb_orbit_phase.argtypes = [C.c_double, C.c_double, u64, P(C.c_double), P(C.c_double)]

@@ -40,6 +40,8 @@ SOURCES = [
     ("nb_bound.hip", ["-ffp-contract=off"]),
     # the neighbour order and the density are specified operation by operation: no FMA contraction
     ("nb_knn.hip", ["-ffp-contract=off"]),
+    # the edge order is nb_knn.hip's distance, specified operation by operation: no FMA contraction
+    ("nb_mst.hip", ["-ffp-contract=off"]),
     # the neighbour list, the terms and the ordered sums are specified operation by operation: no FMA
     # contraction
     ("nb_kinematics.hip", ["-ffp-contract=off"]),

@@ -37,6 +37,7 @@
 //            [--shells K --shells-range RMIN,RMAX [--shells-bins B] [--shells-l L] [--shells-log 0|1]
 //             [--shells-rates 0|1] [--shells-axis X,Y,Z] [--shells-center com|X,Y,Z]]
 //            [--knn K [--knn-k 6]]
+//            [--mst K [--mst-links L1,L2,...] [--mst-min M] [--mst-dump DIR]]
 //            [--kin K [--kin-k 32] [--kin-gradient 0|1]]
 //            [--hop K [--hop-k 64,16,4] [--hop-min M] [--hop-density-min D] [--hop-saddle S --hop-peak P] [--hop-top T]]
 //            [--halo K --halo-link B --halo-range RMIN,RMAX [--halo-bins 32] [--halo-min M] [--halo-top T]
@@ -180,6 +181,13 @@
 // <peak_density> <peak_index>" (every real %.17g): the density centre and its velocity, the largest density and
 // the body that holds it.  The time it takes is not part of any "Step Duration"; without --knn the output is
 // unchanged.
+//
+// --mst K finds the minimum spanning tree (nb_mst_runner) of step 0 and of every K-th step and prints one line
+// "mst <step> <edges> <rounds> <total length> <longest edge> <groups at L1> <groups at L2> ..." (every real %.17g): the
+// groups are the components of at least M bodies (--mst-min, default 1) the tree has at each link of --mst-links, what
+// nb_runner_fof finds at that link.  --mst-dump DIR writes the tree as DIR/mst_<step>.npy: NumPy format 1.0, <f8, shape
+// (edges, 3) -- lo, hi and d2 per edge, in ascending order.  The time it takes is not part of any "Step Duration";
+// without --mst the output is unchanged.
 //
 // --kin K measures how the k nearest neighbours of every body move (nb_local_kinematics_runner, k = --kin-k, default
 // 32; --kin-gradient 1 adds the velocity gradient) at step 0 and at every K-th step and prints one line "kin <step>
@@ -825,6 +833,34 @@ static void print_knn(nbody::OfflineHeadless<Sim> &runner, const KnnOptions &ko)
                 d.stats.peak_index);
 }
 
+struct MstOptions {
+    int every = 0;
+    std::vector<double> links;
+    uint32_t min_members = 1;
+    bool have_min = false;
+    std::string dir;
+};
+
+template <class Sim>
+static bool print_mst(nbody::OfflineHeadless<Sim> &runner, const MstOptions &mo) {
+    const nbody::SpanningTree t = runner.spanning_tree(true);
+    std::printf("mst %llu %llu %u %.17g %.17g", (unsigned long long)t.stats.step_num, (unsigned long long)t.stats.edges,
+                t.stats.rounds, t.total_length(), t.longest());
+    for (uint64_t c : t.group_counts(mo.links, mo.min_members)) std::printf(" %llu", (unsigned long long)c);
+    std::printf("\n");
+    if (mo.dir.empty()) return true;
+    std::vector<double> rows(3 * t.d2.size());
+    for (size_t e = 0; e < t.d2.size(); ++e) {
+        rows[3 * e] = (double)t.edge_lo[e];
+        rows[3 * e + 1] = (double)t.edge_hi[e];
+        rows[3 * e + 2] = t.d2[e];
+    }
+    char name[64], shape[64];
+    std::snprintf(name, sizeof name, "/mst_%llu.npy", (unsigned long long)t.stats.step_num);
+    std::snprintf(shape, sizeof shape, "%zu, 3", t.d2.size());
+    return write_f8(mo.dir + name, shape, rows);
+}
+
 struct KinOptions {
     int every = 0;
     uint32_t k = 32;
@@ -984,7 +1020,8 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
                const ShapesOptions &shapes, const LagrOptions &lagr, const RadiiCliOptions &radii,
                const ModesOptions &modes, const PhaseOptions &phase, const RotcurveOptions &freq,
                const KinOptions &kin, const OrbitsOptions &orbits, const Fof6Options &fof6,
-               const SectionsOptions &sections, const OrbitsOptions &stability, const ShellsOptions &shells) {
+               const SectionsOptions &sections, const OrbitsOptions &stability, const ShellsOptions &shells,
+               const MstOptions &mst) {
     std::puts("Initializing Simulation");
     nbody::OfflineHeadless<Sim> runner = devices.empty() ? nbody::OfflineHeadless<Sim>(sp, ap, init, device)
                                                          : nbody::OfflineHeadless<Sim>(sp, ap, init, devices, let);
@@ -1002,6 +1039,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
     if (fof6.every > 0) print_fof6(runner, fof6);
     if (bound.every > 0) print_bound(runner, bound);
     if (knn.every > 0) print_knn(runner, knn);
+    if (mst.every > 0 && !print_mst(runner, mst)) return 1;
     if (kin.every > 0) print_kin(runner, kin);
     if (hop.every > 0) print_hop(runner, hop);
     if (halo.every > 0) print_halo(runner, halo);
@@ -1031,6 +1069,7 @@ static int run(const nbody::SimParams &sp, const nbody::AddParams &ap, const nbo
         if (fof6.every > 0 && (i + 1) % fof6.every == 0) print_fof6(runner, fof6);
         if (bound.every > 0 && (i + 1) % bound.every == 0) print_bound(runner, bound);
         if (knn.every > 0 && (i + 1) % knn.every == 0) print_knn(runner, knn);
+        if (mst.every > 0 && (i + 1) % mst.every == 0 && !print_mst(runner, mst)) return 1;
         if (kin.every > 0 && (i + 1) % kin.every == 0) print_kin(runner, kin);
         if (hop.every > 0 && (i + 1) % hop.every == 0) print_hop(runner, hop);
         if (halo.every > 0 && (i + 1) % halo.every == 0) print_halo(runner, halo);
@@ -1067,6 +1106,7 @@ int main(int argc, char **argv) {
     SmapOptions smaps;
     FofOptions fof;
     KnnOptions knn;
+    MstOptions mst;
     KinOptions kin;
     OrbitsOptions orbits;
     SectionsOptions sections;
@@ -1399,6 +1439,31 @@ int main(int argc, char **argv) {
             hop.peak = std::atof(v.c_str());
             hop_peak = true;
         } else if (k == "--hop-top") hop.top = std::atoi(v.c_str());
+        else if (k == "--mst") mst.every = std::atoi(v.c_str());
+        else if (k == "--mst-links") {
+            for (const char *c = v.c_str(); *c;) {
+                char *end = nullptr;
+                const double link = std::strtod(c, &end);
+                if (end == c || !(link > 0.0) || !std::isfinite(link) || !(link * link > 0.0) ||
+                    !std::isfinite(link * link) || (*end && *end != ',') || (*end == ',' && !end[1])) {
+                    std::fprintf(stderr, "--mst-links takes L1,L2,... (each finite and > 0), not %s\n", v.c_str());
+                    return 2;
+                }
+                mst.links.push_back(link);
+                c = *end ? end + 1 : end;
+            }
+        }
+        else if (k == "--mst-min") {
+            char *end = nullptr;
+            const unsigned long mm = std::strtoul(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || mm < 1 || mm > 0xfffffffful) {
+                std::fprintf(stderr, "--mst-min takes a count of at least 1, not %s\n", v.c_str());
+                return 2;
+            }
+            mst.min_members = (uint32_t)mm;
+            mst.have_min = true;
+        }
+        else if (k == "--mst-dump") mst.dir = v;
         else if (k == "--knn") knn.every = std::atoi(v.c_str());
         else if (k == "--knn-k") knn.k = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (k == "--orbits") orbits.dir = v;
@@ -1574,6 +1639,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--modes needs --modes-range RMIN,RMAX and --modes-m M >= 2\n");
         return 2;
     }
+    if (mst.every <= 0 && (!mst.links.empty() || !mst.dir.empty() || mst.have_min)) {
+        std::fprintf(stderr, "--mst-links, --mst-min and --mst-dump need --mst K\n");
+        return 2;
+    }
     if (shells.every > 0 && (!shells.have_range || shells.lmax < 2)) {
         std::fprintf(stderr, "--shells needs --shells-range RMIN,RMAX and --shells-l L >= 2\n");
         return 2;
@@ -1592,9 +1661,9 @@ int main(int argc, char **argv) {
     try {
         if (sim == "naive")
             return run<nbody::NaiveSim>(sp, nbody::AddParams::NaiveSimParams(), fn, steps, device, devices, dump, -1, diag,
-                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells);
+                                        diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells, mst);
         return run<nbody::TreeSim>(sp, nbody::AddParams::TreeSimParams(theta), fn, steps, device, devices, dump, let,
-                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells);
+                                       diag, diag_potential, frames, radial, rotcurve, maps, smaps, fof, knn, bound, halo, hop, shapes, lagr, radii, modes, phase, freq, kin, orbits, fof6, sections, stability, shells, mst);
     } catch (const nbody::Error &e) {
         std::fprintf(stderr, "error %d: %s\n", e.code(), e.what());
         return 1;

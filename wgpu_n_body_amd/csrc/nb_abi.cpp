@@ -219,6 +219,13 @@ static int pass_knn(H *h, const nb_knn_params *params, double *r2, uint32_t *kth
 }
 
 template <class H>
+static int pass_mst(H *h, const nb_mst_params *params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+                    uint32_t *degree, nb_mst_stats *stats) {
+    if (int rc = mst_check_params(params)) return rc;
+    return on_sim(h, "mst", [&](SimBase &s) { return sim_mst(s, *params, edge_lo, edge_hi, d2, degree, stats); });
+}
+
+template <class H>
 static int pass_local_kinematics(H *h, const nb_kin_params *params, double *moments, double *grads, double *r2,
                                  uint32_t *kth, double *mass_in, double *density, nb_kin_stats *stats) {
     if (int rc = kin_check_params(params)) return rc;
@@ -342,6 +349,10 @@ static const TuningKey kTuningKeys[] = {
     {"bound_tile", &SimBase::bound_tile, "0, 64 or 256", [](int v) { return v == 0 || v == 64 || v == 256; }},
     {"knn_span_cells", &SimBase::knn_span_cells, "1..8", [](int v) { return v >= 1 && v <= 8; }},
     {"knn_block_queries", &SimBase::knn_block_queries, "1, 2 or 4", [](int v) { return v == 1 || v == 2 || v == 4; }},
+    {"mst_span_cells", &SimBase::mst_span_cells, "1..8", [](int v) { return v >= 1 && v <= 8; }},
+    {"mst_block_queries", &SimBase::mst_block_queries, "1, 2 or 4", [](int v) { return v == 1 || v == 2 || v == 4; }},
+    {"mst_skip_runs", &SimBase::mst_skip_runs, "0 or 1", [](int v) { return v == 0 || v == 1; }},
+    {"mst_shared_bound", &SimBase::mst_shared_bound, "0 or 1", [](int v) { return v == 0 || v == 1; }},
 };
 
 extern "C" {
@@ -701,6 +712,23 @@ int nb_hop_regroup(const nb_fof_group *rows, const double *peak_density, size_t 
         return hop_regroup(rows, peak_density, m, bnd, b, params, merged_of_row, out_rows, out_peak, out_capacity,
                            out_count);
     })
+}
+
+int nb_mst_sim(nb_sim *sim, const nb_mst_params *params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+               uint32_t *degree, nb_mst_stats *stats) {
+    return pass_mst(sim, params, edge_lo, edge_hi, d2, degree, stats);
+}
+int nb_mst_runner(nb_runner *runner, const nb_mst_params *params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+                  uint32_t *degree, nb_mst_stats *stats) {
+    return pass_mst(runner, params, edge_lo, edge_hi, d2, degree, stats);
+}
+int nb_mst_cut(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, const double *d2,
+               const uint32_t *degree, double link, uint32_t *labels, size_t *components) {
+    NB_GUARD({ return mst_cut(n, edges, edge_lo, edge_hi, d2, degree, link, labels, components); })
+}
+int nb_mst_linkage(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, uint32_t *label_a,
+                   uint32_t *label_b, uint32_t *count_a, uint32_t *count_b) {
+    NB_GUARD({ return mst_linkage(n, edges, edge_lo, edge_hi, label_a, label_b, count_a, count_b); })
 }
 
 int nb_sim_halo_profiles(nb_sim *sim, const nb_halo_params *params, nb_halo_head *heads, nb_radial_bin *bins,

@@ -1584,4 +1584,116 @@ int map_edges(double lo, double hi, uint32_t cells, double *edges) {
     return NB_OK;
 }
 
+// nb_mst_sim: everything that can be refused without a device
+int mst_check_params(const nb_mst_params *p) {
+    if (!p) {
+        set_error("mst: null params");
+        return NB_ERR_INVALID;
+    }
+    if (p->flags || p->reserved32 || p->reserved) {
+        set_error("mst: unknown flag bits 0x%x or a reserved field != 0", p->flags);
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+namespace {
+
+// what nb_mst_cut and nb_mst_linkage refuse about an edge list
+int mst_check_edges(const char *what, size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi) {
+    if (n > 0xffffffffull) {
+        set_error("%s: %zu bodies are more than a 32-bit index names", what, n);
+        return NB_ERR_INVALID;
+    }
+    if (edges >= std::max<size_t>(n, 1)) {
+        set_error("%s: %zu edges are not a tree's on %zu bodies", what, edges, n);
+        return NB_ERR_INVALID;
+    }
+    if (edges && (!edge_lo || !edge_hi)) {
+        set_error("%s: null edge_lo or edge_hi for %zu edges", what, edges);
+        return NB_ERR_INVALID;
+    }
+    for (size_t e = 0; e < edges; ++e)
+        if (!(edge_lo[e] < edge_hi[e]) || edge_hi[e] >= n) {
+            set_error("%s: edge %zu (%u, %u) is not lo < hi < n = %zu", what, e, edge_lo[e], edge_hi[e], n);
+            return NB_ERR_INVALID;
+        }
+    return NB_OK;
+}
+
+// the forest of nb_fof.hpp on the host: the larger root under the smaller, so a root is its tree's smallest index
+uint32_t mst_root(std::vector<uint32_t> &parent, uint32_t x) {
+    while (parent[x] != x) {
+        parent[x] = parent[parent[x]];
+        x = parent[x];
+    }
+    return x;
+}
+
+}  // namespace
+
+int mst_cut(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, const double *d2,
+            const uint32_t *degree, double link, uint32_t *labels, size_t *components) {
+    if (int rc = mst_check_edges("mst_cut", n, edges, edge_lo, edge_hi)) return rc;
+    if ((edges && !d2) || (n && !labels)) {
+        set_error("mst_cut: null d2 or labels");
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(link) || !(link > 0.0)) {
+        set_error("mst_cut: link must be finite and > 0 (got %g)", link);
+        return NB_ERR_INVALID;
+    }
+    const double b2 = link * link;  // what the rule compares with, formed once (nb_sim_fof)
+    if (!(b2 > 0.0) || !std::isfinite(b2)) {
+        set_error("mst_cut: link %g squared is not a positive finite double", link);
+        return NB_ERR_INVALID;
+    }
+    std::vector<uint32_t> parent(n);
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    for (size_t e = 0; e < edges; ++e) {
+        if (!(d2[e] <= b2)) continue;
+        const uint32_t a = mst_root(parent, edge_lo[e]), b = mst_root(parent, edge_hi[e]);
+        if (a != b) parent[std::max(a, b)] = std::min(a, b);
+    }
+    size_t count = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (degree && degree[i] == NB_MST_NONE) {
+            labels[i] = NB_FOF_NONE;
+            continue;
+        }
+        labels[i] = mst_root(parent, (uint32_t)i);
+        count += labels[i] == i;
+    }
+    if (components) *components = count;
+    return NB_OK;
+}
+
+int mst_linkage(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, uint32_t *label_a,
+                uint32_t *label_b, uint32_t *count_a, uint32_t *count_b) {
+    if (int rc = mst_check_edges("mst_linkage", n, edges, edge_lo, edge_hi)) return rc;
+    std::vector<uint32_t> parent(n), size(n, 1u);
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    for (size_t e = 0; e < edges; ++e)
+        if (mst_root(parent, edge_lo[e]) == mst_root(parent, edge_hi[e])) {
+            set_error("mst_linkage: edge %zu (%u, %u) closes a cycle", e, edge_lo[e], edge_hi[e]);
+            return NB_ERR_INVALID;
+        } else {
+            const uint32_t ra = mst_root(parent, edge_lo[e]), rb = mst_root(parent, edge_hi[e]);
+            parent[std::max(ra, rb)] = std::min(ra, rb);
+        }
+    // (checked before anything is written: the outputs are written only by a call that succeeds)
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    for (size_t e = 0; e < edges; ++e) {
+        const uint32_t ra = mst_root(parent, edge_lo[e]), rb = mst_root(parent, edge_hi[e]);
+        const uint32_t a = std::min(ra, rb), b = std::max(ra, rb);
+        if (label_a) label_a[e] = a;
+        if (label_b) label_b[e] = b;
+        if (count_a) count_a[e] = size[a];
+        if (count_b) count_b[e] = size[b];
+        parent[b] = a;
+        size[a] += size[b];
+    }
+    return NB_OK;
+}
+
 }  // namespace nb

@@ -15,7 +15,7 @@ struct Workspace {
 };
 enum WorkSlot : int { kWorkDiag = 0, kWorkRender, kWorkRadial, kWorkField, kWorkMap, kWorkFof, kWorkKnn, kWorkSmooth,
                       kWorkBound, kWorkHalo, kWorkHop, kWorkShape, kWorkRadii, kWorkModes, kWorkShell, kWorkPhase, kWorkTidal,
-                      kWorkKin, kWorkOrbits, kWorkFof6, kWorkStability, kWorkSlots };
+                      kWorkKin, kWorkOrbits, kWorkFof6, kWorkStability, kWorkMst, kWorkSlots };
 
 // The exchange regions of a TreeSim (the index of nb_sim_exchange_region_i), for both of its placements.
 enum ExchangeRegion : int {
@@ -136,6 +136,10 @@ class SimBase {
     int shape_chunk_len = 1024;  // "shape_chunk_len": positions of a row's list per work item of nb_sim_group_shapes
     int knn_span_cells = 3;      // "knn_span_cells": octree cells per axis the search of nb_sim_knn opens around a body
     int knn_block_queries = 4;   // "knn_block_queries": bodies (a wave each) per block of that search
+    int mst_span_cells = 3;      // "mst_span_cells": octree cells per axis the search of nb_mst_sim starts from
+    int mst_block_queries = 4;   // "mst_block_queries": bodies (a wave each) per block of that search
+    int mst_skip_runs = 1;       // "mst_skip_runs": stretches of the body's own component are stepped over
+    int mst_shared_bound = 1;    // "mst_shared_bound": a component's bodies share the smallest d2 found so far
 };
 
 // nb_diag.hip: nb_sim_diagnostics behind the handle
@@ -279,6 +283,14 @@ int shell_derive(const nb_shell_head *head, const double *coef, nb_shell_derived
 int knn_check_params(const nb_knn_params *p);
 int sim_knn(SimBase &sim, const nb_knn_params &params, double *r2, uint32_t *kth, double *mass_in, double *density,
             nb_knn_stats *stats);
+// nb_mst.hip: nb_mst_sim behind the handle; mst_cut / mst_linkage: nb_mst_cut / nb_mst_linkage behind the ABI boundary
+int mst_check_params(const nb_mst_params *p);
+int sim_mst(SimBase &sim, const nb_mst_params &params, uint32_t *edge_lo, uint32_t *edge_hi, double *d2,
+            uint32_t *degree, nb_mst_stats *stats);
+int mst_cut(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, const double *d2,
+            const uint32_t *degree, double link, uint32_t *labels, size_t *components);
+int mst_linkage(size_t n, size_t edges, const uint32_t *edge_lo, const uint32_t *edge_hi, uint32_t *label_a,
+                uint32_t *label_b, uint32_t *count_a, uint32_t *count_b);
 // nb_kinematics.hip: nb_local_kinematics_sim behind the handle; kin_derive: nb_local_kinematics_derive behind the
 // ABI boundary
 int kin_check_params(const nb_kin_params *p);

@@ -54,6 +54,7 @@ using RadiiGroup = nb_radii_group;        // 264 B: a row's mass radii, extent a
 using RadiiStats = nb_radii_stats;
 using HopBoundary = nb_hop_boundary;      // 24 B: two labels, their body pairs and the largest pair density
 using HopStats = nb_hop_stats;
+using MstStats = nb_mst_stats;            // the counts, the rounds and the plan of nb_mst_sim
 using KnnStats = nb_knn_stats;            // the counts, the density-weighted sums and the peak of nb_sim_knn
 using KinStats = nb_kin_stats;            // the counts of nb_local_kinematics_sim
 using KinDerived = nb_kin_derived;        // 256 B: a body's local mean velocity, dispersion, Q and velocity gradient
@@ -1129,6 +1130,86 @@ KnnDensity knn_density(int (*call)(H *, const nb_knn_params *, double *, uint32_
 }
 }  // namespace detail
 
+// nb_mst_sim's tree (no reference counterpart): the Euclidean minimum spanning tree of the counted bodies in
+// ascending (d2, lo, hi); degree is empty when not asked for
+struct SpanningTree {
+    std::vector<uint32_t> edge_lo, edge_hi;
+    std::vector<double> d2;
+    std::vector<uint32_t> degree;  // NB_MST_NONE: a body that is not counted
+    MstStats stats{};
+
+    size_t counted() const { return (size_t)(stats.n - stats.nonfinite); }
+    std::vector<double> length() const {
+        std::vector<double> l(d2.size());
+        for (size_t e = 0; e < d2.size(); ++e) l[e] = std::sqrt(d2[e]);
+        return l;
+    }
+    double total_length() const {
+        double t = 0.0;
+        for (double d : d2) t += std::sqrt(d);
+        return t;
+    }
+    // the length of the last edge (0 for a tree without edges)
+    double longest() const { return d2.empty() ? 0.0 : std::sqrt(d2.back()); }
+    // per body the smallest index of its component under the edges with d2 <= link^2 (nb_mst_cut): the labels of
+    // fof_groups(link, 1) of the same state
+    std::vector<uint32_t> cut(double link) const {
+        std::vector<uint32_t> labels((size_t)stats.n);
+        check(nb_mst_cut((size_t)stats.n, d2.size(), edge_lo.data(), edge_hi.data(), d2.data(),
+                         degree.empty() ? nullptr : degree.data(), link, labels.data(), nullptr));
+        return labels;
+    }
+    // the dendrogram (nb_mst_linkage): per edge the two components it joins, smallest indices and sizes
+    struct Linkage {
+        std::vector<uint32_t> label_a, label_b, count_a, count_b;
+    };
+    Linkage linkage() const {
+        const size_t m = d2.size();
+        Linkage l{std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<uint32_t>(m),
+                  std::vector<uint32_t>(m)};
+        check(nb_mst_linkage((size_t)stats.n, m, edge_lo.data(), edge_hi.data(), l.label_a.data(), l.label_b.data(),
+                             l.count_a.data(), l.count_b.data()));
+        return l;
+    }
+    // the percolation curve: per link the components of at least min_members bodies, from one pass over the linkage
+    std::vector<uint64_t> group_counts(const std::vector<double> &links, uint32_t min_members = 1) const {
+        const Linkage l = linkage();
+        const size_t m = d2.size();
+        std::vector<int64_t> after(m + 1);
+        after[0] = min_members <= 1 ? (int64_t)counted() : 0;
+        for (size_t e = 0; e < m; ++e) {
+            const uint64_t a = l.count_a[e], b = l.count_b[e];
+            after[e + 1] = after[e] + (a + b >= min_members) - (a >= min_members) - (b >= min_members);
+        }
+        std::vector<uint64_t> out;
+        for (double link : links) {
+            const double b2 = link * link;
+            out.push_back((uint64_t)after[(size_t)(std::upper_bound(d2.begin(), d2.end(), b2) - d2.begin())]);
+        }
+        return out;
+    }
+};
+
+namespace detail {
+template <class H>
+SpanningTree spanning_tree(int (*call)(H *, const nb_mst_params *, uint32_t *, uint32_t *, double *, uint32_t *,
+                                       nb_mst_stats *),
+                           H *h, size_t n, bool degree) {
+    SpanningTree t;
+    nb_mst_params p{};
+    const size_t room = n ? n - 1 : 0;
+    t.edge_lo.resize(room);
+    t.edge_hi.resize(room);
+    t.d2.resize(room);
+    if (degree) t.degree.resize(n);
+    check(call(h, &p, t.edge_lo.data(), t.edge_hi.data(), t.d2.data(), degree ? t.degree.data() : nullptr, &t.stats));
+    t.edge_lo.resize((size_t)t.stats.edges);
+    t.edge_hi.resize((size_t)t.stats.edges);
+    t.d2.resize((size_t)t.stats.edges);
+    return t;
+}
+}  // namespace detail
+
 // nb_local_kinematics_sim's per-body sums over the k nearest neighbours (no reference counterpart) and the rows
 // nb_local_kinematics_derive makes of them: moments 10 and grads 15 doubles per body, grads and kth empty when not
 // asked for; derived[i].mean_velocity is NaN until derive() is given the state's velocities
@@ -1337,6 +1418,7 @@ struct PassAbi<nb_sim> {
     static constexpr auto fof = nb_sim_fof;
     static constexpr auto bound = nb_sim_bound;
     static constexpr auto knn = nb_sim_knn;
+    static constexpr auto mst = nb_mst_sim;
     static constexpr auto hop = nb_sim_hop;
     static constexpr auto halo_profiles = nb_sim_halo_profiles;
     static constexpr auto group_shapes = nb_sim_group_shapes;
@@ -1363,6 +1445,7 @@ struct PassAbi<nb_runner> {
     static constexpr auto fof = nb_runner_fof;
     static constexpr auto bound = nb_runner_bound;
     static constexpr auto knn = nb_runner_knn;
+    static constexpr auto mst = nb_mst_runner;
     static constexpr auto hop = nb_runner_hop;
     static constexpr auto halo_profiles = nb_runner_halo_profiles;
     static constexpr auto group_shapes = nb_runner_group_shapes;
@@ -1466,6 +1549,8 @@ class Passes {
     KnnDensity knn_density(uint32_t k = 6, bool density = true, bool neighbours = true) {
         return detail::knn_density(Abi::knn, h_, n_bodies(), k, density, neighbours);
     }
+    // the minimum spanning tree of the current state: cut(link) is fof_groups(link, 1)'s labels for every link
+    SpanningTree spanning_tree(bool degree = true) { return detail::spanning_tree(Abi::mst, h_, n_bodies(), degree); }
     // how the k nearest neighbours of every body move: the moments, with gradient the velocity-gradient sums, and
     // the derived rows (sigma, rho / sigma^3, divergence, vorticity, shear)
     LocalKinematics local_kinematics(uint32_t k = 32, bool gradient = false, bool include_self = true,
